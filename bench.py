@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the XC sweep (DFT_ComputeXC) on MI355X.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: set-up, clock spin-up, W warm-up steps, K timed steps, the
+outputs of the last timed step written to DIR (`--dump-outputs`: vxc.npy (nao, nao) and exc.npy (1,),
+float64, rank 0, after the all-reduce for N > 1), then the result line.  Everything else below
+(`occ_entry`, `kernels_ms`, `roofline` and the extra legs) runs only with `--full`.
 
 N > 1 started as a plain `python bench.py --gpus N` (no WORLD_SIZE in the environment) launches its own
 N rank processes -- a `python -m torch.distributed.run` child on 127.0.0.1, started BEFORE anything in
@@ -28,7 +33,7 @@ Output = ONE JSON line on rank 0 (metric grid-points/s).  `roofline` is the WHOL
          second one sharded over the N ranks); `k_build` the factorised exact exchange on the fp64 matrix cores; `small_basis` us per
          synchronous call at bases of at most 32 functions (H2O/def2-SVP ... shapes): default options against the one-pass kernel
          forced on / off (option `tiny`).
-The headline is measured first and its line is complete before any extra leg starts; the legs run under a watchdog
+With `--full` the headline is measured first and its line is complete before any extra leg starts; the legs run under a watchdog
          (`--legs-seconds`) and a leg that fails or hangs only costs its own member (`legs_note` says so).
 """
 import argparse
@@ -616,6 +621,10 @@ def main():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank owns a full-size grid (default, the BASELINE metric); strong: one grid sharded over the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (vxc.npy, exc.npy; float64) to DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure occ_entry, kernels_ms, roofline and the extra legs (the options below apply to it)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target duration of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-k-build", action="store_true", help="skip the factorised exact-exchange (fp64 MFMA) measurement")
@@ -625,6 +634,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend; gloo only to rehearse N>1 on a single card")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -737,6 +748,38 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
+    # what a caller of the timed path receives from its last step (the --full steps below overwrite d_v)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "vxc.npy"), d_v.view(nao, nao).cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "exc.npy"), np.array([exc], dtype=np.float64))
+
+    line = None
+    if rank == 0:
+        t_step = dt / args.steps
+        line = {
+            "metric": "grid_points_per_sec", "value": total_points * args.steps / dt, "unit": "grid-points/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": t_step * 1e3, "spinup_ms": args.spinup_ms, "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"{workload}: DFT_ComputeXC ({xc}) nao={nao} ngrid={ngrid_all}" + (" per GPU" if not strong else f" sharded over {world} GPU(s)") +
+                                   ", synthetic AO/grid (SURVEY 8(d) recipe), inputs resident in HBM",
+                       "functional": xc, "nao": nao, "nocc": nocc, "ngrid_per_gpu": ngrid,
+                       "entry_point": "DFT_ComputeXC (the reference ABI: full density matrix)" if world == 1 else "DFT_ComputeXCAsync (full density matrix) + all-reduce",
+                       "sharding": "grid points" + ("" if world == 1 else f" x{world}, {coll_name} all-reduce of Vxc|Exc ({8 * (nao * nao + 1)} B)")},
+            "backend": args.backend if world > 1 else None,
+            "world_size_seen": (dist.get_world_size() if world > 1 else 1), "device_count": ndev,
+            "exc": exc,
+        }
+    if not args.full:
+        if line is not None:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full only from here on ------------------------------------------------------------------------------------
     # the same K steps through DFT_ComputeXCOcc (same inputs, same barrier / synchronise bracket, max over ranks)
     for _ in range(args.warmup):
         exc_occ = step_occ()
@@ -768,10 +811,8 @@ def main():
         kern = kernel_times(lambda: solver.compute_xc(ngrid, nao, dm, ao, w, d_v, gr))
         kern_occ = kernel_times(lambda: solver.compute_xc_occ(ngrid, nao, nocc, cocc, ao, w, d_v, gr, dm))
 
-    # ---- the headline line is complete here; everything below only adds members to it ---------------------------
-    line = None
+    # ---- the headline line is complete; everything below only adds members to it -----------------------------------
     if rank == 0:
-        t_step = dt / args.steps
         # whole call against SURVEY 8(d): B = ngrid(8 nao c + 8) + 16 nao^2, F = 4 ngrid nao^2 + (2c + 8[c=4]) ngrid nao
         b_all, f_all = kernel_model("xc_sweep", xc, ngrid, nao)
         hbm_frac, mfma_frac = b_all / t_step / 1e9 / HBM_PEAK_GBS, f_all / t_step / 1e12 / F64_MFMA_PEAK_TF
@@ -798,19 +839,8 @@ def main():
                                        "traffic": tr["per_kernel"].get(dom) if tr else None,
                                        "mfma_pipe_busy_pmc": tr["mfma_utilisation"].get(dom) if tr else None,
                                        "mfma_pipe_busy_note": "SQ_VALU_MFMA_BUSY_CYCLES over all SIMD cycles, rocprofv3 counter pass (profiles/r03_pmc_sweep.json)"}
-        line = {
-            "metric": "grid_points_per_sec", "value": total_points * args.steps / dt, "unit": "grid-points/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": t_step * 1e3, "spinup_ms": args.spinup_ms, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{workload}: DFT_ComputeXC ({xc}) nao={nao} ngrid={ngrid_all}" + (" per GPU" if not strong else f" sharded over {world} GPU(s)") +
-                                   ", synthetic AO/grid (SURVEY 8(d) recipe), inputs resident in HBM",
-                       "functional": xc, "nao": nao, "nocc": nocc, "ngrid_per_gpu": ngrid,
-                       "entry_point": "DFT_ComputeXC (the reference ABI: full density matrix)" if world == 1 else "DFT_ComputeXCAsync (full density matrix) + all-reduce",
-                       "sharding": "grid points" + ("" if world == 1 else f" x{world}, {coll_name} all-reduce of Vxc|Exc ({8 * (nao * nao + 1)} B)")},
-            "backend": args.backend if world > 1 else None,
-            "world_size_seen": (dist.get_world_size() if world > 1 else 1), "device_count": ndev,
-            "roofline": roof, "kernels_ms": kern, "exc": exc,
+        line.update({
+            "roofline": roof, "kernels_ms": kern,
             # the same steps through the extension that takes the occupied orbitals (what scf.HipBackend calls): same
             # results, the density step does 4 nao nocc instead of 2 nao^2 flops per grid point
             "occ_entry": {"entry_point": "DFT_ComputeXCOcc (occupied orbitals cocc (nao, nocc), dm = cocc cocc^T)" + ("" if world == 1 else " async + all-reduce"),
@@ -818,7 +848,7 @@ def main():
                           "exc": exc_occ, "exc_rel_diff_to_abi": abs(exc_occ - exc) / max(abs(exc), 1e-300), "kernels_ms": kern_occ,
                           "hbm_frac": b_all / (dt_occ / args.steps) / 1e9 / HBM_PEAK_GBS,
                           "note": "hbm_frac against the same algorithmic bytes as the ABI call; the occupied form reads the AO plane once"},
-        }
+        })
 
     # The extra legs must never cost the headline: a watchdog thread ends the process after `args.legs_seconds` -- rank 0
     # printing the line with whatever legs have finished -- and a leg that raises is recorded and ends the extra legs

@@ -14,10 +14,10 @@ step() { # name timeout cmd...
 }
 [ -x tools/mfma_f64_probe ] && [ -z "$SKIP_PROBE" ] && step probe 120 tools/mfma_f64_probe
 [ -z "$SKIP_TESTS" ] && step pytest_gpu 900 python -m pytest tests -q -m gpu ${PYTEST_ARGS:-}
-[ -z "$SKIP_BENCH" ] && step bench 600 python bench.py ${BENCH_ARGS:-}
+[ -z "$SKIP_BENCH" ] && step bench 600 python bench.py --full ${BENCH_ARGS:-}
 if [ -n "$DO_PROF" ]; then
   export TMPDIR=/tmp
-  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof" -- python3 bench.py --no-cpu-baseline ${BENCH_ARGS:-}
+  step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$PWD/$OUT/prof" -- python3 bench.py --full --no-cpu-baseline ${BENCH_ARGS:-}
   find $OUT/prof -name "*kernel_stats.csv" | head -3
 fi
 echo "=== done"
