@@ -290,8 +290,7 @@ void DFT_ScfTailClose(void *handle);
  * the faster call, which it is at every size measured (0.71-1.00 of the four launches, 20 k-300 k points: profiles/r03_tiny_scan_final.txt);
  * 1 = whenever nao <= 32; 0 = never.  Results agree with the four-launch path to the
  * rounding of the sums, not bit for bit), "ao_pt" (grid points per workgroup of DFT_EvalAO:
- * 8, 16, or 0 = auto), "rho_rows" (grid rows per workgroup of the large-basis
- * density kernel: 64, default, or 128).  Returns 0 if the key is known. */
+ * 8, 16, or 0 = auto).  Returns 0 if the key is known. */
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
 
 /* Run subsequent work on `hip_stream` (a hipStream_t cast to an integer);

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dft_solver.h"
@@ -24,7 +25,6 @@
 #include "cd_kernels.hpp"
 #include "xc_big_kernels.hpp"
 #include "xc_ws_kernels.hpp"
-#include "xc_ws16_kernels.hpp"
 #include "xc_kernels.hpp"
 #include "xc_occ_launch.hpp"
 #include "xc_tiny_launch.hpp"
@@ -74,11 +74,8 @@ struct XCSolver {
     // 1 (opt-in): the reduce kernel's highest-index block finishes Exc itself (one launch and ~1.5 us fewer); the word
     // then only orders consumers on the solver's own stream.
     int fuse_finish = 0;
-    int rho_rows = 64; // grid rows per workgroup of the large-basis rho kernel: 64 (two workgroups per CU) or 128
     int sweep_order = 2; // bit 0: rho kernel walks the grid backwards, bit 1: Vxc kernel does (default: rho forward, Vxc backward)
-    int dbg = 0;       // diagnostics only (ablations of the sixteen-wave kernels: 1 = no plane loads, 2 = no MFMAs)
     int tiny = -1;     // one-pass sweep kernel for nao <= 32 (xc_tiny_kernels.hpp): -1 auto (where it is faster, tiny_pays()), 0 off, 1 on
-    int ws_waves = 0;  // wave-specialised kernels (nao <= 128): 0 auto, 8 = 4+4 waves per workgroup, 16 = 8+8
     int occ = 0;       // DFT_ComputeXCOcc: 0 auto (occupied-orbital density step where it does fewer MFMAs), 1 always, 2 never
     int used_occ = 0;  // what the last sweep did (DFT_GetTimings names say so too)
     int eri_sym = 0;   // 1: the caller vouches that the dense ERI is symmetric as an (N2, N2) matrix: DFT_ComputeCoulomb streams its upper
@@ -198,17 +195,23 @@ int auto_ksplit(const XCSolver *s, long ngrid, int nblk)
     return (int)want;
 }
 
-#define QCDFT_NT_SWITCH(NTV, CALL)              \
-    switch (NTV) {                               \
-    case 1: { constexpr int NT = 1; CALL; } break; \
-    case 2: { constexpr int NT = 2; CALL; } break; \
-    case 3: { constexpr int NT = 3; CALL; } break; \
-    case 4: { constexpr int NT = 4; CALL; } break; \
-    case 5: { constexpr int NT = 5; CALL; } break; \
-    case 6: { constexpr int NT = 6; CALL; } break; \
-    case 7: { constexpr int NT = 7; CALL; } break; \
-    default: { constexpr int NT = 8; CALL; } break; \
+// Runtime values to template arguments, for kernel launches written once as generic lambdas:
+// f(std::integral_constant<int, NT>) for a tile count nt = 1..8, f(std::true_type / std::false_type) for a bool.
+template <int NT = 1, class F>
+void with_nt(int nt, F &&f)
+{
+    if constexpr (NT < 8) {
+        if (nt != NT) return with_nt<NT + 1>(nt, f);
     }
+    f(std::integral_constant<int, NT>{});
+}
+
+template <class F>
+void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else   f(std::false_type{});
+}
 
 // The sweep: everything on s->stream, Exc left in s->exc (device).
 // `cocc` (nao, nocc) with dm = cocc cocc^T switches the density step to the occupied-orbital form where that
@@ -266,7 +269,6 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     const bool fast = s->path == 0 && nao <= 128 && fits32;
     const bool big = s->path == 0 && nao > 128;   // nao <= 128 with planes >= 4 GiB: the generic MFMA kernels below
     const int ntv = NP / 16;
-    const bool ws16 = fast && s->ws_waves == 16; // opt-in: measured equal to the eight-wave kernels at NT = 8, slower below
     int nslab;
     long chunk = 0;
     const int nA = (nao + BG_BM - 1) / BG_BM, nB = (nao + BG_BN - 1) / BG_BN, npair = nA * nB;
@@ -321,6 +323,8 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
            *exc = exc_out ? exc_out : (double *)s->exc.p;   // the asynchronous entries' caller-owned scalar: written by the finishing kernel itself
     const double *gx = ao_grad, *gy = gga ? ao_grad + ng * nao : nullptr,
                  *gz = gga ? ao_grad + 2 * ng * nao : nullptr;
+    // 16-byte plane loads: even nao and every plane 16-byte aligned
+    const bool vec16 = (nao % 2 == 0) && ((((uintptr_t)ao | (uintptr_t)gx | (uintptr_t)gy | (uintptr_t)gz) & 15) == 0);
     hipStream_t st = s->stream;
 
     if (tiny) {
@@ -331,7 +335,6 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     if (use_occ) {
         ScopedTimer t(s, "rho_occ");
         if (!reserve(s, s->occ_cp, sizeof(double) * oplan.cp_doubles, "hipMalloc(packed cocc)")) return false;
-        const bool vec16 = (nao % 2 == 0) && ((((uintptr_t)ao | (uintptr_t)gx | (uintptr_t)gy | (uintptr_t)gz) & 15) == 0);
         if (!hip_ok(s, launch_rho_occ(st, s->num_cu, oplan, gga, vec16, ngrid, nao, nocc, cocc, (double *)s->occ_cp.p, ao, gx, gy, gz,
                                       rho, grad, sigma), "occupied-orbital density launch"))
             return false;
@@ -343,42 +346,20 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     }
     if (!use_occ && !tiny) {
         ScopedTimer t(s, "rho");
-        const int vec16 = (nao % 2 == 0) && ((((uintptr_t)ao | (uintptr_t)gx | (uintptr_t)gy | (uintptr_t)gz) & 15) == 0);
-        if (fast && ws16) {
-            dim3 g((unsigned)nslab);
-#define QCDFT_RHO(G, V) QCDFT_NT_SWITCH(ntv, hipLaunchKernelGGL((k_rho_ws16<NT, G, V>), g, dim3(W16_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, dm, rho, grad, sigma, s->dbg | ((s->sweep_order & 1) << 16)))
-            if (gga) { if (vec16) { QCDFT_RHO(true, true) } else { QCDFT_RHO(true, false) } }
-            else     { if (vec16) { QCDFT_RHO(false, true) } else { QCDFT_RHO(false, false) } }
-#undef QCDFT_RHO
-        } else if (fast) {
-            dim3 g((unsigned)nslab);
-#define QCDFT_RHO(G, V) QCDFT_NT_SWITCH(ntv, hipLaunchKernelGGL((k_rho_ws<NT, G, V>), g, dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, dm, rho, grad, sigma, s->sweep_order & 1))
-            if (gga) { if (vec16) { QCDFT_RHO(true, true) } else { QCDFT_RHO(true, false) } }
-            else     { if (vec16) { QCDFT_RHO(false, true) } else { QCDFT_RHO(false, false) } }
-#undef QCDFT_RHO
-        } else if (big) {
-            if (s->rho_rows == 128) {
-                dim3 g((unsigned)((ngrid + BG_BM - 1) / BG_BM));
-                if (gga) { if (vec16) hipLaunchKernelGGL((k_rho_big<true, true>), g, dim3(BG_THREADS), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-                           else       hipLaunchKernelGGL((k_rho_big<true, false>), g, dim3(BG_THREADS), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma); }
-                else     { if (vec16) hipLaunchKernelGGL((k_rho_big<false, true>), g, dim3(BG_THREADS), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-                           else       hipLaunchKernelGGL((k_rho_big<false, false>), g, dim3(BG_THREADS), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma); }
-            } else { // 64-row workgroups, two per CU
-                dim3 g((unsigned)((ngrid + R6_BM - 1) / R6_BM));
-                if (gga) { if (vec16) hipLaunchKernelGGL((k_rho_big64<true, true>), g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-                           else       hipLaunchKernelGGL((k_rho_big64<true, false>), g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma); }
-                else     { if (vec16) hipLaunchKernelGGL((k_rho_big64<false, true>), g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-                           else       hipLaunchKernelGGL((k_rho_big64<false, false>), g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma); }
-            }
-        } else if (s->path != 1) {
-            dim3 g((unsigned)((ngrid + 63) / 64));
-            if (gga) hipLaunchKernelGGL(k_rho_mfma<true>, g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-            else     hipLaunchKernelGGL(k_rho_mfma<false>, g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-        } else {
-            dim3 g((unsigned)((ngrid + 3) / 4));
-            if (gga) hipLaunchKernelGGL(k_rho_valu<true>, g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-            else     hipLaunchKernelGGL(k_rho_valu<false>, g, dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-        }
+        with_bool(gga, [&](auto G) {
+            if (fast)
+                with_bool(vec16, [&](auto V) { with_nt(ntv, [&](auto NT) {
+                    hipLaunchKernelGGL((k_rho_ws<NT, G, V>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, dm, rho, grad, sigma, s->sweep_order & 1);
+                }); });
+            else if (big) // 64-row workgroups, two per CU
+                with_bool(vec16, [&](auto V) {
+                    hipLaunchKernelGGL((k_rho_big64<G, V>), dim3((unsigned)((ngrid + R6_BM - 1) / R6_BM)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
+                });
+            else if (s->path != 1)
+                hipLaunchKernelGGL(k_rho_mfma<G>, dim3((unsigned)((ngrid + 63) / 64)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
+            else
+                hipLaunchKernelGGL(k_rho_valu<G>, dim3((unsigned)((ngrid + 3) / 4)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
+        });
     }
     if (!tiny) {
         ScopedTimer t(s, "xc_points");
@@ -389,35 +370,24 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     }
     if (!tiny) {
         ScopedTimer t(s, "vxc");
-        const int vec16 = (nao % 2 == 0) && ((((uintptr_t)ao | (uintptr_t)gx | (uintptr_t)gy | (uintptr_t)gz) & 15) == 0);
-        if (fast && ws16) {
-            dim3 g((unsigned)nslab);
-#define QCDFT_VXC(G, V, S) QCDFT_NT_SWITCH(ntv, hipLaunchKernelGGL((k_vxc_ws16<NT, G, V, S>), g, dim3(W16_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, s->dbg | ((s->sweep_order & 2) << 15)))
-            if (s->type == SOLVER_B3LYP) { if (vec16) { QCDFT_VXC(true, true, true) } else { QCDFT_VXC(true, false, true) } }
-            else if (gga) { if (vec16) { QCDFT_VXC(true, true, false) } else { QCDFT_VXC(true, false, false) } }
-            else          { if (vec16) { QCDFT_VXC(false, true, false) } else { QCDFT_VXC(false, false, false) } }
-#undef QCDFT_VXC
-        } else if (fast) {
-            dim3 g((unsigned)nslab);
-#define QCDFT_VXC(G, V, S) QCDFT_NT_SWITCH(ntv, hipLaunchKernelGGL((k_vxc_ws<NT, G, V, S>), g, dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1))
-            if (s->type == SOLVER_B3LYP) { if (vec16) { QCDFT_VXC(true, true, true) } else { QCDFT_VXC(true, false, true) } }
-            else if (gga) { if (vec16) { QCDFT_VXC(true, true, false) } else { QCDFT_VXC(true, false, false) } }
-            else          { if (vec16) { QCDFT_VXC(false, true, false) } else { QCDFT_VXC(false, false, false) } }
-#undef QCDFT_VXC
-        } else if (big) {
-            dim3 g((unsigned)(nslab * npair));
-            if (gga) { if (vec16) hipLaunchKernelGGL((k_vxc_big<true, true>), g, dim3(BG_THREADS), 0, st, ngrid, nao, chunk, nB, npair, ao, gx, gy, gz, coef, slabs);
-                       else       hipLaunchKernelGGL((k_vxc_big<true, false>), g, dim3(BG_THREADS), 0, st, ngrid, nao, chunk, nB, npair, ao, gx, gy, gz, coef, slabs); }
-            else     { if (vec16) hipLaunchKernelGGL((k_vxc_big<false, true>), g, dim3(BG_THREADS), 0, st, ngrid, nao, chunk, nB, npair, ao, gx, gy, gz, coef, slabs);
-                       else       hipLaunchKernelGGL((k_vxc_big<false, false>), g, dim3(BG_THREADS), 0, st, ngrid, nao, chunk, nB, npair, ao, gx, gy, gz, coef, slabs); }
-        } else if (s->path != 1) {
-            dim3 g((unsigned)nslab, nblk, nblk);
-            if (gga) hipLaunchKernelGGL(k_vxc_mfma<true>, g, dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
-            else     hipLaunchKernelGGL(k_vxc_mfma<false>, g, dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
-        } else {
-            dim3 g((unsigned)nslab);
-            if (gga) hipLaunchKernelGGL(k_vxc_valu<true>, g, dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
-            else     hipLaunchKernelGGL(k_vxc_valu<false>, g, dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
+        auto launch = [&](auto G, auto S) { // S: B3LYP, the wave-specialised kernels write symmetrised slabs
+            if (fast)
+                with_bool(vec16, [&](auto V) { with_nt(ntv, [&](auto NT) {
+                    hipLaunchKernelGGL((k_vxc_ws<NT, G, V, S>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1);
+                }); });
+            else if (big)
+                with_bool(vec16, [&](auto V) {
+                    hipLaunchKernelGGL((k_vxc_big<G, V>), dim3((unsigned)(nslab * npair)), dim3(BG_THREADS), 0, st, ngrid, nao, chunk, nB, npair, ao, gx, gy, gz, coef, slabs);
+                });
+            else if (s->path != 1)
+                hipLaunchKernelGGL(k_vxc_mfma<G>, dim3((unsigned)nslab, nblk, nblk), dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
+            else
+                hipLaunchKernelGGL(k_vxc_valu<G>, dim3((unsigned)nslab), dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
+        };
+        switch (s->type) { // (G, S)
+        case SOLVER_LDA: launch(std::false_type{}, std::false_type{}); break;
+        case SOLVER_GGA: launch(std::true_type{}, std::false_type{}); break;
+        default:         launch(std::true_type{}, std::true_type{}); break;
         }
     }
     {
@@ -494,8 +464,7 @@ void jk(XCSolver *s, int nao, const double *eri, const double *dm, double *J, do
         if (!reserve(s, s->jpart, sizeof(double) * nslab * N2, "hipMalloc(Jpart)")) return;
         double *jp = (double *)s->jpart.p;
         const bool vec = (n % 2 == 0) && (((uintptr_t)eri & 15) == 0);
-        if (vec) hipLaunchKernelGGL((k_j_sym<true>), dim3(ncb, n), dim3(256), 0, s->stream, n, KB, eri, dm, jp);
-        else     hipLaunchKernelGGL((k_j_sym<false>), dim3(ncb, n), dim3(256), 0, s->stream, n, KB, eri, dm, jp);
+        with_bool(vec, [&](auto V) { hipLaunchKernelGGL((k_j_sym<V>), dim3(ncb, n), dim3(256), 0, s->stream, n, KB, eri, dm, jp); });
         hipLaunchKernelGGL(k_sum_slabs8, dim3((unsigned)((N2 + 31) / 32)), dim3(256), 0, s->stream, N2, nslab, N2, jp, J);
         hip_ok(s, hipGetLastError(), "J launch");
         return;
@@ -510,15 +479,12 @@ void jk(XCSolver *s, int nao, const double *eri, const double *dm, double *J, do
     dim3 g(ncb, ni * jsplit);
     hipStream_t st = s->stream;
     const bool vec = (n % 2 == 0) && (((uintptr_t)eri & 15) == 0);
-#define QCDFT_JK(WJ, WK)                                                                                                  \
-    do {                                                                                                                  \
-        if (vec) hipLaunchKernelGGL((k_jk_stream<WJ, WK, true>), g, dim3(256), 0, st, n, KB, jsplit, i0, ni, eri, dm, jp, kp);    \
-        else     hipLaunchKernelGGL((k_jk_stream<WJ, WK, false>), g, dim3(256), 0, st, n, KB, jsplit, i0, ni, eri, dm, jp, kp);   \
-    } while (0)
-    if (J && K) QCDFT_JK(true, true);
-    else if (J) QCDFT_JK(true, false);
-    else        QCDFT_JK(false, true);
-#undef QCDFT_JK
+    const auto launch = [&](auto WJ, auto WK) {
+        with_bool(vec, [&](auto V) { hipLaunchKernelGGL((k_jk_stream<WJ, WK, V>), g, dim3(256), 0, st, n, KB, jsplit, i0, ni, eri, dm, jp, kp); });
+    };
+    if (J && K) launch(std::true_type{}, std::true_type{});
+    else if (J) launch(std::true_type{}, std::false_type{});
+    else        launch(std::false_type{}, std::true_type{});
     if (J) hipLaunchKernelGGL(k_sum_slabs8, dim3((unsigned)((N2 + 31) / 32)), dim3(256), 0, st, N2, nslabJ, N2, jp, J);
     if (K) {
         const size_t nk = (size_t)ni * n;
@@ -1138,11 +1104,8 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "strict_sync")) { s->strict_sync = value != 0.0; return 0; }
     if (!strcmp(key, "fuse_finish")) { s->fuse_finish = value != 0.0; return 0; }
     if (!strcmp(key, "sweep_order")) { s->sweep_order = (int)value & 3; return 0; }
-    if (!strcmp(key, "dbg")) { s->dbg = (int)value; return 0; }
     if (!strcmp(key, "occ")) { s->occ = value == 1.0 ? 1 : value == 2.0 ? 2 : 0; return 0; }
     if (!strcmp(key, "tiny")) { s->tiny = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
-    if (!strcmp(key, "ws_waves")) { s->ws_waves = value == 16.0 ? 16 : value == 8.0 ? 8 : 0; return 0; }
-    if (!strcmp(key, "rho_rows")) { s->rho_rows = value == 128.0 ? 128 : 64; return 0; }
     if (!strcmp(key, "ao_pt")) { s->ao_pt = value == 16.0 ? 16 : value == 8.0 ? 8 : 0; return 0; }
     if (!strcmp(key, "ksplit")) { s->ksplit = value > 0 ? (int)value : 0; return 0; }
     return -1;

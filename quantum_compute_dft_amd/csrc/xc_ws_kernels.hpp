@@ -53,7 +53,7 @@ template <int NT> struct WsCfg {
 
 // Sub-tile of workgroup `b` at its s-th step; `rev` walks the grid from its END (the Vxc kernel does:
 // it starts where the density kernel stopped, so the tail of the planes is still in the Infinity Cache:
-// -5 % on either kernel, tools/ws_order.py).
+// -5 % on either kernel, profiles/r02_sweep_experiments.txt item 5).
 __device__ __forceinline__ unsigned ws_tile(unsigned ntile, unsigned b, unsigned s, unsigned nwg, int rev)
 {
     const unsigned t = b + s * nwg;

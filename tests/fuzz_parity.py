@@ -32,8 +32,6 @@ while time.time() < t_end:
         if rng.random() < 0.3: w[rng.integers(0, ngrid, size=max(1, ngrid // 7))] = 0.0
         e_ref, v_ref = oracle.compute_xc(xc, dm, ao, w, gr if xc else None, quirks=bool(quirks))
         s = q.DFTSolverWrapper(q.library_path(), names[xc]); s.set_option("path", path); s.set_option("quirks", quirks)
-        if rng.random() < 0.5: s.set_option("rho_rows", 128)
-        if rng.random() < 0.3: s.set_option("ws_waves", 16)
         if nao <= 32 and rng.random() < 0.4: s.set_option("tiny", int(rng.choice([0, 1])))   # the one-pass kernel forced on / off (default: auto)
         s.set_option("sweep_order", int(rng.integers(0, 4)))
         d_v = torch.full((nao, nao), 3.0, dtype=torch.float64, device=dev)

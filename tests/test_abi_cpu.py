@@ -51,6 +51,9 @@ def test_wrapper_error_behaviour(libpath):
         q.DFTSolverWrapper(libpath, "MP2")
     w = q.DFTSolverWrapper(libpath, "b3lyp")  # case-insensitive like the reference
     assert w.functional_type == "B3LYP" and w.solver
+    for key in ("ws_waves", "rho_rows", "dbg"):   # retired options: unknown keys like any other
+        with pytest.raises(KeyError):
+            w.set_option(key, 0)
 
 
 def test_bad_solver_type_returns_null_and_null_solver_is_inert(libpath):

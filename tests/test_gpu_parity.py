@@ -103,14 +103,14 @@ def test_alternative_kernel_paths_match_oracle(dev, xc_type, path):
 
 
 @pytest.mark.parametrize("xc_type", [0, 1, 2])
-def test_sixteen_wave_kernels_match_oracle(dev, xc_type):
-    """Option ws_waves = 16: the 8 MFMA + 8 loader wave form of the nao <= 128 kernels (csrc/xc_ws16_kernels.hpp),
-    every tile count NT = 1..8, ragged grids, both walking orders."""
+def test_eight_wave_kernels_match_oracle(dev, xc_type):
+    """The 4 MFMA + 4 loader wave kernels of nao <= 128 (csrc/xc_ws_kernels.hpp; tiny = 0 so that bases of at most
+    32 functions reach them too): every tile count NT = 1..8, ragged grids, both walking orders."""
     for ngrid, nao in ((7, 3), (1025, 17), (3001, 36), (1531, 65), (2500, 114), (1300, 128), (999, 90)):
         dm, ao, gr, w = synth_inputs(ngrid, nao, seed=900 + ngrid + nao)
         exc_ref, v_ref = oracle.compute_xc(xc_type, dm, ao, w, gr)
         for order in (0, 3):
-            exc, v = _run(_solver(xc_type, ws_waves=16, sweep_order=order), dm, ao, gr if xc_type else None, w, dev)
+            exc, v = _run(_solver(xc_type, tiny=0, sweep_order=order), dm, ao, gr if xc_type else None, w, dev)
             _check(exc, v, exc_ref, v_ref)
 
 
@@ -127,13 +127,13 @@ def test_walking_order_of_the_contraction_kernels_does_not_change_results_beyond
     _check(got[0], got[1], exc_ref, v_ref)
 
 
-@pytest.mark.parametrize("opt,val", [("rho_rows", 128), ("rho_rows", 64), ("ksplit", 3)])
-def test_large_basis_kernel_options_match_oracle(dev, opt, val):
-    """nao > 128 takes the tiled kernels: both density tilings (64-row two-per-CU, 128-row) and a forced
-    chunk count of the Vxc split give the oracle's numbers."""
+@pytest.mark.parametrize("opts", [{}, {"ksplit": 3}], ids=["default", "ksplit-3"])
+def test_large_basis_kernel_options_match_oracle(dev, opts):
+    """nao > 128 takes the tiled kernels: the default options (chunk count of the Vxc split chosen by the plan) and a
+    forced chunk count give the oracle's numbers."""
     dm, ao, gr, w = synth_inputs(700, 150, seed=55)
     exc_ref, v_ref = oracle.compute_xc(2, dm, ao, w, gr)
-    exc, v = _run(_solver(2, **{opt: val}), dm, ao, gr, w, dev)
+    exc, v = _run(_solver(2, **opts), dm, ao, gr, w, dev)
     _check(exc, v, exc_ref, v_ref)
 
 
