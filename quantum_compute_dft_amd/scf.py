@@ -417,6 +417,8 @@ class HipBackend:
         want_tail = (self.occ_solver is not None and device_resident is not False and ao_mode == "resident"
                      and scf_tail.supported(nao, inp.nocc)) if fused_tail is None else bool(fused_tail)
         self.fused = bool(want_tail)
+        # one rank: the fused loop queues the next cycle's J / K and sweep behind this cycle's tail, before it waits (False: after)
+        self.prequeue = True
         if want_tail:
             if not scf_tail.supported(nao, inp.nocc) or ao_mode != "resident":
                 raise ValueError(f"fused_tail: resident AO planes, nao <= {scf_tail.MAX_NAO} and nocc <= {scf_tail.MAX_NOCC} are needed")
@@ -579,6 +581,7 @@ def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     _log_header(log)
     E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
     res = {"converged": False}
+    per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
     want_k = functional == "B3LYP"
     import os
     prof = [] if os.environ.get("QCDFT_SCF_PROFILE") else None      # per-part times of the host side of a cycle
@@ -622,6 +625,7 @@ def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
             log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
         res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1,
                    dm=dm_new, mo_energy=e)
+        per_cycle.append((E_tot, ddm))
         if abs(dE) < conv_e and ddm < conv_dm:                                         # dft.py:243; same scalars on every rank
             # The rotation solver follows the occupied space continuously; that it is still the AUFBAU one is checked
             # once, here, against eigh(F, S) of the converged Fock matrix (which also supplies the exact orbital
@@ -692,6 +696,7 @@ def _run_scf_device(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     _log_header(log)
     E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
     res = {"converged": False}
+    per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
     want_k = functional == "B3LYP"
     scal = t.zeros(4, dtype=f64, device=dev)
     import os
@@ -734,6 +739,7 @@ def _run_scf_device(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
         if log:
             log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
         res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1)
+        per_cycle.append((E_tot, ddm))
         if abs(dE) < conv_e and ddm < conv_dm:
             ok = t.ones(1, dtype=f64, device=dev)
             if rot[0]:                                                                 # as in _run_scf
@@ -805,24 +811,30 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     _log_header(log)
     E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
     res = {"converged": False}
+    per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
     rotate, last_ddm = True, None
     d_K = backend.d_K if want_k else None
-    d_exc = t.zeros(1, dtype=t.float64, device=backend.dev)
-    marks, tail_log = [], []                                                           # (start, J/K done, XC done) events; (status, fixed-point steps, Jacobi sweeps)
+    marks, tail_log = [], []      # (start, J/K done, XC done) events; (status, fixed-point steps, Jacobi sweeps, continued, queued ahead)
     sol = backend.solver
     pool = [t.cuda.Event(enable_timing=True) for _ in range(3 * 40)] if world == 1 else []   # made here: not in the cycles' time
     # One rank: the next cycle's J/K and sweep are queued BEHIND this cycle's tail before the host has seen its result -- they only
     # need dm / cocc, which the tail leaves in place -- so the GPU never waits for the host between cycles (30 us of a 0.65 ms
     # Benzene cycle).  Two sets of [J | K | Vxc] in turn: a cycle whose rotation is refused after all still owns intact matrices
     # for DFT_ScfTailFinish, and the parts queued ahead of it (from the density that was not replaced) are simply queued again.
+    # The same holds when the step needed more fixed-point steps than it queued (memory-resident rotation, status 3): the step
+    # leaves dm / cocc alone and DFT_ScfTailMore writes them after the parts queued ahead have read the old ones.  Each set has
+    # its own Exc scalar: a continuation reads its cycle's Exc after the sweep queued ahead has run.
+    ahead = world == 1 and backend.prequeue
     n2 = backend.nao * backend.nao
     sets = [(backend.d_J, backend.d_K, backend.d_v)]
+    d_excs = [t.zeros(1, dtype=t.float64, device=backend.dev) for _ in range(2)]
     if world == 1:
         spare = t.zeros_like(backend._down)
         sets.append(tuple(spare[k * n2:(k + 1) * n2].view(backend.nao, backend.nao) for k in range(3)))
 
     def enqueue_parts(k):
         backend.d_J, backend.d_K, backend.d_v = sets[k % 2]
+        d_exc = d_excs[k % 2]
         ev = pool[3 * len(marks):3 * len(marks) + 3] if 3 * len(marks) + 3 <= len(pool) else [t.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         backend._jk_device(want_k)
@@ -850,14 +862,14 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
             xc_times.append(t_xc); jk_times.append(time.time() - t_it - t_xc)
         if root:
             tol = 1e-10 if last_ddm is None else min(max(1e-10, 1e-3 * last_ddm), 1e-5)    # as OccupiedRotation.occupied(accuracy)
-            tail.step(rotate, c_hf, tol, d_J, d_K, d_V, backend.d_dm, backend.d_cocc, d_exc=d_exc if world == 1 else None)
-            if world == 1 and last_status == 0 and rotate:                             # the last rotation went through: expect this one to
+            tail.step(rotate, c_hf, tol, d_J, d_K, d_V, backend.d_dm, backend.d_cocc, d_exc=d_excs[cycle % 2] if world == 1 else None)
+            if ahead and last_status == 0 and rotate:                                  # the last rotation went through: expect this one to
                 enqueue_parts(cycle + 1); queued = cycle + 1
             E_one, E_coul, E_ex, ddm, status, steps, sweeps, exc_dev = tail.wait()
-            tail_log.append((status, steps, sweeps))
+            tail_log.append((status, steps, sweeps, tail.continued, queued > cycle))
             last_status = status
-            if status != 0 and queued > cycle:                                         # queued ahead from a density that stays: not this cycle's successor
-                queued = cycle; marks.pop()
+            if (status != 0 or tail.continued) and queued > cycle:                     # queued ahead from the density the step started from:
+                queued = cycle; marks.pop()                                            # not this cycle's successor
             if status == 2:                                                            # singular Pulay system: least squares on the host
                 tail.step(rotate, c_hf, tol, d_J, d_K, d_V, backend.d_dm, backend.d_cocc,
                           coef=tail.pulay_coefficients_on_host(), repeat=True)
@@ -884,6 +896,7 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
         if log:
             log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
         res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1)
+        per_cycle.append((E_tot, ddm))
         if abs(dE) < conv_e and ddm < conv_dm:                                         # the same scalars on every rank
             ok = t.ones(1, dtype=t.float64, device=backend.dev)
             if rotate:                                                                 # as in _run_scf: the followed space against eigh(F, S)

@@ -9,6 +9,7 @@ import numpy as np
 
 MAX_NAO, MAX_NOCC, SPACE = 512, 64, 8      # up to 128 x 32 the rotation's matrices live in LDS (k_tail_rot), above in memory (k_tail_rot_big)
 STATUS_DONE, STATUS_DIAGONALISE, STATUS_SINGULAR, STATUS_MORE = 0, 1, 2, 3
+STEPS_HINT, STEPS_HINT_CAP = 6, 16         # fixed-point steps queued per step on the memory-resident path: at open, and at most after a wait
 
 
 def supported(nao, nocc):
@@ -49,6 +50,9 @@ class ScfTail:
             raise RuntimeError(f"DFT_ScfTailOpen failed (nao {n} <= {MAX_NAO}, nocc {nocc} <= {MAX_NOCC} and a device are needed)")
         lib.DFT_ScfTailSetStream(self._h, torch.cuda.current_stream(device).cuda_stream)
         self._out = (ctypes.c_double * 8)()
+        self.hint_cap = STEPS_HINT_CAP     # wait() sets the next hint to min(max(steps + 2, 3), hint_cap)
+        self.max_inner = 60                # fixed-point steps a step may take (step()'s default)
+        self.continued = False             # the last wait() had to queue more steps (DFT_ScfTailMore)
         self.reset()
 
     def close(self):
@@ -62,11 +66,15 @@ class ScfTail:
         """Forget the DIIS history (the basis stays)."""
         self.hist = []
 
+    def set_steps_hint(self, nsteps):
+        """Fixed-point steps the next step queues on the memory-resident path (the library clamps it to [1, 60])."""
+        self._check(self.lib.DFT_ScfTailSetStepsHint(self._h, int(nsteps)))
+
     def _check(self, rc):
         if rc != 0:
             raise RuntimeError("libdft: " + (self.lib.DFT_ScfTailLastError(self._h) or b"").decode())
 
-    def step(self, rotate, c_hf, tol, d_J, d_K, d_vraw, d_dm, d_cocc, coef=None, canon_tol=0.0, max_inner=60, repeat=False, d_exc=None):
+    def step(self, rotate, c_hf, tol, d_J, d_K, d_vraw, d_dm, d_cocc, coef=None, canon_tol=0.0, max_inner=None, repeat=False, d_exc=None):
         """Queue one cycle's end.  `repeat`: the same cycle again (after status 2), into the same ring slot.  `d_exc`: the
         device scalar of a DFT_ComputeXC*Async call queued before; wait() then returns Exc too."""
         if not repeat:
@@ -75,6 +83,7 @@ class ScfTail:
         slot = self.hist[-1]
         hist = (ctypes.c_int * len(self.hist))(*self.hist)
         cf = None if coef is None else (ctypes.c_double * len(self.hist))(*[float(x) for x in coef])
+        max_inner = self.max_inner if max_inner is None else max_inner
         self._last = (d_J, d_K, d_dm, d_cocc, d_exc)       # DFT_ScfTailMore continues this step (memory-resident rotation, status 3)
         self._check(self.lib.DFT_ScfTailStep(self._h, int(bool(rotate)), float(c_hf), float(tol), float(canon_tol), int(max_inner), slot,
                                              len(self.hist), hist, cf, d_J.data_ptr(), 0 if d_K is None else d_K.data_ptr(),
@@ -90,6 +99,7 @@ class ScfTail:
         self._check(self.lib.DFT_ScfTailWait(self._h, self._out))
         o = self._out
         more = 8
+        self.continued = int(o[4]) == STATUS_MORE          # the step's dm / cocc are written by the continuation, not by the step
         while int(o[4]) == STATUS_MORE:                    # above 128 functions the fixed point's steps are launches of their own,
             d_J, d_K, d_dm, d_cocc, d_exc = self._last     # queued in advance: this many were not enough -- queue more, wait again
             self._check(self.lib.DFT_ScfTailMore(self._h, more, d_J.data_ptr(), 0 if d_K is None else d_K.data_ptr(), d_dm.data_ptr(),
@@ -97,7 +107,7 @@ class ScfTail:
             self._check(self.lib.DFT_ScfTailWait(self._h, self._out))
             more = min(2 * more, 32)
         if int(o[4]) == STATUS_DONE and int(o[5]) > 0:     # next time: two more than this cycle needed
-            self.lib.DFT_ScfTailSetStepsHint(self._h, min(max(int(o[5]) + 2, 3), 16))
+            self.lib.DFT_ScfTailSetStepsHint(self._h, min(max(int(o[5]) + 2, 3), self.hint_cap))
         return o[0], o[1], o[2], o[3], int(o[4]), int(o[5]), int(o[6]), o[7]
 
     def gram(self):
