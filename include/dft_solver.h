@@ -34,7 +34,12 @@ extern "C" {
 typedef struct XCSolver XCSolver;
 
 /* src/dft_solver.h:67-71 */
-enum SolverType { SOLVER_LDA = 0, SOLVER_GGA = 1, SOLVER_B3LYP = 2 };
+enum SolverType { SOLVER_LDA = 0, SOLVER_GGA = 1, SOLVER_B3LYP = 2,
+                  SOLVER_MIX = 3 /* extension: a weighted sum of components, DFT_CreateSolverMix only */ };
+
+/* The pointwise components a mix solver can combine (extension), in the order of its weight vector. */
+enum XCComponent { XC_SLATER_X = 0, XC_VWN5_C, XC_VWN_RPA_C, XC_PW92_C,
+                   XC_PBE_X, XC_PBE_C, XC_B88_X, XC_LYP_C, XC_NCOMP };
 
 /* ---- reference ABI ------------------------------------------------------ */
 
@@ -69,6 +74,27 @@ void DFT_ComputeCoulomb(XCSolver *solver, int nao,
 
 /* ABI version of this library (bumped when an extension changes). */
 int DFT_GetVersion(void);
+
+/* A solver for a MIXED functional: eps = sum_k weights[k] eps_k over the XC_NCOMP components above (type SOLVER_MIX;
+ * DFT_CreateSolver(SOLVER_MIX) stays NULL, it has no weights).  NULL unless ncomp == XC_NCOMP, every weight is finite
+ * and at least one is non-zero; negative weights are allowed.  The weights are fixed for the solver's life (recorded
+ * HIP graphs hold them): there is no setter.  Per grid point with rho >= 1e-12 (below: no contribution, as in the
+ * three built-in bodies):
+ *     e = sum c_k e_k    vrho = sum c_k vrho_k    vsigma = sum c_k vsigma_k
+ *     B88 in its closed-shell form, as the B3LYP body takes it: b88(rho/2, sigma/4), vsigma halved
+ *     Exc += w rho e     B[g,:] = w vrho phi + 4 w vsigma (grad rho . grad phi)     V = B^T phi
+ * i.e. the GGA convention of DFT_ComputeXC whatever the components: factor 4, a ONE-SIDED matrix, no symmetrisation
+ * in the library -- the caller takes (V + V^T)/2, as the driver and DFT_ScfTailStep do for every type.  With B3LYP's
+ * coefficients that average equals SOLVER_B3LYP's output (which halves vrho, uses factor 2 and adds M + M^T).
+ * Option "quirks" keeps its meaning for XC_VWN5_C and XC_PBE_C.  With weights XC_PBE_X..XC_LYP_C all zero the solver
+ * is an LDA-class one (one-plane kernels, d_ao_grad_ptr may be 0); otherwise a null ao_grad is the error it is for
+ * SOLVER_GGA.  A component with weight 0 is not evaluated.  Every entry that takes an XCSolver* accepts a mix solver. */
+XCSolver *DFT_CreateSolverMix(const double *weights, int ncomp);
+
+/* The weights of a mix solver, or the equivalent of a built-in type under the convention above (LDA: slater 1,
+ * vwn5 1; GGA: pbe_x 1, pbe_c 1; B3LYP: slater 0.80, b88 0.72, vwn_rpa 0.19, lyp 0.81).  0, or -1 for a null handle
+ * or ncomp != XC_NCOMP. */
+int DFT_GetMix(XCSolver *solver, double *weights_out, int ncomp);
 
 /* Same as DFT_ComputeXC with a 64-bit grid count (the reference's `int`
  * products overflow once ngrid*nao >= 2^30, src/dft_solver.cu:597,634). */
@@ -289,7 +315,9 @@ void DFT_ScfTailClose(void *handle);
  * whole sweep -- density, functional, Vxc contraction of a 16-point sub-tile -- in ONE kernel plus the slab sum where that is
  * the faster call, which it is at every size measured (0.71-1.00 of the four launches, 20 k-300 k points: profiles/r03_tiny_scan_final.txt);
  * 1 = whenever nao <= 32; 0 = never.  Results agree with the four-launch path to the
- * rounding of the sums, not bit for bit), "ao_pt" (grid points per workgroup of DFT_EvalAO:
+ * rounding of the sums, not bit for bit.  A SOLVER_MIX solver never takes it, whatever the option says: the one-pass
+ * kernel is register-critical and instantiated for the three built-in bodies only, so a mix runs the general kernels at
+ * every nao), "ao_pt" (grid points per workgroup of DFT_EvalAO:
  * 8, 16, or 0 = auto).  Returns 0 if the key is known. */
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
 

@@ -58,6 +58,8 @@ struct SweepGraph {
 
 struct XCSolver {
     int type = 0;
+    bool needs_grad = false;     // the functional reads grad rho: four planes, ao_grad required (every type but LDA and LDA-class mixes)
+    xc::MixWeights mix = {};     // SOLVER_MIX: the eight coefficients, fixed at creation (recorded graphs hold them)
     hipStream_t stream = nullptr;
     bool device_ok = false;
     int device = 0; // the device that was current at DFT_CreateSolver: every entry point runs there
@@ -230,7 +232,7 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
         set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao);
         return false;
     }
-    const bool gga = s->type != SOLVER_LDA;
+    const bool gga = s->needs_grad;
     if (gga && !ao_grad) {
         set_error(s, "ao_grad pointer is null for a gradient-corrected functional");
         return false;
@@ -247,7 +249,7 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     // full matrix; taken when it does clearly fewer (the two kernels run at similar matrix-pipe efficiency), on the
     // production path only.
     // Small bases: the whole sweep in one kernel (planes below 4 GiB: one buffer descriptor each)
-    const bool tiny = s->path == 0 && s->tiny != 0 && nao <= TINY_MAX_NAO && (double)ngrid * nao * 8.0 < 4294967296.0 &&
+    const bool tiny = s->path == 0 && s->tiny != 0 && s->type != SOLVER_MIX && nao <= TINY_MAX_NAO && (double)ngrid * nao * 8.0 < 4294967296.0 &&
                       (s->tiny > 0 || tiny_pays(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid));
     OccPlan oplan;
     bool use_occ = false;
@@ -366,7 +368,9 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
         dim3 g((unsigned)nxb);
         if (s->type == SOLVER_LDA)      hipLaunchKernelGGL(k_xc_points<0>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
         else if (s->type == SOLVER_GGA) hipLaunchKernelGGL(k_xc_points<1>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
-        else                            hipLaunchKernelGGL(k_xc_points<2>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
+        else if (s->type == SOLVER_B3LYP) hipLaunchKernelGGL(k_xc_points<2>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
+        else if (gga)                   hipLaunchKernelGGL(k_xc_points_mix<true>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
+        else                            hipLaunchKernelGGL(k_xc_points_mix<false>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
     }
     if (!tiny) {
         ScopedTimer t(s, "vxc");
@@ -387,6 +391,10 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
         switch (s->type) { // (G, S)
         case SOLVER_LDA: launch(std::false_type{}, std::false_type{}); break;
         case SOLVER_GGA: launch(std::true_type{}, std::false_type{}); break;
+        case SOLVER_MIX: // GGA convention: one-sided, never symmetrised here; an LDA-class mix takes the one-plane kernels
+            if (gga) launch(std::true_type{}, std::false_type{});
+            else     launch(std::false_type{}, std::false_type{});
+            break;
         default:         launch(std::true_type{}, std::true_type{}); break;
         }
     }
@@ -733,14 +741,21 @@ __global__ void k_accumulate_chunk(long n2, int add, const double *__restrict__ 
 
 extern "C" {
 
-int DFT_GetVersion(void) { return 3; }
+int DFT_GetVersion(void) { return 4; }   // 4: DFT_CreateSolverMix / DFT_GetMix
 
-XCSolver *DFT_CreateSolver(int type)
+static XCSolver *create_solver(int type, const double *mix)
 {
-    if (type != SOLVER_LDA && type != SOLVER_GGA && type != SOLVER_B3LYP) return nullptr;
     XCSolver *s = new (std::nothrow) XCSolver();
     if (!s) return nullptr;
     s->type = type;
+    s->needs_grad = type != SOLVER_LDA;
+    if (mix) {
+        s->needs_grad = false;
+        for (int k = 0; k < XC_NCOMP; ++k) {
+            s->mix.c[k] = mix[k];
+            if (k >= XC_PBE_X && mix[k] != 0.0) s->needs_grad = true;
+        }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
         int dev = 0;
@@ -763,6 +778,40 @@ XCSolver *DFT_CreateSolver(int type)
         s->last_error = "no usable HIP device";
     }
     return s;
+}
+
+XCSolver *DFT_CreateSolver(int type)
+{
+    if (type != SOLVER_LDA && type != SOLVER_GGA && type != SOLVER_B3LYP) return nullptr;   // SOLVER_MIX needs weights
+    return create_solver(type, nullptr);
+}
+
+XCSolver *DFT_CreateSolverMix(const double *weights, int ncomp)
+{
+    if (!weights || ncomp != XC_NCOMP) return nullptr;
+    bool any = false;
+    for (int k = 0; k < XC_NCOMP; ++k) {
+        if (!std::isfinite(weights[k])) return nullptr;
+        any = any || weights[k] != 0.0;
+    }
+    if (!any) return nullptr;
+    return create_solver(SOLVER_MIX, weights);
+}
+
+int DFT_GetMix(XCSolver *s, double *weights_out, int ncomp)
+{
+    if (!s || !weights_out || ncomp != XC_NCOMP) return -1;
+    for (int k = 0; k < XC_NCOMP; ++k) weights_out[k] = 0.0;
+    switch (s->type) {
+    case SOLVER_LDA: weights_out[XC_SLATER_X] = 1.0; weights_out[XC_VWN5_C] = 1.0; break;
+    case SOLVER_GGA: weights_out[XC_PBE_X] = 1.0; weights_out[XC_PBE_C] = 1.0; break;
+    case SOLVER_B3LYP:   // the mixing of xc::b3lyp_point
+        weights_out[XC_SLATER_X] = 0.80; weights_out[XC_B88_X] = 0.72; weights_out[XC_VWN_RPA_C] = 0.19; weights_out[XC_LYP_C] = 0.81;
+        break;
+    default:
+        for (int k = 0; k < XC_NCOMP; ++k) weights_out[k] = s->mix.c[k];
+    }
+    return 0;
 }
 
 void DFT_DestroySolver(XCSolver *s)
@@ -1062,7 +1111,7 @@ int DFT_ComputeXCDirect(XCSolver *s, long long ngrid, int nao, int nshell, const
     if (ngrid <= 0 || nao <= 0 || !d_coords || !d_w || !d_dm || !d_vxc) { set_error(s, "bad arguments to DFT_ComputeXCDirect"); return -1; }
     AoTable tab;
     if (!prepare_ao_table(s, nao, nshell, shl_xyz, shl_l, shl_nprim, shl_off, shl_ao, prim_exp, prim_coef, nprim_total, tab)) return -1;
-    const bool gga = s->type != SOLVER_LDA;
+    const bool gga = s->needs_grad;
     const int nplane = gga ? 4 : 1;
     // chunk: its planes stay within ~96 MB (they are written by the AO kernel and read twice right after: an
     // Infinity-Cache-sized working set), but never fewer than 64 sixteen-point tiles per CU; a multiple of 256

@@ -112,11 +112,11 @@ __device__ __forceinline__ Gga pbe_x(double rho, double sigma)
 }
 
 // PBE correlation, src/dft_solver.cu:244-283.
-__device__ __forceinline__ Gga pbe_c(double rho, double sigma, bool quirks)
+// `l` = pw92_c(rho), so that a caller which needs PW92 on its own as well evaluates it once.
+__device__ __forceinline__ Gga pbe_c_with(const Lda l, double rho, double sigma, bool quirks)
 {
     if (rho < kRhoCut) return {0.0, 0.0, 0.0};
     constexpr double beta = 0.066725, gamma = 0.03109069086965489503;
-    const Lda l = pw92_c(rho);
     const double kF = cbrt(3.0 * kPi * kPi * rho);
     const double den16 = 16.0 * kF * rho * rho;
     double t2 = 0.0;
@@ -145,6 +145,12 @@ __device__ __forceinline__ Gga pbe_c(double rho, double sigma, bool quirks)
     o.vs = rho * dH_dt2 * dt2_ds;
     o.vr = l.v + H + rho * (dH_dA * dA_drho + dH_dt2 * dt2_drho);
     return o;
+}
+
+__device__ __forceinline__ Gga pbe_c(double rho, double sigma, bool quirks)
+{
+    if (rho < kRhoCut) return {0.0, 0.0, 0.0};
+    return pbe_c_with(pw92_c(rho), rho, sigma, quirks);
 }
 
 // Becke-88 gradient correction, per-spin arguments, src/dft_solver.cu:78-104.
@@ -238,6 +244,38 @@ __device__ __forceinline__ PointXC b3lyp_point(double rho, double sigma, double 
     const double vr = 0.5 * (cL * xl.v + cB * xb.vr + cV * cv.v + cY * cy.vr);
     const double f = w * 2.0 * (cB * xb.vs + cY * cy.vs);
     return {rho * eps, w * vr, f * gx, f * gy, f * gz};
+}
+
+// A weighted sum of the eight components above (solver type SOLVER_MIX; order = enum XCComponent of
+// include/dft_solver.h).  GGA convention whatever the components: vrho whole, factor 4 on vsigma, a one-sided
+// matrix that the caller averages with its transpose -- so (V + V^T)/2 with B3LYP's four coefficients is what
+// b3lyp_point's halved vrho, factor 2 and M + M^T give.  B88 enters in its closed-shell form, as in b3lyp_point.
+// The weights are kernel arguments, the same for every lane: a zero weight is a scalar branch around the whole
+// component (PBE0 pays for no exp of LYP, no atan / log of VWN).  GGA = false: components 4..7 are not looked at.
+struct MixWeights { double c[8]; };
+
+template <bool GGA>
+__device__ __forceinline__ PointXC mix_point(const MixWeights &m, double rho, double sigma, double gx, double gy,
+                                             double gz, double w, bool quirks)
+{
+    if (rho < kRhoCut) return {0.0, 0.0, 0.0, 0.0, 0.0};
+    double e = 0.0, vr = 0.0, vs = 0.0;
+    if (m.c[0] != 0.0) { const Lda x = slater_x(rho);       e += m.c[0] * x.e; vr += m.c[0] * x.v; }
+    if (m.c[1] != 0.0) { const Lda x = vwn5_c(rho, quirks); e += m.c[1] * x.e; vr += m.c[1] * x.v; }
+    if (m.c[2] != 0.0) { const Lda x = vwn_rpa_c(rho);      e += m.c[2] * x.e; vr += m.c[2] * x.v; }
+    const bool with_pbe_c = GGA && m.c[5] != 0.0;
+    if (m.c[3] != 0.0 || with_pbe_c) {
+        const Lda l = pw92_c(rho);                          // once for PW92 itself and inside PBE correlation
+        if (m.c[3] != 0.0) { e += m.c[3] * l.e; vr += m.c[3] * l.v; }
+        if (with_pbe_c) { const Gga x = pbe_c_with(l, rho, sigma, quirks); e += m.c[5] * x.e; vr += m.c[5] * x.vr; vs += m.c[5] * x.vs; }
+    }
+    if (GGA) {
+        if (m.c[4] != 0.0) { const Gga x = pbe_x(rho, sigma); e += m.c[4] * x.e; vr += m.c[4] * x.vr; vs += m.c[4] * x.vs; }
+        if (m.c[6] != 0.0) { const Gga x = b88_x(0.5 * rho, 0.25 * sigma); e += m.c[6] * x.e; vr += m.c[6] * x.vr; vs += m.c[6] * (0.5 * x.vs); }
+        if (m.c[7] != 0.0) { const Gga x = lyp_c(rho, sigma); e += m.c[7] * x.e; vr += m.c[7] * x.vr; vs += m.c[7] * x.vs; }
+    }
+    const double f = w * 4.0 * vs;
+    return {rho * e, w * vr, f * gx, f * gy, f * gz};
 }
 
 } // namespace xc

@@ -236,6 +236,43 @@ __global__ __launch_bounds__(256) void k_xc_points(long ngrid, const double *__r
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// SOLVER_MIX: the same kernel around xc::mix_point.  The weights travel by value in the kernel arguments (fixed for
+// the solver's life, so a recorded graph holds them too).  GGA = false: an LDA-class mix, one coefficient plane, no
+// sigma / grad read.
+template <bool GGA>
+__global__ __launch_bounds__(256) void k_xc_points_mix(long ngrid, const double *__restrict__ rho,
+                                                       const double *__restrict__ sigma,
+                                                       const double *__restrict__ grad,
+                                                       const double *__restrict__ w,
+                                                       double *__restrict__ coef,
+                                                       double *__restrict__ partial, int quirks, xc::MixWeights m)
+{
+    __shared__ double red[4];
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    double e = 0.0;
+    if (g < ngrid) {
+        const double wt = w[g], r = rho[g];
+        xc::PointXC p;
+        if (GGA) {
+            const double ax = grad[3 * g], ay = grad[3 * g + 1], az = grad[3 * g + 2];
+            p = xc::mix_point<true>(m, r, sigma[g], ax, ay, az, wt, quirks != 0);
+        } else {
+            p = xc::mix_point<false>(m, r, 0.0, 0.0, 0.0, 0.0, wt, quirks != 0);
+        }
+        coef[g] = p.c0;
+        if (GGA) {
+            coef[(size_t)ngrid + g] = p.c1;
+            coef[2 * (size_t)ngrid + g] = p.c2;
+            coef[3 * (size_t)ngrid + g] = p.c3;
+        }
+        e = wt * p.exc;
+    }
+    for (int m_ = 32; m_ >= 1; m_ >>= 1) e += __shfl_down(e, m_, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // ---------------------------------------------------------------- Vxc ------
 // blockIdx.x = grid chunk, .y/.z = 128-wide blocks of the a / b index.
 // Per 32 grid points: Q[g][a] = sum_c coef_c[g] * plane_c[g][a] and P[g][b] = AO[g][b]

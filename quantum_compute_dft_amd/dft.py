@@ -1,5 +1,6 @@
 """`python -m quantum_compute_dft_amd.dft <LDA|GGA|B3LYP> <Molecule>` -- the reference's driver
-surface (dft.py:101-297: same positionals, same printed lines) on the MI355X engine.
+surface (dft.py:101-297: same positionals, same printed lines) on the MI355X engine.  The functional may also be any
+other name of functionals.TABLE (PBE0, BLYP, ...) or an expression such as "0.75*pbe_x + pbe_c + 0.25*hf".
 Extra flags (defaults = what the reference hard-codes): --basis sto-3g, --grid-level 3, --quirks 1."""
 import argparse
 import importlib.util
@@ -7,12 +8,23 @@ import os
 import sys
 import time
 
-from . import inputs, scf
+from . import functionals, inputs, scf
+
+
+def _functional(spec):
+    try:
+        functionals.resolve(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    return spec.strip().upper() if spec.strip().upper() in functionals.TABLE else spec.strip()
 
 
 def main(argv=None):
     p = argparse.ArgumentParser(description="Run DFT (LDA/GGA/B3LYP) using the MI355X HIP backend.")
-    p.add_argument("functional", type=str, choices=["LDA", "GGA", "B3LYP"], help="Functional type")
+    p.add_argument("functional", type=_functional,
+                   help="Functional: LDA, GGA, B3LYP (the reference's three), another name of the table (" +
+                        ", ".join(k for k, f in functionals.TABLE.items() if f.builtin_type is None) +
+                        ") or an expression over " + ", ".join(functionals.COMPONENTS) + " and hf")
     p.add_argument("xyzfile", type=str, help="Molecule name (e.g., H2O)")
     p.add_argument("--basis", default="sto-3g")            # grid.py:45 hard-codes sto-3g
     p.add_argument("--basis-file", default=None, help="NWChem / Gaussian94 basis file (Basis Set Exchange export) to register "
@@ -44,6 +56,7 @@ def main(argv=None):
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
     args = p.parse_args(argv)
+    fn = functionals.resolve(args.functional)
 
     # one process per GPU: `python -m torch.distributed.run --nproc-per-node N -m quantum_compute_dft_amd.dft ...`
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -80,7 +93,7 @@ def main(argv=None):
         args.eri = "dense" if 8.0 * _nao ** 4 <= 8.0e9 else "cholesky"
     inp = inputs.build(atom_path, args.basis, args.grid_level, device=device, eri_mode=args.eri, chol_tol=args.chol_tol, rank=rank, world=world)
     print(f"System Info: NAO={inp.shells.nao}, Grid={inp.grids.size}, Occupied={inp.nocc}")
-    print(f"Calculating AO Gradients ({args.functional} mode)..." if args.functional != "LDA" else "Skipping AO Gradients (LDA mode).")
+    print(f"Calculating AO Gradients ({args.functional} mode)..." if fn.needs_gradient else f"Skipping AO Gradients ({args.functional} mode).")
     print("Moving data to GPU...")
     try:
         backend = scf.HipBackend(inp, args.functional, args.lib, quirks=bool(args.quirks), rank=rank, world=world, device=device,
@@ -94,7 +107,7 @@ def main(argv=None):
     res = scf.run_scf(inp, backend, args.functional)
     eig_stats = dict(backend.occ_solver.stats) if backend.occ_solver is not None else None   # of THIS run (the second one below adds to the counters)
     other = None
-    if args.both_quirks and args.functional != "B3LYP":   # B3LYP's four components are derivative-correct: one answer
+    if args.both_quirks and fn.uses_quirks:   # only VWN5 and PBE-c have two forms (B3LYP's four components are derivative-correct: one answer)
         backend.solver.set_option("quirks", 0 if args.quirks else 1)
         if backend.occ_solver is not None:
             backend.occ_solver.reset()            # fresh full solve: the second SCF does not start from the first one's rotation
@@ -105,7 +118,7 @@ def main(argv=None):
         print(f"Total Energy: {res['E_tot']:.8f} Ha"); print(f"E_one       : {res['E_one']:.8f} Ha")
         print(f"E_coul      : {res['E_coul']:.8f} Ha"); print(f"E_nuc       : {inp.E_nuc:.8f} Ha")
         print(f"E_xc_dft    : {res['E_xc']:.8f} Ha")
-        if args.functional == "B3LYP":
+        if fn.c_hf != 0.0:
             print(f"E_ex_hf     : {res['E_ex_hf']:.8f} Ha")
         print(f"Total Time  : {res['total_time']:.4f} s"); print("-" * 80)
         print("Kernel Statistics (Avg per iter):"); print(f"XC(Exc+Vxc) Time: {res['xc_ms_avg']:.4f} ms")
@@ -129,6 +142,7 @@ def main(argv=None):
     import json
     record = {"functional": args.functional, "molecule": os.path.splitext(atom_file)[0], "basis": args.basis, "grid_level": args.grid_level,
               "nao": int(inp.shells.nao), "ngrid": int(inp.grids.size), "nocc": int(inp.nocc), "n_gpus": world, "eri": args.eri,
+              "c_hf": fn.c_hf, "weights": fn.weights,
               "quirks": int(args.quirks), "converged": bool(res["converged"]), "cycles": int(res.get("cycles", 0)),
               "E_tot": res.get("E_tot"), "E_one": res.get("E_one"), "E_coul": res.get("E_coul"), "E_xc": res.get("E_xc"),
               "E_ex_hf": res.get("E_ex_hf"), "E_nuc": float(inp.E_nuc), "total_time_s": res.get("total_time"),
@@ -147,14 +161,15 @@ def main(argv=None):
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
-    if importlib.util.find_spec("pyscf") is None or rank:   # dft.py:272-297 needs PySCF
+    pyscf_xc = {"LDA": "slater,vwn5", "GGA": "PBE,PBE", "B3LYP": "b3lyp"}.get(args.functional)
+    if importlib.util.find_spec("pyscf") is None or rank or pyscf_xc is None:   # dft.py:272-297 needs PySCF; the three reference functionals only
         print("\nPySCF not importable here: reference cross-check skipped.")
         return res
     print("\nRunning PySCF reference calculation...")
     from pyscf import dft as pdft, gto
     mol = gto.Mole(); mol.atom = "".join(open(atom_path).readlines()[2:]); mol.basis = args.basis; mol.verbose = 0; mol.build()
     mf = pdft.RKS(mol); mf.grids.level = args.grid_level
-    mf.xc = {"LDA": "slater,vwn5", "GGA": "PBE,PBE", "B3LYP": "b3lyp"}[args.functional]
+    mf.xc = pyscf_xc
     t0 = time.time(); mf.kernel(); el = time.time() - t0
     print(f"PySCF ({mf.xc}) Energy : {mf.e_tot:.8f} Hartree")
     print(f"Difference             : {abs(mf.e_tot - res['E_tot']):.2e} Hartree")

@@ -26,6 +26,8 @@ import time
 import numpy as np
 from scipy.linalg import eigh
 
+from . import functionals
+
 
 class CDIIS:
     """Pulay DIIS on the commutator SDF - FDS (PySCF scf.diis.CDIIS as used at dft.py:184,225).
@@ -327,7 +329,7 @@ class HipBackend:
         if self.dev.index is not None:
             torch.cuda.set_device(self.dev)
         self.functional = functional.upper()
-        self.solver = DFTSolverWrapper(lib_path or library_path(), self.functional)
+        self.solver = DFTSolverWrapper(lib_path or library_path(), functional)   # any name or expression of functionals.resolve()
         self.solver.set_option("quirks", 1 if quirks else 0)
         t0 = time.time()
         self.rank, self.world = rank, world
@@ -353,7 +355,7 @@ class HipBackend:
         self.d_ao = self.d_gr = None
         if ao_mode == "resident":
             self.d_ao = torch.zeros((n1, nao), dtype=f64, device=self.dev)
-            self.d_gr = torch.zeros((3, n1, nao), dtype=f64, device=self.dev) if self.functional != "LDA" else None
+            self.d_gr = torch.zeros((3, n1, nao), dtype=f64, device=self.dev) if self.solver.needs_gradient else None
             if ngrid:
                 self.solver.eval_ao(inp.shells, d_coords, ngrid, self.d_ao, self.d_gr)  # grid.py:30,38 on the device
         else:
@@ -370,7 +372,7 @@ class HipBackend:
             # pass streams its upper triangle alone -- half the bytes of dft_solver.cu:550-555's GEMV, which is all a J build costs
             # ... and when it is symmetric in each index pair too, (ij|kl) = (ji|kl) = (ij|lk), the unique eighth alone (k_j_sym8;
             # the loop's dm = cocc cocc^T is symmetric bit for bit)
-            if world == 1 and self.functional != "B3LYP" and self.d_eri is not None and bool(torch.equal(self.d_eri, self.d_eri.T)):
+            if world == 1 and self.solver.c_hf == 0.0 and self.d_eri is not None and bool(torch.equal(self.d_eri, self.d_eri.T)):
                 e4 = self.d_eri.view(nao, nao, nao * nao)
                 eightfold = bool(torch.equal(e4, e4.transpose(0, 1)))
                 self.solver.set_option("eri_symmetric", 2 if eightfold else 1)
@@ -553,8 +555,7 @@ def _finish(res, t_start, xc_times, jk_times, it_times):
 def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     """Host form of the loop body (dft.py:199-266).  `backend` supplies either fock_parts(want_k) (HipBackend)
     or the reference-shaped pair jk(want_k) / xc() (the oracle backend of the tests)."""
-    functional = functional.upper()
-    c_hf = 0.2 if functional == "B3LYP" else 0.0                                       # dft.py:197
+    c_hf = functionals.resolve(functional).c_hf                                        # dft.py:197 (0.2 for B3LYP, else 0) for any functional
     Hcore, S, nocc = inp.Hcore, inp.S, inp.nocc
     root = getattr(backend, "rank", 0) == 0
     sync = getattr(backend, "replica_sync", None)
@@ -582,7 +583,7 @@ def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
     res = {"converged": False}
     per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
-    want_k = functional == "B3LYP"
+    want_k = c_hf != 0.0
     import os
     prof = [] if os.environ.get("QCDFT_SCF_PROFILE") else None      # per-part times of the host side of a cycle
     for cycle in range(max_cycle):
@@ -661,8 +662,7 @@ def _run_scf_device(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     """Device-resident form of the same loop: nothing but scalars crosses PCIe per cycle."""
     t = backend.torch
     dev, f64 = backend.dev, backend.torch.float64
-    functional = functional.upper()
-    c_hf = 0.2 if functional == "B3LYP" else 0.0
+    c_hf = functionals.resolve(functional).c_hf
     nocc = inp.nocc
     root, sync = backend.rank == 0, backend.replica_sync
     H = t.as_tensor(inp.Hcore, dtype=f64, device=dev)
@@ -697,7 +697,7 @@ def _run_scf_device(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
     res = {"converged": False}
     per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
-    want_k = functional == "B3LYP"
+    want_k = c_hf != 0.0
     scal = t.zeros(4, dtype=f64, device=dev)
     import os
     prof = [] if os.environ.get("QCDFT_SCF_PROFILE") else None      # per-part times of the host-side-of-the-cycle (adds syncs)
@@ -779,9 +779,8 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     t = backend.torch
     tail, rot_stats = backend.tail, backend.occ_solver.stats
     root, sync, world = backend.rank == 0, backend.replica_sync, backend.world
-    functional = functional.upper()
-    c_hf = 0.2 if functional == "B3LYP" else 0.0
-    want_k = functional == "B3LYP"
+    c_hf = functionals.resolve(functional).c_hf
+    want_k = c_hf != 0.0
     nocc, Xh = inp.nocc, backend.eigh.Xh
     sqrt2 = float(np.sqrt(2.0))
     on_dev = inp.S.shape[0] >= 400          # hipSOLVER from 400 functions, one LAPACK thread below (FockDiagonaliser)

@@ -9,11 +9,15 @@ torch tensors (`.data_ptr()`), CuPy arrays (`.data.ptr`, what the reference
 passes) or plain integer device addresses.
 
 Extensions beyond the reference class: compute_exchange / compute_jk /
-eval_ao / set_option / timings, all thin calls into the extra C symbols.
+eval_ao / set_option / timings, all thin calls into the extra C symbols; and the
+functional may be any name or expression functionals.resolve() knows ("PBE0",
+"0.75*pbe_x + pbe_c + 0.25*hf"): the three reference names keep their built-in
+solver types, everything else becomes a mix solver (DFT_CreateSolverMix).
 """
 import ctypes
 import os
 
+from . import functionals
 from .build import LIB_PATH
 
 _u64 = ctypes.c_uint64
@@ -60,7 +64,12 @@ class DFTSolverWrapper:
         if not os.path.exists(lib_path):
             raise FileNotFoundError(f"Shared library not found at: {lib_path}")
         self.lib = load_library(lib_path)
-        self.functional_type = functional_type.upper()
+        self.functional_type = functional_type.upper() if isinstance(functional_type, str) else functional_type.name
+        # ValueError for an unknown name (dft.py:66-67), before anything is created
+        self.functional = functionals.resolve(functional_type)
+        self.c_hf = self.functional.c_hf                       # exact-exchange fraction the SCF loop applies
+        self.needs_gradient = self.functional.needs_gradient   # ao_grad is required
+        self.weights = self.functional.weight_vector()         # the eight coefficients, functionals.COMPONENTS order
         L = self.lib
         # --- the four reference symbols, declared exactly as dft.py:27-50 does
         L.DFT_CreateSolver.argtypes = [ctypes.c_int]
@@ -111,17 +120,15 @@ class DFTSolverWrapper:
         L.DFT_GetTimings.restype = ctypes.c_int
         L.DFT_GetVersion.argtypes = []
         L.DFT_GetVersion.restype = ctypes.c_int
+        L.DFT_CreateSolverMix.argtypes = [dp, ctypes.c_int]
+        L.DFT_CreateSolverMix.restype = ctypes.c_void_p
+        L.DFT_GetMix.argtypes = [ctypes.c_void_p, dp, ctypes.c_int]
+        L.DFT_GetMix.restype = ctypes.c_int
 
-        if self.functional_type == "LDA":
-            c_type = self.TYPE_LDA
-        elif self.functional_type == "GGA":
-            c_type = self.TYPE_GGA
-        elif self.functional_type == "B3LYP":
-            c_type = self.TYPE_B3LYP
+        if self.functional.builtin_type is not None:
+            self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
         else:
-            raise ValueError(f"Unsupported functional type: {self.functional_type}")
-
-        self.solver = L.DFT_CreateSolver(c_type)
+            self.solver = L.DFT_CreateSolverMix((ctypes.c_double * len(self.weights))(*self.weights), len(self.weights))
         if not self.solver:
             raise RuntimeError("Failed to create C++ DFT Solver instance.")
 
@@ -222,6 +229,13 @@ class DFTSolverWrapper:
                                           _u64(_ptr(d_dm)), _u64(_ptr(d_vxc)), _u64(_ptr(d_exc)), int(chunk_points))
         self._check()
         return rc
+
+    def mix(self):
+        """The solver's weights as the library reports them (DFT_GetMix; for a built-in type: its equivalent mix)."""
+        out = (ctypes.c_double * len(functionals.COMPONENTS))()
+        if self.lib.DFT_GetMix(self.solver, out, len(out)) != 0:
+            raise RuntimeError("DFT_GetMix failed")
+        return list(out)
 
     def set_option(self, key, value):
         if self.lib.DFT_SetOption(self.solver, key.encode(), float(value)) != 0:
