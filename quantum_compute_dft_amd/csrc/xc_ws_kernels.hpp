@@ -16,7 +16,8 @@
 // rewritten only after a later barrier than its last read, so no flags are needed:
 //   vxc : loaders write stage i (sub-tile i) at step i, MFMA waves read it at step i+2.
 //   rho : loaders write AO stage i at step i, MFMA waves form X(i) at step i+1 into an
-//         X ring, loaders take the row dots of sub-tile i at step i+2.
+//         X ring, loaders take their share of the row dots of sub-tile i at step i+2 and
+//         MFMA waves add the 16 shares of a row at step i+3.
 // Persistent: workgroup b owns sub-tiles b, b+grid, ... (neighbouring CUs stream
 // neighbouring HBM pages).  LDS leading dimensions: AO tile = 2 or 18 (mod 32) doubles (the
 // 16-row x 2-k A-operand read hits 32 distinct bank pairs), X/P/Q tiles = 16 (mod 32)
@@ -287,6 +288,15 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_vxc_ws(long ngrid, int nao,
 // ------------------------------------------------------------------ rho ----
 // rho_g = sum_v X[g][v] AO[g][v],  grad rho_g = 2 sum_v X[g][v] dAO[g][v],  X = AO . Ds.
 // MFMA wave w owns column tiles {w, w+4}: their slices of Ds stay in registers.
+//
+// The row dots are split between the roles.  Loader thread (row, seg) sums its own <= 8 columns and
+// leaves the four partial sums in a small LDS tile S_q[row][seg]; one step later MFMA wave q takes
+// the sum over the 16 segments as S_q . 1 (four MFMAs; . 2 for the gradients, which carries their
+// factor) and puts it into the result ring.  The matrix pipe is idle half the time in this kernel;
+// the loader waves are what paces it, and a 16-lane DPP reduction of four fp64 values cost them 80
+// vector instructions per sub-tile.
+//   step s : loaders write AO(s) and the partial sums of sub-tile s-2,
+//            MFMA waves form X(s-1) and finish the sums of sub-tile s-3.
 template <int NT, bool GRAD, bool VEC>
 __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
                                                           const double *__restrict__ ao,
@@ -302,18 +312,27 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
     constexpr int NKS = 4 * NT;       // k-steps over the padded AO index
     constexpr int NTW = (NT + 3) / 4; // column tiles per MFMA wave
     constexpr int ATILE = WS_ROWS * C::LDA, XTILE = WS_ROWS * C::LDX;
+    constexpr int NQ = GRAD ? 4 : 1;  // rho, d/dx, d/dy, d/dz
+    // partial-sum tiles: leading dimension 18 = 2 (mod 32) for the A-operand read (as LDA); the planes of
+    // the four quantities lie 5 x 64 doubles apart, so a loader thread stores its four sums with two
+    // ds_write2st64_b64.  Two slots: written at step s, read at s+1, rewritten at s+2.
+    constexpr int LDS_ = WS_ROWS + 2, SQ = 320, STILE = NQ * SQ;
+    static_assert(WS_ROWS * LDS_ <= SQ, "a partial-sum plane must fit its stride");
     __shared__ double As[WS_RING * ATILE];
     __shared__ double Xs[2 * XTILE];
+    __shared__ double Ss[2 * STILE];
     // Results leave in BURSTS: rho / grad rho of WS_OT sub-tiles are collected here and written by the loader waves in
     // one go (40 bytes per grid row, 1 % of the traffic -- but stored sub-tile by sub-tile the trickle of writes keeps
     // turning the HBM channels around under the read stream: 10 us of 85 in tools/stream_pattern_probe4.hip).
     __shared__ double Ob[(WS_OT + 1) * WS_ROWS * 4];
 
+    // 32-bit step and tile arithmetic throughout: the host takes this path only when a plane is below 4 GiB
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long ntile = (ngrid + WS_ROWS - 1) / WS_ROWS;
-    const long nloc = (ntile > (long)blockIdx.x) ? (ntile - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
-    const long nstep = nloc + 2;
+    const unsigned ntile = (unsigned)((ngrid + WS_ROWS - 1) / WS_ROWS);
+    const unsigned nwg = gridDim.x, wg = blockIdx.x;
+    const unsigned nloc = ntile > wg ? (ntile - wg + nwg - 1) / nwg : 0u;
+    const unsigned nstep = nloc + 3; // X one step, partial sums two, their reduction three steps behind the AO stage
 
     if (wave < 4) {
         // ---------------------------------------------------------- MFMA role
@@ -336,10 +355,15 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
                 dreg[i][ks] = in ? v : 0.0;
             }
         }
-        for (long base = 0; base < nstep; base += WS_RING) {
+        // quantity `wave` of sub-tile step-3: its slot in the result ring is a wrapped counter
+        const double *sp = Ss + min(wave, NQ - 1) * SQ + li * LDS_ + lk;
+        const double ones = wave == 0 ? 1.0 : 2.0; // grad rho = 2 sum: exact, whichever side of the sum it is taken on
+        double *op = Ob + lk * 4 + wave;
+        unsigned oslot = 0;
+        for (unsigned base = 0; base < nstep; base += WS_RING) {
 #pragma unroll
             for (int u = 0; u < WS_RING; ++u) {
-                const long step = base + u;
+                const unsigned step = base + u;
                 if (step >= 1 && step <= nloc && wave < NT) { // X(step-1) from AO stage (u+3)%4
                     const double *ap = As + ((u + 3) % WS_RING) * ATILE + li * C::LDA + lk;
                     double *X = Xs + ((u + 1) & 1) * XTILE;
@@ -364,6 +388,18 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
                         }
                     }
                 }
+                if (step >= 3 && step - 3 < nloc && wave < NQ) { // partial sums written at step-1: slot (u+1)&1
+                    const double *S = sp + ((u + 1) & 1) * STILE;
+                    d4 t = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                    for (int ks = 0; ks < WS_ROWS / 4; ++ks) t = mfma_f64(S[4 * ks], ones, t);
+                    if (li == 0) { // every column of t holds the 16 row sums: rows lk, lk+4, lk+8, lk+12
+                        double *o = op + oslot * (WS_ROWS * 4);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) o[16 * r] = t[r];
+                    }
+                    oslot = oslot == WS_OT ? 0u : oslot + 1u;
+                }
                 __syncthreads();
             }
         }
@@ -374,19 +410,26 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
         double ph[2][2 * C::JN];                                           // AO of sub-tiles s, s+1
         double pgx[2][2 * C::JN], pgy[2][2 * C::JN], pgz[2][2 * C::JN];   // gradients of s-2.., see below
 
-        auto row_of = [&](long s) { return (long)ws_tile((unsigned)ntile, blockIdx.x, (unsigned)s, gridDim.x, rev) * WS_ROWS + row; };
         // unconditional issue, drain steps out of range: see k_vxc_ws
         const long plane = ngrid * (long)nao;
         const unsigned voff = (unsigned)(row * nao + 2 * seg) * 8u;
         const unsigned tile_b = (unsigned)(WS_ROWS * nao) * 8u, plane_b = (unsigned)(plane * 8);
         const __amdgpu_buffer_rsrc_t r0 = plane_rsrc(ao, plane), r1 = plane_rsrc(GRAD ? gx : ao, plane),
                                      r2 = plane_rsrc(GRAD ? gy : ao, plane), r3 = plane_rsrc(GRAD ? gz : ao, plane);
-        auto tile_off = [&](unsigned s) {
-            return s < (unsigned)nloc ? ws_tile((unsigned)ntile, blockIdx.x, s, gridDim.x, rev) * tile_b : plane_b;
+        // The byte offset of the workgroup's next sub-tile is carried forward (one add, one compare, one select per
+        // step) instead of being rebuilt from the step number for every load group; o_a / o_b are the offsets of
+        // sub-tiles step and step+1, whose gradients are issued two steps after their AO rows.  Past the last
+        // live sub-tile the running offset is never used (it may wrap).
+        unsigned o_run = (rev ? ntile - 1u - wg : wg) * tile_b, left = nloc;
+        const unsigned o_inc = rev ? 0u - nwg * tile_b : nwg * tile_b;
+        auto next_off = [&]() {
+            const unsigned o = left ? o_run : plane_b;
+            left = left ? left - 1u : 0u;
+            o_run += o_inc;
+            return o;
         };
-        auto issue_ao = [&](int set, unsigned s) { buf_load_row<C::JN, VEC>(r0, voff, tile_off(s), ph[set]); };
-        auto issue_grad = [&](int set, unsigned s) {
-            const unsigned so = tile_off(s);
+        auto issue_ao = [&](int set, unsigned so) { buf_load_row<C::JN, VEC>(r0, voff, so, ph[set]); };
+        auto issue_grad = [&](int set, unsigned so) {
             buf_load_row<C::JN, VEC>(r1, voff, so, pgx[set]);
             buf_load_row<C::JN, VEC>(r2, voff, so, pgy[set]);
             buf_load_row<C::JN, VEC>(r3, voff, so, pgz[set]);
@@ -397,23 +440,26 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
         // the entry path and the back edge of "loads younger than the set consumed first": a prologue that
         // issues fewer or reordered loads turned that wait into vmcnt(0) -- a drain of the whole prefetch
         // once per trip (round-1 ISA).
-        issue_ao(0, 0);
+        unsigned o_a = next_off(), o_b = next_off();
+        issue_ao(0, o_a);
         __builtin_amdgcn_sched_barrier(0);
-        if (GRAD) issue_grad(0, (unsigned)nloc);
+        if (GRAD) issue_grad(0, plane_b);
         __builtin_amdgcn_sched_barrier(0);
-        issue_ao(1, 1);
+        issue_ao(1, o_b);
         __builtin_amdgcn_sched_barrier(0);
-        if (GRAD) issue_grad(1, (unsigned)nloc);
+        if (GRAD) issue_grad(1, plane_b);
         __builtin_amdgcn_sched_barrier(0);
 
-        long flushed = 0;
-        auto flush = [&](long j0, long j1) {
-            const long j = j0 + (lt >> 4);
+        // burst of the WS_OT sub-tiles from the workgroup's j0-th on (ring slot `slot0`), thread = (sub-tile, row)
+        auto flush = [&](unsigned j0, unsigned slot0) {
+            const unsigned j = j0 + (unsigned)(lt >> 4);
             const int r = lt & 15;
-            if (j < j1 && j < nloc) {
-                const long g = (long)ws_tile((unsigned)ntile, blockIdx.x, (unsigned)j, gridDim.x, rev) * WS_ROWS + r;
+            if (j < nloc) {
+                const long g = (long)ws_tile(ntile, wg, j, nwg, rev) * WS_ROWS + r;
                 if (g < ngrid) {
-                    const double *o = Ob + ((j % (WS_OT + 1)) * WS_ROWS + r) * 4;
+                    unsigned slot = slot0 + (unsigned)(lt >> 4);
+                    slot = slot > (unsigned)WS_OT ? slot - (WS_OT + 1) : slot;
+                    const double *o = Ob + (slot * WS_ROWS + r) * 4;
                     rho[g] = o[0];
                     if (GRAD) {
                         const double ax = o[1], ay = o[2], az = o[3];
@@ -425,11 +471,15 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
                 }
             }
         };
-        for (long base = 0; base < nstep; base += WS_RING) {
+        // The result of sub-tile j is complete after the barrier of step j+3, so sub-tiles [flushed, flushed + WS_OT)
+        // leave at step flushed + WS_OT + 3: a down-counter, the ring slot of `flushed` a wrapped counter.
+        unsigned flushed = 0, fslot = 0, fcount = WS_OT + 3 + 1;
+        double *const sw = Ss + row * LDS_ + seg;
+        for (unsigned base = 0; base < nstep; base += WS_RING) {
 #pragma unroll
             for (int u = 0; u < WS_RING; ++u) {
-                const long step = base + u;
                 const int set = u & 1;
+                const unsigned o_c = next_off(); // sub-tile step+2
                 // (a) AO(step) -> ring slot u, then refill the register set with AO(step+2)
                 {
                     double *A = As + u * ATILE;
@@ -439,14 +489,13 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
                         if (c < C::NCOL)
                             *reinterpret_cast<double2 *>(&A[row * C::LDA + c]) = make_double2(ph[set][2 * j], ph[set][2 * j + 1]);
                     }
-                    issue_ao(set, (unsigned)step + 2u);
+                    issue_ao(set, o_c);
                 }
-                // (b) row dots of sub-tile step-2: X from the X ring, AO from ring slot (u+2)%4,
-                //     gradients from register set `set` (loaded at step-2)
-                { // for step < 2 this runs on never-written LDS; nothing is stored (row_ok false)
-                    const bool in_range = step >= 2 && step - 2 < nloc;
-                    const long g = row_of(in_range ? step - 2 : 0);
-                    const bool row_ok = in_range && g < ngrid;
+                // (b) this thread's share of the row dots of sub-tile step-2: X from the X ring, AO from ring slot
+                //     (u+2)%4, gradients from register set `set` (loaded at step-2).  Unconditional: before step 2
+                //     and on drain steps it runs on data nobody uses (the MFMA waves store sub-tiles 0..nloc-1 only),
+                //     and every word of the S slot is written on every step (threads without columns store zeros).
+                {
                     const double *A = As + ((u + 2) % WS_RING) * ATILE;
                     const double *X = Xs + (u & 1) * XTILE;
                     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
@@ -456,40 +505,38 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_rho_ws(long ngrid, int nao,
                         if (c < C::NCOL) {
                             const double2 x = *reinterpret_cast<const double2 *>(&X[row * C::LDX + c]);
                             const double2 p = *reinterpret_cast<const double2 *>(&A[row * C::LDA + c]);
-                            s0 += x.x * p.x + x.y * p.y;
-                            if (GRAD) {
-                                // X columns >= nao are exact zeros (zero-padded Ds); rows past the grid read as 0
-                                s1 += x.x * pgx[set][2 * j] + x.y * pgx[set][2 * j + 1];
-                                s2 += x.x * pgy[set][2 * j] + x.y * pgy[set][2 * j + 1];
-                                s3 += x.x * pgz[set][2 * j] + x.y * pgz[set][2 * j + 1];
+                            // X columns >= nao are exact zeros (zero-padded Ds); rows past the grid read as 0
+                            const double t0 = x.x * p.x + x.y * p.y;
+                            const double t1 = x.x * pgx[set][2 * j] + x.y * pgx[set][2 * j + 1];
+                            const double t2 = x.x * pgy[set][2 * j] + x.y * pgy[set][2 * j + 1];
+                            const double t3 = x.x * pgz[set][2 * j] + x.y * pgz[set][2 * j + 1];
+                            if (j == 0) { // the first term starts the sums (0.0 + t is an instruction per quantity)
+                                s0 = t0;
+                                if (GRAD) { s1 = t1; s2 = t2; s3 = t3; }
+                            } else {
+                                s0 += t0;
+                                if (GRAD) { s1 += t1; s2 += t2; s3 += t3; }
                             }
                         }
                     }
-                    s0 = row16_sum(s0);
-                    if (GRAD) {
-                        s1 = row16_sum(s1);
-                        s2 = row16_sum(s2);
-                        s3 = row16_sum(s3);
-                    }
-                    (void)row_ok;
-                    if (seg == 0 && in_range) { // slot of sub-tile step-2 in the result ring
-                        double *o = Ob + (((step - 2) % (WS_OT + 1)) * WS_ROWS + row) * 4;
-                        o[0] = s0;
-                        if (GRAD) { o[1] = 2.0 * s1; o[2] = 2.0 * s2; o[3] = 2.0 * s3; }
-                    }
+                    double *S = sw + (u & 1) * STILE;
+                    S[0] = s0;
+                    if (GRAD) { S[SQ] = s1; S[2 * SQ] = s2; S[3 * SQ] = s3; }
                 }
-                // the results of sub-tiles [flushed, step-2) are complete (written before the previous barrier):
-                // one burst per WS_OT of them, thread = (sub-tile, row)
-                if (step - 2 - flushed == WS_OT) {
-                    flush(flushed, step - 2);
-                    flushed = step - 2;
+                if (--fcount == 0) {
+                    flush(flushed, fslot);
+                    flushed += WS_OT;
+                    fslot = fslot == 0 ? (unsigned)WS_OT : fslot - 1u; // + WS_OT (mod WS_OT + 1)
+                    fcount = WS_OT;
                 }
                 // (c) gradients of sub-tile `step` into the set just freed (consumed at step+2)
-                if (GRAD) issue_grad(set, (unsigned)step);
+                if (GRAD) issue_grad(set, o_a);
+                o_a = o_b;
+                o_b = o_c;
                 __syncthreads();
             }
         }
-        flush(flushed, nloc); // the rest (at most WS_OT sub-tiles; the loop's last barrier made them visible)
+        flush(flushed, fslot); // the rest (at most WS_OT sub-tiles; the loop's last barrier made them visible)
     }
 }
 
