@@ -15,9 +15,10 @@
 //                       U_v' = T + (T K) X K^T,        T = U_v - U_o K^T,   X = -L^-T (1 + L)^-1
 //                   (the Cholesky form of the completion: no eigen-decomposition of K^T K, and
 //                    (1 + K X^T K^T)(1 + K K^T)(1 + K X K^T) = 1 exactly)
-//   k_tail_rot_big  (to nao 512, nocc 64) the same with operands in memory; its fixed-point steps are launches of their own
-//                   (k_rb_qb, k_rb_r, k_rb_decide: state in memory, early-out when the iteration is over, status 3 = queue more)
-//                   and so are its long contractions (k_rb_fop, k_tail_gemm)
+//   k_rb_*          (to nao 512, nocc 64) the same with operands in memory, as launches: k_rb_start (K0, its 0.5 test, the
+//                   iteration's state), the fixed-point steps (k_rb_qb, k_rb_r, k_rb_decide: state in memory, early-out when
+//                   the iteration is over, status 3 = queue more), the long contractions (k_rb_fop, k_tail_gemm) and
+//                   k_rb_finish (ONE workgroup: Cholesky, Jacobi, the small blocks of W)
 //   k_tail_gemm     U' = U W
 //   k_tail_density  dm' = c' c'^T, tr(dm' H), tr(dm' J)/2, -c_hf tr(dm' K)/4, |dm' - dm|; the last workgroup adds the
 //                   row partials in a fixed order and publishes them (and the sweep's Exc) to host-mapped memory
@@ -42,7 +43,7 @@ namespace {
 
 constexpr int TL_MAXN = 128;   // basis functions of the LDS-resident rotation kernel (k_tail_rot)
 constexpr int TL_MAXO = 32;    // occupied orbitals of it (half a wave per Jacobi pair, LDS copies of the small matrices)
-constexpr int TL_BIGN = 512;   // ... of the memory-resident one (k_tail_rot_big) and of every other kernel here
+constexpr int TL_BIGN = 512;   // ... of the memory-resident one (k_rb_*) and of every other kernel here
 constexpr int TL_BIGO = 64;
 constexpr int TL_SPACE = 8;    // DIIS ring
 constexpr int TL_ROT_T = 512;  // threads of the rotation kernels (eight waves: 256 registers each)
@@ -56,10 +57,31 @@ struct TailArgs {
     double c_hf, tol, canon_tol;
 };
 
-struct RbState;
+// the memory-resident fixed point's state (see k_rb_qb)
+struct RbState {
+    int done, ok, steps, cur;
+    double prev;
+    unsigned long long rmax_bits;
+};
+
+// the device's status block, behind the blob
+struct TailStatus {
+    int word[8];            // [0] status, [1] inner steps, [2] Jacobi sweeps, [3] ticket (the kernels take this as `int *status`)
+    long long stamps[16];   // k_tail_rot's phases (DFT_ScfTailStamps)
+    RbState state;
+};
 
 struct RotLds {   // offsets (doubles) into the rotation kernel's dynamic LDS; -1 = the matrix stays in memory
     int km, bm, qm, rm, smalls;
+};
+
+// the completion's ten n_occ x n_occ matrices, carved out of one buffer (LDS in k_tail_rot, memory behind k_rb_finish)
+struct Smalls {
+    static constexpr int COUNT = 10;
+    double *Fo, *Pm, *W1, *Fop, *Vo, *cd, *Xm, *Lig, *L1g, *MX;
+    __host__ __device__ Smalls(double *base, size_t n2o)
+        : Fo(base), Pm(base + n2o), W1(base + 2 * n2o), Fop(base + 3 * n2o), Vo(base + 4 * n2o), cd(base + 5 * n2o), Xm(base + 6 * n2o),
+          Lig(base + 7 * n2o), L1g(base + 8 * n2o), MX(base + 9 * n2o) {}
 };
 
 struct TailDev {
@@ -68,11 +90,10 @@ struct TailDev {
     double *U = nullptr, *Fx = nullptr, *eig = nullptr;       // caller's
     double *blob = nullptr;                                   // everything below
     double *Fb, *Eb, *Gb, *FC, *SC, *gpart, *FU, *A, *Unew, *Km, *Rm, *Qm, *Bm, *epart, *rden, *smalls, *Kfix, *KXg, *Kt, *Kt2, *K2;
-    bool big = false;           // k_tail_rot_big: operands in memory
-    RbState *state = nullptr;   // the memory-resident fixed point's state (device)
+    bool big = false;           // k_rb_*: operands in memory
     int steps_hint = 6;         // fixed-point steps queued per DFT_ScfTailStep on that path
     TailArgs last{};            // of the last step: DFT_ScfTailMore continues it
-    int *status = nullptr;     // [0] status, [1] inner steps, [2] Jacobi sweeps, [3] ticket
+    TailStatus *status = nullptr;   // (device)
     double *h_out = nullptr, *h_out_dev = nullptr;            // host-mapped: 8 doubles + sequence word
     unsigned long seq = 0;
     RotLds lo{-1, -1, -1, -1, 0}; // where the fixed point's matrices live
@@ -311,16 +332,12 @@ __global__ __launch_bounds__(128) void k_tail_mix(TailArgs a, const double *__re
     }
 }
 
-// One 16 x 16 tile of C (M x N) = A B per workgroup on the fp64 matrix cores, the contraction split over four waves
-// (thirty-two contraction steps per round: eight per wave, all operands loaded before the round's first MFMA):
-// A(i, k) = a[i ars + k acs], B(k, j) = b[k brs + j bcs].
-__global__ __launch_bounds__(256) void k_tail_gemm(int M, int N, int Kd, const double *__restrict__ a, int ars, int acs,
-                                                   const double *__restrict__ b, int brs, int bcs, double *__restrict__ c, int ldc,
-                                                   double alpha, int add_diag, const int *__restrict__ status)
+// One 16 x 16 tile of A B (M x N) on the fp64 matrix cores, the contraction split over a workgroup's four waves (thirty-two
+// contraction steps per round: eight per wave, all operands loaded before the round's first MFMA), summed into every wave's
+// registers: A(i, k) = a[i ars + k acs], B(k, j) = b[k brs + j bcs].
+__device__ __forceinline__ void tile_splitk(int i0, int j0, int M, int N, int Kd, const double *a, int ars, int acs, const double *b, int brs,
+                                            int bcs, double (*part)[4][64], double (&out)[4])
 {
-    __shared__ double part[4][4][64];
-    if (status[0] != 0) return;
-    const int nt = (N + 15) >> 4, tile = blockIdx.x, i0 = (tile / nt) << 4, j0 = (tile % nt) << 4;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, kq = lane >> 4;
     const int ia = i0 + li, jb = j0 + li;
     const bool aok = ia < M, bok = jb < N;
@@ -342,15 +359,27 @@ __global__ __launch_bounds__(256) void k_tail_gemm(int M, int N, int Kd, const d
 #pragma unroll
     for (int r = 0; r < 4; ++r) part[wave][r][lane] = acc0[r] + acc1[r];
     __syncthreads();
-    if (wave == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[r] = (part[0][r][lane] + part[1][r][lane]) + (part[2][r][lane] + part[3][r][lane]);
+}
+
+// C (M x N, ldc) = alpha A B (+ 1 on the diagonal), a tile per workgroup; nothing after a step that has failed
+__global__ __launch_bounds__(256) void k_tail_gemm(int M, int N, int Kd, const double *__restrict__ a, int ars, int acs,
+                                                   const double *__restrict__ b, int brs, int bcs, double *__restrict__ c, int ldc,
+                                                   double alpha, int add_diag, const int *__restrict__ status)
+{
+    __shared__ double part[4][4][64];
+    if (status[0] != 0) return;
+    const int nt = (N + 15) >> 4, tile = blockIdx.x, i0 = (tile / nt) << 4, j0 = (tile % nt) << 4;
+    const int lane = threadIdx.x & 63, li = lane & 15, kq = lane >> 4;
+    double v[4];
+    tile_splitk(i0, j0, M, N, Kd, a, ars, acs, b, brs, bcs, part, v);
+    if (threadIdx.x < 64)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = i0 + kq + 4 * r, col = j0 + li;
-            if (row < M && col < N)
-                c[(size_t)row * ldc + col] = alpha * ((part[0][r][lane] + part[1][r][lane]) + (part[2][r][lane] + part[3][r][lane])) +
-                                             (add_diag && row == col ? 1.0 : 0.0);
+            if (row < M && col < N) c[(size_t)row * ldc + col] = alpha * v[r] + (add_diag && row == col ? 1.0 : 0.0);
         }
-    }
 }
 
 // C (M x N, ldc) = alpha sum_k A(i, k) B(k, j) + beta D(i, j) by the whole workgroup on the fp64 matrix cores, one 16 x 16 tile
@@ -370,7 +399,7 @@ template <> struct TailPtr<true> {
 };
 
 template <bool LDS>
-__device__ __forceinline__ void wg_gemm_t(int M, int N, int Kd, const double *a_, int ars, int acs, const double *b_, int brs, int bcs,
+__device__ __forceinline__ void wg_gemm(int M, int N, int Kd, const double *a_, int ars, int acs, const double *b_, int brs, int bcs,
                                           double alpha, double beta, const double *d_, int ldd, double *c_, int ldc)
 {
     typename TailPtr<LDS>::ro a = (typename TailPtr<LDS>::ro)a_, b = (typename TailPtr<LDS>::ro)b_, d = (typename TailPtr<LDS>::ro)d_;
@@ -426,15 +455,12 @@ __device__ __forceinline__ void wg_gemm_t(int M, int N, int Kd, const double *a_
         }
     }
 }
-__device__ __forceinline__ void wg_gemm(int M, int N, int Kd, const double *a, int ars, int acs, const double *b, int brs, int bcs,
-                        double alpha, double beta, const double *d, int ldd, double *c, int ldc)
+// the LDS form when every operand of the product is there (lds is uniform and loop-invariant in its callers)
+__device__ __forceinline__ void wg_gemm_if(bool lds, int M, int N, int Kd, const double *a, int ars, int acs, const double *b, int brs, int bcs,
+                                           double alpha, double beta, const double *d, int ldd, double *c, int ldc)
 {
-    wg_gemm_t<false>(M, N, Kd, a, ars, acs, b, brs, bcs, alpha, beta, d, ldd, c, ldc);
-}
-__device__ __forceinline__ void wg_gemm_lds(int M, int N, int Kd, const double *a, int ars, int acs, const double *b, int brs, int bcs,
-                            double alpha, double beta, const double *d, int ldd, double *c, int ldc)
-{
-    wg_gemm_t<true>(M, N, Kd, a, ars, acs, b, brs, bcs, alpha, beta, d, ldd, c, ldc);
+    if (lds) wg_gemm<true>(M, N, Kd, a, ars, acs, b, brs, bcs, alpha, beta, d, ldd, c, ldc);
+    else     wg_gemm<false>(M, N, Kd, a, ars, acs, b, brs, bcs, alpha, beta, d, ldd, c, ldc);
 }
 
 __device__ double block_max(double v, double *scratch)
@@ -448,12 +474,14 @@ __device__ double block_max(double v, double *scratch)
     return m;
 }
 
-// sum over the (at most 32) lanes of a wave that hold a column's rows; every lane gets the total
-__device__ __forceinline__ double half_sum(double v)
+// sum over the MAXO lanes of a wave that hold a column's rows (32: an aligned half of the wave); every one of them gets the total
+template <int MAXO> __device__ __forceinline__ double pair_sum(double v);
+template <> __device__ __forceinline__ double pair_sum<32>(double v)
 {
     v = row16_sum(v);
-    return bcast(v, 0) + bcast(v, 16);
+    return v + __shfl_xor(v, 16, 64);
 }
+template <> __device__ __forceinline__ double pair_sum<64>(double v) { return wave_sum(v); }
 
 // Cholesky P = L L^T (P = 1 + Pm symmetrised) by wave 0, left-looking, in LDS: lane i owns row i and subtracts
 // sum_k<j L[i][k] L[j][k] from P[i][j] (row j is read by every lane at the same address: a broadcast); then L^-1 (wave 0) and
@@ -528,9 +556,115 @@ __device__ __forceinline__ double fast_rsqrt(double x)
     return y * fma(-0.5 * x * y, y, 1.5);
 }
 
-__global__ __launch_bounds__(TL_ROT_T) void k_tail_rot(TailArgs a, RotLds lo, const double *__restrict__ A, const double *__restrict__ U,
-                                                       double *Km_g, double *Rm_g, double *Qm_g, double *Bm_g, double *W,
-                                                       double *eig, int *status, long long *stamps)
+// Eigenvectors Vo (n_occ x n_occ, row-major) and eigenvalues (into dd[0 .. n_occ)) of the symmetrised G = Fop, by
+// one-sided Jacobi on the columns of G - sigma (sigma above the spectrum: all eigenvalues of one sign, so orthogonal
+// columns of (G - sigma) V are eigenvectors of G itself).  MAXO lanes per column pair (lane = row: half a wave or a whole one),
+// the pairs of a round by the circle method; a pair whose columns are already orthogonal to a tenth of the tolerance is
+// left alone.  Wc, Vc: the columns, in LDS.  Returns the number of sweeps.
+template <int MAXO>
+__device__ __forceinline__ int jacobi_occ(int no, double canon_tol, const double *Fop, double (*Wc)[MAXO + 1], double (*Vc)[MAXO + 1],
+                                          double *Vo, double *dd, double *red, int *flag)
+{
+    constexpr int PER_WAVE = 64 / MAXO, PER_ROUND = PER_WAVE * (TL_ROT_T / 64);   // column pairs at a time
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, row = lane & (MAXO - 1);
+    const int n2o = no * no, ne = (no + 1) & ~1, npair = ne >> 1;
+    double gs = 0.0;
+    if (t < no) {
+        double rs = 0.0;
+        for (int j = 0; j < no; ++j) rs += fabs(0.5 * (Fop[t * no + j] + Fop[j * no + t]));
+        gs = rs;
+    }
+    const double sigma = block_max(gs, red) + 1.0;   // Gershgorin bound on |lambda|, plus a margin
+    // An occupied block that is diagonal to canon_tol (Hartree) already is left as it is: the fixed point's denominators
+    // only cross the gap, where off-diagonal elements of that size do not count (the virtual block is never diagonalised
+    // at all), and the orbital energies reported are Rayleigh quotients, exact to second order.
+    double off = 0.0;
+    for (int e = t; e < n2o; e += TL_ROT_T)
+        if (e / no != e % no) off = fmax(off, fabs(0.5 * (Fop[e] + Fop[(e % no) * no + e / no])));
+    const bool skip_sweeps = block_max(off, red) <= canon_tol;
+    for (int e = t; e < MAXO * MAXO; e += TL_ROT_T) {
+        const int j = e / MAXO, i = e - j * MAXO;   // column j, row i
+        double g = 0.0;
+        if (i < no && j < no) g = 0.5 * (Fop[i * no + j] + Fop[j * no + i]) - (i == j ? sigma : 0.0);
+        Wc[j][i] = g;
+        Vc[j][i] = i == j ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    // Rotations converge quadratically: a sweep that met no pair with |cos| above canon_tol leaves all of them below
+    // ~canon_tol^2, which ends the iteration (canon_tol 1e-3: an occupied block diagonal to ~1e-6 of its scale -- the
+    // next cycle's denominators want no more, and the orbitals are exactly orthonormal whatever the rotations were).
+    const double stop2 = canon_tol * canon_tol, skip2 = 1e-26;
+    int sweeps = 0;
+    for (int sweep = 0; sweep < 12 && !skip_sweeps; ++sweep) {
+        int big = 0;
+        for (int round = 0; round < ne - 1; ++round) {
+            for (int p0 = PER_WAVE * wave; p0 < npair; p0 += PER_ROUND) {
+                const int pr = p0 + lane / MAXO;
+                const bool live = pr < npair && row < ne;
+                // circle method: position 0 is held by column ne - 1, the others rotate
+                const int p = !live ? 0 : pr == 0 ? ne - 1 : (round + pr) % (ne - 1);
+                const int q = !live ? 0 : pr == 0 ? round : (round - pr + (ne - 1)) % (ne - 1);
+                const double wp = live ? Wc[p][row] : 0.0, wq = live ? Wc[q][row] : 0.0;
+                const double vp = live ? Vc[p][row] : 0.0, vq = live ? Vc[q][row] : 0.0;
+                const double al = pair_sum<MAXO>(wp * wp), be = pair_sum<MAXO>(wq * wq), ga = pair_sum<MAXO>(wp * wq);
+                const double g2 = ga * ga, ab = al * be;
+                if (live && g2 > skip2 * ab) {
+                    big |= g2 > stop2 * ab;
+                    const double zeta = 0.5 * (be - al) * fast_rcp(ga);
+                    const double az = fabs(zeta);
+                    const double hyp = az < 1e150 ? (1.0 + zeta * zeta) * fast_rsqrt(1.0 + zeta * zeta) : az;   // sqrt(1 + zeta^2)
+                    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) * fast_rcp(az + hyp);
+                    const double cs = fast_rsqrt(1.0 + tt * tt), sn = cs * tt;
+                    Wc[p][row] = cs * wp - sn * wq;
+                    Wc[q][row] = sn * wp + cs * wq;
+                    Vc[p][row] = cs * vp - sn * vq;
+                    Vc[q][row] = sn * vp + cs * vq;
+                }
+            }
+            __syncthreads();
+        }
+        ++sweeps;
+        const int any = __ballot(big) != 0;
+        if (lane == 0) flag[wave] = any;
+        __syncthreads();
+        int more = 0;
+        for (int k = 0; k < TL_ROT_T / 64; ++k) more |= flag[k];
+        __syncthreads();
+        if (!more) break;
+    }
+    // eigenvalues lambda_j = v_j . (G v_j) = v_j . w_j + sigma
+    for (int j = wave; j < no; j += TL_ROT_T / 64) {
+        const double s = pair_sum<MAXO>(lane < ne ? Vc[j][lane] * Wc[j][lane] : 0.0);
+        if (lane == 0) dd[j] = s + sigma;   // the occupied slots of dd now hold the new orbital energies
+    }
+    for (int e = t; e < n2o; e += TL_ROT_T) {
+        const int i = e / no, j = e - i * no;
+        Vo[e] = Vc[j][i];
+    }
+    __syncthreads();
+    return sweeps;
+}
+
+// aufbau order: highest new occupied level against the lowest virtual diagonal (a necessary test only; the
+// caller checks the converged state against a full diagonalisation, as scf.py does); the orbital energies when it holds
+__device__ __forceinline__ bool aufbau_and_eig(int n, int no, const double *dd, double *red, double *eig)
+{
+    const int t = threadIdx.x;
+    double eo = -INFINITY, dv = INFINITY;
+    for (int i = t; i < n; i += TL_ROT_T) {
+        if (i < no) eo = fmax(eo, dd[i]);
+        else dv = fmin(dv, dd[i]);
+    }
+    const double eomax = block_max(eo, red), dvmin = -block_max(-dv, red);
+    if (eomax > dvmin - 1e-3) return false;
+    if (eig)
+        for (int i = t; i < n; i += TL_ROT_T) eig[i] = dd[i];
+    return true;
+}
+
+__global__ __launch_bounds__(TL_ROT_T) void k_tail_rot(TailArgs a, RotLds lo, const double *__restrict__ A, double *Km_g, double *Rm_g,
+                                                       double *Qm_g, double *Bm_g, double *W, double *eig, int *status,
+                                                       long long *stamps)
 {
 #define QCDFT_STAMP(k) do { if (threadIdx.x == 0) stamps[k] = (long long)wall_clock64(); } while (0)
     // dynamic LDS: [A (n x n) during the fixed point | the completion's small matrices afterwards][K][B][Q][R] as they fit
@@ -591,17 +725,11 @@ __global__ __launch_bounds__(TL_ROT_T) void k_tail_rot(TailArgs a, RotLds lo, co
     int steps = 0;
     const bool all_lds = lo.km >= 0 && lo.bm >= 0 && lo.qm >= 0 && lo.rm >= 0;   // Benzene-sized problems: everything the loop touches
     for (int it = 0; it < a.max_inner; ++it) {
-        if (all_lds) {
-            wg_gemm_lds(nv, no, nv, Avv, n, 1, Km, no, 1, 1.0, 1.0, Avo, n, Qm, no);
-            wg_gemm_lds(no, no, nv, Aov, n, 1, Km, no, 1, 1.0, 1.0, Aoo, n, Bm, no);
-        } else {
-            wg_gemm(nv, no, nv, Avv, n, 1, Km, no, 1, 1.0, 1.0, Avo, n, Qm, no);
-            wg_gemm(no, no, nv, Aov, n, 1, Km, no, 1, 1.0, 1.0, Aoo, n, Bm, no);
-        }
+        wg_gemm_if(all_lds, nv, no, nv, Avv, n, 1, Km, no, 1, 1.0, 1.0, Avo, n, Qm, no);
+        wg_gemm_if(all_lds, no, no, nv, Aov, n, 1, Km, no, 1, 1.0, 1.0, Aoo, n, Bm, no);
         __syncthreads();
         if (it == 0) QCDFT_STAMP(2);
-        if (all_lds) wg_gemm_lds(nv, no, no, Km, no, 1, Bm, no, 1, -1.0, 1.0, Qm, no, Rm, no);
-        else         wg_gemm(nv, no, no, Km, no, 1, Bm, no, 1, -1.0, 1.0, Qm, no, Rm, no);
+        wg_gemm_if(all_lds, nv, no, no, Km, no, 1, Bm, no, 1, -1.0, 1.0, Qm, no, Rm, no);
         __syncthreads();
         if (it == 0) QCDFT_STAMP(3);
         double r = 0.0, rv[EPT];
@@ -639,152 +767,50 @@ __global__ __launch_bounds__(TL_ROT_T) void k_tail_rot(TailArgs a, RotLds lo, co
     double (*Lm)[TL_LD] = (double (*)[TL_LD])sp, (*Li)[TL_LD] = (double (*)[TL_LD])(sp + TL_MAXO * TL_LD),
            (*L1)[TL_LD] = (double (*)[TL_LD])(sp + 2 * TL_MAXO * TL_LD), (*Wc)[TL_LD] = (double (*)[TL_LD])(sp + 3 * TL_MAXO * TL_LD),
            (*Vc)[TL_LD] = (double (*)[TL_LD])(sp + 4 * TL_MAXO * TL_LD);
-    double *cm = sp + 5 * TL_MAXO * TL_LD;
-    double *Fo = cm, *Pm = cm + n2o, *W1 = cm + 2 * n2o, *Fop = cm + 3 * n2o, *Vo = cm + 4 * n2o, *cd = cm + 5 * n2o, *Xm = cm + 6 * n2o,
-           *Lig = cm + 7 * n2o, *L1g = cm + 8 * n2o, *MX = cm + 9 * n2o;
+    const Smalls m(sp + 5 * TL_MAXO * TL_LD, n2o);
     // Fo = Y^T F Y in the U basis (Y = Uo + Uv K), M = K^T K (P = Y^T Y = 1 + M)
-    if (all_lds) {
-        wg_gemm_lds(no, no, nv, Km, 1, no, Qm, no, 1, 1.0, 1.0, Bm, no, Fo, no);
-        wg_gemm_lds(no, no, nv, Km, 1, no, Km, no, 1, 1.0, 0.0, Km, 0, Pm, no);
-    } else {
-        wg_gemm(no, no, nv, Km, 1, no, Qm, no, 1, 1.0, 1.0, Bm, no, Fo, no);
-        wg_gemm(no, no, nv, Km, 1, no, Km, no, 1, 1.0, 0.0, nullptr, 0, Pm, no);
-    }
+    wg_gemm_if(all_lds, no, no, nv, Km, 1, no, Qm, no, 1, 1.0, 1.0, Bm, no, m.Fo, no);
+    wg_gemm_if(all_lds, no, no, nv, Km, 1, no, Km, no, 1, 1.0, 0.0, Km, 0, m.Pm, no);
     __syncthreads();
     QCDFT_STAMP(6);
-    chol_and_inverses<TL_MAXO>(no, Pm, Lm, Li, L1);
+    chol_and_inverses<TL_MAXO>(no, m.Pm, Lm, Li, L1);
     QCDFT_STAMP(7);
     for (int e = t; e < n2o; e += TL_ROT_T) {
         const int i = e / no, j = e - i * no;
-        Lig[e] = Li[i][j];
-        L1g[e] = L1[i][j];
+        m.Lig[e] = Li[i][j];
+        m.L1g[e] = L1[i][j];
     }
     __syncthreads();
     // G = L^-1 Fo L^-T
-    wg_gemm_lds(no, no, no, Lig, no, 1, Fo, no, 1, 1.0, 0.0, Fo, 0, W1, no);
+    wg_gemm<true>(no, no, no, m.Lig, no, 1, m.Fo, no, 1, 1.0, 0.0, m.Fo, 0, m.W1, no);
     __syncthreads();
-    wg_gemm_lds(no, no, no, W1, no, 1, Lig, 1, no, 1.0, 0.0, Fo, 0, Fop, no);
+    wg_gemm<true>(no, no, no, m.W1, no, 1, m.Lig, 1, no, 1.0, 0.0, m.Fo, 0, m.Fop, no);
     __syncthreads();
     QCDFT_STAMP(8);
-    // One-sided Jacobi on the columns of G - sigma (sigma above the spectrum: all eigenvalues of one sign, so orthogonal
-    // columns of (G - sigma) V are eigenvectors of G itself).  Half a wave per column pair (lane = row), the pairs of a
-    // round by the circle method; a pair whose columns are already orthogonal to a tenth of the tolerance is left alone.
-    const int ne = (no + 1) & ~1;
-    {
-        double gs = 0.0;
-        if (t < no) {
-            double rs = 0.0;
-            for (int j = 0; j < no; ++j) rs += fabs(0.5 * (Fop[t * no + j] + Fop[j * no + t]));
-            gs = rs;
-        }
-        const double sigma = block_max(gs, red) + 1.0;   // Gershgorin bound on |lambda|, plus a margin
-        // An occupied block that is diagonal to canon_tol (Hartree) already is left as it is: the fixed point's denominators
-        // only cross the gap, where off-diagonal elements of that size do not count (the virtual block is never diagonalised
-        // at all), and the orbital energies reported are Rayleigh quotients, exact to second order.
-        double off = 0.0;
-        for (int e = t; e < n2o; e += TL_ROT_T)
-            if (e / no != e % no) off = fmax(off, fabs(0.5 * (Fop[e] + Fop[(e % no) * no + e / no])));
-        const bool skip_sweeps = block_max(off, red) <= a.canon_tol;
-        for (int e = t; e < TL_MAXO * TL_MAXO; e += TL_ROT_T) {
-            const int j = e / TL_MAXO, i = e - j * TL_MAXO;   // column j, row i
-            double g = 0.0;
-            if (i < no && j < no) g = 0.5 * (Fop[i * no + j] + Fop[j * no + i]) - (i == j ? sigma : 0.0);
-            Wc[j][i] = g;
-            Vc[j][i] = i == j ? 1.0 : 0.0;
-        }
-        __syncthreads();
-        const int wave = t >> 6, lane = t & 63, npair = ne >> 1, row = lane & 31;
-        // Rotations converge quadratically: a sweep that met no pair with |cos| above canon_tol leaves all of them below
-        // ~canon_tol^2, which ends the iteration (canon_tol 1e-3: an occupied block diagonal to ~1e-6 of its scale -- the
-        // next cycle's denominators want no more, and the orbitals are exactly orthonormal whatever the rotations were).
-        const double stop2 = a.canon_tol * a.canon_tol, skip2 = 1e-26;
-        int sweeps = 0;
-        for (int sweep = 0; sweep < 12 && !skip_sweeps; ++sweep) {
-            int big = 0;
-            for (int round = 0; round < ne - 1; ++round) {
-                const int pr = 2 * wave + (lane >> 5);   // sixteen pairs at a time
-                if (2 * wave < npair) {
-                    const bool live = pr < npair && row < ne;
-                    // circle method: position 0 is held by column ne - 1, the others rotate
-                    const int p = !live ? 0 : pr == 0 ? ne - 1 : (round + pr) % (ne - 1);
-                    const int q = !live ? 0 : pr == 0 ? round : (round - pr + (ne - 1)) % (ne - 1);
-                    const double wp = live ? Wc[p][row] : 0.0, wq = live ? Wc[q][row] : 0.0;
-                    const double vp = live ? Vc[p][row] : 0.0, vq = live ? Vc[q][row] : 0.0;
-                    double al = row16_sum(wp * wp), be = row16_sum(wq * wq), ga = row16_sum(wp * wq);
-                    al += __shfl_xor(al, 16, 64); be += __shfl_xor(be, 16, 64); ga += __shfl_xor(ga, 16, 64);   // the pair's 32 lanes
-                    const double g2 = ga * ga, ab = al * be;
-                    if (live && g2 > skip2 * ab) {
-                        big |= g2 > stop2 * ab;
-                        const double zeta = 0.5 * (be - al) * fast_rcp(ga);
-                        const double az = fabs(zeta);
-                        const double hyp = az < 1e150 ? (1.0 + zeta * zeta) * fast_rsqrt(1.0 + zeta * zeta) : az;   // sqrt(1 + zeta^2)
-                        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) * fast_rcp(az + hyp);
-                        const double cs = fast_rsqrt(1.0 + tt * tt), sn = cs * tt;
-                        Wc[p][row] = cs * wp - sn * wq;
-                        Wc[q][row] = sn * wp + cs * wq;
-                        Vc[p][row] = cs * vp - sn * vq;
-                        Vc[q][row] = sn * vp + cs * vq;
-                    }
-                }
-                __syncthreads();
-            }
-            ++sweeps;
-            const int any = __ballot(big) != 0;
-            if (lane == 0) flag[wave] = any;
-            __syncthreads();
-            int more = 0;
-            for (int k = 0; k < TL_ROT_T / 64; ++k) more |= flag[k];
-            __syncthreads();
-            if (!more) break;
-        }
-        if (t == 0) status[2] = sweeps;
-        // eigenvalues lambda_j = v_j . (G v_j) = v_j . w_j + sigma
-        for (int j = wave; j < no; j += TL_ROT_T / 64) {
-            const double s = half_sum(lane < ne ? Vc[j][lane] * Wc[j][lane] : 0.0);
-            if (lane == 0) dd[j] = s + sigma;   // the occupied slots of dd now hold the new orbital energies
-        }
-        for (int e = t; e < n2o; e += TL_ROT_T) {
-            const int i = e / no, j = e - i * no;
-            Vo[e] = Vc[j][i];
-        }
-        __syncthreads();
-    }
+    const int sweeps = jacobi_occ<TL_MAXO>(no, a.canon_tol, m.Fop, Wc, Vc, m.Vo, dd, red, flag);   // half a wave per column pair
+    if (t == 0) status[2] = sweeps;
     QCDFT_STAMP(9);
-    // aufbau order: highest new occupied level against the lowest virtual diagonal (a necessary test only; the
-    // caller checks the converged state against a full diagonalisation, as scf.py does)
-    {
-        double eo = -INFINITY, dv = INFINITY;
-        if (t < no) eo = dd[t];
-        else if (t < n) dv = dd[t];
-        const double eomax = block_max(eo, red), dvmin = -block_max(-dv, red);
-        if (eomax > dvmin - 1e-3) {
-            if (t == 0) status[0] = 1;
-            return;
-        }
+    if (!aufbau_and_eig(n, no, dd, red, eig)) {
+        if (t == 0) status[0] = 1;
+        return;
     }
-    if (eig && t < n) eig[t] = dd[t];
     // The new basis as ONE product U' = U W (the next launch, on the whole chip):
     //   U_o' = (U_o + U_v K) c,   c = L^-T V                      ->  W[:, :no] = [c; K c]
     //   U_v' = T (1 + K X K^T),   T = U_v - U_o K^T, X = -L^-T (1 + L)^-1  ->  W[:, no:] = [-(1 + M X) K^T; 1 + (K X) K^T]
     double *Kc = Qm, *KX = Rm;   // Q and R are done with
-    wg_gemm_lds(no, no, no, Lig, 1, no, Vo, no, 1, 1.0, 0.0, Vo, 0, cd, no);           // c = L^-T V
-    wg_gemm_lds(no, no, no, Lig, 1, no, L1g, no, 1, -1.0, 0.0, Vo, 0, Xm, no);         // X = -L^-T (1 + L)^-1
+    wg_gemm<true>(no, no, no, m.Lig, 1, no, m.Vo, no, 1, 1.0, 0.0, m.Vo, 0, m.cd, no);           // c = L^-T V
+    wg_gemm<true>(no, no, no, m.Lig, 1, no, m.L1g, no, 1, -1.0, 0.0, m.Vo, 0, m.Xm, no);         // X = -L^-T (1 + L)^-1
     __syncthreads();
-    if (all_lds) {
-        wg_gemm_lds(nv, no, no, Km, no, 1, cd, no, 1, 1.0, 0.0, cd, 0, Kc, no);
-        wg_gemm_lds(nv, no, no, Km, no, 1, Xm, no, 1, 1.0, 0.0, cd, 0, KX, no);
-    } else {
-        wg_gemm(nv, no, no, Km, no, 1, cd, no, 1, 1.0, 0.0, nullptr, 0, Kc, no);
-        wg_gemm(nv, no, no, Km, no, 1, Xm, no, 1, 1.0, 0.0, nullptr, 0, KX, no);
-    }
-    wg_gemm_lds(no, no, no, Pm, no, 1, Xm, no, 1, 1.0, 0.0, cd, 0, MX, no);            // M X
-    for (int e = t; e < n2o; e += TL_ROT_T) W[(size_t)(e / no) * n + e % no] = cd[e];
+    wg_gemm_if(all_lds, nv, no, no, Km, no, 1, m.cd, no, 1, 1.0, 0.0, m.cd, 0, Kc, no);
+    wg_gemm_if(all_lds, nv, no, no, Km, no, 1, m.Xm, no, 1, 1.0, 0.0, m.cd, 0, KX, no);
+    wg_gemm<true>(no, no, no, m.Pm, no, 1, m.Xm, no, 1, 1.0, 0.0, m.cd, 0, m.MX, no);            // M X
+    for (int e = t; e < n2o; e += TL_ROT_T) W[(size_t)(e / no) * n + e % no] = m.cd[e];
     __syncthreads();
-    for (int e = t; e < n2o; e += TL_ROT_T) MX[e] += e / no == e % no ? 1.0 : 0.0;     // 1 + M X
+    for (int e = t; e < n2o; e += TL_ROT_T) m.MX[e] += e / no == e % no ? 1.0 : 0.0;     // 1 + M X
     for (int e = t; e < nk; e += TL_ROT_T) W[(size_t)(no + e / no) * n + e % no] = Kc[e];
     __syncthreads();
-    wg_gemm(no, nv, no, MX, no, 1, Km, 1, no, -1.0, 0.0, nullptr, 0, W + no, n);                      // -(1 + M X) K^T
-    wg_gemm(nv, nv, no, KX, no, 1, Km, 1, no, 1.0, 0.0, nullptr, 0, W + (size_t)no * n + no, n);      // (K X) K^T ...
+    wg_gemm<false>(no, nv, no, m.MX, no, 1, Km, 1, no, -1.0, 0.0, nullptr, 0, W + no, n);                      // -(1 + M X) K^T
+    wg_gemm<false>(nv, nv, no, KX, no, 1, Km, 1, no, 1.0, 0.0, nullptr, 0, W + (size_t)no * n + no, n);      // (K X) K^T ...
     __syncthreads();
     if (t < nv) W[(size_t)(no + t) * n + no + t] += 1.0;                                              // ... + 1
     QCDFT_STAMP(10);
@@ -798,40 +824,6 @@ __global__ __launch_bounds__(TL_ROT_T) void k_tail_rot(TailArgs a, RotLds lo, co
 // iteration's state (converged / failed, step count, which of the two K buffers is current, the last residual) lives in
 // memory, every kernel of a step returns at once when the iteration is over, and the host queues a few more steps than the
 // last cycle needed (status 3 asks for more).
-struct RbState {
-    int done, ok, steps, cur;
-    double prev;
-    unsigned long long rmax_bits;
-};
-
-// one 16 x 16 tile of A B on four waves (the contraction dealt to them), summed into wave 0's registers; see k_tail_gemm
-__device__ __forceinline__ void tile_splitk(int i0, int j0, int M, int N, int Kd, const double *a, int ars, int acs, const double *b, int brs,
-                                            int bcs, double (*part)[4][64], double (&out)[4])
-{
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, kq = lane >> 4;
-    const int ia = i0 + li, jb = j0 + li;
-    const bool aok = ia < M, bok = jb < N;
-    d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < Kd; k0 += 128) {
-        double av[8], bv[8];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int k = k0 + 4 * (4 * s + wave) + kq;
-            av[s] = aok && k < Kd ? a[(size_t)ia * ars + (size_t)k * acs] : 0.0;
-            bv[s] = bok && k < Kd ? b[(size_t)k * brs + (size_t)jb * bcs] : 0.0;
-        }
-#pragma unroll
-        for (int s = 0; s < 8; s += 2) {
-            acc0 = mfma_f64(av[s], bv[s], acc0);
-            acc1 = mfma_f64(av[s + 1], bv[s + 1], acc1);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) part[wave][r][lane] = acc0[r] + acc1[r];
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[r] = (part[0][r][lane] + part[1][r][lane]) + (part[2][r][lane] + part[3][r][lane]);
-}
 
 // Qt = Aov + K^T Avv (tiles [0, ntq)) and Bt = Aoo + K^T Avo (the rest), K = the current buffer
 __global__ __launch_bounds__(256) void k_rb_qb(const RbState *__restrict__ st, int n, int no, const double *__restrict__ A,
@@ -947,26 +939,17 @@ __global__ void k_tail_clear_more(int *status)
 // occupied): one workgroup again -- a barrier across workgroups costs 4 us plus 0.3 us per workgroup on this chip
 // (tools/gridsync_probe.hip, agent-scope fences either side), more than the phases it would separate -- with every operand in
 // memory (L2-resident: A is 0.5-2 MB) behind generic pointers, the n_occ x n_occ triangular matrices alone in LDS.
-__global__ __launch_bounds__(TL_ROT_T) void k_tail_rot_big(TailArgs a, const double *__restrict__ A, double *Km, double *K2, double *Kt,
-                                                           double *Kt2, double *Qt, double *Rt, double *Bt, double *rdt, double *smalls,
-                                                           double *W, double *eig, int *status, long long *stamps, double *Kfix, double *KXg,
-                                                           int mode, RbState *st)
+// k_rb_start: K0, its 0.5 test and the iteration's state, before the step launches; k_rb_finish: the completion, from the
+// state those left (Fo and M from k_rb_fop; K c, K X and the wide blocks of W by the tile launches behind it).
+__global__ __launch_bounds__(TL_ROT_T) void k_rb_start(int n, int no, const double *__restrict__ A, double *Km, double *Kt, double *rdt,
+                                                       int *status, RbState *st)
 {
-    // mode 0: everything here; 1: the start only (K0, its test, the iteration's state) -- the steps run as launches of
-    // their own (k_rb_qb / k_rb_r / k_rb_decide); 2: the completion only, from the state those left
-#define QCDFT_STAMP(k) do { if (threadIdx.x == 0) stamps[k] = (long long)wall_clock64(); } while (0)
-    extern __shared__ double dyn[];   // L, L^-1, (1 + L)^-1; the Jacobi columns reuse the last two
     __shared__ double dd[TL_BIGN], red[TL_ROT_T / 64];
-    __shared__ int flag[TL_ROT_T / 64];
-    const int n = a.n, no = a.no, nv = n - no, t = threadIdx.x, nk = nv * no, n2o = no * no;
+    const int nv = n - no, t = threadIdx.x, nk = nv * no;
     if (status[0] != 0) return;
-    QCDFT_STAMP(0);
-    const double *Aoo = A, *Aov = A + no, *Avo = A + (size_t)no * n, *Avv = A + (size_t)no * n + no;
+    const double *Aov = A + no;
     for (int i = t; i < n; i += TL_ROT_T) dd[i] = A[(size_t)i * n + i];
     __syncthreads();
-    bool ok = false;
-    int steps = 0;
-    if (mode != 2) {
     // K lives twice, as K[v][o] and as its transpose Kt[o][v]: with both, every large operand below is read along its rows
     // (16 lanes x 8 B from one 128-byte line; the strided alternative touches 16 lines per load and is bound by that, 4x slower)
     double kmax = 0.0;
@@ -981,195 +964,65 @@ __global__ __launch_bounds__(TL_ROT_T) void k_tail_rot_big(TailArgs a, const dou
         if (!(fabs(x) <= 0.5)) kmax = 1.0;
     }
     kmax = block_max(kmax, red);
-    if (!(kmax <= 0.5)) {
-        if (t == 0) { status[0] = 1; if (mode == 1) { st->done = 1; st->ok = 0; st->steps = 0; } }
+    if (t != 0) return;
+    const bool go = kmax <= 0.5;   // (false for NaN too)
+    if (!go) status[0] = 1;
+    st->done = !go; st->ok = 0; st->steps = 0; st->cur = 0; st->prev = INFINITY; st->rmax_bits = 0ULL;
+}
+
+__global__ __launch_bounds__(TL_ROT_T) void k_rb_finish(TailArgs a, const double *__restrict__ A, const double *K0, const double *K1,
+                                                        double *smalls, double *W, double *eig, int *status, double *Kfix,
+                                                        const RbState *st)
+{
+    extern __shared__ double dyn[];   // L, L^-1, (1 + L)^-1; the Jacobi columns reuse the last two
+    __shared__ double dd[TL_BIGN], red[TL_ROT_T / 64];
+    __shared__ int flag[TL_ROT_T / 64];
+    const int n = a.n, no = a.no, nv = n - no, t = threadIdx.x, nk = nv * no, n2o = no * no;
+    if (status[0] != 0) return;
+    for (int i = t; i < n; i += TL_ROT_T) dd[i] = A[(size_t)i * n + i];
+    __syncthreads();
+    if (!st->done) {
+        if (t == 0) status[0] = 3;   // more steps, please
         return;
     }
-    QCDFT_STAMP(1);
-    if (mode == 1) {
-        if (t == 0) { st->done = 0; st->ok = 0; st->steps = 0; st->cur = 0; st->prev = INFINITY; st->rmax_bits = 0ULL; }
-        return;
-    }
-    double prev = INFINITY;
-    for (int it = 0; it < a.max_inner; ++it) {
-        // Qt = (Avo + Avv K)^T = Aov + K^T Avv,  Bt = (Aoo + Aov K)^T = Aoo + K^T Avo   (A symmetric)
-        wg_gemm(no, nv, nv, Km, 1, no, Avv, n, 1, 1.0, 1.0, Aov, n, Qt, nv);
-        wg_gemm(no, no, nv, Km, 1, no, Avo, n, 1, 1.0, 1.0, Aoo, n, Bt, no);
-        __syncthreads();
-        if (it == 0) QCDFT_STAMP(2);
-        // Rt = (Q - K B)^T = Qt - Bt Kt
-        wg_gemm(no, nv, no, Bt, no, 1, Kt, nv, 1, -1.0, 1.0, Qt, nv, Rt, nv);
-        __syncthreads();
-        if (it == 0) QCDFT_STAMP(3);
-        double r = 0.0;
-        for (int e0 = 0; e0 < nk; e0 += 4 * TL_ROT_T) {   // four elements per thread in flight
-            double rv[4], kv[4], dv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int e = e0 + k * TL_ROT_T + t;
-                rv[k] = e < nk ? Rt[e] : 0.0; kv[k] = e < nk ? Kt[e] : 0.0; dv[k] = e < nk ? rdt[e] : 0.0;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int e = e0 + k * TL_ROT_T + t;
-                const double x = fabs(rv[k]);
-                r = fmax(r, x);
-                if (!(x == x)) r = INFINITY;
-                if (e < nk) {   // the tentative update, in both layouts
-                    const double kn = kv[k] - rv[k] * dv[k];
-                    Kt2[e] = kn;
-                    K2[(size_t)(e % nv) * no + e / nv] = kn;
-                }
-            }
-        }
-        r = block_max(r, red);
-        ++steps;
-        if (r < a.tol) { ok = true; break; }
-        if (!(r < 4.0 * prev)) break;
-        prev = fmin(prev, r);
-        { double *tmp = Km; Km = K2; K2 = tmp; tmp = Kt; Kt = Kt2; Kt2 = tmp; }
-        if (it == 0) QCDFT_STAMP(4);
-    }
-    } else {   // mode 2: what the step launches left
-        if (!st->done) {
-            if (t == 0) status[0] = 3;   // more steps, please
-            return;
-        }
-        ok = st->ok != 0;
-        steps = st->steps;
-        if (st->cur) { Km = K2; Kt = Kt2; }
-    }
-    QCDFT_STAMP(5);
-    if (t == 0) status[1] = steps;
-    if (!ok) {
+    if (t == 0) status[1] = st->steps;
+    if (!st->ok) {
         if (t == 0) status[0] = 1;
         return;
     }
+    const double *Km = st->cur ? K1 : K0;   // wherever the iteration left K
     double (*Lm)[TL_BLD] = (double (*)[TL_BLD])dyn, (*Li)[TL_BLD] = (double (*)[TL_BLD])(dyn + TL_BIGO * TL_BLD),
            (*L1)[TL_BLD] = (double (*)[TL_BLD])(dyn + 2 * TL_BIGO * TL_BLD);
-    double *Fo = smalls, *Pm = smalls + n2o, *W1 = smalls + 2 * n2o, *Fop = smalls + 3 * n2o, *Vo = smalls + 4 * n2o, *cd = smalls + 5 * n2o,
-           *Xm = smalls + 6 * n2o, *Lig = smalls + 7 * n2o, *L1g = smalls + 8 * n2o, *MX = smalls + 9 * n2o;
-    // Fo^T = Bt + Q^T K (the transpose does as well: only the symmetrised G = L^-1 Fo L^-T is used), M = K^T K
-    if (mode != 2) {   // (mode 2: k_rb_fop has left both)
-        wg_gemm(no, no, nv, Qt, nv, 1, Km, no, 1, 1.0, 1.0, Bt, no, Fo, no);
-        wg_gemm(no, no, nv, Km, 1, no, Km, no, 1, 1.0, 0.0, nullptr, 0, Pm, no);
-        __syncthreads();
-    }
-    QCDFT_STAMP(6);
-    chol_and_inverses<TL_BIGO>(no, Pm, Lm, Li, L1);
-    QCDFT_STAMP(7);
+    // k_rb_fop has left Fo^T = Bt + Q^T K (the transpose does as well: only the symmetrised G = L^-1 Fo L^-T is used) and M = K^T K
+    const Smalls m(smalls, n2o);
+    chol_and_inverses<TL_BIGO>(no, m.Pm, Lm, Li, L1);
     for (int e = t; e < n2o; e += TL_ROT_T) {
         const int i = e / no, j = e - i * no;
-        Lig[e] = Li[i][j];
-        L1g[e] = L1[i][j];
+        m.Lig[e] = Li[i][j];
+        m.L1g[e] = L1[i][j];
     }
     __syncthreads();
-    wg_gemm(no, no, no, Lig, no, 1, Fo, no, 1, 1.0, 0.0, nullptr, 0, W1, no);
+    wg_gemm<false>(no, no, no, m.Lig, no, 1, m.Fo, no, 1, 1.0, 0.0, nullptr, 0, m.W1, no);
     __syncthreads();
-    wg_gemm(no, no, no, W1, no, 1, Lig, 1, no, 1.0, 0.0, nullptr, 0, Fop, no);
+    wg_gemm<false>(no, no, no, m.W1, no, 1, m.Lig, 1, no, 1.0, 0.0, nullptr, 0, m.Fop, no);
     __syncthreads();
-    QCDFT_STAMP(8);
-    {
-        // Jacobi as in k_tail_rot, a whole wave per column pair (lane = row, up to 64 rows), eight pairs at a time
-        double (*Wc)[TL_BLD] = Li, (*Vc)[TL_BLD] = L1;   // their contents are in memory now
-        const int ne = (no + 1) & ~1, wave = t >> 6, lane = t & 63, npair = ne >> 1;
-        double gs = 0.0, off = 0.0;
-        if (t < no)
-            for (int j = 0; j < no; ++j) gs += fabs(0.5 * (Fop[t * no + j] + Fop[j * no + t]));
-        const double sigma = block_max(gs, red) + 1.0;
-        for (int e = t; e < n2o; e += TL_ROT_T)
-            if (e / no != e % no) off = fmax(off, fabs(0.5 * (Fop[e] + Fop[(e % no) * no + e / no])));
-        const bool skip_sweeps = block_max(off, red) <= a.canon_tol;
-        for (int e = t; e < TL_BIGO * TL_BIGO; e += TL_ROT_T) {
-            const int j = e / TL_BIGO, i = e - j * TL_BIGO;
-            double g = 0.0;
-            if (i < no && j < no) g = 0.5 * (Fop[i * no + j] + Fop[j * no + i]) - (i == j ? sigma : 0.0);
-            Wc[j][i] = g;
-            Vc[j][i] = i == j ? 1.0 : 0.0;
-        }
-        __syncthreads();
-        const double stop2 = a.canon_tol * a.canon_tol, skip2 = 1e-26;
-        int sweeps = 0;
-        for (int sweep = 0; sweep < 12 && !skip_sweeps; ++sweep) {
-            int big = 0;
-            for (int round = 0; round < ne - 1; ++round) {
-                for (int pr = wave; pr < npair; pr += TL_ROT_T / 64) {
-                    const bool live = lane < ne;
-                    const int p = pr == 0 ? ne - 1 : (round + pr) % (ne - 1);
-                    const int q = pr == 0 ? round : (round - pr + (ne - 1)) % (ne - 1);
-                    const double wp = live ? Wc[p][lane] : 0.0, wq = live ? Wc[q][lane] : 0.0;
-                    const double vp = live ? Vc[p][lane] : 0.0, vq = live ? Vc[q][lane] : 0.0;
-                    const double al = wave_sum(wp * wp), be = wave_sum(wq * wq), ga = wave_sum(wp * wq);
-                    const double g2 = ga * ga, ab = al * be;
-                    if (live && g2 > skip2 * ab) {
-                        big |= g2 > stop2 * ab;
-                        const double zeta = 0.5 * (be - al) * fast_rcp(ga);
-                        const double az = fabs(zeta);
-                        const double hyp = az < 1e150 ? (1.0 + zeta * zeta) * fast_rsqrt(1.0 + zeta * zeta) : az;
-                        const double tt = (zeta >= 0.0 ? 1.0 : -1.0) * fast_rcp(az + hyp);
-                        const double cs = fast_rsqrt(1.0 + tt * tt), sn = cs * tt;
-                        Wc[p][lane] = cs * wp - sn * wq;
-                        Wc[q][lane] = sn * wp + cs * wq;
-                        Vc[p][lane] = cs * vp - sn * vq;
-                        Vc[q][lane] = sn * vp + cs * vq;
-                    }
-                }
-                __syncthreads();
-            }
-            ++sweeps;
-            const int any = __ballot(big) != 0;
-            if (lane == 0) flag[wave] = any;
-            __syncthreads();
-            int more = 0;
-            for (int k = 0; k < TL_ROT_T / 64; ++k) more |= flag[k];
-            __syncthreads();
-            if (!more) break;
-        }
-        if (t == 0) status[2] = sweeps;
-        for (int j = wave; j < no; j += TL_ROT_T / 64) {
-            const double sj = wave_sum(lane < ne ? Vc[j][lane] * Wc[j][lane] : 0.0);
-            if (lane == 0) dd[j] = sj + sigma;
-        }
-        for (int e = t; e < n2o; e += TL_ROT_T) {
-            const int i = e / no, j = e - i * no;
-            Vo[e] = Vc[j][i];
-        }
-        __syncthreads();
+    // a whole wave per column pair (up to 64 rows), eight pairs at a time; Li and L1 are in memory now: their space takes the columns
+    const int sweeps = jacobi_occ<TL_BIGO>(no, a.canon_tol, m.Fop, Li, L1, m.Vo, dd, red, flag);
+    if (t == 0) status[2] = sweeps;
+    if (!aufbau_and_eig(n, no, dd, red, eig)) {
+        if (t == 0) status[0] = 1;
+        return;
     }
-    QCDFT_STAMP(9);
-    {
-        double eo = -INFINITY, dv = INFINITY;
-        for (int i = t; i < n; i += TL_ROT_T) {
-            if (i < no) eo = fmax(eo, dd[i]);
-            else dv = fmin(dv, dd[i]);
-        }
-        const double eomax = block_max(eo, red), dvmin = -block_max(-dv, red);
-        if (eomax > dvmin - 1e-3) {
-            if (t == 0) status[0] = 1;
-            return;
-        }
-    }
-    if (eig)
-        for (int i = t; i < n; i += TL_ROT_T) eig[i] = dd[i];
-    // W = [c, -(1 + M X) K^T; K c, 1 + (K X) K^T] (see k_tail_rot): the two left blocks and the small factors here, the two
-    // right blocks (n_virt columns: hundreds of tiles) by the launches behind this kernel, which read K, K X and 1 + M X
-    double *Kc = Qt;   // (n_virt x n_occ, row-major; Q is done with)
-    wg_gemm(no, no, no, Lig, 1, no, Vo, no, 1, 1.0, 0.0, nullptr, 0, cd, no);
-    wg_gemm(no, no, no, Lig, 1, no, L1g, no, 1, -1.0, 0.0, nullptr, 0, Xm, no);
-    for (int e = t; e < nk; e += TL_ROT_T) Kfix[e] = Km[e];   // wherever the iteration left K
+    // W = [c, -(1 + M X) K^T; K c, 1 + (K X) K^T] (see k_tail_rot): the upper left block and the small factors here, the
+    // other three (n_virt rows or columns: hundreds of tiles) by the launches behind this kernel, which read K, K X and 1 + M X
+    wg_gemm<false>(no, no, no, m.Lig, 1, no, m.Vo, no, 1, 1.0, 0.0, nullptr, 0, m.cd, no);
+    wg_gemm<false>(no, no, no, m.Lig, 1, no, m.L1g, no, 1, -1.0, 0.0, nullptr, 0, m.Xm, no);
+    for (int e = t; e < nk; e += TL_ROT_T) Kfix[e] = Km[e];
     __syncthreads();
-    if (mode != 2) {   // (mode 2: K c straight into W and K X by tile launches behind this kernel)
-        wg_gemm(nv, no, no, Kfix, no, 1, cd, no, 1, 1.0, 0.0, nullptr, 0, Kc, no);
-        wg_gemm(nv, no, no, Kfix, no, 1, Xm, no, 1, 1.0, 0.0, nullptr, 0, KXg, no);
-    }
-    wg_gemm(no, no, no, Pm, no, 1, Xm, no, 1, 1.0, 0.0, nullptr, 0, MX, no);
-    for (int e = t; e < n2o; e += TL_ROT_T) W[(size_t)(e / no) * n + e % no] = cd[e];
+    wg_gemm<false>(no, no, no, m.Pm, no, 1, m.Xm, no, 1, 1.0, 0.0, nullptr, 0, m.MX, no);
+    for (int e = t; e < n2o; e += TL_ROT_T) W[(size_t)(e / no) * n + e % no] = m.cd[e];
     __syncthreads();
-    for (int e = t; e < n2o; e += TL_ROT_T) MX[e] += e / no == e % no ? 1.0 : 0.0;
-    if (mode != 2)
-        for (int e = t; e < nk; e += TL_ROT_T) W[(size_t)(no + e / no) * n + e % no] = Kc[e];
-    QCDFT_STAMP(10);
-#undef QCDFT_STAMP
+    for (int e = t; e < n2o; e += TL_ROT_T) m.MX[e] += e / no == e % no ? 1.0 : 0.0;
 }
 
 // Row i of dm' = c' c'^T and of the energy traces; on success the new basis and orbitals replace the old ones.  The last
@@ -1257,29 +1110,31 @@ void launch_big_finish(TailDev *c, const TailArgs &a)
 {
     const int n = c->n, no = c->no, nv = n - no, nto = (no + 15) / 16, ntv = (nv + 15) / 16;
     hipStream_t st = c->stream;
-    double *W = c->FU, *sm = c->smalls;
-    const size_t n2o = (size_t)no * no;
-    hipLaunchKernelGGL(k_rb_fop, dim3(2 * nto * nto), dim3(256), 0, st, c->state, n, no, c->Km, c->K2, c->Qm, c->Bm, sm, sm + n2o);
-    hipLaunchKernelGGL(k_tail_rot_big, dim3(1), dim3(TL_ROT_T), c->rot_lds, st, a, c->A, c->Km, c->K2, c->Kt, c->Kt2, c->Qm, c->Rm, c->Bm,
-                       c->rden, sm, W, c->eig, c->status, (long long *)(c->status + 8), c->Kfix, c->KXg, 2, c->state);
-    hipLaunchKernelGGL(k_tail_gemm, dim3(ntv * nto), dim3(256), 0, st, nv, no, no, c->Kfix, no, 1, sm + 5 * n2o, no, 1,
-                       W + (size_t)no * n, n, 1.0, 0, c->status);                                  // K c (W's lower left block)
-    hipLaunchKernelGGL(k_tail_gemm, dim3(ntv * nto), dim3(256), 0, st, nv, no, no, c->Kfix, no, 1, sm + 6 * n2o, no, 1,
-                       c->KXg, no, 1.0, 0, c->status);                                             // K X
-    hipLaunchKernelGGL(k_tail_gemm, dim3(nto * ntv), dim3(256), 0, st, no, nv, no, sm + 9 * n2o, no, 1, c->Kfix, 1, no,
-                       W + no, n, -1.0, 0, c->status);                                             // -(1 + M X) K^T
+    double *W = c->FU;
+    int *status = c->status->word;
+    const Smalls m(c->smalls, (size_t)no * no);
+    hipLaunchKernelGGL(k_rb_fop, dim3(2 * nto * nto), dim3(256), 0, st, &c->status->state, n, no, c->Km, c->K2, c->Qm, c->Bm, m.Fo, m.Pm);
+    hipLaunchKernelGGL(k_rb_finish, dim3(1), dim3(TL_ROT_T), c->rot_lds, st, a, c->A, c->Km, c->K2, c->smalls, W, c->eig, status, c->Kfix,
+                       &c->status->state);
+    hipLaunchKernelGGL(k_tail_gemm, dim3(ntv * nto), dim3(256), 0, st, nv, no, no, c->Kfix, no, 1, m.cd, no, 1,
+                       W + (size_t)no * n, n, 1.0, 0, status);                                     // K c (W's lower left block)
+    hipLaunchKernelGGL(k_tail_gemm, dim3(ntv * nto), dim3(256), 0, st, nv, no, no, c->Kfix, no, 1, m.Xm, no, 1,
+                       c->KXg, no, 1.0, 0, status);                                                // K X
+    hipLaunchKernelGGL(k_tail_gemm, dim3(nto * ntv), dim3(256), 0, st, no, nv, no, m.MX, no, 1, c->Kfix, 1, no,
+                       W + no, n, -1.0, 0, status);                                                // -(1 + M X) K^T
     hipLaunchKernelGGL(k_tail_gemm, dim3(ntv * ntv), dim3(256), 0, st, nv, nv, no, c->KXg, no, 1, c->Kfix, 1, no,
-                       W + (size_t)no * n + no, n, 1.0, 1, c->status);                             // 1 + (K X) K^T
+                       W + (size_t)no * n + no, n, 1.0, 1, status);                                // 1 + (K X) K^T
 }
 
 // `nsteps` fixed-point steps of the memory-resident rotation, three launches each (they return at once when the iteration is over)
 void launch_big_steps(TailDev *c, const TailArgs &a, int nsteps)
 {
     const int n = c->n, no = c->no, nv = n - no, nto = (no + 15) / 16, ntv = (nv + 15) / 16;
+    RbState *state = &c->status->state;
     for (int k = 0; k < nsteps; ++k) {
-        hipLaunchKernelGGL(k_rb_qb, dim3(nto * ntv + nto * nto), dim3(256), 0, c->stream, c->state, n, no, c->A, c->Km, c->K2, c->Qm, c->Bm);
-        hipLaunchKernelGGL(k_rb_r, dim3(nto * ntv), dim3(256), 0, c->stream, c->state, n, no, c->Qm, c->Bm, c->rden, c->Km, c->K2, c->Kt, c->Kt2);
-        hipLaunchKernelGGL(k_rb_decide, dim3(1), dim3(1), 0, c->stream, c->state, a.tol, a.max_inner);
+        hipLaunchKernelGGL(k_rb_qb, dim3(nto * ntv + nto * nto), dim3(256), 0, c->stream, state, n, no, c->A, c->Km, c->K2, c->Qm, c->Bm);
+        hipLaunchKernelGGL(k_rb_r, dim3(nto * ntv), dim3(256), 0, c->stream, state, n, no, c->Qm, c->Bm, c->rden, c->Km, c->K2, c->Kt, c->Kt2);
+        hipLaunchKernelGGL(k_rb_decide, dim3(1), dim3(1), 0, c->stream, state, a.tol, a.max_inner);
     }
 }
 
@@ -1287,6 +1142,21 @@ void tail_error(TailDev *c, const char *what, hipError_t e)
 {
     snprintf(c->err, sizeof c->err, "%s: %s", what, hipGetErrorString(e));
     fprintf(stderr, "libdft: %s\n", c->err);
+}
+
+// The end of a step: U' = U W behind a rotation, the density kernel, and the check of every launch so far
+int launch_basis_density(TailDev *c, const TailArgs &a, bool rotated, unsigned long long d_J, unsigned long long d_K, unsigned long long d_dm,
+                         unsigned long long d_cocc, unsigned long long d_exc)
+{
+    const int n = c->n, nt = (n + 15) / 16;
+    int *status = c->status->word;
+    if (rotated)
+        hipLaunchKernelGGL(k_tail_gemm, dim3(nt * nt), dim3(256), 0, c->stream, n, n, n, c->U, n, 1, c->FU, n, 1, c->Unew, n, 1.0, 0, status);
+    hipLaunchKernelGGL(k_tail_density, dim3(n), dim3(128), 0, c->stream, a, 0, ++c->seq, c->H, (const double *)d_J, (const double *)d_K, c->U,
+                       c->Unew, (double *)d_dm, (double *)d_cocc, c->epart, status, (const double *)d_exc, c->h_out_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { tail_error(c, "SCF tail launch", e); return -1; }
+    return 0;
 }
 
 } // namespace
@@ -1305,12 +1175,17 @@ void *DFT_ScfTailOpen(int nao, int nocc, unsigned long long d_hcore, unsigned lo
     c->U = (double *)d_basis; c->Fx = (double *)d_fock_out; c->eig = (double *)d_mo_energy;
     c->big = nao > TL_MAXN || nocc > TL_MAXO;
     const size_t bigk = c->big ? nv * no : 0;
-    const size_t sizes[] = {TL_SPACE * n2, TL_SPACE * n2, TL_SPACE * TL_SPACE, n * no, n * no, n * TL_SPACE, n2, n2, n2,
-                            nv * no, nv * no, nv * no, no * no, 4 * n, bigk, c->big ? 10 * no * no : 0, bigk, bigk, bigk, bigk, bigk};
+    // the blob's buffers in order (Rm is read by k_tail_rot alone; rden .. K2 exist on the memory-resident path only)
+    const struct { double *TailDev::*buf; size_t size; } blob[] = {
+        {&TailDev::Fb, TL_SPACE * n2}, {&TailDev::Eb, TL_SPACE * n2}, {&TailDev::Gb, TL_SPACE * TL_SPACE}, {&TailDev::FC, n * no},
+        {&TailDev::SC, n * no}, {&TailDev::gpart, n * TL_SPACE}, {&TailDev::FU, n2}, {&TailDev::A, n2}, {&TailDev::Unew, n2},
+        {&TailDev::Km, nv * no}, {&TailDev::Rm, nv * no}, {&TailDev::Qm, nv * no}, {&TailDev::Bm, no * no}, {&TailDev::epart, 4 * n},
+        {&TailDev::rden, bigk}, {&TailDev::smalls, c->big ? Smalls::COUNT * no * no : 0}, {&TailDev::Kfix, bigk}, {&TailDev::KXg, bigk},
+        {&TailDev::Kt, bigk}, {&TailDev::Kt2, bigk}, {&TailDev::K2, bigk}};
     size_t total = 0;
-    for (size_t s : sizes) total += (s + 1) & ~(size_t)1;
-    if (hipMalloc((void **)&c->blob, total * sizeof(double) + 512) != hipSuccess ||
-        hipMemset(c->blob, 0, total * sizeof(double) + 512) != hipSuccess ||
+    for (const auto &e : blob) total += (e.size + 1) & ~(size_t)1;   // every buffer on a 16-byte boundary
+    const size_t bytes = total * sizeof(double) + sizeof(TailStatus);
+    if (hipMalloc((void **)&c->blob, bytes) != hipSuccess || hipMemset(c->blob, 0, bytes) != hipSuccess ||
         hipHostMalloc((void **)&c->h_out, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -1319,19 +1194,16 @@ void *DFT_ScfTailOpen(int nao, int nocc, unsigned long long d_hcore, unsigned lo
         delete c;
         return nullptr;
     }
-    double **slots[] = {&c->Fb, &c->Eb, &c->Gb, &c->FC, &c->SC, &c->gpart, &c->FU, &c->A, &c->Unew, &c->Km, &c->Rm, &c->Qm, &c->Bm, &c->epart,
-                        &c->rden, &c->smalls, &c->Kfix, &c->KXg, &c->Kt, &c->Kt2, &c->K2};
     double *p = c->blob;
-    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
-        *slots[i] = p;
-        p += (sizes[i] + 1) & ~(size_t)1;
+    for (const auto &e : blob) {
+        c->*e.buf = p;
+        p += (e.size + 1) & ~(size_t)1;
     }
-    c->status = (int *)p;
-    c->state = (RbState *)(c->status + 40);   // [0..3] status words, [8..39] the rotation kernels' stamps, then the state
+    c->status = (TailStatus *)p;
     memset(c->h_out, 0, 16 * sizeof(double));
     // k_tail_rot: A in LDS during the fixed point (the completion's small matrices reuse its space), then K, B, Q, R as 160 KB allow
     {
-        const size_t smalls = 5 * (size_t)TL_MAXO * TL_LD + 10 * no * no, budget = (160 * 1024 - 2048) / sizeof(double);
+        const size_t smalls = 5 * (size_t)TL_MAXO * TL_LD + Smalls::COUNT * no * no, budget = (160 * 1024 - 2048) / sizeof(double);
         size_t off = (std::max(n2, smalls) + 1) & ~(size_t)1;
         const size_t want[4] = {nv * no, no * no, nv * no, nv * no};
         int *where[4] = {&c->lo.km, &c->lo.bm, &c->lo.qm, &c->lo.rm};
@@ -1342,7 +1214,7 @@ void *DFT_ScfTailOpen(int nao, int nocc, unsigned long long d_hcore, unsigned lo
         c->rot_lds = (unsigned)(off * sizeof(double));
     }
     if (c->big) c->rot_lds = (unsigned)(3 * (size_t)TL_BIGO * TL_BLD * sizeof(double));
-    if (hipFuncSetAttribute(c->big ? (const void *)k_tail_rot_big : (const void *)k_tail_rot, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(c->big ? (const void *)k_rb_finish : (const void *)k_tail_rot, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)c->rot_lds) != hipSuccess) {
         (void)hipGetLastError();
         DFT_ScfTailClose(c);
@@ -1401,36 +1273,28 @@ int DFT_ScfTailStep(void *h, int rotate, double c_hf, double tol, double canon_t
     a.c_hf = c_hf; a.tol = tol; a.canon_tol = canon_tol > 0.0 ? canon_tol : 1e-3;
     c->last = a;
     const int n = c->n;
-    const double *J = (const double *)d_J, *K = (const double *)d_K, *V = (const double *)d_vraw;
-    double *dm = (double *)d_dm, *cocc = (double *)d_cocc;
+    const double *J = (const double *)d_J, *K = (const double *)d_K, *V = (const double *)d_vraw, *cocc = (const double *)d_cocc;
     hipStream_t st = c->stream;
-    const unsigned long seq = ++c->seq;
+    int *status = c->status->word;
     const int nt = (n + 15) / 16;
-    hipLaunchKernelGGL(k_tail_fock, dim3(n), dim3(256), 0, st, a, c->H, c->S, J, K, V, cocc, c->Fb, c->FC, c->SC, c->status);
+    hipLaunchKernelGGL(k_tail_fock, dim3(n), dim3(256), 0, st, a, c->H, c->S, J, K, V, cocc, c->Fb, c->FC, c->SC, status);
     hipLaunchKernelGGL(k_tail_err, dim3(n), dim3(128), 0, st, a, c->FC, c->SC, c->Eb, c->gpart);
-    hipLaunchKernelGGL(k_tail_mix, dim3(n), dim3(128), 0, st, a, c->gpart, c->Gb, c->Fb, c->Fx, c->status);
+    hipLaunchKernelGGL(k_tail_mix, dim3(n), dim3(128), 0, st, a, c->gpart, c->Gb, c->Fb, c->Fx, status);
     if (a.rotate) {
-        hipLaunchKernelGGL(k_tail_gemm, dim3(nt * nt), dim3(256), 0, st, n, n, n, c->Fx, n, 1, c->U, n, 1, c->FU, n, 1.0, 0, c->status);   // F_ext U
-        hipLaunchKernelGGL(k_tail_gemm, dim3(nt * nt), dim3(256), 0, st, n, n, n, c->U, 1, n, c->FU, n, 1, c->A, n, 1.0, 0, c->status);    // U^T (F_ext U)
-        long long *stamps = (long long *)(c->status + 8);
+        hipLaunchKernelGGL(k_tail_gemm, dim3(nt * nt), dim3(256), 0, st, n, n, n, c->Fx, n, 1, c->U, n, 1, c->FU, n, 1.0, 0, status);   // F_ext U
+        hipLaunchKernelGGL(k_tail_gemm, dim3(nt * nt), dim3(256), 0, st, n, n, n, c->U, 1, n, c->FU, n, 1, c->A, n, 1.0, 0, status);    // U^T (F_ext U)
         if (!c->big) {
-            hipLaunchKernelGGL(k_tail_rot, dim3(1), dim3(TL_ROT_T), c->rot_lds, st, a, c->lo, c->A, c->U, c->Km, c->Rm, c->Qm, c->Bm, c->FU,
-                               c->eig, c->status, stamps);
+            hipLaunchKernelGGL(k_tail_rot, dim3(1), dim3(TL_ROT_T), c->rot_lds, st, a, c->lo, c->A, c->Km, c->Rm, c->Qm, c->Bm, c->FU, c->eig,
+                               status, c->status->stamps);
         } else {
-            hipLaunchKernelGGL(k_tail_rot_big, dim3(1), dim3(TL_ROT_T), c->rot_lds, st, a, c->A, c->Km, c->K2, c->Kt, c->Kt2, c->Qm, c->Rm, c->Bm,
-                               c->rden, c->smalls, c->FU, c->eig, c->status, stamps, c->Kfix, c->KXg, 1, c->state);
+            hipLaunchKernelGGL(k_rb_start, dim3(1), dim3(TL_ROT_T), 0, st, n, c->no, c->A, c->Km, c->Kt, c->rden, status, &c->status->state);
             launch_big_steps(c, a, c->steps_hint);
             launch_big_finish(c, a);
         }
-        hipLaunchKernelGGL(k_tail_gemm, dim3(nt * nt), dim3(256), 0, st, n, n, n, c->U, n, 1, c->FU, n, 1, c->Unew, n, 1.0, 0, c->status);   // U' = U W
     } else {
-        hipLaunchKernelGGL(k_tail_need_exact, dim3(1), dim3(1), 0, st, c->status);
+        hipLaunchKernelGGL(k_tail_need_exact, dim3(1), dim3(1), 0, st, status);
     }
-    hipLaunchKernelGGL(k_tail_density, dim3(n), dim3(128), 0, st, a, 0, seq, c->H, J, K, c->U, c->Unew, dm, cocc, c->epart,
-                       c->status, (const double *)d_exc, c->h_out_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { tail_error(c, "SCF tail launch", e); return -1; }
-    return 0;
+    return launch_basis_density(c, a, a.rotate != 0, d_J, d_K, d_dm, d_cocc, d_exc);
 }
 
 // After status 3 (the memory-resident rotation ran out of queued fixed-point steps): `nsteps` more, then the rest of the step.
@@ -1441,18 +1305,10 @@ int DFT_ScfTailMore(void *h, int nsteps, unsigned long long d_J, unsigned long l
     if (!c || !c->big || !d_J || !d_dm || !d_cocc || nsteps < 1) return -1;
     c->err[0] = 0;
     const TailArgs a = c->last;
-    const int n = c->n, nt = (n + 15) / 16;
-    hipStream_t st = c->stream;
-    const unsigned long seq = ++c->seq;
-    hipLaunchKernelGGL(k_tail_clear_more, dim3(1), dim3(1), 0, st, c->status);
+    hipLaunchKernelGGL(k_tail_clear_more, dim3(1), dim3(1), 0, c->stream, c->status->word);
     launch_big_steps(c, a, nsteps);
     launch_big_finish(c, a);
-    hipLaunchKernelGGL(k_tail_gemm, dim3(nt * nt), dim3(256), 0, st, n, n, n, c->U, n, 1, c->FU, n, 1, c->Unew, n, 1.0, 0, c->status);
-    hipLaunchKernelGGL(k_tail_density, dim3(n), dim3(128), 0, st, a, 0, seq, c->H, (const double *)d_J, (const double *)d_K, c->U, c->Unew,
-                       (double *)d_dm, (double *)d_cocc, c->epart, c->status, (const double *)d_exc, c->h_out_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { tail_error(c, "SCF tail launch", e); return -1; }
-    return 0;
+    return launch_basis_density(c, a, true, d_J, d_K, d_dm, d_cocc, d_exc);
 }
 
 // Fixed-point steps queued per DFT_ScfTailStep on the memory-resident path (the caller knows how many the last cycle took)
@@ -1473,9 +1329,9 @@ int DFT_ScfTailFinish(void *h, double c_hf, unsigned long long d_J, unsigned lon
     TailArgs a{};
     a.n = c->n; a.no = c->no; a.c_hf = c_hf;
     const unsigned long seq = ++c->seq;
-    hipLaunchKernelGGL(k_tail_begin, dim3(1), dim3(1), 0, c->stream, c->status);
+    hipLaunchKernelGGL(k_tail_begin, dim3(1), dim3(1), 0, c->stream, c->status->word);
     hipLaunchKernelGGL(k_tail_density, dim3(c->n), dim3(128), 0, c->stream, a, 1, seq, c->H, (const double *)d_J, (const double *)d_K,
-                       c->U, c->Unew, (double *)d_dm, (double *)d_cocc, c->epart, c->status, (const double *)nullptr, c->h_out_dev);
+                       c->U, c->Unew, (double *)d_dm, (double *)d_cocc, c->epart, c->status->word, (const double *)nullptr, c->h_out_dev);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { tail_error(c, "SCF tail launch", e); return -1; }
     return 0;
@@ -1510,7 +1366,7 @@ int DFT_ScfTailStamps(void *h, long long *host_out16)
     TailDev *c = (TailDev *)h;
     if (!c || !host_out16) return -1;
     if (hipStreamSynchronize(c->stream) != hipSuccess ||
-        hipMemcpy(host_out16, c->status + 8, 16 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        hipMemcpy(host_out16, c->status->stamps, sizeof c->status->stamps, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return 0;
 }
 

@@ -7,7 +7,7 @@ import ctypes
 
 import numpy as np
 
-MAX_NAO, MAX_NOCC, SPACE = 512, 64, 8      # up to 128 x 32 the rotation's matrices live in LDS (k_tail_rot), above in memory (k_tail_rot_big)
+MAX_NAO, MAX_NOCC, SPACE = 512, 64, 8      # up to 128 x 32 the rotation's matrices live in LDS (k_tail_rot), above in memory (k_rb_*)
 STATUS_DONE, STATUS_DIAGONALISE, STATUS_SINGULAR, STATUS_MORE = 0, 1, 2, 3
 STEPS_HINT, STEPS_HINT_CAP = 6, 16         # fixed-point steps queued per step on the memory-resident path: at open, and at most after a wait
 

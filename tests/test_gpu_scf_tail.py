@@ -102,7 +102,7 @@ def _first_order_step(U, F, no):
 
 
 @pytest.mark.parametrize("n,no", [(40, 9),                                    # k_tail_rot: operands in LDS
-                                  (150, 20), (127, 33), (512, 64)])           # k_tail_rot_big: above 128 functions or 32 occupied
+                                  (150, 20), (127, 33), (512, 64)])           # k_rb_*: above 128 functions or 32 occupied
 def test_status_paths_diis_only_finish_and_singular_system(n, no):
     import torch
     from scipy.linalg import eigh
