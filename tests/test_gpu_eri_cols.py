@@ -1,7 +1,9 @@
 """DFT_EriColumns (csrc/eri_cols.hip) -- the ERI columns of a ket shell pair on the device -- against the host engine
-(csrc/integrals.c::qc_eri_cols2, itself pinned by tests/test_integrals.py and test_integral_identities.py; the reference
-takes these integrals from libcint, grid.py:65).  Every angular-momentum class up to (ff|ff), swapped shell order,
-Schwarz screening, and the Cholesky factorisation built on it."""
+(csrc/integrals.c::qc_eri_cols2: the product's own engine in the same McMurchie-Davidson formulation, so this file
+shows that the two AGREE, not that either is right; both are compared element by element with an independent
+high-precision reference in tests/test_eri_reference_cpu.py (host) and tests/test_gpu_eri_reference.py (device); the
+reference takes these integrals from libcint, grid.py:65).  Every angular-momentum class up to (ff|ff), swapped shell
+order, Schwarz screening, and the Cholesky factorisation built on it."""
 import numpy as np
 import pytest
 
