@@ -247,6 +247,30 @@ int DFT_EriColumnsSetStream(void *handle, unsigned long long hip_stream);
 const char *DFT_EriColumnsLastError(void *handle);
 void DFT_EriColumnsClose(void *handle);
 
+/* One-electron Coulomb integrals at points, A[c][mu][nu] = int phi_mu(r) phi_nu(r) / |r - R_c| dr, contracted on the device
+ * without being stored (csrc/point_coulomb.hip; device counterpart of the host engine's qc_point_matrix /
+ * qc_point_contract: the McMurchie-Davidson nuclear-attraction integral of csrc/integrals.c::qc_int1e for arbitrary
+ * centres, s-f shells).  Shell table as for DFT_EvalAO (host arrays, copied once).  Open returns NULL without a device
+ * or for a shell with l > 3.
+ *   Matrix    d_out (nao, nao), overwritten: M = sum_c w_c A[c], both triangles, M == M^T bit for bit -- the matrix of
+ *             npts point charges w_c at d_points_xyz (npts, 3) bohr, with the sign of A: the external potential of
+ *             charges q in Hcore is -M(q).  Sums over points in a fixed order, no atomics: the same bits every run.
+ *   Contract  d_out (npts), overwritten: u[c] = sum_{mu nu} D[mu][nu] A[c][mu][nu] for any (nao, nao) matrix D (it need
+ *             not be symmetric); for a density matrix the electronic part of the electrostatic potential is -u.
+ * npts is 64-bit; npts == 0 is valid (Matrix writes zeros, Contract writes nothing).  Asynchronous on the handle's
+ * stream (default: the null stream); every entry runs on the device that was current at Open.  Returns 0 or -1
+ * (DFT_PointCoulombLastError); nothing aborts. */
+void *DFT_PointCoulombOpen(int nshell, const double *shl_xyz, const int *shl_l, const int *shl_nprim,
+                           const int *shl_off, const int *shl_ao, const double *prim_exp, const double *prim_coef,
+                           int nao, int nprim_total);
+int DFT_PointCoulombMatrix(void *handle, long long npts, unsigned long long d_points_xyz, unsigned long long d_weights,
+                           unsigned long long d_out);
+int DFT_PointCoulombContract(void *handle, long long npts, unsigned long long d_points_xyz, unsigned long long d_dm,
+                             unsigned long long d_out);
+int DFT_PointCoulombSetStream(void *handle, unsigned long long hip_stream);
+const char *DFT_PointCoulombLastError(void *handle);
+void DFT_PointCoulombClose(void *handle);
+
 /* The rest of an SCF cycle on the device: between the cycle's J / K / Vxc and the next density the
  * reference's loop runs on the host -- Fock assembly (dft.py:212-223), Pulay DIIS (dft.py:225), eigh(F, S) (dft.py:227),
  * dm = 2 C_occ C_occ^T (dft.py:228) and the energy traces (dft.py:231-234).  DFT_ScfTailStep queues all of it behind

@@ -741,7 +741,7 @@ __global__ void k_accumulate_chunk(long n2, int add, const double *__restrict__ 
 
 extern "C" {
 
-int DFT_GetVersion(void) { return 4; }   // 4: DFT_CreateSolverMix / DFT_GetMix
+int DFT_GetVersion(void) { return 5; }   // 4: DFT_CreateSolverMix / DFT_GetMix; 5: DFT_PointCoulomb*
 
 static XCSolver *create_solver(int type, const double *mix)
 {

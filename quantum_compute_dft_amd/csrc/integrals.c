@@ -1,6 +1,7 @@
 /*
- * Gaussian integrals for the SCF driver: overlap, kinetic, nuclear attraction and the dense
- * two-electron tensor over contracted real-spherical shells (s, p, d, f).
+ * Gaussian integrals for the SCF driver: overlap, kinetic, nuclear attraction, the Coulomb integrals at
+ * arbitrary points (external charges, electrostatic potential) and the dense two-electron tensor over
+ * contracted real-spherical shells (s, p, d, f).
  *
  * Host-side counterpart of what the reference obtains from PySCF/libcint at grid.py:61-65
  * (mol.intor('int1e_ovlp' | 'int1e_kin' | 'int1e_nuc' | 'int2e')), same conventions: real
@@ -222,6 +223,173 @@ int qc_int1e(int nshell, const double *xyz, const int *ls, const int *nprim, con
             put_sph2(la, lb, ct, T, nao, ao0[A], ao0[B]);
             put_sph2(la, lb, cv, V, nao, ao0[A], ao0[B]);
         }
+    return 0;
+}
+
+/* ---- one-electron Coulomb integrals at arbitrary points -------------------------------------- */
+/* A[c][mu][nu] = <mu| 1/|r - R_c| |nu> (the nuclear-attraction integral of qc_int1e for a unit charge at any point,
+ * positive sign), never stored: qc_point_matrix sums it over points with weights, qc_point_contract contracts it with
+ * a matrix.  Host counterparts of csrc/point_coulomb.hip.  Shell pairs A >= B; primitive pairs whose Gaussian-product
+ * prefactor is below 1e-18 are dropped as in ctx_build_pairs. */
+static int prim_pair_kept(double a, double b, double cc, double R2) { return !(fabs(cc) * exp(-a * b / (a + b) * R2) < 1e-18); }
+
+static double dist2(const double *RA, const double *RB)
+{
+    return (RA[0] - RB[0]) * (RA[0] - RB[0]) + (RA[1] - RB[1]) * (RA[1] - RB[1]) + (RA[2] - RB[2]) * (RA[2] - RB[2]);
+}
+
+/* M[mu][nu] = sum_c w[c] A[c][mu][nu]: (nao, nao), both triangles written, M == M^T bit for bit */
+int qc_point_matrix(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                    const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                    const double *pts, const double *w, double *M)
+{
+    for (int s = 0; s < nshell; ++s)
+        if (ls[s] < 0 || ls[s] > LMAX) return -1;
+    const int npairs = nshell * (nshell + 1) / 2;
+#pragma omp parallel for schedule(dynamic)
+    for (int k = 0; k < npairs; ++k) {
+        int A = (int)((sqrt(8.0 * k + 1.0) - 1.0) / 2.0);
+        while (A * (A + 1) / 2 > k) --A;
+        while ((A + 1) * (A + 2) / 2 <= k) ++A;
+        const int B = k - A * (A + 1) / 2;
+        const int la = ls[A], lb = ls[B], nca = NCART(la), ncb = NCART(lb), L = la + lb;
+        int ax[MAXCART], ay[MAXCART], az[MAXCART], bx[MAXCART], by[MAXCART], bz[MAXCART];
+        cart_components(la, ax, ay, az);
+        cart_components(lb, bx, by, bz);
+        double cart[MAXCART * MAXCART] = {0};
+        const double *RA = xyz + 3 * A, *RB = xyz + 3 * B;
+        const double R2 = dist2(RA, RB);
+        for (int pa = 0; pa < nprim[A]; ++pa)
+            for (int pb = 0; pb < nprim[B]; ++pb) {
+                const double a = ex[off[A] + pa], b = ex[off[B] + pb], p = a + b;
+                const double cc = cf[off[A] + pa] * cf[off[B] + pb];
+                if (!prim_pair_kept(a, b, cc, R2)) continue;
+                double E[3][LMAX + 3][LMAX + 3][2 * LMAX + 5];
+                for (int d = 0; d < 3; ++d) hermite_E(la, lb, a, b, RA[d] - RB[d], E[d]);
+                const double P[3] = {(a * RA[0] + b * RB[0]) / p, (a * RA[1] + b * RB[1]) / p, (a * RA[2] + b * RB[2]) / p};
+                double W[HDIM][HDIM][HDIM] = {{{0}}};
+                for (long long c = 0; c < npts; ++c) {
+                    static _Thread_local double R[RDIM][RDIM][RDIM];
+                    const double PC[3] = {P[0] - pts[3 * c], P[1] - pts[3 * c + 1], P[2] - pts[3 * c + 2]};
+                    hermite_R(L, p, PC, R);
+                    for (int t = 0; t <= L; ++t)
+                        for (int u = 0; u <= L - t; ++u)
+                            for (int v = 0; v <= L - t - u; ++v) W[t][u][v] += w[c] * R[t][u][v];
+                }
+                const double pref = 2.0 * M_PI / p * cc;
+                for (int ca = 0; ca < nca; ++ca)
+                    for (int cb = 0; cb < ncb; ++cb) {
+                        double v = 0.0;
+                        for (int t = 0; t <= ax[ca] + bx[cb]; ++t)
+                            for (int u = 0; u <= ay[ca] + by[cb]; ++u)
+                                for (int q = 0; q <= az[ca] + bz[cb]; ++q)
+                                    v += E[0][ax[ca]][bx[cb]][t] * E[1][ay[ca]][by[cb]][u] * E[2][az[ca]][bz[cb]][q] * W[t][u][q];
+                        cart[ca * ncb + cb] += pref * v;
+                    }
+            }
+        double blk[7 * 7];
+        put_sph2(la, lb, cart, blk, 7, 0, 0);
+        for (int ma = 0; ma < 2 * la + 1; ++ma)
+            for (int mb = 0; mb < (A == B ? ma + 1 : 2 * lb + 1); ++mb) { /* a diagonal block from its lower triangle */
+                const size_t i = ao0[A] + ma, j = ao0[B] + mb;
+                M[i * nao + j] = blk[ma * 7 + mb];
+                M[j * nao + i] = blk[ma * 7 + mb];
+            }
+    }
+    return 0;
+}
+
+/* u[c] = sum_{mu nu} D[mu][nu] A[c][mu][nu] for any (nao, nao) matrix D.  Two steps: the Hermite densities Lambda_tuv of
+ * every kept primitive pair from D[A,B] + D[B,A]^T (OpenMP over shell pairs), then u[c] = sum_pairs sum_tuv Lambda_tuv
+ * R_tuv(p, P - R_c) (OpenMP over points: every point adds its pairs in the same order). */
+int qc_point_contract(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                      const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                      const double *pts, const double *D, double *out)
+{
+    for (int s = 0; s < nshell; ++s)
+        if (ls[s] < 0 || ls[s] > LMAX) return -1;
+    const int npairs = nshell * (nshell + 1) / 2;
+    int *pbeg = (int *)malloc(sizeof(int) * (npairs + 1));
+    int npp = 0;
+    for (int A = 0, k = 0; A < nshell; ++A)
+        for (int B = 0; B <= A; ++B, ++k) {
+            pbeg[k] = npp;
+            const double R2 = dist2(xyz + 3 * A, xyz + 3 * B);
+            for (int pa = 0; pa < nprim[A]; ++pa)
+                for (int pb = 0; pb < nprim[B]; ++pb)
+                    npp += prim_pair_kept(ex[off[A] + pa], ex[off[B] + pb], cf[off[A] + pa] * cf[off[B] + pb], R2);
+        }
+    pbeg[npairs] = npp;
+    const int NT = HDIM * (HDIM + 1) * (HDIM + 2) / 6; /* 84 entries t + u + v <= 6, in the order t, u, v */
+    double *geom = (double *)malloc(sizeof(double) * 4 * (npp + 1));
+    int *Ls = (int *)malloc(sizeof(int) * (npp + 1));
+    double *lam = (double *)calloc((size_t)NT * (npp + 1), sizeof(double));
+#pragma omp parallel for schedule(dynamic)
+    for (int A = 0; A < nshell; ++A)
+        for (int B = 0; B <= A; ++B) {
+            const int k = A * (A + 1) / 2 + B;
+            const int la = ls[A], lb = ls[B], nca = NCART(la), ncb = NCART(lb), nsa = 2 * la + 1, nsb = 2 * lb + 1, L = la + lb;
+            int ax[MAXCART], ay[MAXCART], az[MAXCART], bx[MAXCART], by[MAXCART], bz[MAXCART];
+            cart_components(la, ax, ay, az);
+            cart_components(lb, bx, by, bz);
+            double Ta[7][MAXCART], Tb[7][MAXCART], Dc[MAXCART * MAXCART] = {0};
+            sph_matrix(la, Ta);
+            sph_matrix(lb, Tb);
+            for (int ma = 0; ma < nsa; ++ma)
+                for (int mb = 0; mb < nsb; ++mb) { /* A is symmetric: an off-diagonal shell pair stands for both triangles of D */
+                    const size_t i = ao0[A] + ma, j = ao0[B] + mb;
+                    const double d = A == B ? D[i * nao + j] : D[i * nao + j] + D[j * nao + i];
+                    for (int ca = 0; ca < nca; ++ca)
+                        for (int cb = 0; cb < ncb; ++cb) Dc[ca * ncb + cb] += Ta[ma][ca] * Tb[mb][cb] * d;
+                }
+            const double *RA = xyz + 3 * A, *RB = xyz + 3 * B;
+            const double R2 = dist2(RA, RB);
+            int pp = pbeg[k];
+            for (int pa = 0; pa < nprim[A]; ++pa)
+                for (int pb = 0; pb < nprim[B]; ++pb) {
+                    const double a = ex[off[A] + pa], b = ex[off[B] + pb], p = a + b;
+                    const double cc = cf[off[A] + pa] * cf[off[B] + pb];
+                    if (!prim_pair_kept(a, b, cc, R2)) continue;
+                    double E[3][LMAX + 3][LMAX + 3][2 * LMAX + 5];
+                    for (int d = 0; d < 3; ++d) hermite_E(la, lb, a, b, RA[d] - RB[d], E[d]);
+                    geom[4 * pp] = p;
+                    for (int d = 0; d < 3; ++d) geom[4 * pp + 1 + d] = (a * RA[d] + b * RB[d]) / p;
+                    Ls[pp] = L;
+                    const double pref = 2.0 * M_PI / p * cc;
+                    double *lm = lam + (size_t)NT * pp;
+                    int n = 0;
+                    for (int t = 0; t <= L; ++t)
+                        for (int u = 0; u <= L - t; ++u)
+                            for (int v = 0; v <= L - t - u; ++v, ++n) {
+                                double s = 0.0;
+                                for (int ca = 0; ca < nca; ++ca)
+                                    for (int cb = 0; cb < ncb; ++cb)
+                                        if (t <= ax[ca] + bx[cb] && u <= ay[ca] + by[cb] && v <= az[ca] + bz[cb])
+                                            s += Dc[ca * ncb + cb] * E[0][ax[ca]][bx[cb]][t] * E[1][ay[ca]][by[cb]][u] * E[2][az[ca]][bz[cb]][v];
+                                lm[n] = pref * s;
+                            }
+                    ++pp;
+                }
+        }
+#pragma omp parallel for schedule(static)
+    for (long long c = 0; c < npts; ++c) {
+        static _Thread_local double R[RDIM][RDIM][RDIM];
+        double acc = 0.0;
+        for (int pp = 0; pp < npp; ++pp) {
+            const double PC[3] = {geom[4 * pp + 1] - pts[3 * c], geom[4 * pp + 2] - pts[3 * c + 1], geom[4 * pp + 3] - pts[3 * c + 2]};
+            const int L = Ls[pp];
+            hermite_R(L, geom[4 * pp], PC, R);
+            const double *lm = lam + (size_t)NT * pp;
+            double s = 0.0;
+            int n = 0;
+            for (int t = 0; t <= L; ++t)
+                for (int u = 0; u <= L - t; ++u)
+                    for (int v = 0; v <= L - t - u; ++v, ++n) s += lm[n] * R[t][u][v];
+            acc += s;
+        }
+        out[c] = acc;
+    }
+    free(pbeg); free(geom); free(Ls); free(lam);
     return 0;
 }
 

@@ -1,7 +1,9 @@
 """`python -m quantum_compute_dft_amd.dft <LDA|GGA|B3LYP> <Molecule>` -- the reference's driver
 surface (dft.py:101-297: same positionals, same printed lines) on the MI355X engine.  The functional may also be any
 other name of functionals.TABLE (PBE0, BLYP, ...) or an expression such as "0.75*pbe_x + pbe_c + 0.25*hf".
-Extra flags (defaults = what the reference hard-codes): --basis sto-3g, --grid-level 3, --quirks 1."""
+Extra flags (defaults = what the reference hard-codes): --basis sto-3g, --grid-level 3, --quirks 1.
+--point-charges FILE runs the molecule in the field of external point charges (rows `x y z q`); --esp-points FILE with
+--esp-out FILE writes the electrostatic potential of the converged density at the given points."""
 import argparse
 import importlib.util
 import os
@@ -17,6 +19,37 @@ def _functional(spec):
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e)) from None
     return spec.strip().upper() if spec.strip().upper() in functionals.TABLE else spec.strip()
+
+
+def read_point_rows(path, ncol, unit="angstrom"):
+    """(n, ncol) float64 from a text file of rows `x y z [q ...]` (blank lines and #-comments skipped); the first three
+    columns converted to bohr when `unit` is "angstrom" (the unit of the .xyz files), taken as they are for "bohr"."""
+    import numpy as np
+    from .basis import BOHR
+    if unit not in ("angstrom", "bohr"):
+        raise ValueError(f"unit {unit!r}: expected 'angstrom' or 'bohr'")
+    rows = []
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            f = line.split("#", 1)[0].split()
+            if not f:
+                continue
+            if len(f) != ncol:
+                raise ValueError(f"{path}:{n}: expected {ncol} numbers per row, found {len(f)}")
+            rows.append([float(x) for x in f])
+    a = np.array(rows, dtype=np.float64).reshape(-1, ncol)
+    if unit == "angstrom":
+        a[:, :3] /= BOHR
+    return a
+
+
+def write_esp_rows(path, points_bohr, esp, unit="angstrom"):
+    """Rows `x y z esp`: the coordinates back in `unit`, the potential in atomic units (Ha / e)."""
+    from .basis import BOHR
+    scale = BOHR if unit == "angstrom" else 1.0
+    with open(path, "w") as fh:
+        for (x, y, z), v in zip(points_bohr, esp):
+            fh.write(f"{x * scale:.10f} {y * scale:.10f} {z * scale:.10f} {v:.12e}\n")
 
 
 def main(argv=None):
@@ -53,9 +86,20 @@ def main(argv=None):
     p.add_argument("--both-quirks", action="store_true",
                    help="LDA/GGA: run the SCF twice, with the reference's formulas as shipped (its CUDA path) and with the "
                         "corrected VWN5 / PBE-c derivatives (what PySCF's slater,vwn5 / PBE,PBE compute), and report both energies")
+    p.add_argument("--point-charges", default=None, metavar="FILE",
+                   help="external point charges, text rows `x y z q` (electrostatic embedding: they enter the core Hamiltonian and the "
+                        "nuclear repulsion; their interaction among themselves is not included)")
+    p.add_argument("--point-charges-unit", default="angstrom", choices=["angstrom", "bohr"],
+                   help="unit of the coordinates in --point-charges and --esp-points (default: angstrom, the unit of the .xyz file)")
+    p.add_argument("--esp-points", default=None, metavar="FILE", help="text rows `x y z`: points at which the electrostatic potential of the "
+                                                                      "converged density is evaluated (needs --esp-out)")
+    p.add_argument("--esp-out", default=None, metavar="FILE", help="receives rows `x y z esp` (coordinates in the unit given, potential in Ha/e; "
+                                                                  "nuclei and electrons of the molecule, without the external charges)")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
     args = p.parse_args(argv)
+    if bool(args.esp_points) != bool(args.esp_out):
+        p.error("--esp-points and --esp-out go together")
     fn = functionals.resolve(args.functional)
 
     # one process per GPU: `python -m torch.distributed.run --nproc-per-node N -m quantum_compute_dft_amd.dft ...`
@@ -91,7 +135,11 @@ def main(argv=None):
         from . import basis as _basis
         _nao = _basis.build_shells(*_basis.parse_xyz(atom_path), args.basis).nao
         args.eri = "dense" if 8.0 * _nao ** 4 <= 8.0e9 else "cholesky"
-    inp = inputs.build(atom_path, args.basis, args.grid_level, device=device, eri_mode=args.eri, chol_tol=args.chol_tol, rank=rank, world=world)
+    charges = read_point_rows(args.point_charges, 4, args.point_charges_unit) if args.point_charges else None
+    inp = inputs.build(atom_path, args.basis, args.grid_level, device=device, eri_mode=args.eri, chol_tol=args.chol_tol, rank=rank, world=world,
+                       point_charges=charges)
+    if charges is not None:
+        print(f"External point charges: {len(charges)} (total {charges[:, 3].sum():+.6f} e), nuclei-charges repulsion {inp.E_nuc_ext:.8f} Ha")
     print(f"System Info: NAO={inp.shells.nao}, Grid={inp.grids.size}, Occupied={inp.nocc}")
     print(f"Calculating AO Gradients ({args.functional} mode)..." if fn.needs_gradient else f"Skipping AO Gradients ({args.functional} mode).")
     print("Moving data to GPU...")
@@ -139,6 +187,11 @@ def main(argv=None):
         a, b = ("reference formulas as shipped", "corrected derivatives") if args.quirks else ("corrected derivatives", "reference formulas as shipped")
         print(f"Total Energy, {a:32s}: {res['E_tot']:.8f} Ha   (this run; --quirks {args.quirks})")
         print(f"Total Energy, {b:32s}: {other['E_tot']:.8f} Ha   (difference {res['E_tot'] - other['E_tot']:+.2e} Ha)")
+    if args.esp_points and res["converged"] and not rank:
+        from . import properties
+        esp_pts = read_point_rows(args.esp_points, 3, args.point_charges_unit)
+        write_esp_rows(args.esp_out, esp_pts, properties.electrostatic_potential(inp, res["dm"], esp_pts, device=device), args.point_charges_unit)
+        print(f"Electrostatic potential at {len(esp_pts)} points written to {args.esp_out}")
     import json
     record = {"functional": args.functional, "molecule": os.path.splitext(atom_file)[0], "basis": args.basis, "grid_level": args.grid_level,
               "nao": int(inp.shells.nao), "ngrid": int(inp.grids.size), "nocc": int(inp.nocc), "n_gpus": world, "eri": args.eri,
@@ -149,6 +202,8 @@ def main(argv=None):
               "xc_ms_avg": res.get("xc_ms_avg"), "xc_ms": res.get("xc_ms"), "jk_ms": res.get("jk_ms"), "iter_ms": res.get("iter_ms"),
               "cycle_ms": res.get("cycle_ms"), "gpu_init_s": backend.init_time, "device_resident": bool(backend.device_resident), "loop": res.get("loop", "device" if backend.device_resident else "host"), "ao": args.ao, "eigensolver": args.eigensolver,
               "eigensolver_stats": eig_stats, "xc_occ": int(backend.xc_occ)}
+    if charges is not None:
+        record["n_point_charges"] = int(len(charges)); record["E_nuc_ext"] = float(inp.E_nuc_ext)
     if other is not None:
         record["E_tot_other_quirks"] = other.get("E_tot"); record["other_quirks"] = 0 if args.quirks else 1
     line = json.dumps(record)

@@ -28,15 +28,39 @@ class SCFInputs:
     nelec: int
     chol: np.ndarray = None  # (naux, nao, nao) Cholesky vectors of the ERI (eri_mode='cholesky')
     chol_range: tuple = None  # (lo, hi, naux): `chol` is only THIS rank's slice of the naux vectors (build(..., world > 1))
+    point_charges: np.ndarray = None  # (n, 4): x, y, z (bohr), q of the external point charges (build(..., point_charges=...))
+    V_ext: np.ndarray = None  # (nao, nao) potential of those charges on the electrons, already part of Hcore
+    E_nuc_ext: float = 0.0    # nuclei -- external charges repulsion, already part of E_nuc
+
+
+def external_charges(symbols, atom_xyz, shells, point_charges, device="cpu"):
+    """(charges (n, 4), V_ext, E_nuc_ext) of external point charges x, y, z (bohr), q:
+         V_ext[mu, nu] = -sum_c q_c <mu| 1/|r - R_c| |nu>      E_nuc_ext = sum_{A, c} Z_A q_c / |R_A - R_c|
+    The interaction of the charges among themselves is NOT included (a constant of the environment, not of the
+    molecule).  ValueError when a charge sits within 1e-8 bohr of a nucleus."""
+    pc = np.array(point_charges, dtype=np.float64)
+    if pc.ndim != 2 or pc.shape[1] != 4:
+        raise ValueError(f"point_charges: expected an (n, 4) array of x, y, z (bohr), q; got shape {pc.shape}")
+    xyz = np.asarray(atom_xyz, dtype=np.float64)
+    z = np.array([basis.atomic_number(s) for s in symbols], dtype=np.float64)
+    dist = np.linalg.norm(xyz[:, None, :] - pc[None, :, :3], axis=2)              # (natm, n)
+    if dist.size and dist.min() < 1e-8:
+        a, c = np.unravel_index(np.argmin(dist), dist.shape)
+        raise ValueError(f"point charge {c} sits on nucleus {a} ({symbols[a]}): |R_A - R_c| = {dist[a, c]:.1e} bohr")
+    V_ext = -integrals.point_coulomb(shells, pc[:, :3], weights=pc[:, 3], device=device)
+    return pc, V_ext, float(np.sum(z[:, None] * pc[None, :, 3] / dist))
 
 
 def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=True, eri_mode="dense",
-          chol_tol=1e-9, rank=0, world=1, group=None):
+          chol_tol=1e-9, rank=0, world=1, group=None, point_charges=None):
     """grid.py:42-67.  `atom_path`: an .xyz file (or a molecule name resolved in data/).
     eri_mode "dense": the (nao^4) tensor of grid.py:65; "cholesky": pivoted Cholesky vectors only.
     world > 1 (torch.distributed initialised): the Cholesky factorisation -- the one expensive step, host integral columns
     + device algebra -- runs on rank 0 ALONE, on the whole node's CPU allowance while the other ranks wait, and every
-    rank receives only its slice of the vectors (grid_shard.scatter_vectors); `chol_range` records the slice."""
+    rank receives only its slice of the vectors (grid_shard.scatter_vectors); `chol_range` records the slice.
+    point_charges: (n, 4) x, y, z (bohr), q -- electrostatic embedding (external_charges): Hcore = T + V + V_ext and E_nuc
+    gains the nuclei--charges repulsion, so every SCF loop runs in the field of the charges unchanged; their interaction
+    among themselves is not included.  Every rank computes V_ext itself (deterministic: nothing is broadcast)."""
     if not os.path.exists(atom_path):
         cand = os.path.join(DATA_DIR, atom_path if atom_path.endswith(".xyz") else atom_path + ".xyz")
         if os.path.exists(cand):
@@ -85,5 +109,9 @@ def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=Tr
             print(f"Cholesky vectors of the ERI: {chol.shape[0]} (threshold {chol_tol:g}, {time.time() - t0:.1f} s; {where})")
     else:
         raise ValueError(f"eri_mode {eri_mode!r}: expected 'dense' or 'cholesky'")
-    return SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V, eri,
-                     integrals.energy_nuc(symbols, xyz), nocc, nelec, chol, chol_range)
+    if point_charges is None:
+        return SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V, eri,
+                         integrals.energy_nuc(symbols, xyz), nocc, nelec, chol, chol_range)
+    pc, V_ext, E_ext = external_charges(symbols, xyz, shells, point_charges, device)
+    return SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V + V_ext, eri,
+                     integrals.energy_nuc(symbols, xyz) + E_ext, nocc, nelec, chol, chol_range, pc, V_ext, E_ext)

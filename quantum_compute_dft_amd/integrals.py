@@ -1,6 +1,8 @@
 """S, T, V, dense ERI and E_nuc for the SCF driver -- host-side counterpart of the PySCF calls at
 grid.py:61-66 (`mol.intor('int1e_ovlp'|'int1e_kin'|'int1e_nuc'|'int2e')`, `mol.energy_nuc()`).
-The arithmetic is csrc/integrals.c (McMurchie-Davidson, OpenMP), built in-tree with gcc.
+The arithmetic is csrc/integrals.c (McMurchie-Davidson, OpenMP), built in-tree with gcc.  Also the one-electron Coulomb
+integrals at arbitrary points (external point charges, electrostatic potential): point_coulomb_matrix / point_coulomb_contract
+on the host, PointCoulomb on the device, point_coulomb() choosing between them.
 
 PARITY UNPINNED against PySCF/libcint (not installed); pinned offline by quadrature on the
 Becke grid, textbook H2/STO-3G integrals and RHF energies (tests/test_integrals.py)."""
@@ -61,6 +63,9 @@ def _load():
         L.qc_eri_cols2.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, dp, ctypes.c_int]
         L.qc_set_threads.restype = None
         L.qc_set_threads.argtypes = [ctypes.c_int]
+        for f in (L.qc_point_matrix, L.qc_point_contract):
+            f.restype = ctypes.c_int
+            f.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ctypes.c_longlong, dp, dp, dp]
         from .hostinfo import host_cpu_share
         L.qc_set_threads(host_cpu_share())
         _lib = L
@@ -224,3 +229,138 @@ class DeviceEriColumns:
             raise RuntimeError("libdft: " + (self.lib.DFT_EriColumnsLastError(self._h) or b"").decode())
         return out.view(-1)[:tot * n2].view(tot, self.nao, self.nao)
 
+
+
+def _points(points):
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points: expected an (n, 3) array in bohr, got shape {pts.shape}")
+    return pts
+
+
+def point_coulomb_matrix(shells, points, weights):
+    """M[mu, nu] = sum_c weights[c] <mu| 1/|r - points[c]| |nu> on the host (csrc/integrals.c::qc_point_matrix): the
+    (nao, nao) matrix of point charges `weights` at `points` (n, 3) bohr, with the sign of the integral -- the potential of
+    charges q that electrons feel is -M(q) (inp.V is -M(atom_xyz, Z)).  M == M.T bit for bit."""
+    pts = _points(points)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (len(pts),):
+        raise ValueError(f"weights: expected shape ({len(pts)},), got {w.shape}")
+    keep, p = _args(shells)
+    n = shells.nao
+    M = np.zeros((n, n))
+    dp = ctypes.POINTER(ctypes.c_double)
+    if len(pts) and _load().qc_point_matrix(shells.nshell, *p, n, len(pts), pts.ctypes.data_as(dp), w.ctypes.data_as(dp), M.ctypes.data_as(dp)) != 0:
+        raise ValueError("integrals: angular momentum above f is not supported")
+    return M
+
+
+def point_coulomb_contract(shells, points, dm):
+    """u[c] = sum_{mu nu} dm[mu, nu] <mu| 1/|r - points[c]| |nu> on the host (qc_point_contract), for any (nao, nao) matrix
+    (it need not be symmetric).  For a density matrix: int rho(r) / |r - points[c]| dr."""
+    pts = _points(points)
+    n = shells.nao
+    D = np.ascontiguousarray(dm, dtype=np.float64)
+    if D.shape != (n, n):
+        raise ValueError(f"dm: expected shape ({n}, {n}), got {D.shape}")
+    keep, p = _args(shells)
+    u = np.zeros(len(pts))
+    dp = ctypes.POINTER(ctypes.c_double)
+    if len(pts) and _load().qc_point_contract(shells.nshell, *p, n, len(pts), pts.ctypes.data_as(dp), D.ctypes.data_as(dp), u.ctypes.data_as(dp)) != 0:
+        raise ValueError("integrals: angular momentum above f is not supported")
+    return u
+
+
+class PointCoulomb:
+    """The same two operations ON THE DEVICE (libdft.so: csrc/point_coulomb.hip, DFT_PointCoulomb*) on torch tensors:
+    `matrix(points, weights)` -> (nao, nao), `contract(points, dm)` -> (n,).  Asynchronous on the null stream (or the one
+    given to set_stream), like torch's own kernels; the tensors live on the device that was current at construction."""
+
+    def __init__(self, shells, lib_path=None):
+        from .build import library_path
+        from .solver import load_library
+        self.lib = load_library(lib_path or library_path())
+        L = self.lib
+        dp, ip, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.c_uint64
+        L.DFT_PointCoulombOpen.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ctypes.c_int]
+        L.DFT_PointCoulombOpen.restype = ctypes.c_void_p
+        L.DFT_PointCoulombMatrix.argtypes = [ctypes.c_void_p, ctypes.c_longlong, u64, u64, u64]
+        L.DFT_PointCoulombMatrix.restype = ctypes.c_int
+        L.DFT_PointCoulombContract.argtypes = [ctypes.c_void_p, ctypes.c_longlong, u64, u64, u64]
+        L.DFT_PointCoulombContract.restype = ctypes.c_int
+        L.DFT_PointCoulombSetStream.argtypes = [ctypes.c_void_p, u64]
+        L.DFT_PointCoulombSetStream.restype = ctypes.c_int
+        L.DFT_PointCoulombLastError.argtypes = [ctypes.c_void_p]
+        L.DFT_PointCoulombLastError.restype = ctypes.c_char_p
+        L.DFT_PointCoulombClose.argtypes = [ctypes.c_void_p]
+        L.DFT_PointCoulombClose.restype = None
+        keep, p = _args(shells)
+        self.shells, self.nao = shells, shells.nao
+        self._h = L.DFT_PointCoulombOpen(shells.nshell, *p, shells.nao, len(shells.exp))
+        if not self._h:
+            raise RuntimeError("DFT_PointCoulombOpen failed (no device, or angular momentum above f)")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.DFT_PointCoulombClose(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _error(self):
+        return RuntimeError("libdft: " + (self.lib.DFT_PointCoulombLastError(self._h) or b"").decode())
+
+    def set_stream(self, stream):
+        """`stream`: a torch.cuda.Stream, or None for the null stream."""
+        self.lib.DFT_PointCoulombSetStream(self._h, ctypes.c_uint64(stream.cuda_stream if stream is not None else 0))
+
+    @staticmethod
+    def _check(t, shape, what):
+        import torch
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"{what}: expected a contiguous float64 device tensor of shape {shape}")
+
+    def matrix(self, points, weights, out=None):
+        import torch
+        n = int(points.shape[0])
+        self._check(points, (n, 3), "points"); self._check(weights, (n,), "weights")
+        if out is None:
+            out = torch.empty((self.nao, self.nao), dtype=torch.float64, device=points.device)
+        self._check(out, (self.nao, self.nao), "out")
+        if self.lib.DFT_PointCoulombMatrix(self._h, n, ctypes.c_uint64(points.data_ptr() if n else 0),
+                                           ctypes.c_uint64(weights.data_ptr() if n else 0), ctypes.c_uint64(out.data_ptr())) != 0:
+            raise self._error()
+        return out
+
+    def contract(self, points, dm, out=None):
+        import torch
+        n = int(points.shape[0])
+        self._check(points, (n, 3), "points"); self._check(dm, (self.nao, self.nao), "dm")
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=points.device)
+        self._check(out, (n,), "out")
+        if self.lib.DFT_PointCoulombContract(self._h, n, ctypes.c_uint64(points.data_ptr() if n else 0), ctypes.c_uint64(dm.data_ptr()),
+                                             ctypes.c_uint64(out.data_ptr() if n else 0)) != 0:
+            raise self._error()
+        return out
+
+
+def point_coulomb(shells, points, weights=None, dm=None, device="cpu"):
+    """The one entry the rest of the package calls: `weights` given -> the (nao, nao) matrix, `dm` given -> the values
+    at the points; numpy in, numpy out.  On a CUDA device the kernels of libdft.so (PointCoulomb), otherwise the host
+    engine -- there is no quiet fall-back from one to the other."""
+    if (weights is None) == (dm is None):
+        raise ValueError("point_coulomb: give either weights (matrix) or dm (contraction)")
+    if not str(device).startswith("cuda"):
+        return point_coulomb_matrix(shells, points, weights) if dm is None else point_coulomb_contract(shells, points, dm)
+    import torch
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        pc = PointCoulomb(shells)
+        try:
+            t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
+            pts = t(_points(points))
+            res = pc.matrix(pts, t(weights)) if dm is None else pc.contract(pts, t(dm))
+            return res.cpu().numpy()         # the copy waits for the kernels
+        finally:
+            pc.close()
