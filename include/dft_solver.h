@@ -257,7 +257,12 @@ void DFT_EriColumnsClose(void *handle);
  *             charges q in Hcore is -M(q).  Sums over points in a fixed order, no atomics: the same bits every run.
  *   Contract  d_out (npts), overwritten: u[c] = sum_{mu nu} D[mu][nu] A[c][mu][nu] for any (nao, nao) matrix D (it need
  *             not be symmetric); for a density matrix the electronic part of the electrostatic potential is -u.
- * npts is 64-bit; npts == 0 is valid (Matrix writes zeros, Contract writes nothing).  Asynchronous on the handle's
+ *   Field     d_out (npts, 3), overwritten: G[c][k] = sum_{mu nu} D[mu][nu] dA[c][mu][nu] / dR_c,k, k = x, y, z -- the
+ *             gradient of Contract's u with respect to the point (exact: the basis does not move with the point).  For a
+ *             density matrix the electronic part of the electric field is +G.  Same arguments, error returns and
+ *             determinism as Contract.  Added without a change of DFT_GetVersion (it stays 5): a caller that may meet an
+ *             older library detects this entry by looking the symbol up (dlsym), not by the version.
+ * npts is 64-bit; npts == 0 is valid (Matrix writes zeros, Contract and Field write nothing).  Asynchronous on the handle's
  * stream (default: the null stream); every entry runs on the device that was current at Open.  Returns 0 or -1
  * (DFT_PointCoulombLastError); nothing aborts. */
 void *DFT_PointCoulombOpen(int nshell, const double *shl_xyz, const int *shl_l, const int *shl_nprim,
@@ -267,6 +272,8 @@ int DFT_PointCoulombMatrix(void *handle, long long npts, unsigned long long d_po
                            unsigned long long d_out);
 int DFT_PointCoulombContract(void *handle, long long npts, unsigned long long d_points_xyz, unsigned long long d_dm,
                              unsigned long long d_out);
+int DFT_PointCoulombField(void *handle, long long npts, unsigned long long d_points_xyz, unsigned long long d_dm,
+                          unsigned long long d_out);
 int DFT_PointCoulombSetStream(void *handle, unsigned long long hip_stream);
 const char *DFT_PointCoulombLastError(void *handle);
 void DFT_PointCoulombClose(void *handle);

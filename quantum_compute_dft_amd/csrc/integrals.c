@@ -238,11 +238,14 @@ static double dist2(const double *RA, const double *RB)
     return (RA[0] - RB[0]) * (RA[0] - RB[0]) + (RA[1] - RB[1]) * (RA[1] - RB[1]) + (RA[2] - RB[2]) * (RA[2] - RB[2]);
 }
 
-/* M[mu][nu] = sum_c w[c] A[c][mu][nu]: (nao, nao), both triangles written, M == M^T bit for bit */
-int qc_point_matrix(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
-                    const int *ao0, const double *ex, const double *cf, int nao, long long npts,
-                    const double *pts, const double *w, double *M)
+/* M[mu][nu] = sum_c w[c] A[c][mu][nu]: (nao, nao), both triangles written, M == M^T bit for bit.
+ * field != 0: M (3, nao, nao), M[k] = sum_c w[c] dA[c] / dR_c,k -- the sums W_tuv of -R_{t+1,u,v}, -R_{t,u+1,v}, -R_{t,u,v+1}
+ * from a table one order higher (see point_contract), everything else the same. */
+static int point_matrix(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                        const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                        const double *pts, const double *w, int field, double *M)
 {
+    const int ncomp = field ? 3 : 1;
     for (int s = 0; s < nshell; ++s)
         if (ls[s] < 0 || ls[s] > LMAX) return -1;
     const int npairs = nshell * (nshell + 1) / 2;
@@ -256,7 +259,7 @@ int qc_point_matrix(int nshell, const double *xyz, const int *ls, const int *npr
         int ax[MAXCART], ay[MAXCART], az[MAXCART], bx[MAXCART], by[MAXCART], bz[MAXCART];
         cart_components(la, ax, ay, az);
         cart_components(lb, bx, by, bz);
-        double cart[MAXCART * MAXCART] = {0};
+        double cart[3][MAXCART * MAXCART] = {{0}};
         const double *RA = xyz + 3 * A, *RB = xyz + 3 * B;
         const double R2 = dist2(RA, RB);
         for (int pa = 0; pa < nprim[A]; ++pa)
@@ -267,44 +270,72 @@ int qc_point_matrix(int nshell, const double *xyz, const int *ls, const int *npr
                 double E[3][LMAX + 3][LMAX + 3][2 * LMAX + 5];
                 for (int d = 0; d < 3; ++d) hermite_E(la, lb, a, b, RA[d] - RB[d], E[d]);
                 const double P[3] = {(a * RA[0] + b * RB[0]) / p, (a * RA[1] + b * RB[1]) / p, (a * RA[2] + b * RB[2]) / p};
-                double W[HDIM][HDIM][HDIM] = {{{0}}};
+                double W[3][HDIM][HDIM][HDIM] = {{{{0}}}};
                 for (long long c = 0; c < npts; ++c) {
                     static _Thread_local double R[RDIM][RDIM][RDIM];
                     const double PC[3] = {P[0] - pts[3 * c], P[1] - pts[3 * c + 1], P[2] - pts[3 * c + 2]};
-                    hermite_R(L, p, PC, R);
+                    hermite_R(L + (field != 0), p, PC, R);
                     for (int t = 0; t <= L; ++t)
                         for (int u = 0; u <= L - t; ++u)
-                            for (int v = 0; v <= L - t - u; ++v) W[t][u][v] += w[c] * R[t][u][v];
+                            for (int v = 0; v <= L - t - u; ++v) {
+                                if (!field) { W[0][t][u][v] += w[c] * R[t][u][v]; continue; }
+                                W[0][t][u][v] -= w[c] * R[t + 1][u][v];
+                                W[1][t][u][v] -= w[c] * R[t][u + 1][v];
+                                W[2][t][u][v] -= w[c] * R[t][u][v + 1];
+                            }
                 }
                 const double pref = 2.0 * M_PI / p * cc;
-                for (int ca = 0; ca < nca; ++ca)
-                    for (int cb = 0; cb < ncb; ++cb) {
-                        double v = 0.0;
-                        for (int t = 0; t <= ax[ca] + bx[cb]; ++t)
-                            for (int u = 0; u <= ay[ca] + by[cb]; ++u)
-                                for (int q = 0; q <= az[ca] + bz[cb]; ++q)
-                                    v += E[0][ax[ca]][bx[cb]][t] * E[1][ay[ca]][by[cb]][u] * E[2][az[ca]][bz[cb]][q] * W[t][u][q];
-                        cart[ca * ncb + cb] += pref * v;
-                    }
+                for (int k = 0; k < ncomp; ++k)
+                    for (int ca = 0; ca < nca; ++ca)
+                        for (int cb = 0; cb < ncb; ++cb) {
+                            double v = 0.0;
+                            for (int t = 0; t <= ax[ca] + bx[cb]; ++t)
+                                for (int u = 0; u <= ay[ca] + by[cb]; ++u)
+                                    for (int q = 0; q <= az[ca] + bz[cb]; ++q)
+                                        v += E[0][ax[ca]][bx[cb]][t] * E[1][ay[ca]][by[cb]][u] * E[2][az[ca]][bz[cb]][q] * W[k][t][u][q];
+                            cart[k][ca * ncb + cb] += pref * v;
+                        }
             }
-        double blk[7 * 7];
-        put_sph2(la, lb, cart, blk, 7, 0, 0);
-        for (int ma = 0; ma < 2 * la + 1; ++ma)
-            for (int mb = 0; mb < (A == B ? ma + 1 : 2 * lb + 1); ++mb) { /* a diagonal block from its lower triangle */
-                const size_t i = ao0[A] + ma, j = ao0[B] + mb;
-                M[i * nao + j] = blk[ma * 7 + mb];
-                M[j * nao + i] = blk[ma * 7 + mb];
-            }
+        for (int k = 0; k < ncomp; ++k) {
+            double blk[7 * 7];
+            double *Mk = M + (size_t)k * nao * nao;
+            put_sph2(la, lb, cart[k], blk, 7, 0, 0);
+            for (int ma = 0; ma < 2 * la + 1; ++ma)
+                for (int mb = 0; mb < (A == B ? ma + 1 : 2 * lb + 1); ++mb) { /* a diagonal block from its lower triangle */
+                    const size_t i = ao0[A] + ma, j = ao0[B] + mb;
+                    Mk[i * nao + j] = blk[ma * 7 + mb];
+                    Mk[j * nao + i] = blk[ma * 7 + mb];
+                }
+        }
     }
     return 0;
 }
 
+int qc_point_matrix(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                    const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                    const double *pts, const double *w, double *M)
+{
+    return point_matrix(nshell, xyz, ls, nprim, off, ao0, ex, cf, nao, npts, pts, w, 0, M);
+}
+
+/* M (3, nao, nao), M[k][mu][nu] = sum_c w[c] dA[c][mu][nu] / dR_c,k: the derivative integrals themselves (one point of unit
+ * weight: dA[c]), host only -- what the contraction of qc_point_field and the device kernel are checked against. */
+int qc_point_field_matrix(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                          const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                          const double *pts, const double *w, double *M)
+{
+    return point_matrix(nshell, xyz, ls, nprim, off, ao0, ex, cf, nao, npts, pts, w, 1, M);
+}
+
 /* u[c] = sum_{mu nu} D[mu][nu] A[c][mu][nu] for any (nao, nao) matrix D.  Two steps: the Hermite densities Lambda_tuv of
  * every kept primitive pair from D[A,B] + D[B,A]^T (OpenMP over shell pairs), then u[c] = sum_pairs sum_tuv Lambda_tuv
- * R_tuv(p, P - R_c) (OpenMP over points: every point adds its pairs in the same order). */
-int qc_point_contract(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
-                      const int *ao0, const double *ex, const double *cf, int nao, long long npts,
-                      const double *pts, const double *D, double *out)
+ * R_tuv(p, P - R_c) (OpenMP over points: every point adds its pairs in the same order).
+ * field != 0: the gradient of u with respect to the point instead, out (npts, 3).  The basis does not move with the point,
+ * so only R depends on it: d R_tuv(p, P - C) / d C_x = -R_{t+1,u,v}, the same Lambda against a table one order higher,
+ * G[c][x] = -sum_pairs sum_tuv Lambda_tuv R_{t+1,u,v} (y: u + 1, z: v + 1). */
+static int point_contract(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                          const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                          const double *pts, const double *D, int field, double *out)
 {
     for (int s = 0; s < nshell; ++s)
         if (ls[s] < 0 || ls[s] > LMAX) return -1;
@@ -374,23 +405,52 @@ int qc_point_contract(int nshell, const double *xyz, const int *ls, const int *n
 #pragma omp parallel for schedule(static)
     for (long long c = 0; c < npts; ++c) {
         static _Thread_local double R[RDIM][RDIM][RDIM];
-        double acc = 0.0;
+        double acc = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
         for (int pp = 0; pp < npp; ++pp) {
             const double PC[3] = {geom[4 * pp + 1] - pts[3 * c], geom[4 * pp + 2] - pts[3 * c + 1], geom[4 * pp + 3] - pts[3 * c + 2]};
             const int L = Ls[pp];
-            hermite_R(L, geom[4 * pp], PC, R);
+            hermite_R(L + (field != 0), geom[4 * pp], PC, R);
             const double *lm = lam + (size_t)NT * pp;
-            double s = 0.0;
             int n = 0;
+            if (field) {
+                double sx = 0.0, sy = 0.0, sz = 0.0;
+                for (int t = 0; t <= L; ++t)
+                    for (int u = 0; u <= L - t; ++u)
+                        for (int v = 0; v <= L - t - u; ++v, ++n) {
+                            sx += lm[n] * R[t + 1][u][v];
+                            sy += lm[n] * R[t][u + 1][v];
+                            sz += lm[n] * R[t][u][v + 1];
+                        }
+                gx -= sx; gy -= sy; gz -= sz;
+                continue;
+            }
+            double s = 0.0;
             for (int t = 0; t <= L; ++t)
                 for (int u = 0; u <= L - t; ++u)
                     for (int v = 0; v <= L - t - u; ++v, ++n) s += lm[n] * R[t][u][v];
             acc += s;
         }
-        out[c] = acc;
+        if (field) { out[3 * c] = gx; out[3 * c + 1] = gy; out[3 * c + 2] = gz; }
+        else out[c] = acc;
     }
     free(pbeg); free(geom); free(Ls); free(lam);
     return 0;
+}
+
+int qc_point_contract(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                      const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                      const double *pts, const double *D, double *out)
+{
+    return point_contract(nshell, xyz, ls, nprim, off, ao0, ex, cf, nao, npts, pts, D, 0, out);
+}
+
+/* G[c][k] = sum_{mu nu} D[mu][nu] dA[c][mu][nu] / dR_c,k, k = x, y, z: out (npts, 3).  For a density matrix the electronic
+ * part of the electric field at the point (the electronic potential is -u). */
+int qc_point_field(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                   const int *ao0, const double *ex, const double *cf, int nao, long long npts,
+                   const double *pts, const double *D, double *out)
+{
+    return point_contract(nshell, xyz, ls, nprim, off, ao0, ex, cf, nao, npts, pts, D, 1, out);
 }
 
 /* ---- two-electron integrals ------------------------------------------------------------------ */

@@ -2,6 +2,7 @@
 // device without ever being stored:
 //   matrix    M[mu, nu] = sum_c w_c A[c, mu, nu]          (external point charges: V_ext = -M)
 //   contract  u[c]      = sum_{mu nu} D[mu, nu] A[c, mu, nu]   (electrostatic potential of a density)
+//   field     G[c, k]   = d u[c] / d R_c,k, k = x, y, z        (electric field of a density, forces on point charges)
 // Device counterpart of integrals.c::qc_point_matrix / qc_point_contract (same McMurchie-Davidson formulation as the
 // nuclear attraction of qc_int1e: same Boys function, same recurrences, same 1e-18 cut on primitive pairs); s-f shells.
 //
@@ -14,6 +15,8 @@
 //   contract  k_pc_lambda  (one workgroup per shell pair A >= B) turns D into Hermite densities Lambda_tuv per
 //             primitive pair: D[A,B] + D[B,A]^T, solid harmonics -> Cartesians, contraction with E, prefactor;
 //             k_pc_contract<L>  u[c] += sum_pairs sum_tuv Lambda_tuv R_tuv, primitive pairs staged through LDS.
+//   field     the same k_pc_lambda; k_pc_field<L>  G[c] -= sum_pairs sum_tuv Lambda_tuv (R_t+1,u,v, R_t,u+1,v, R_t,u,v+1)
+//             with the table of order L + 1.
 //   matrix    k_pc_wsum<L>  (primitive pair x chunk of points) W_tuv = sum_c w_c R_tuv: per-lane sums, a butterfly over
 //             the wave, the four waves added in order -- no atomics, the same bits in every run; k_pc_matrix (one
 //             workgroup per shell pair) adds the chunks in order, contracts with E, sums the primitive pairs, rotates
@@ -186,6 +189,63 @@ __global__ __launch_bounds__(PC_T) void k_pc_contract(long long npts, const doub
             }
     }
     if (live) out[c] += acc;
+}
+
+// ---- field ---------------------------------------------------------------------------------------------------------
+// The gradient of the contraction with respect to the point, G[c][k] = d u[c] / d R_c,k.  The basis does not move with the
+// point, so only R depends on it and d R_tuv(p, P - C) / d C_x = -R_{t+1,u,v}: the Lambda of k_pc_lambda unchanged against
+// a table one order higher, G_x = -sum_pairs sum_tuv Lambda_tuv R_{t+1,u,v} (y: u + 1, z: v + 1).  Same shape as
+// k_pc_contract<L>: one point per lane, the class's primitive pairs in tiles through LDS, the table of order L + 1 in
+// registers, every index a compile-time constant.  `out` (npts, 3) was cleared by the caller.
+template <int L>
+__global__ __launch_bounds__(PC_T) void k_pc_field(long long npts, const double *__restrict__ pts, int npp,
+                                                   const int *__restrict__ list, const double *__restrict__ geom,
+                                                   const long long *__restrict__ tuvoff, const double *__restrict__ lam,
+                                                   double *__restrict__ out)
+{
+    constexpr int NT = ntuv(L);
+    __shared__ double s_lam[PC_TILE * NT], s_g[PC_TILE * 4];
+    const int tid = threadIdx.x;
+    const long long c = (long long)blockIdx.x * PC_T + tid;
+    const bool live = c < npts;
+    double cx = 0.0, cy = 0.0, cz = 0.0;
+    if (live) { cx = pts[3 * c]; cy = pts[3 * c + 1]; cz = pts[3 * c + 2]; }
+    double gx = 0.0, gy = 0.0, gz = 0.0;
+    for (int base = 0; base < npp; base += PC_TILE) {
+        const int nt = min(PC_TILE, npp - base);
+        __syncthreads();
+        for (int e = tid; e < nt * NT; e += PC_T) {
+            const int k = e / NT, i = e - k * NT;
+            s_lam[e] = lam[tuvoff[list[base + k]] + i];
+        }
+        for (int e = tid; e < nt * 4; e += PC_T) s_g[e] = geom[4 * (size_t)list[base + (e >> 2)] + (e & 3)];
+        __syncthreads();
+        if (live)
+            for (int k = 0; k < nt; ++k) {
+                double R[ntuv(L + 1)];
+                hermite_R_regs<L + 1>(s_g[4 * k], s_g[4 * k + 1] - cx, s_g[4 * k + 2] - cy, s_g[4 * k + 3] - cz, R);
+                double sx = 0.0, sy = 0.0, sz = 0.0;
+                static_for<0, L + 1>([&](auto t_) {
+                    constexpr int t = decltype(t_)::value;
+                    static_for<0, L - t + 1>([&](auto u_) {
+                        constexpr int u = decltype(u_)::value;
+                        static_for<0, L - t - u + 1>([&](auto v_) {
+                            constexpr int v = decltype(v_)::value;
+                            const double l = s_lam[k * NT + tuv_index(L, t, u, v)];
+                            sx += l * R[tuv_index(L + 1, t + 1, u, v)];
+                            sy += l * R[tuv_index(L + 1, t, u + 1, v)];
+                            sz += l * R[tuv_index(L + 1, t, u, v + 1)];
+                        });
+                    });
+                });
+                gx -= sx; gy -= sy; gz -= sz;
+            }
+    }
+    if (live) {
+        out[3 * c] += gx;
+        out[3 * c + 1] += gy;
+        out[3 * c + 2] += gz;
+    }
 }
 
 // ---- matrix --------------------------------------------------------------------------------------------------------
@@ -472,6 +532,37 @@ int DFT_PointCoulombContract(void *h, long long npts, unsigned long long d_point
     PC_CONTRACT(0); PC_CONTRACT(1); PC_CONTRACT(2); PC_CONTRACT(3); PC_CONTRACT(4); PC_CONTRACT(5); PC_CONTRACT(6);
 #undef PC_CONTRACT
     return check_launches(c, "DFT_PointCoulombContract launch failed");
+}
+
+int DFT_PointCoulombField(void *h, long long npts, unsigned long long d_points_xyz, unsigned long long d_dm, unsigned long long d_out)
+{
+    PcDev *c = (PcDev *)h;
+    if (!c) return -1;
+    c->err[0] = 0;
+    if (npts < 0 || (npts > 0 && (!d_points_xyz || !d_dm || !d_out))) {
+        snprintf(c->err, sizeof c->err, "DFT_PointCoulombField: null pointer or negative point count");
+        return -1;
+    }
+    if (npts == 0) return 0;
+    const long long nblk = (npts + PC_T - 1) / PC_T;
+    if (nblk > INT_MAX) {
+        snprintf(c->err, sizeof c->err, "DFT_PointCoulombField: more than %lld points in one call", (long long)INT_MAX * PC_T);
+        return -1;
+    }
+    PcGuard g(c);
+    const double *pts = (const double *)d_points_xyz;
+    double *out = (double *)d_out;
+    hipLaunchKernelGGL(k_pc_lambda, dim3((unsigned)c->npairs), dim3(PC_TS), 0, c->stream, c->nao, c->xyz, c->ls, c->ao0, c->pA, c->pB,
+                       c->pp_begin, c->pp_ab, c->pp_cc, c->tuvoff, (const double *)d_dm, c->lam);
+    const hipError_t e = hipMemsetAsync(out, 0, sizeof(double) * 3 * (size_t)npts, c->stream);
+    if (e != hipSuccess) return fail(c, "clearing the output", e);
+#define PC_FIELD(LL)                                                                                                        \
+    if (c->cls_off[LL + 1] > c->cls_off[LL])                                                                                \
+        hipLaunchKernelGGL(k_pc_field<LL>, dim3((unsigned)nblk), dim3(PC_T), 0, c->stream, npts, pts,                       \
+                           c->cls_off[LL + 1] - c->cls_off[LL], c->cls_list + c->cls_off[LL], c->geom, c->tuvoff, c->lam, out)
+    PC_FIELD(0); PC_FIELD(1); PC_FIELD(2); PC_FIELD(3); PC_FIELD(4); PC_FIELD(5); PC_FIELD(6);
+#undef PC_FIELD
+    return check_launches(c, "DFT_PointCoulombField launch failed");
 }
 
 } // extern "C"

@@ -3,7 +3,8 @@ surface (dft.py:101-297: same positionals, same printed lines) on the MI355X eng
 other name of functionals.TABLE (PBE0, BLYP, ...) or an expression such as "0.75*pbe_x + pbe_c + 0.25*hf".
 Extra flags (defaults = what the reference hard-codes): --basis sto-3g, --grid-level 3, --quirks 1.
 --point-charges FILE runs the molecule in the field of external point charges (rows `x y z q`); --esp-points FILE with
---esp-out FILE writes the electrostatic potential of the converged density at the given points."""
+--esp-out FILE writes the electrostatic potential of the converged density at the given points and --field-out FILE its
+electric field; --charge-forces-out FILE writes the forces of the molecule on the point charges."""
 import argparse
 import importlib.util
 import os
@@ -52,6 +53,24 @@ def write_esp_rows(path, points_bohr, esp, unit="angstrom"):
             fh.write(f"{x * scale:.10f} {y * scale:.10f} {z * scale:.10f} {v:.12e}\n")
 
 
+def write_field_rows(path, points_bohr, field, unit="angstrom"):
+    """Rows `x y z Ex Ey Ez`: the coordinates back in `unit`, the field in atomic units (Ha / (e bohr))."""
+    from .basis import BOHR
+    scale = BOHR if unit == "angstrom" else 1.0
+    with open(path, "w") as fh:
+        for (x, y, z), e in zip(points_bohr, field):
+            fh.write(f"{x * scale:.10f} {y * scale:.10f} {z * scale:.10f} {e[0]:.12e} {e[1]:.12e} {e[2]:.12e}\n")
+
+
+def write_charge_force_rows(path, charges_bohr, forces, unit="angstrom"):
+    """Rows `x y z q Fx Fy Fz`: the charges' coordinates back in `unit`, the forces in Ha / bohr."""
+    from .basis import BOHR
+    scale = BOHR if unit == "angstrom" else 1.0
+    with open(path, "w") as fh:
+        for (x, y, z, q), f in zip(charges_bohr, forces):
+            fh.write(f"{x * scale:.10f} {y * scale:.10f} {z * scale:.10f} {q:.12e} {f[0]:.12e} {f[1]:.12e} {f[2]:.12e}\n")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Run DFT (LDA/GGA/B3LYP) using the MI355X HIP backend.")
     p.add_argument("functional", type=_functional,
@@ -92,14 +111,21 @@ def main(argv=None):
     p.add_argument("--point-charges-unit", default="angstrom", choices=["angstrom", "bohr"],
                    help="unit of the coordinates in --point-charges and --esp-points (default: angstrom, the unit of the .xyz file)")
     p.add_argument("--esp-points", default=None, metavar="FILE", help="text rows `x y z`: points at which the electrostatic potential of the "
-                                                                      "converged density is evaluated (needs --esp-out)")
+                                                                      "converged density is evaluated (needs --esp-out and / or --field-out)")
     p.add_argument("--esp-out", default=None, metavar="FILE", help="receives rows `x y z esp` (coordinates in the unit given, potential in Ha/e; "
                                                                   "nuclei and electrons of the molecule, without the external charges)")
+    p.add_argument("--field-out", default=None, metavar="FILE", help="receives rows `x y z Ex Ey Ez` for the --esp-points (coordinates in the unit given, "
+                                                                    "electric field in Ha/(e bohr); the molecule's field, without the external charges)")
+    p.add_argument("--charge-forces-out", default=None, metavar="FILE",
+                   help="receives rows `x y z q Fx Fy Fz`: the force of the molecule on every charge of --point-charges in Ha/bohr "
+                        "(the charges' forces on each other are not included)")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
     args = p.parse_args(argv)
-    if bool(args.esp_points) != bool(args.esp_out):
-        p.error("--esp-points and --esp-out go together")
+    if bool(args.esp_points) != bool(args.esp_out or args.field_out):
+        p.error("--esp-points goes with --esp-out and / or --field-out")
+    if args.charge_forces_out and not args.point_charges:
+        p.error("--charge-forces-out needs --point-charges")
     fn = functionals.resolve(args.functional)
 
     # one process per GPU: `python -m torch.distributed.run --nproc-per-node N -m quantum_compute_dft_amd.dft ...`
@@ -190,8 +216,19 @@ def main(argv=None):
     if args.esp_points and res["converged"] and not rank:
         from . import properties
         esp_pts = read_point_rows(args.esp_points, 3, args.point_charges_unit)
-        write_esp_rows(args.esp_out, esp_pts, properties.electrostatic_potential(inp, res["dm"], esp_pts, device=device), args.point_charges_unit)
-        print(f"Electrostatic potential at {len(esp_pts)} points written to {args.esp_out}")
+        if args.esp_out:
+            write_esp_rows(args.esp_out, esp_pts, properties.electrostatic_potential(inp, res["dm"], esp_pts, device=device), args.point_charges_unit)
+            print(f"Electrostatic potential at {len(esp_pts)} points written to {args.esp_out}")
+        if args.field_out:
+            write_field_rows(args.field_out, esp_pts, properties.electric_field(inp, res["dm"], esp_pts, device=device), args.point_charges_unit)
+            print(f"Electric field at {len(esp_pts)} points written to {args.field_out}")
+    charge_forces = None
+    if charges is not None and res["converged"] and not rank:
+        from . import properties
+        charge_forces = properties.point_charge_forces(inp, res["dm"], device=device)
+        if args.charge_forces_out:
+            write_charge_force_rows(args.charge_forces_out, inp.point_charges, charge_forces, args.point_charges_unit)
+            print(f"Forces on {len(charge_forces)} point charges written to {args.charge_forces_out}")
     import json
     record = {"functional": args.functional, "molecule": os.path.splitext(atom_file)[0], "basis": args.basis, "grid_level": args.grid_level,
               "nao": int(inp.shells.nao), "ngrid": int(inp.grids.size), "nocc": int(inp.nocc), "n_gpus": world, "eri": args.eri,
@@ -204,6 +241,7 @@ def main(argv=None):
               "eigensolver_stats": eig_stats, "xc_occ": int(backend.xc_occ)}
     if charges is not None:
         record["n_point_charges"] = int(len(charges)); record["E_nuc_ext"] = float(inp.E_nuc_ext)
+        record["point_charge_forces"] = charge_forces.tolist() if charge_forces is not None else None
     if other is not None:
         record["E_tot_other_quirks"] = other.get("E_tot"); record["other_quirks"] = 0 if args.quirks else 1
     line = json.dumps(record)

@@ -2,7 +2,8 @@
 grid.py:61-66 (`mol.intor('int1e_ovlp'|'int1e_kin'|'int1e_nuc'|'int2e')`, `mol.energy_nuc()`).
 The arithmetic is csrc/integrals.c (McMurchie-Davidson, OpenMP), built in-tree with gcc.  Also the one-electron Coulomb
 integrals at arbitrary points (external point charges, electrostatic potential): point_coulomb_matrix / point_coulomb_contract
-on the host, PointCoulomb on the device, point_coulomb() choosing between them.
+on the host, PointCoulomb on the device, point_coulomb() choosing between them; and the gradient of the contraction
+with respect to the point (electric field of a density): point_coulomb_field, PointCoulomb.field, point_field().
 
 PARITY UNPINNED against PySCF/libcint (not installed); pinned offline by quadrature on the
 Becke grid, textbook H2/STO-3G integrals and RHF energies (tests/test_integrals.py)."""
@@ -63,7 +64,7 @@ def _load():
         L.qc_eri_cols2.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, dp, ctypes.c_int]
         L.qc_set_threads.restype = None
         L.qc_set_threads.argtypes = [ctypes.c_int]
-        for f in (L.qc_point_matrix, L.qc_point_contract):
+        for f in (L.qc_point_matrix, L.qc_point_contract, L.qc_point_field, L.qc_point_field_matrix):
             f.restype = ctypes.c_int
             f.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ctypes.c_longlong, dp, dp, dp]
         from .hostinfo import host_cpu_share
@@ -271,9 +272,44 @@ def point_coulomb_contract(shells, points, dm):
     return u
 
 
+def point_coulomb_field(shells, points, dm):
+    """G[c, k] = sum_{mu nu} dm[mu, nu] d<mu| 1/|r - R| |nu> / dR_k at R = points[c], k = x, y, z, on the host
+    (qc_point_field): (n, 3), the gradient of point_coulomb_contract's value with respect to the point, for any
+    (nao, nao) matrix.  Exact -- the basis does not move with the point.  For a density matrix the electronic part of the
+    electric field is +G (the electronic potential is -u)."""
+    pts = _points(points)
+    n = shells.nao
+    D = np.ascontiguousarray(dm, dtype=np.float64)
+    if D.shape != (n, n):
+        raise ValueError(f"dm: expected shape ({n}, {n}), got {D.shape}")
+    keep, p = _args(shells)
+    G = np.zeros((len(pts), 3))
+    dp = ctypes.POINTER(ctypes.c_double)
+    if len(pts) and _load().qc_point_field(shells.nshell, *p, n, len(pts), pts.ctypes.data_as(dp), D.ctypes.data_as(dp), G.ctypes.data_as(dp)) != 0:
+        raise ValueError("integrals: angular momentum above f is not supported")
+    return G
+
+
+def point_coulomb_field_matrix(shells, points, weights):
+    """(3, nao, nao): M[k, mu, nu] = sum_c weights[c] d<mu| 1/|r - R| |nu> / dR_k at R = points[c], on the host
+    (qc_point_field_matrix) -- for one point of unit weight the derivative integrals themselves.  Host only (the device has
+    the contraction): what point_coulomb_field and PointCoulomb.field are checked against.  M[k] == M[k].T bit for bit."""
+    pts = _points(points)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (len(pts),):
+        raise ValueError(f"weights: expected shape ({len(pts)},), got {w.shape}")
+    keep, p = _args(shells)
+    n = shells.nao
+    M = np.zeros((3, n, n))
+    dp = ctypes.POINTER(ctypes.c_double)
+    if len(pts) and _load().qc_point_field_matrix(shells.nshell, *p, n, len(pts), pts.ctypes.data_as(dp), w.ctypes.data_as(dp), M.ctypes.data_as(dp)) != 0:
+        raise ValueError("integrals: angular momentum above f is not supported")
+    return M
+
+
 class PointCoulomb:
-    """The same two operations ON THE DEVICE (libdft.so: csrc/point_coulomb.hip, DFT_PointCoulomb*) on torch tensors:
-    `matrix(points, weights)` -> (nao, nao), `contract(points, dm)` -> (n,).  Asynchronous on the null stream (or the one
+    """The same operations ON THE DEVICE (libdft.so: csrc/point_coulomb.hip, DFT_PointCoulomb*) on torch tensors:
+    `matrix(points, weights)` -> (nao, nao), `contract(points, dm)` -> (n,), `field(points, dm)` -> (n, 3).  Asynchronous on the null stream (or the one
     given to set_stream), like torch's own kernels; the tensors live on the device that was current at construction."""
 
     def __init__(self, shells, lib_path=None):
@@ -288,6 +324,8 @@ class PointCoulomb:
         L.DFT_PointCoulombMatrix.restype = ctypes.c_int
         L.DFT_PointCoulombContract.argtypes = [ctypes.c_void_p, ctypes.c_longlong, u64, u64, u64]
         L.DFT_PointCoulombContract.restype = ctypes.c_int
+        L.DFT_PointCoulombField.argtypes = [ctypes.c_void_p, ctypes.c_longlong, u64, u64, u64]
+        L.DFT_PointCoulombField.restype = ctypes.c_int
         L.DFT_PointCoulombSetStream.argtypes = [ctypes.c_void_p, u64]
         L.DFT_PointCoulombSetStream.restype = ctypes.c_int
         L.DFT_PointCoulombLastError.argtypes = [ctypes.c_void_p]
@@ -344,6 +382,18 @@ class PointCoulomb:
             raise self._error()
         return out
 
+    def field(self, points, dm, out=None):
+        import torch
+        n = int(points.shape[0])
+        self._check(points, (n, 3), "points"); self._check(dm, (self.nao, self.nao), "dm")
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float64, device=points.device)
+        self._check(out, (n, 3), "out")
+        if self.lib.DFT_PointCoulombField(self._h, n, ctypes.c_uint64(points.data_ptr() if n else 0), ctypes.c_uint64(dm.data_ptr()),
+                                          ctypes.c_uint64(out.data_ptr() if n else 0)) != 0:
+            raise self._error()
+        return out
+
 
 def point_coulomb(shells, points, weights=None, dm=None, device="cpu"):
     """The one entry the rest of the package calls: `weights` given -> the (nao, nao) matrix, `dm` given -> the values
@@ -362,5 +412,21 @@ def point_coulomb(shells, points, weights=None, dm=None, device="cpu"):
             pts = t(_points(points))
             res = pc.matrix(pts, t(weights)) if dm is None else pc.contract(pts, t(dm))
             return res.cpu().numpy()         # the copy waits for the kernels
+        finally:
+            pc.close()
+
+
+def point_field(shells, points, dm, device="cpu"):
+    """(n, 3) gradient of point_coulomb(dm=...)'s values with respect to the points; numpy in, numpy out.  On a CUDA
+    device PointCoulomb.field, otherwise point_coulomb_field -- no quiet fall-back from one to the other."""
+    if not str(device).startswith("cuda"):
+        return point_coulomb_field(shells, points, dm)
+    import torch
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        pc = PointCoulomb(shells)
+        try:
+            t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
+            return pc.field(t(_points(points)), t(dm)).cpu().numpy()         # the copy waits for the kernels
         finally:
             pc.close()

@@ -1,5 +1,6 @@
-"""Properties of a converged density.  Electrostatic potential at arbitrary points, on the device where one is in use
-(csrc/point_coulomb.hip through integrals.point_coulomb)."""
+"""Properties of a converged density.  Electrostatic potential and electric field at arbitrary points and the forces on
+the external point charges of an embedded run, on the device where one is in use (csrc/point_coulomb.hip through
+integrals.point_coulomb / integrals.point_field)."""
 import numpy as np
 
 from . import basis, integrals
@@ -22,3 +23,36 @@ def electrostatic_potential(inp, dm, points, device="cpu", electronic_only=False
         c, a = np.unravel_index(np.argmin(dist), dist.shape)
         raise ValueError(f"point {c} sits on nucleus {a} ({inp.symbols[a]}): the nuclear potential is singular there")
     return (z[None, :] / dist).sum(axis=1) - u
+
+
+def electric_field(inp, dm, points, device="cpu", electronic_only=False):
+    """E(r) = sum_A Z_A (r - R_A) / |r - R_A|^3 + G(r) in atomic units (Ha / (e bohr)) at `points` (n, 3) bohr: (n, 3),
+    minus the gradient of electrostatic_potential.  G[c, k] = sum_{mu nu} dm[mu, nu] d<mu| 1/|r - R| |nu> / dR_k at
+    R = points[c] is the electronic part (integrals.point_field; exact, the basis does not move with the point).  The
+    field of the MOLECULE: external point charges of an embedded run are not included.  `electronic_only`: G alone.
+    ValueError for a point within 1e-8 bohr of a nucleus (not checked with electronic_only)."""
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points: expected an (n, 3) array in bohr, got shape {pts.shape}")
+    G = integrals.point_field(inp.shells, pts, np.asarray(dm, dtype=np.float64), device=device)
+    if electronic_only:
+        return G
+    z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
+    d = pts[:, None, :] - np.asarray(inp.atom_xyz, dtype=np.float64)[None, :, :]                                  # (n, natm, 3)
+    dist = np.linalg.norm(d, axis=2)
+    if dist.size and dist.min() < 1e-8:
+        c, a = np.unravel_index(np.argmin(dist), dist.shape)
+        raise ValueError(f"point {c} sits on nucleus {a} ({inp.symbols[a]}): the nuclear potential is singular there")
+    return (z[None, :, None] * d / dist[:, :, None] ** 3).sum(axis=1) + G
+
+
+def point_charge_forces(inp, dm, device="cpu"):
+    """F_c = q_c E(R_c) in Ha / bohr, (ncharges, 3): the force the molecule (nuclei and the density `dm`) exerts on every
+    external point charge of `inp` (inputs.build(..., point_charges=...)), E = electric_field.  For a converged density
+    -F_c is the derivative of the total energy with respect to R_c (Hellmann-Feynman: no basis function moves with a
+    charge).  The forces of the charges on each other are NOT included, just as their mutual energy is not part of
+    inp.E_nuc.  ValueError if `inp` has no point charges."""
+    pc = getattr(inp, "point_charges", None)
+    if pc is None or len(pc) == 0:
+        raise ValueError("point_charge_forces: the inputs were built without point charges")
+    return pc[:, 3:4] * electric_field(inp, dm, pc[:, :3], device=device)
