@@ -349,8 +349,23 @@ void DFT_ScfTailClose(void *handle);
  * rounding of the sums, not bit for bit.  A SOLVER_MIX solver never takes it, whatever the option says: the one-pass
  * kernel is register-critical and instantiated for the three built-in bodies only, so a mix runs the general kernels at
  * every nao), "ao_pt" (grid points per workgroup of DFT_EvalAO:
- * 8, 16, or 0 = auto).  Returns 0 if the key is known. */
+ * 8, 16, or 0 = auto), "vxc_fringe" (the wave-specialised Vxc kernel at nao = 16 k + 1..4, k >= 1, every solver type but
+ * B3LYP: -1 = auto and 1: the matrix cores take the k x k whole tiles and one wave adds the 1..4 fringe lines on the vector
+ * ALU, instead of padding to k + 1 tiles per side; 0 = the padded kernel.  Same slabs, Vxc equal to the rounding of the
+ * fringe sums, Exc bit for bit), "publish" (how the synchronous calls learn that the sweep has completed, with
+ * fuse_finish = 0: 0 = a one-thread kernel behind the Vxc reduce copies Exc to the host-mapped word; 1 = the reduce kernel
+ * stores Exc there itself and a stream memory write (hipStreamWriteValue64) behind it raises a per-call sequence word
+ * the host waits for -- same contract, no launch; taken only where a probe at DFT_CreateSolver found the runtime
+ * performs the operation, else the kernel stays; -1 = auto, default: the kernel, which measured 1-2 us faster per call.
+ * A recorded graph always ends with the kernel).  Returns 0 if the key is known. */
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
+
+/* Read-back of "publish", "vxc_fringe", "fuse_finish", "strict_sync", "spin_wait", "graph", "tiny", "sweep_order", "path",
+ * "quirks", and of what the library made of them: "publish_probe" (1 = the creation-time probe of the stream memory
+ * write passed), "publish_live" (1 = a synchronous call now completes by stream write), "used_publish" and
+ * "used_vxc_fringe" (what the last synchronous call / the last sweep did).  NaN for an unknown key.  Added without a
+ * change of DFT_GetVersion: a caller that may meet an older library looks the symbol up. */
+double DFT_GetOption(XCSolver *solver, const char *key);
 
 /* Run subsequent work on `hip_stream` (a hipStream_t cast to an integer);
  * 0 restores the null stream. */

@@ -48,7 +48,7 @@ RESOURCES_PATH = LIB_PATH + ".resources.json"
 VALIDATION_KERNELS = ("k_rho_mfma", "k_vxc_mfma", "k_rho_valu", "k_vxc_valu")
 SPILL_ALLOW = {
     # demangled-name prefix: (max scratch bytes per lane, reason)
-    "void qcdft::k_vxc_ws<8, true, false, false>": (8, "one dword (the thread index) stored before and reloaded after the step loop, "
+    "void qcdft::k_vxc_ws<8, true, false, false, false>": (8, "one dword (the thread index) stored before and reloaded after the step loop, "
                                                        "never inside it (ISA checked); the 8-byte-load GGA variant for odd nao / "
                                                        "unaligned planes at nao 113-128 only"),
 }

@@ -80,6 +80,9 @@ struct XCSolver {
     int tiny = -1;     // one-pass sweep kernel for nao <= 32 (xc_tiny_kernels.hpp): -1 auto (where it is faster, tiny_pays()), 0 off, 1 on
     int occ = 0;       // DFT_ComputeXCOcc: 0 auto (occupied-orbital density step where it does fewer MFMAs), 1 always, 2 never
     int used_occ = 0;  // what the last sweep did (DFT_GetTimings names say so too)
+    int vxc_fringe = -1;  // k_vxc_ws at nao = 16 k + 1..4: whole-tile-row MFMA role with a vector fringe (1, -1 auto) or the padded grid (0)
+    int used_vxc_fringe = 0; // what the last sweep's Vxc kernel was (DFT_GetOption "used_vxc_fringe")
+    int used_publish = 0; // the last synchronous call was completed by 1: the stream write, 0: a kernel (DFT_GetOption "used_publish")
     int eri_sym = 0;   // 1: the caller vouches that the dense ERI is symmetric as an (N2, N2) matrix: DFT_ComputeCoulomb streams its upper
                        // triangle only; 2: ... and in each index pair, and dm = dm^T: the unique eighth only
     // A synchronous call seen before with the same pointers and sizes is replayed as one recorded HIP graph (one submission
@@ -96,6 +99,17 @@ struct XCSolver {
     int strict_sync = 0; // 1: after the Exc word, also poll the stream until it reports complete (+8-10 us per call)
     double *h_exc = nullptr;   // pinned, host-mapped: the reduce kernel writes Exc here
     double *h_exc_dev = nullptr; // device alias of h_exc
+    // Completion without a kernel (option "publish"): the reduce kernel's finishing block stores Exc to h_exc itself, and the
+    // word that says "the whole call has completed" is a per-call sequence number, written BEHIND that kernel by a stream
+    // memory operation (hipStreamWriteValue64: performed after all earlier commands of the stream have completed).  The
+    // synchronous call spins on the sequence word, then reads Exc.  Probed once at creation; where the runtime refuses the
+    // operation on this allocation the one-thread k_publish_exc launch stays.
+    int publish = -1;          // 0: k_publish_exc, 1: stream write (where the probe passed), -1 auto (= 1 where the probe passed)
+    bool publish_ok = false;   // the probe's verdict
+    unsigned long long *h_seq = nullptr, *h_seq_dev = nullptr; // pinned, host-mapped sequence word and its device alias
+    unsigned long long seq = 0; // value of the last stream write that was enqueued
+    bool recording = false;    // xc_sweep is being recorded into a graph: stream memory operations are not recorded
+    int wait_mode = 0;         // how the last sweep with want_host_exc signals completion: 0 Exc word, 1 sequence word, 2 neither (synchronise)
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -224,6 +238,8 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
 {
     s->last_error.clear();
     s->n_timed = 0;
+    s->wait_mode = 0;
+    s->used_vxc_fringe = 0;
     if (!s->device_ok) {
         set_error(s, "no usable HIP device");
         return false;
@@ -374,9 +390,19 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     }
     if (!tiny) {
         ScopedTimer t(s, "vxc");
+        // Option "vxc_fringe": at nao = 16 k + 1..4 (k >= 1) the one-sided kernels leave the k x k whole tiles to the matrix
+        // pipe and take the fringe lines on the vector ALU (vxc_ws_mfma_fringe) instead of padding to k + 1 tiles per side
+        const bool fringe = fast && s->type != SOLVER_B3LYP && s->vxc_fringe != 0 && nao > 16 && nao % 16 >= 1 && nao % 16 <= 4;
+        s->used_vxc_fringe = fringe;
         auto launch = [&](auto G, auto S) { // S: B3LYP, the wave-specialised kernels write symmetrised slabs
             if (fast)
                 with_bool(vec16, [&](auto V) { with_nt(ntv, [&](auto NT) {
+                    if constexpr (NT >= 2 && !S) {
+                        if (fringe) {
+                            hipLaunchKernelGGL((k_vxc_ws<NT, G, V, false, true>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1);
+                            return;
+                        }
+                    }
                     hipLaunchKernelGGL((k_vxc_ws<NT, G, V, S>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1);
                 }); });
             else if (big)
@@ -419,8 +445,24 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
             // Exc is summed by the reduce kernel's highest-index block into the DEVICE scalar only; publishing it to the host
             // is left to a one-thread kernel behind it (stream order: the whole call has completed when the word appears) --
             // the shortest launch there is, instead of a finishing kernel that still has the partials to add up
-            hipLaunchKernelGGL((k_reduce_slabs8<false, true>), g, dim3(256), 0, st, nao, nslab, slabs, vxc, nxb, partial, exc, (double *)nullptr);
-            if (want_host_exc && s->h_exc_dev) hipLaunchKernelGGL(k_publish_exc, dim3(1), dim3(1), 0, st, exc, s->h_exc_dev);
+            // Option "publish" (where the creation-time probe passed): no publishing launch -- the reduce kernel's finishing
+            // block stores Exc to the host word, and a stream memory write behind the kernel raises the sequence word the
+            // host waits for.  Same meaning (stream order: after every store of the call), no dispatch.
+            const bool sw = want_host_exc && s->h_exc_dev && s->publish > 0 && s->publish_ok && !s->recording;
+            hipLaunchKernelGGL((k_reduce_slabs8<false, true>), g, dim3(256), 0, st, nao, nslab, slabs, vxc, nxb, partial, exc,
+                               sw ? s->h_exc_dev : (double *)nullptr);
+            if (sw) {
+                if (hipStreamWriteValue64(st, s->h_seq_dev, s->seq + 1, 0) == hipSuccess) {
+                    ++s->seq;
+                    s->wait_mode = 1;
+                } else { // refused after all: this call is waited for on the stream, later ones publish by kernel
+                    (void)hipGetLastError();
+                    s->publish_ok = false;
+                    s->wait_mode = 2;
+                }
+            } else if (want_host_exc && s->h_exc_dev) {
+                hipLaunchKernelGGL(k_publish_exc, dim3(1), dim3(1), 0, st, exc, s->h_exc_dev);
+            }
             return hip_ok(s, hipGetLastError(), "XC sweep launch");
         }
         // last launch of the call: Exc to the device scalar and to host-mapped memory
@@ -743,6 +785,28 @@ extern "C" {
 
 int DFT_GetVersion(void) { return 5; }   // 4: DFT_CreateSolverMix / DFT_GetMix; 5: DFT_PointCoulomb*
 
+// Option "publish": does this runtime perform a stream memory write on a pinned, host-mapped word?  Asked once, with an
+// ordinary call on the stream a new solver uses (the null stream); any error code, or a value that did not arrive, leaves
+// the kernel path in place.
+static void probe_publish(XCSolver *s)
+{
+    if (!s->h_exc_dev) return;
+    if (hipHostMalloc((void **)&s->h_seq, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&s->h_seq_dev, s->h_seq, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        if (s->h_seq) (void)hipHostFree(s->h_seq);
+        s->h_seq = s->h_seq_dev = nullptr;
+        return;
+    }
+    *s->h_seq = 0;
+    s->seq = 1;
+    if (hipStreamWriteValue64(s->stream, s->h_seq_dev, s->seq, 0) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    s->publish_ok = *(volatile unsigned long long *)s->h_seq == s->seq;
+}
+
 static XCSolver *create_solver(int type, const double *mix)
 {
     XCSolver *s = new (std::nothrow) XCSolver();
@@ -772,6 +836,7 @@ static XCSolver *create_solver(int type, const double *mix)
                 s->h_exc = nullptr;
                 s->h_exc_dev = nullptr;
             }
+            probe_publish(s);
         }
     } else {
         (void)hipGetLastError();
@@ -828,6 +893,7 @@ void DFT_DestroySolver(XCSolver *s)
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
+        if (s->h_seq) (void)hipHostFree(s->h_seq);
         for (Timing &t : s->timings) {
             (void)hipEventDestroy(t.t0);
             (void)hipEventDestroy(t.t1);
@@ -870,7 +936,9 @@ static bool record_sweep(XCSolver *s, const SweepArgs &a)
     }
     hipStream_t user = s->stream;
     s->stream = s->cap_stream;
+    s->recording = true;   // replay keeps the publishing kernel: stream memory operations are not recorded
     const bool ok = xc_sweep(s, a.ngrid, a.nao, a.dm, a.ao, a.grad, a.w, a.vxc, true, a.cocc, a.nocc);
+    s->recording = false;
     s->stream = user;
     hipGraph_t graph = nullptr;
     const hipError_t e = hipStreamEndCapture(s->cap_stream, &graph);
@@ -946,13 +1014,31 @@ static double xc_call_sync(XCSolver *s, long long ngrid, int nao, unsigned long 
                       (const double *)d_w, (double *)d_vxc, (const double *)d_cocc};
     const bool graphed = !s->profile && s->h_exc_dev && ngrid > 0 && nao > 0 &&
                          (s->graph > 0 || (s->graph < 0 && (double)ngrid * nao <= GRAPH_AUTO_ELEMS));
-    if (!(graphed && replay_sweep(s, a)) &&
-        !xc_sweep(s, a.ngrid, nao, a.dm, a.ao, a.grad, a.w, a.vxc, true, a.cocc, nocc))
+    if (graphed && replay_sweep(s, a)) s->wait_mode = 0; // a recorded sweep ends with the publishing kernel
+    else if (!xc_sweep(s, a.ngrid, nao, a.dm, a.ao, a.grad, a.w, a.vxc, true, a.cocc, nocc))
         return nan;
     if (graphed) note_sweep(s, a);
+    s->used_publish = s->wait_mode == 1;
     if (s->h_exc_dev) { // Exc is written into host-mapped memory by the call's last kernel
         volatile double *hx = s->h_exc;
-        if (s->spin_wait) {
+        if (s->spin_wait && s->wait_mode == 1) {
+            // Option "publish": the completion word is this call's sequence number, stored by a stream memory write that
+            // the runtime performs after every earlier command of the stream -- the reduce kernel, whose finishing block
+            // left Exc in *hx, included.  The same bounded spin, the same meaning ("the whole call has completed"); a
+            // faulted stream ends it, and the stream is then polled to completion as below.
+            volatile unsigned long long *hs = s->h_seq;
+            const unsigned long long want = s->seq;
+            for (unsigned spins = 1; *hs != want; ++spins) {
+                if ((spins & 0xFFF) == 0 && hipStreamQuery(s->stream) != hipErrorNotReady) break;
+                __builtin_ia32_pause();
+            }
+            __atomic_thread_fence(__ATOMIC_ACQUIRE); // Exc is read after the sequence word
+            if (s->strict_sync || *hs != want || std::isnan(*hx)) {
+                hipError_t q;
+                while ((q = hipStreamQuery(s->stream)) == hipErrorNotReady) __builtin_ia32_pause();
+                if (!hip_ok(s, q, "XC sweep")) return nan;
+            }
+        } else if (s->spin_wait && s->wait_mode == 0) {
             // The word is stored by the call's LAST kernel.  Default: that is the one-block k_finish_exc, which stream
             // order starts only after the Vxc reduce (and everything before it) has completed -- seeing the word means
             // the whole call is done, for consumers on any stream and for host reads, the reference's contract
@@ -1152,12 +1238,35 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "spin_wait")) { s->spin_wait = value != 0.0; return 0; }
     if (!strcmp(key, "strict_sync")) { s->strict_sync = value != 0.0; return 0; }
     if (!strcmp(key, "fuse_finish")) { s->fuse_finish = value != 0.0; return 0; }
+    if (!strcmp(key, "vxc_fringe")) { s->vxc_fringe = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
+    if (!strcmp(key, "publish")) { s->publish = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
     if (!strcmp(key, "sweep_order")) { s->sweep_order = (int)value & 3; return 0; }
     if (!strcmp(key, "occ")) { s->occ = value == 1.0 ? 1 : value == 2.0 ? 2 : 0; return 0; }
     if (!strcmp(key, "tiny")) { s->tiny = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
     if (!strcmp(key, "ao_pt")) { s->ao_pt = value == 16.0 ? 16 : value == 8.0 ? 8 : 0; return 0; }
     if (!strcmp(key, "ksplit")) { s->ksplit = value > 0 ? (int)value : 0; return 0; }
     return -1;
+}
+
+double DFT_GetOption(XCSolver *s, const char *key)
+{
+    const double unknown = std::numeric_limits<double>::quiet_NaN();
+    if (!s || !key) return unknown;
+    if (!strcmp(key, "publish")) return s->publish;
+    if (!strcmp(key, "publish_probe")) return s->publish_ok ? 1.0 : 0.0;                        // the creation-time probe's verdict
+    if (!strcmp(key, "publish_live")) return s->publish > 0 && s->publish_ok ? 1.0 : 0.0;      // what a default-path call does now
+    if (!strcmp(key, "used_publish")) return s->used_publish;                                   // what the last synchronous call did
+    if (!strcmp(key, "vxc_fringe")) return s->vxc_fringe;
+    if (!strcmp(key, "used_vxc_fringe")) return s->used_vxc_fringe;                            // what the last sweep's Vxc kernel was
+    if (!strcmp(key, "fuse_finish")) return s->fuse_finish;
+    if (!strcmp(key, "strict_sync")) return s->strict_sync;
+    if (!strcmp(key, "spin_wait")) return s->spin_wait;
+    if (!strcmp(key, "graph")) return s->graph;
+    if (!strcmp(key, "tiny")) return s->tiny;
+    if (!strcmp(key, "sweep_order")) return s->sweep_order;
+    if (!strcmp(key, "path")) return s->path;
+    if (!strcmp(key, "quirks")) return s->quirks;
+    return unknown;
 }
 
 int DFT_SetStream(XCSolver *s, unsigned long long hip_stream)

@@ -63,9 +63,140 @@ __device__ __forceinline__ unsigned ws_tile(unsigned ntile, unsigned b, unsigned
 
 // ------------------------------------------------------------------ Vxc ----
 // V[a][b] += sum_g Q[g][a] P[g][b],  Q = sum_c coef_c * plane_c,  P = AO.
+//
+// MFMA role of k_vxc_ws<.., FR = true>: widths of NF = NT - 1 whole tiles plus 1..4 fringe lines (nao = 16 NF + 1..4,
+// Benzene/def2-SVP's 114).  The padded grid pays a full tile row and a full tile column for those lines (15 of 64 tiles
+// at NT = 8 for 2 live lines of 16).  Here the matrix pipe takes the NF x NF whole tiles only, dealt by tile ROW: wave w
+// owns rows {2w, 2w+1} below NF times all NF tile columns (at most 14 tiles, 3584 pipe cycles per sub-tile against 4096),
+// and the last wave, which holds the odd row or none, also accumulates the fringe on the vector ALU from the ring
+// slot it is reading anyway: V[a][b] for a >= 16 NF (all b) and for b >= 16 NF (a < 16 NF), lane l owning the opposite
+// indices l and l + 64.  The fringe lines are taken in pairs (one 16-byte broadcast read per operand), the second pair
+// only when nao has it.  Loader role, ring, barriers: those of the padded kernel, untouched.
+// FP: 0 for waves 0-2, else the fringe's wave (wave 3: tile row 6 if there is one, and FP = 1 or 2 pairs of fringe lines).
+// The roles are separate instances so that neither carries the other's accumulators (14 tiles = 112 VGPRs against
+// 7 tiles + 16 fringe sums), and the pair count is an instance too: a branch per grid row around the second pair cut
+// the k-step into blocks the register allocator spilled across.
+template <int NT, int FP>
+__device__ __forceinline__ void vxc_ws_mfma_fringe(const double *Ps, const double *Qs, int tid, int wave, int nao, long nstep,
+                                                   double *__restrict__ slab)
+{
+    using C = WsCfg<NT>;
+    constexpr int NF = NT - 1, F0 = 16 * NF;           // whole tiles per side, first fringe line
+    constexpr int TILE = WS_ROWS * C::LDX;
+    constexpr int NOPP = F0 + 4 > 64 ? 2 : 1;          // opposite indices per lane
+    static_assert(NT >= 2 && F0 + 4 <= 128, "one whole tile at least, two opposite indices per lane at most");
+    const int lane = tid & 63, li = lane & 15, lk = lane >> 4;
+    constexpr bool FRW = FP > 0;
+    constexpr int ROWS = FRW ? (NF > 6 ? 1 : 0) : 2, RA = ROWS ? ROWS : 1, NL = FRW ? 2 * FP : 1;
+    const int nr = FRW || NF >= 6 ? ROWS : min(2, max(0, NF - 2 * wave)); // owned tile rows 2 wave + i, i < nr (wave-uniform)
+    d4 acc[RA][NF];
+#pragma unroll
+    for (int i = 0; i < RA; ++i)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+    double fa[NL][NOPP], fb[NL][NOPP];                 // fa: rows F0 + f (column l + 64 j), fb: columns F0 + f (row l + 64 j)
+#pragma unroll
+    for (int f = 0; f < NL; ++f)
+#pragma unroll
+        for (int j = 0; j < NOPP; ++j) { fa[f][j] = 0.0; fb[f][j] = 0.0; }
+    int opp[NOPP];                                     // clamped into the staged row: lanes past it compute what nobody stores
+#pragma unroll
+    for (int j = 0; j < NOPP; ++j) opp[j] = min(lane + 64 * j, C::NCOL - 1);
+
+    // fragments one k-step ahead, across the step barrier: as in the padded kernel's MFMA role
+    const int fo = lk * C::LDX + li;
+    double af[RA], bf[NF];
+    auto load_frags = [&](int slot, int ks, double (&a_)[RA], double (&b_)[NF]) {
+        if (ROWS == 0) return;
+        const double *P = Ps + slot * TILE + fo + 4 * ks * C::LDX;
+        const double *Q = Qs + slot * TILE + fo + 4 * ks * C::LDX;
+#pragma unroll
+        for (int i = 0; i < RA; ++i) a_[i] = Q[16 * min(2 * wave + i, NF - 1)]; // clamped: unowned rows skipped below
+#pragma unroll
+        for (int j = 0; j < NF; ++j) b_[j] = P[16 * j];
+    };
+    auto fringe_pair = [&](const double *Pr, const double *Qr, const double (&po)[NOPP], const double (&qo)[NOPP], int f) {
+        const double2 pf = *reinterpret_cast<const double2 *>(&Pr[F0 + f]);
+        const double2 qf = *reinterpret_cast<const double2 *>(&Qr[F0 + f]);
+#pragma unroll
+        for (int j = 0; j < NOPP; ++j) {
+            fa[f][j] += qf.x * po[j];
+            fa[f + 1][j] += qf.y * po[j];
+            fb[f][j] += qo[j] * pf.x;
+            fb[f + 1][j] += qo[j] * pf.y;
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < RA; ++i) af[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) bf[j] = 0.0;
+    for (long base = 0; base < nstep; base += WS_RING) {
+#pragma unroll
+        for (int u = 0; u < WS_RING; ++u) {
+            const long step = base + u;
+            if (step >= 2 && step < nstep) { // consume sub-tile step-2 from stage (u+2)%4
+                if (step == 2) load_frags((u + 2) % WS_RING, 0, af, bf);
+#pragma unroll
+                for (int ks = 0; ks < WS_ROWS / 4; ++ks) {
+                    double an[RA], bn[NF];
+                    if (ks + 1 < WS_ROWS / 4) load_frags((u + 2) % WS_RING, ks + 1, an, bn);
+                    else                      load_frags((u + 3) % WS_RING, 0, an, bn); // next step's slot (may be unused garbage at the tail)
+#pragma unroll
+                    for (int i = 0; i < ROWS; ++i)
+                        if (i < nr) {
+#pragma unroll
+                            for (int j = 0; j < NF; ++j) acc[i][j] = mfma_f64(af[i], bf[j], acc[i][j]);
+                        }
+                    if (FRW) { // the four grid rows of this k-step, one after the other
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk) {
+                            const double *Pr = Ps + ((u + 2) % WS_RING) * TILE + (4 * ks + kk) * C::LDX;
+                            const double *Qr = Qs + ((u + 2) % WS_RING) * TILE + (4 * ks + kk) * C::LDX;
+                            double po[NOPP], qo[NOPP];
+#pragma unroll
+                            for (int j = 0; j < NOPP; ++j) { po[j] = Pr[opp[j]]; qo[j] = Qr[opp[j]]; }
+                            fringe_pair(Pr, Qr, po, qo, 0);
+                            if (FP > 1) fringe_pair(Pr, Qr, po, qo, 2);
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < RA; ++i) af[i] = an[i];
+#pragma unroll
+                    for (int j = 0; j < NF; ++j) bf[j] = bn[j];
+                    __builtin_amdgcn_sched_barrier(0); // one k-step's operands in flight, not a whole sub-tile's
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // whole tiles: every element is inside nao x nao
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) {
+        if (i >= nr) continue;
+#pragma unroll
+        for (int j = 0; j < NF; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                slab[(size_t)(16 * (2 * wave + i) + lk + 4 * r) * nao + 16 * j + li] = acc[i][j][r];
+    }
+    if (FRW) {
+#pragma unroll
+        for (int f = 0; f < NL; ++f) {
+            if (F0 + f >= nao) continue;
+#pragma unroll
+            for (int j = 0; j < NOPP; ++j) {
+                const int o = lane + 64 * j;
+                if (o < nao) slab[(size_t)(F0 + f) * nao + o] = fa[f][j];
+                if (o < F0)  slab[(size_t)o * nao + F0 + f] = fb[f][j];
+            }
+        }
+    }
+}
+
 // SYM: the workgroup writes M + M^T of its partial (B3LYP, symmetrize_matrix_kernel
 // src/dft_solver.cu:515-527) -- transposed through LDS so the slab reduce stays a coalesced sum.
-template <int NT, bool GRAD, bool VEC, bool SYM>
+// FR: the whole-tile-row MFMA role with a vector fringe above (non-SYM, nao = 16 (NT - 1) + 1..4 only).
+template <int NT, bool GRAD, bool VEC, bool SYM, bool FR = false>
 __global__ __launch_bounds__(WS_THREADS, 2) void k_vxc_ws(long ngrid, int nao,
                                                           const double *__restrict__ ao,
                                                           const double *__restrict__ gx,
@@ -87,7 +218,14 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_vxc_ws(long ngrid, int nao,
     const long nloc = (ntile > (long)blockIdx.x) ? (ntile - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
     const long nstep = nloc + 2; // ring latency of two steps
 
-    if (wave < 4) {
+    if constexpr (FR) {
+        static_assert(!FR || !SYM, "the fringe variant writes one-sided slabs");
+        double *slab = slabs + (size_t)blockIdx.x * nao * nao;
+        if (wave < 3)                                 vxc_ws_mfma_fringe<NT, 0>(Ps, Qs, tid, wave, nao, nstep, slab);
+        else if (wave == 3 && nao - 16 * (NT - 1) <= 2) vxc_ws_mfma_fringe<NT, 1>(Ps, Qs, tid, 3, nao, nstep, slab);
+        else if (wave == 3)                           vxc_ws_mfma_fringe<NT, 2>(Ps, Qs, tid, 3, nao, nstep, slab);
+    }
+    if (!FR && wave < 4) {
         // ---------------------------------------------------------- MFMA role
         const int lane = tid & 63, li = lane & 15, lk = lane >> 4;
         const int wa = wave >> 1, wb = wave & 1;
@@ -179,7 +317,7 @@ __global__ __launch_bounds__(WS_THREADS, 2) void k_vxc_ws(long ngrid, int nao,
                     for (int r = 0; r < 4; ++r) M[(16 * (wa + 2 * i) + lk + 4 * r) * LDM + b] = acc[i][j][r];
                 }
         }
-    } else {
+    } else if (wave >= 4) {
         // -------------------------------------------------------- loader role
         // The loader stream is short (~200 instructions per step) but latency-critical; at equal
         // priority the SIMD's arbiter (oldest first) lets the back-to-back MFMA wave starve it

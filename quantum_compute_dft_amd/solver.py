@@ -112,6 +112,8 @@ class DFTSolverWrapper:
         L.DFT_ComputeXCDirect.restype = ctypes.c_int
         L.DFT_SetOption.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double]
         L.DFT_SetOption.restype = ctypes.c_int
+        L.DFT_GetOption.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        L.DFT_GetOption.restype = ctypes.c_double
         L.DFT_SetStream.argtypes = [ctypes.c_void_p, _u64]
         L.DFT_SetStream.restype = ctypes.c_int
         L.DFT_GetLastError.argtypes = [ctypes.c_void_p]
@@ -240,6 +242,13 @@ class DFTSolverWrapper:
     def set_option(self, key, value):
         if self.lib.DFT_SetOption(self.solver, key.encode(), float(value)) != 0:
             raise KeyError(key)
+
+    def get_option(self, key):
+        """Read-back of an option, or of what the library did with it ("publish_probe", "publish_live", "used_publish")."""
+        v = self.lib.DFT_GetOption(self.solver, key.encode())
+        if v != v:
+            raise KeyError(key)
+        return v
 
     def set_stream(self, hip_stream):
         self.lib.DFT_SetStream(self.solver, _u64(int(hip_stream)))
