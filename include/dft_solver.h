@@ -226,6 +226,24 @@ int DFT_ComputeXCDirect(XCSolver *solver, long long ngrid, int nao, int nshell,
                         unsigned long long d_exc_ptr,
                         long long chunk_points);
 
+/* dm = L L^T on the device, for a caller that holds the density matrix and nothing else (what the reference's loop
+ * passes, dft.py:200; its dm = 2 C_occ C_occ^T has the rank of the occupied space): pivoted Cholesky in one workgroup
+ * (csrc/dm_factor.hip), then an acceptance check of |dm - L L^T| over the whole matrix with the bound the factorised J/K
+ * build uses (1e-11 relative to |L| |L|^T + |dm|, plus 1e-14).  L (nao, rank), C order, is the `cocc` of DFT_ComputeXCOcc
+ * and DFT_ComputeJKFactorized.  dm (nao, nao) device in; d_cocc_out: nao * max_rank doubles, device out.  max_rank <= 0
+ * means nao / 2 (values above nao are cut to nao), tol <= 0 means 1e-13: the factorisation stops when the largest
+ * residual diagonal entry is <= tol * max_i dm_ii.  Synchronous on the solver's stream and device.  Returns
+ *   the rank (>= 1): L is in the first nao * rank doubles of d_cocc_out;
+ *   0: dm is not such a product with rank <= max_rank (d_cocc_out holds nothing the caller may rely on);
+ *   -1: an error (DFT_GetLastError); nothing aborts.
+ * info4, if not NULL, receives {steps taken, last residual maximum / scale, reason, scale = max_i dm_ii} with reason
+ * 0 = accepted, 1 = max_rank exceeded, 2 = a negative residual or a non-positive (or non-finite) diagonal, 3 = the
+ * acceptance check failed (a non-symmetric dm ends here: the factorisation reads pivot rows only; so does one with a
+ * NaN or an infinity in it), 4 = nao outside 2..8192.  Added without a change of DFT_GetVersion (it stays 5): a caller
+ * that may meet an older library looks the symbol up. */
+int DFT_FactorDensity(XCSolver *solver, int nao, unsigned long long d_dm_ptr, int max_rank, double tol,
+                      unsigned long long d_cocc_out_ptr, double *info4);
+
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
  * reference builds the whole tensor on the host with PySCF, `mol.intor('int2e')` at grid.py:65).  Device counterpart
@@ -337,7 +355,15 @@ void DFT_ScfTailClose(void *handle);
  * fewer: DFT_ComputeXC may then return while that kernel's last blocks still store Vxc, which only
  * consumers on the solver's own stream are ordered behind), "strict_sync" (with fuse_finish = 1: 1 =
  * DFT_ComputeXC also waits for the stream to report complete before returning), "occ" (DFT_ComputeXCOcc:
- * 0 = auto, 1 = always the occupied-orbital density step, 2 = never), "eri_symmetric" (0, default: DFT_ComputeCoulomb is
+ * 0 = auto, 1 = always the occupied-orbital density step, 2 = never), "dm_factor" (DFT_ComputeXC / DFT_ComputeXC64,
+ * which receive a dm and no orbitals: 0 = never, the default; 1 = try: with path = 0, outside the "tiny" plan and with
+ * occ != 2, dm is factorised as by DFT_FactorDensity (default max_rank and tol) into a workspace of the solver, and where
+ * it is accepted AND the "occ" rule takes the occupied form at that rank, the sweep runs as DFT_ComputeXCOcc does with the
+ * factor as cocc; in every other case the call runs exactly as with 0, the same kernels and the same bits.  Such a call is
+ * neither recorded nor replayed as a graph.  The asynchronous entries, DFT_ComputeXCOcc* and DFT_ComputeXCDirect ignore
+ * the option.  Its initial value is 1 when the environment variable QCDFT_DM_FACTOR is "1" at DFT_CreateSolver /
+ * DFT_CreateSolverMix -- the variable is sampled once, there: how an unmodified caller of the four reference symbols
+ * opts in), "eri_symmetric" (0, default: DFT_ComputeCoulomb is
  * eri^T . vec(dm) for any matrix, the reference's GEMV; 1 = the caller vouches that eri is symmetric as an (nao^2, nao^2)
  * matrix, (ij|kl) = (kl|ij), as every real ERI is: only its upper triangle is read, half the bytes and half the time; 2 = ... and
  * in each index pair, (ij|kl) = (ji|kl) = (ij|lk), and dm = dm^T: only the unique eighth is read, 51 against 240 us at Benzene/def2-SVP; below 48 functions both values keep the full pass), "graph" (the synchronous calls: -1 = auto, default:
@@ -361,7 +387,9 @@ void DFT_ScfTailClose(void *handle);
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
 
 /* Read-back of "publish", "vxc_fringe", "fuse_finish", "strict_sync", "spin_wait", "graph", "tiny", "sweep_order", "path",
- * "quirks", and of what the library made of them: "publish_probe" (1 = the creation-time probe of the stream memory
+ * "quirks", "occ", "dm_factor", and of what the library made of them: "used_occ" (1 = the last sweep took the
+ * occupied-orbital density step), "used_dm_factor" (1 = the last synchronous call swept with the factor of its dm),
+ * "dm_factor_rank" (the rank its attempt found; 0 = rejected, or nothing was attempted), "publish_probe" (1 = the creation-time probe of the stream memory
  * write passed), "publish_live" (1 = a synchronous call now completes by stream write), "used_publish" and
  * "used_vxc_fringe" (what the last synchronous call / the last sweep did).  NaN for an unknown key.  Added without a
  * change of DFT_GetVersion: a caller that may meet an older library looks the symbol up. */
@@ -376,7 +404,8 @@ int DFT_SetStream(XCSolver *solver, unsigned long long hip_stream);
 const char *DFT_GetLastError(XCSolver *solver);
 
 /* With option "profile"=1: durations (ms) of the kernels of the last
- * DFT_ComputeXC* call, in launch order; names[i] (if non-NULL) receives a
+ * DFT_ComputeXC* call (with option "dm_factor": "dm_factor" and "dm_factor_check" in front) or of the last
+ * DFT_FactorDensity, in launch order; names[i] (if non-NULL) receives a
  * static string.  Returns the number of entries written (<= max_entries). */
 int DFT_GetTimings(XCSolver *solver, double *ms, const char **names, int max_entries);
 

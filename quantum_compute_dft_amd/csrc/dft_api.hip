@@ -28,6 +28,7 @@
 #include "xc_kernels.hpp"
 #include "xc_occ_launch.hpp"
 #include "xc_tiny_launch.hpp"
+#include "dm_factor_launch.hpp"
 
 using namespace qcdft;
 
@@ -80,6 +81,13 @@ struct XCSolver {
     int tiny = -1;     // one-pass sweep kernel for nao <= 32 (xc_tiny_kernels.hpp): -1 auto (where it is faster, tiny_pays()), 0 off, 1 on
     int occ = 0;       // DFT_ComputeXCOcc: 0 auto (occupied-orbital density step where it does fewer MFMAs), 1 always, 2 never
     int used_occ = 0;  // what the last sweep did (DFT_GetTimings names say so too)
+    // DFT_ComputeXC / DFT_ComputeXC64 (a dm and no orbitals): 1 = factorise dm on the device (dm_factor.hip) and sweep with the
+    // factor as occupied orbitals where the "occ" rule takes that form; 0 (default, or QCDFT_DM_FACTOR=1 in the environment
+    // at DFT_CreateSolver for 1) = never
+    int dm_factor = 0;
+    int used_dm_factor = 0;  // the last synchronous call swept with the factor
+    int dm_factor_rank = 0;  // the rank the last attempt found (0: rejected, or nothing was attempted)
+    size_t timed_base = 0;   // timings a sweep keeps in front of its own (the factor kernels of the same call)
     int vxc_fringe = -1;  // k_vxc_ws at nao = 16 k + 1..4: whole-tile-row MFMA role with a vector fringe (1, -1 auto) or the padded grid (0)
     int used_vxc_fringe = 0; // what the last sweep's Vxc kernel was (DFT_GetOption "used_vxc_fringe")
     int used_publish = 0; // the last synchronous call was completed by 1: the stream write, 0: a kernel (DFT_GetOption "used_publish")
@@ -94,7 +102,7 @@ struct XCSolver {
     hipStream_t cap_stream = nullptr; // recording happens here (the caller's stream may be the null stream, which cannot record)
     unsigned long graph_clock = 0, graph_gen = 0;
     // workspace
-    DevBuf dsym, rho, sigma, grad, coef, partial, slabs, exc, jpart, kpart, shells, msym, cdy, cdc, cdv, ao_ws, vtmp, occ_cp, occ_dm;
+    DevBuf dsym, rho, sigma, grad, coef, partial, slabs, exc, jpart, kpart, shells, msym, cdy, cdc, cdv, ao_ws, vtmp, occ_cp, occ_dm, dmf_lt, dmf_c, dmf_st;
     int spin_wait = 1; // poll the host-mapped Exc instead of sleeping in hipStreamSynchronize
     int strict_sync = 0; // 1: after the Exc word, also poll the stream until it reports complete (+8-10 us per call)
     double *h_exc = nullptr;   // pinned, host-mapped: the reduce kernel writes Exc here
@@ -229,6 +237,13 @@ void with_bool(bool b, F &&f)
     else   f(std::false_type{});
 }
 
+// Small bases: the whole sweep in one kernel (planes below 4 GiB: one buffer descriptor each)
+bool takes_tiny(const XCSolver *s, long ngrid, int nao)
+{
+    return s->path == 0 && s->tiny != 0 && s->type != SOLVER_MIX && nao <= TINY_MAX_NAO && (double)ngrid * nao * 8.0 < 4294967296.0 &&
+           (s->tiny > 0 || tiny_pays(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid));
+}
+
 // The sweep: everything on s->stream, Exc left in s->exc (device).
 // `cocc` (nao, nocc) with dm = cocc cocc^T switches the density step to the occupied-orbital form where that
 // pays (xc_occ_kernels.hpp); `dm` may then be null.
@@ -237,7 +252,8 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
               const double *cocc = nullptr, int nocc = 0, double *exc_out = nullptr)
 {
     s->last_error.clear();
-    s->n_timed = 0;
+    s->n_timed = s->timed_base;   // non-zero only for the sweep of a call that factorised its dm first
+    s->timed_base = 0;
     s->wait_mode = 0;
     s->used_vxc_fringe = 0;
     if (!s->device_ok) {
@@ -264,9 +280,7 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     // Occupied-orbital density step: 16 nch nocc_tiles MFMAs per 16 grid rows (8 for LDA) against 4 NT^2 through the
     // full matrix; taken when it does clearly fewer (the two kernels run at similar matrix-pipe efficiency), on the
     // production path only.
-    // Small bases: the whole sweep in one kernel (planes below 4 GiB: one buffer descriptor each)
-    const bool tiny = s->path == 0 && s->tiny != 0 && s->type != SOLVER_MIX && nao <= TINY_MAX_NAO && (double)ngrid * nao * 8.0 < 4294967296.0 &&
-                      (s->tiny > 0 || tiny_pays(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid));
+    const bool tiny = takes_tiny(s, ngrid, nao);
     OccPlan oplan;
     bool use_occ = false;
     if (cocc && s->path == 0 && s->occ != 2 && !tiny) {
@@ -674,6 +688,59 @@ int jk_factorized(XCSolver *s, int nao, int naux, int nocc, const double *L, con
     return hip_ok(s, hipGetLastError(), "factorised J/K launch") ? 0 : -1;
 }
 
+// dm = L L^T on the device (dm_factor.hip): the rank (>= 1) with L (nao, rank) C-order in `out` (nao * max_rank doubles),
+// 0 when dm is not such a product with rank <= max_rank (info[2] says why), -1 on an error.  Synchronous: the rank decides
+// what is launched next, and the acceptance flag is the answer.  Accepted means k_dm_consistency -- the bound the
+// factorised J/K build already trusts -- found |dm - L L^T| within round-off over the WHOLE matrix: the factorisation
+// itself reads pivot rows only, so this is also what rejects a non-symmetric dm.
+int factor_density(XCSolver *s, int nao, const double *dm, int max_rank, double tol, double *out, double *info)
+{
+    double st4[DMF_STATUS_DOUBLES] = {0.0, 0.0, (double)DMF_SIZE, 0.0};
+    auto done = [&](int rc) {
+        if (info) std::copy(st4, st4 + DMF_STATUS_DOUBLES, info);
+        return rc;
+    };
+    s->last_error.clear();
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return done(-1); }
+    if (nao <= 0 || !dm || !out) { set_error(s, "density factorisation: bad arguments (nao=%d)", nao); return done(-1); }
+    if (nao < DMF_MIN_NAO || nao > DMF_MAX_NAO) return done(0);
+    if (max_rank <= 0) max_rank = nao / 2;
+    max_rank = std::min(max_rank, nao);
+    if (!(tol > 0.0)) tol = 1e-13;
+    if (!reserve(s, s->dmf_lt, sizeof(double) * (size_t)max_rank * nao, "hipMalloc(dm factor)") ||
+        !reserve(s, s->dmf_st, sizeof(double) * (DMF_STATUS_DOUBLES + 1), "hipMalloc(dm factor status)"))
+        return done(-1);
+    hipStream_t st = s->stream;
+    double *Lt = (double *)s->dmf_lt.p, *dst = (double *)s->dmf_st.p;
+    int *flag = (int *)(dst + DMF_STATUS_DOUBLES);
+    {
+        ScopedTimer t(s, "dm_factor");
+        if (!hip_ok(s, launch_dm_factor(st, nao, max_rank, tol, dm, Lt, dst), "density factorisation launch")) return done(-1);
+    }
+    if (!hip_ok(s, hipMemcpyAsync(st4, dst, sizeof st4, hipMemcpyDeviceToHost, st), "copy factorisation status") ||
+        !hip_ok(s, hipStreamSynchronize(st), "density factorisation"))
+        return done(-1);
+    const int rank = (int)st4[0];
+    if ((int)st4[2] != DMF_OK || rank < 1 || rank > max_rank) return done(0);
+    int h_flag = 1;
+    {
+        ScopedTimer t(s, "dm_factor_check");
+        (void)hipMemsetAsync(flag, 0, sizeof(int), st);
+        if (!hip_ok(s, launch_dm_factor_pack(st, nao, rank, Lt, out), "factor pack launch")) return done(-1);
+        const long n2 = (long)nao * nao;
+        hipLaunchKernelGGL(k_dm_consistency, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, nao, rank, dm, (const double *)out, flag);
+        if (!hip_ok(s, launch_dm_nonfinite(st, nao, dm, flag), "factor check launch")) return done(-1);
+    }
+    if (!hip_ok(s, hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st), "copy factorisation flag") ||
+        !hip_ok(s, hipStreamSynchronize(st), "density factorisation check"))
+        return done(-1);
+    if (h_flag) {
+        st4[2] = (double)DMF_INCONSISTENT;
+        return done(0);
+    }
+    return done(rank);
+}
+
 // The AO shell table on the device: validated, packed and uploaded once per distinct table
 // ([AoShell x nshell][exp x nprim][coef x nprim][AoChunk x nchunk][order x nshell]).
 struct AoTable {
@@ -813,6 +880,7 @@ static XCSolver *create_solver(int type, const double *mix)
     if (!s) return nullptr;
     s->type = type;
     s->needs_grad = type != SOLVER_LDA;
+    if (const char *e = getenv("QCDFT_DM_FACTOR")) s->dm_factor = !strcmp(e, "1");   // sampled here, once
     if (mix) {
         s->needs_grad = false;
         for (int k = 0; k < XC_NCOMP; ++k) {
@@ -889,7 +957,7 @@ void DFT_DestroySolver(XCSolver *s)
         if (s->cap_stream) (void)hipStreamDestroy(s->cap_stream);
         DevBuf *bufs[] = {&s->dsym, &s->rho, &s->sigma, &s->grad, &s->coef, &s->partial,
                           &s->slabs, &s->exc, &s->jpart, &s->kpart, &s->shells, &s->msym,
-                          &s->cdy, &s->cdc, &s->cdv, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm};
+                          &s->cdy, &s->cdc, &s->cdv, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st};
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
@@ -1010,9 +1078,33 @@ static double xc_call_sync(XCSolver *s, long long ngrid, int nao, unsigned long 
     DeviceGuard dg(s);
     const double nan = std::numeric_limits<double>::quiet_NaN();
     if (s->h_exc) *s->h_exc = nan; // before anything is enqueued: the last kernel overwrites it
-    const SweepArgs a{(long)ngrid, nao, nocc, (const double *)d_dm, (const double *)d_ao, (const double *)d_ao_grad,
-                      (const double *)d_w, (double *)d_vxc, (const double *)d_cocc};
-    const bool graphed = !s->profile && s->h_exc_dev && ngrid > 0 && nao > 0 &&
+    SweepArgs a{(long)ngrid, nao, nocc, (const double *)d_dm, (const double *)d_ao, (const double *)d_ao_grad,
+                (const double *)d_w, (double *)d_vxc, (const double *)d_cocc};
+    // Option "dm_factor": a caller that holds dm alone.  The factor of dm stands in for the occupied orbitals where the rule of
+    // xc_sweep takes the occupied form for its rank; a dm that does not factorise, or a rank at which the dm kernels do fewer
+    // MFMAs, leaves the call exactly as it is without the option.
+    const bool dmf = s->dm_factor && d_dm && !d_cocc;
+    s->used_dm_factor = 0;
+    s->timed_base = 0;
+    if (dmf) {
+        s->dm_factor_rank = 0;
+        s->n_timed = 0;
+        if (s->device_ok && s->path == 0 && s->occ != 2 && ngrid > 0 && nao > 0 && !takes_tiny(s, (long)ngrid, nao) &&
+            reserve(s, s->dmf_c, sizeof(double) * (size_t)nao * std::max(nao / 2, 1), "hipMalloc(dm factor, packed)")) {
+            const int rank = factor_density(s, nao, a.dm, 0, 0.0, (double *)s->dmf_c.p, nullptr);
+            if (rank > 0) {
+                s->dm_factor_rank = rank;
+                const OccPlan pl = occ_plan(nao, rank, s->needs_grad);
+                if (s->occ == 1 || pl.mfma_occ <= 0.85 * pl.mfma_full) {
+                    a.cocc = (const double *)s->dmf_c.p;
+                    a.nocc = nocc = rank;
+                    s->used_dm_factor = 1;
+                }
+            }
+            s->timed_base = s->n_timed;   // with "profile": the factor kernels stay in front of the sweep's
+        }
+    }
+    const bool graphed = !dmf && !s->profile && s->h_exc_dev && ngrid > 0 && nao > 0 &&
                          (s->graph > 0 || (s->graph < 0 && (double)ngrid * nao <= GRAPH_AUTO_ELEMS));
     if (graphed && replay_sweep(s, a)) s->wait_mode = 0; // a recorded sweep ends with the publishing kernel
     else if (!xc_sweep(s, a.ngrid, nao, a.dm, a.ao, a.grad, a.w, a.vxc, true, a.cocc, nocc))
@@ -1166,6 +1258,15 @@ int DFT_ComputeJKFactorized(XCSolver *s, int nao, int naux, int nocc, unsigned l
                          (const double *)d_cocc, (double *)d_J, (double *)d_K);
 }
 
+int DFT_FactorDensity(XCSolver *s, int nao, unsigned long long d_dm, int max_rank, double tol,
+                      unsigned long long d_cocc_out, double *info4)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    s->n_timed = 0;
+    return factor_density(s, nao, (const double *)d_dm, max_rank, tol, (double *)d_cocc_out, info4);
+}
+
 int DFT_EvalAO(XCSolver *s, long long ngrid, int nao, int nshell, const double *shl_xyz,
                const int *shl_l, const int *shl_nprim, const int *shl_off, const int *shl_ao,
                const double *prim_exp, const double *prim_coef, int nprim_total,
@@ -1242,6 +1343,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "publish")) { s->publish = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
     if (!strcmp(key, "sweep_order")) { s->sweep_order = (int)value & 3; return 0; }
     if (!strcmp(key, "occ")) { s->occ = value == 1.0 ? 1 : value == 2.0 ? 2 : 0; return 0; }
+    if (!strcmp(key, "dm_factor")) { s->dm_factor = value != 0.0; return 0; }
     if (!strcmp(key, "tiny")) { s->tiny = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
     if (!strcmp(key, "ao_pt")) { s->ao_pt = value == 16.0 ? 16 : value == 8.0 ? 8 : 0; return 0; }
     if (!strcmp(key, "ksplit")) { s->ksplit = value > 0 ? (int)value : 0; return 0; }
@@ -1266,6 +1368,11 @@ double DFT_GetOption(XCSolver *s, const char *key)
     if (!strcmp(key, "sweep_order")) return s->sweep_order;
     if (!strcmp(key, "path")) return s->path;
     if (!strcmp(key, "quirks")) return s->quirks;
+    if (!strcmp(key, "occ")) return s->occ;
+    if (!strcmp(key, "used_occ")) return s->used_occ;                                          // what the last sweep's density step was
+    if (!strcmp(key, "dm_factor")) return s->dm_factor;
+    if (!strcmp(key, "used_dm_factor")) return s->used_dm_factor;                              // the last synchronous call swept with the factor of dm
+    if (!strcmp(key, "dm_factor_rank")) return s->dm_factor_rank;                              // the rank its attempt found (0: rejected / not attempted)
     return unknown;
 }
 

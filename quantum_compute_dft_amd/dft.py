@@ -102,6 +102,10 @@ def main(argv=None):
     p.add_argument("--xc-occ", type=int, default=1, choices=[0, 1],
                    help="1 (default): the XC sweep's density step through the occupied orbitals (DFT_ComputeXCOcc, 4 nao nocc flops "
                         "per grid point); 0: the reference's call with the full density matrix (DFT_ComputeXC, dft.py:206)")
+    p.add_argument("--dm-factor", action="store_true",
+                   help="with --xc-occ 0: the reference's call, with the library factorising the density matrix on the device "
+                        "(option dm_factor, DFT_FactorDensity) and sweeping through the factor where the occupied form pays; "
+                        "acts in the synchronous DFT_ComputeXC of the host loop (--device-resident 0 --fused-tail 0 above 80 functions)")
     p.add_argument("--both-quirks", action="store_true",
                    help="LDA/GGA: run the SCF twice, with the reference's formulas as shipped (its CUDA path) and with the "
                         "corrected VWN5 / PBE-c derivatives (what PySCF's slater,vwn5 / PBE,PBE compute), and report both energies")
@@ -173,7 +177,7 @@ def main(argv=None):
         backend = scf.HipBackend(inp, args.functional, args.lib, quirks=bool(args.quirks), rank=rank, world=world, device=device,
                                  device_resident=None if args.device_resident < 0 else bool(args.device_resident),
                                  fused_tail=None if args.fused_tail < 0 else bool(args.fused_tail),
-                                 eigensolver=args.eigensolver, ao_mode=args.ao, xc_occ=bool(args.xc_occ))
+                                 eigensolver=args.eigensolver, ao_mode=args.ao, xc_occ=bool(args.xc_occ), dm_factor=args.dm_factor)
     except Exception as e:  # dft.py:149-153
         print(e)
         sys.exit(1)
@@ -238,7 +242,7 @@ def main(argv=None):
               "E_ex_hf": res.get("E_ex_hf"), "E_nuc": float(inp.E_nuc), "total_time_s": res.get("total_time"),
               "xc_ms_avg": res.get("xc_ms_avg"), "xc_ms": res.get("xc_ms"), "jk_ms": res.get("jk_ms"), "iter_ms": res.get("iter_ms"),
               "cycle_ms": res.get("cycle_ms"), "gpu_init_s": backend.init_time, "device_resident": bool(backend.device_resident), "loop": res.get("loop", "device" if backend.device_resident else "host"), "ao": args.ao, "eigensolver": args.eigensolver,
-              "eigensolver_stats": eig_stats, "xc_occ": int(backend.xc_occ)}
+              "eigensolver_stats": eig_stats, "xc_occ": int(backend.xc_occ), "dm_factor": int(backend.dm_factor)}
     if charges is not None:
         record["n_point_charges"] = int(len(charges)); record["E_nuc_ext"] = float(inp.E_nuc_ext)
         record["point_charge_forces"] = charge_forces.tolist() if charge_forces is not None else None

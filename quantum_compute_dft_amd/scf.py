@@ -319,7 +319,7 @@ class HipBackend:
 
     def __init__(self, inp, functional, lib_path=None, quirks=True, rank=0, world=1, device=None, group=None,
                  device_resident=None, device_from=200, eigensolver="auto", ao_mode="resident", ao_chunk=0, xc_occ=True,
-                 fused_tail=None):
+                 fused_tail=None, dm_factor=False):
         import torch
         from .build import library_path
         from .grid_shard import ReplicaSync, ShardedFock, eri_row_bounds, shard_bounds, vector_bounds
@@ -352,6 +352,11 @@ class HipBackend:
         # the sweep's density step through the occupied orbitals (DFT_ComputeXCOcc: the loop holds cocc with
         # dm = cocc cocc^T in every cycle, dft.py:181-182); False = the reference's call with the full matrix
         self.xc_occ = bool(xc_occ)
+        # the reference's call, with the library factorising dm on the device and sweeping through the factor where that
+        # pays (option "dm_factor", DFT_FactorDensity): what an unmodified reference driver gets from QCDFT_DM_FACTOR=1
+        self.dm_factor = bool(dm_factor) and not self.xc_occ
+        if self.dm_factor:
+            self.solver.set_option("dm_factor", 1)
         self.d_ao = self.d_gr = None
         if ao_mode == "resident":
             self.d_ao = torch.zeros((n1, nao), dtype=f64, device=self.dev)

@@ -103,6 +103,9 @@ class DFTSolverWrapper:
         L.DFT_ComputeJKFactorized.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               _u64, _u64, _u64, _u64, _u64]
         L.DFT_ComputeJKFactorized.restype = ctypes.c_int
+        L.DFT_FactorDensity.argtypes = [ctypes.c_void_p, ctypes.c_int, _u64, ctypes.c_int, ctypes.c_double, _u64,
+                                        ctypes.POINTER(ctypes.c_double)]
+        L.DFT_FactorDensity.restype = ctypes.c_int
         dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
         L.DFT_EvalAO.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                  dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, _u64, _u64, _u64]
@@ -203,6 +206,24 @@ class DFTSolverWrapper:
                                               _u64(_ptr(d_dm)), _u64(_ptr(d_cocc)), _u64(_ptr(d_J)), _u64(_ptr(d_K)))
         self._check()
         return rc
+
+    def factor_density(self, d_dm, max_rank=None, tol=None):
+        """dm = L L^T on the device (DFT_FactorDensity): (L, rank) with L a (nao, rank) torch tensor on d_dm's device -- the
+        `d_cocc` of compute_xc_occ / compute_jk_factorized -- or None when dm is no such product with rank <= max_rank
+        (default nao // 2); `self.factor_info` then says why ({steps, last residual / scale, reason, scale})."""
+        import torch
+        nao = int(d_dm.shape[0])
+        cap = min(nao, int(max_rank)) if max_rank and max_rank > 0 else max(nao // 2, 1)
+        buf = torch.empty(nao * cap, dtype=torch.float64, device=d_dm.device)
+        info = (ctypes.c_double * 4)()
+        rank = self.lib.DFT_FactorDensity(self.solver, nao, _u64(_ptr(d_dm)), cap, float(tol) if tol else 0.0, _u64(_ptr(buf)), info)
+        self.factor_info = list(info)
+        if rank < 0:
+            self._check()
+            raise RuntimeError("libdft: DFT_FactorDensity failed")
+        if rank == 0:
+            return None
+        return buf[:nao * rank].view(nao, rank), rank
 
     @staticmethod
     def _shell_args(shells):
