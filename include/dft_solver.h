@@ -244,6 +244,28 @@ int DFT_ComputeXCDirect(XCSolver *solver, long long ngrid, int nao, int nshell,
 int DFT_FactorDensity(XCSolver *solver, int nao, unsigned long long d_dm_ptr, int max_rank, double tol,
                       unsigned long long d_cocc_out_ptr, double *info4);
 
+/* Linear response of Vxc: V1 = d/dt DFT_ComputeXC(dm0 + t dm1).vxc at t = 0, element for element the derivative of what
+ * DFT_ComputeXC writes for the solver's type and options (one-sided for SOLVER_GGA and SOLVER_MIX, M + M^T with the halved
+ * vrho for SOLVER_B3LYP, symmetric for SOLVER_LDA; the caller symmetrises as it does for Vxc).  With option "quirks" = 1
+ * that is the derivative of the SHIPPED vrho / vsigma formulas (forward-mode differentiation of the functional bodies),
+ * the only definition consistent with DFT_ComputeXC there.  Points with rho below the cut-off contribute nothing; every
+ * clamp and cut-off of the bodies takes the branch of the value.
+ *
+ * DFT_FxcPrepare runs the ground-state density step of a sweep (through d_cocc (nao, nocc), dm0 = cocc cocc^T, under
+ * the rule of DFT_ComputeXCOcc when d_cocc is not 0; d_dm0 may then be 0) and keeps the derivative table of the
+ * functional and grad rho0 in the solver.  DFT_FxcApply takes any matrix dm1 (its symmetric part counts), the same planes,
+ * and leaves V1 in d_v1 (nao, nao): density kernels on dm1, one arithmetic kernel, then the contraction and reduce
+ * kernels of the sweep with the sweep's choices ("path", "vxc_fringe", nao, plane size).  No energy, no host wait:
+ * asynchronous on the solver's stream.  Apply may be called any number of times after one Prepare; DFT_ComputeXC* calls
+ * in between are allowed and change nothing.  Both return 0, or -1 with DFT_GetLastError (nothing aborts): Apply before
+ * Prepare, ngrid or nao differing from Prepare's, a null ao_grad on a gradient solver.  DFT_SetOption("quirks") after
+ * Prepare invalidates the table.  Added without a change of DFT_GetVersion: look the symbols up. */
+int DFT_FxcPrepare(XCSolver *solver, long long ngrid, int nao, int nocc, unsigned long long d_cocc_ptr,
+                   unsigned long long d_dm0_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
+                   unsigned long long d_weights_ptr);
+int DFT_FxcApply(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm1_ptr, unsigned long long d_ao_ptr,
+                 unsigned long long d_ao_grad_ptr, unsigned long long d_v1_ptr);
+
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
  * reference builds the whole tensor on the host with PySCF, `mol.intor('int2e')` at grid.py:65).  Device counterpart
@@ -405,7 +427,8 @@ const char *DFT_GetLastError(XCSolver *solver);
 
 /* With option "profile"=1: durations (ms) of the kernels of the last
  * DFT_ComputeXC* call (with option "dm_factor": "dm_factor" and "dm_factor_check" in front) or of the last
- * DFT_FactorDensity, in launch order; names[i] (if non-NULL) receives a
+ * DFT_FactorDensity, DFT_FxcPrepare ("rho" or "rho_occ", "fxc_table") or DFT_FxcApply ("rho", "fxc_coef", "fxc_vxc",
+ * "fxc_reduce"), in launch order; names[i] (if non-NULL) receives a
  * static string.  Returns the number of entries written (<= max_entries). */
 int DFT_GetTimings(XCSolver *solver, double *ms, const char **names, int max_entries);
 

@@ -26,9 +26,9 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdft.so")
 STAMP_PATH = LIB_PATH + ".srchash"
-SOURCES = ["dft_api.hip", "xc_occ.hip", "eri_cols.hip", "scf_tail.hip", "xc_tiny.hip", "point_coulomb.hip", "dm_factor.hip"]   # one object each, compiled in parallel, linked into libdft.so
+SOURCES = ["dft_api.hip", "xc_occ.hip", "eri_cols.hip", "scf_tail.hip", "xc_tiny.hip", "point_coulomb.hip", "dm_factor.hip", "xc_response.hip"]   # one object each, compiled in parallel, linked into libdft.so
 HEADERS = ["xc_functionals.hpp", "xc_kernels.hpp", "xc_ws_kernels.hpp", "xc_big_kernels.hpp",
-           "xc_occ_kernels.hpp", "xc_occ_launch.hpp", "xc_tiny_kernels.hpp", "xc_tiny_launch.hpp", "dm_factor_launch.hpp", "jk_kernels.hpp", "ao_kernels.hpp", "cd_kernels.hpp", "device_util.hpp", "md_device.hpp",
+           "xc_occ_kernels.hpp", "xc_occ_launch.hpp", "xc_tiny_kernels.hpp", "xc_tiny_launch.hpp", "dm_factor_launch.hpp", "xc_response_launch.hpp", "jk_kernels.hpp", "ao_kernels.hpp", "cd_kernels.hpp", "device_util.hpp", "md_device.hpp",
            os.path.join("..", "..", "include", "dft_solver.h")]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950's register file is unified);
 # without it hipcc 7.2 can wrap every MFMA group of a loop in v_accvgpr_write/read copy storms
@@ -38,6 +38,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 # per-source additions (the reason is at the top of the source file)
 EXTRA_FLAGS = {"xc_tiny.hip": ["-mllvm", "-disable-machine-licm"]}
 RESOURCES_PATH = LIB_PATH + ".resources.json"
+# Host counterpart of xc_response.hip: the same xc_functionals.hpp through g++ (response.fxc_table_host).  No contraction
+# of a * b + c into one rounding: the CPU tests hold value parts against each other bit for bit.
+FXC_HOST_PATH = os.path.join(LIB_DIR, "libqcfxc.so")
+FXC_HOST_SOURCES = ["xc_response_host.cpp", "xc_functionals.hpp"]
+FXC_HOST_FLAGS = ["-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off"]
 
 # Register-spill guard.  Every kernel's resource usage is read from the compiler's own report
 # (-Rpass-analysis=kernel-resource-usage) and the build FAILS when a kernel spills vector registers or uses scratch
@@ -131,8 +136,35 @@ def library_path():
     return LIB_PATH
 
 
+def _fxc_host_hash():
+    return source_hash([os.path.join(CSRC, f) for f in FXC_HOST_SOURCES], FXC_HOST_FLAGS)
+
+
+def build_fxc_host(force=False):
+    """g++ -> lib/libqcfxc.so (same contract as build_library: only build() and the test fixtures compile)."""
+    want = _fxc_host_hash()
+    if force or not _stamp_ok(FXC_HOST_PATH, FXC_HOST_PATH + ".srchash", want):
+        with build_lock(FXC_HOST_PATH):
+            if force or not _stamp_ok(FXC_HOST_PATH, FXC_HOST_PATH + ".srchash", want):
+                tmp = FXC_HOST_PATH + f".tmp{os.getpid()}"
+                subprocess.run(["g++"] + FXC_HOST_FLAGS + [os.path.join(CSRC, FXC_HOST_SOURCES[0]), "-o", tmp, "-lm"], check=True, env=compile_env())
+                os.replace(tmp, FXC_HOST_PATH)
+                with open(FXC_HOST_PATH + ".srchash", "w") as fh:
+                    fh.write(want + "\n")
+    return FXC_HOST_PATH
+
+
+def fxc_host_library_path():
+    """Path of an up-to-date libqcfxc.so; raises instead of compiling."""
+    if not _stamp_ok(FXC_HOST_PATH, FXC_HOST_PATH + ".srchash", _fxc_host_hash()):
+        raise RuntimeError(f"{FXC_HOST_PATH} is missing or older than csrc/: run `python __graft_entry__.py` first")
+    return FXC_HOST_PATH
+
+
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -> quantum_compute_dft_amd/lib/libdft.so."""
+    """hipcc --offload-arch=gfx950 -> quantum_compute_dft_amd/lib/libdft.so (and g++ -> lib/libqcfxc.so, its host counterpart
+    of the response table: the two are built together so that every caller of this function has both)."""
+    build_fxc_host(force)
     want = source_hash()
     if not force and _stamp_ok(LIB_PATH, STAMP_PATH, want):
         return LIB_PATH

@@ -29,6 +29,7 @@
 #include "xc_occ_launch.hpp"
 #include "xc_tiny_launch.hpp"
 #include "dm_factor_launch.hpp"
+#include "xc_response_launch.hpp"
 
 using namespace qcdft;
 
@@ -118,6 +119,11 @@ struct XCSolver {
     unsigned long long seq = 0; // value of the last stream write that was enqueued
     bool recording = false;    // xc_sweep is being recorded into a graph: stream memory operations are not recorded
     int wait_mode = 0;         // how the last sweep with want_host_exc signals completion: 0 Exc word, 1 sequence word, 2 neither (synchronise)
+    // Linear response of Vxc (DFT_FxcPrepare / DFT_FxcApply): the weighted derivative table of the functional at the ground-state
+    // density and that density's gradient, kept between the two entries in buffers nothing else writes
+    DevBuf fxc_table, fxc_g0;
+    long fxc_ngrid = 0;   // what the table was prepared for (0: nothing prepared, or invalidated)
+    int fxc_nao = 0;
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -244,6 +250,210 @@ bool takes_tiny(const XCSolver *s, long ngrid, int nao)
            (s->tiny > 0 || tiny_pays(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid));
 }
 
+// How a sweep over (ngrid, nao) planes is cut up: which kernel family, how many slabs, the chunk of a split-K launch.
+// Shared by the ground-state sweep and the response entries (DFT_FxcPrepare / DFT_FxcApply), which must choose alike.
+struct SweepPlan {
+    int NP = 0, nblk = 0, ntv = 0, nslab = 0, nA = 0, nB = 0, npair = 0;
+    long chunk = 0;
+    bool gga = false, fits32 = false, fast = false, big = false, vec16 = false;
+    const double *gx = nullptr, *gy = nullptr, *gz = nullptr;
+};
+
+SweepPlan plan_sweep(const XCSolver *s, long ngrid, int nao, const double *ao, const double *ao_grad, bool tiny)
+{
+    const bool gga = s->needs_grad;
+    const int NP = ((nao + 15) / 16) * 16;
+    const int nblk = (nao + 127) / 128;
+    // the wave-specialised kernels address a plane through ONE buffer descriptor: planes of 4 GiB or more
+    // (ngrid*nao >= 2^29) take the generic tiled kernels
+    const bool fits32 = (double)ngrid * nao * 8.0 < 4294967296.0;
+    const bool fast = s->path == 0 && nao <= 128 && fits32;
+    const bool big = s->path == 0 && nao > 128;   // nao <= 128 with planes >= 4 GiB: the generic MFMA kernels below
+    const int ntv = NP / 16;
+    int nslab;
+    long chunk = 0;
+    const int nA = (nao + BG_BM - 1) / BG_BM, nB = (nao + BG_BN - 1) / BG_BN, npair = nA * nB;
+    if (big) {
+        // split-K over grid chunks; chunks are dealt to XCDs (blockIdx % 8), so ksplit is a multiple of 8
+        // chunks per XCD: the candidate (<= 32, slabs <= 2 GB, >= 64 grid rows per chunk) whose workgroup
+        // count fills whole waves of the chip best (360 workgroups on 256 CUs lost 30 % to the tail)
+        long per_xcd = 1;
+        double best = 0.0;
+        for (long c = 1; c <= 32; ++c) {
+            const long wgs = 8L * npair * c;
+            if (8 * c * 64 > ngrid && c > 1) break;
+            if ((double)(8 * c) * nao * nao * 8.0 > 2.0e9 && c > 1) break;
+            const long rounds = (wgs + s->num_cu - 1) / s->num_cu;
+            const double eff = (double)wgs / (double)(rounds * s->num_cu);
+            if (eff > best + 1e-9) { best = eff; per_xcd = c; }
+        }
+        // a chunk of one plane stays below 4 GiB: k_vxc_big addresses it through one buffer descriptor
+        while ((double)((ngrid + 8 * per_xcd - 1) / (8 * per_xcd) + BG_BK) * nao * 8.0 >= 4294967296.0) ++per_xcd;
+        nslab = (int)(8 * per_xcd);
+        chunk = (ngrid + nslab - 1) / nslab;
+        chunk = ((chunk + BG_BK - 1) / BG_BK) * BG_BK;
+    } else if (tiny) {
+        nslab = tiny_workgroups(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid);
+    } else if (fast) {
+        const long ntile = (ngrid + WS_ROWS - 1) / WS_ROWS;
+        nslab = (int)std::min<long>(s->num_cu, ntile); // one persistent, wave-specialised workgroup per CU
+    } else {
+        const int nsplit = auto_ksplit(s, ngrid, nblk * nblk);
+        chunk = (ngrid + nsplit - 1) / nsplit;
+        chunk = ((chunk + 31) / 32) * 32;
+        nslab = (int)((ngrid + chunk - 1) / chunk);
+    }
+    SweepPlan P;
+    P.NP = NP; P.nblk = nblk; P.ntv = ntv; P.nslab = nslab; P.nA = nA; P.nB = nB; P.npair = npair;
+    P.chunk = chunk;
+    P.gga = gga; P.fits32 = fits32; P.fast = fast; P.big = big;
+    const size_t ng = (size_t)ngrid;
+    P.gx = ao_grad; P.gy = gga ? ao_grad + ng * nao : nullptr; P.gz = gga ? ao_grad + 2 * ng * nao : nullptr;
+    // 16-byte plane loads: even nao and every plane 16-byte aligned
+    P.vec16 = (nao % 2 == 0) && ((((uintptr_t)ao | (uintptr_t)P.gx | (uintptr_t)P.gy | (uintptr_t)P.gz) & 15) == 0);
+    return P;
+}
+
+// Density step through the matrix: rho, grad rho (interleaved, 3 per point) and sigma of ANY dm (the kernels see its
+// symmetric part).  Linear in dm, so the same launches give rho1 / grad rho1 of a perturbation.
+void launch_density(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm, const double *ao, double *Dp,
+                    double *rho, double *grad, double *sigma)
+{
+    const int NP = P.NP, ntv = P.ntv, nslab = P.nslab;
+    const bool gga = P.gga, fast = P.fast, big = P.big, vec16 = P.vec16;
+    const double *gx = P.gx, *gy = P.gy, *gz = P.gz;
+    hipStream_t st = s->stream;
+    if (!fast) { // the wave-specialised rho kernel symmetrises D in its prologue
+        ScopedTimer t(s, "sym_dm");
+        dim3 b(16, 16), g(NP / 16, NP / 16);
+        hipLaunchKernelGGL(k_sym_dm, g, b, 0, st, nao, NP, dm, Dp);
+    }
+    {
+        ScopedTimer t(s, "rho");
+        with_bool(gga, [&](auto G) {
+            if (fast)
+                with_bool(vec16, [&](auto V) { with_nt(ntv, [&](auto NT) {
+                    hipLaunchKernelGGL((k_rho_ws<NT, G, V>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, dm, rho, grad, sigma, s->sweep_order & 1);
+                }); });
+            else if (big) // 64-row workgroups, two per CU
+                with_bool(vec16, [&](auto V) {
+                    hipLaunchKernelGGL((k_rho_big64<G, V>), dim3((unsigned)((ngrid + R6_BM - 1) / R6_BM)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
+                });
+            else if (s->path != 1)
+                hipLaunchKernelGGL(k_rho_mfma<G>, dim3((unsigned)((ngrid + 63) / 64)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
+            else
+                hipLaunchKernelGGL(k_rho_valu<G>, dim3((unsigned)((ngrid + 3) / 4)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
+        });
+    }
+}
+
+// Contraction of the coefficient planes with the AO planes into slabs, and the slab reduce into V (for B3LYP: M + M^T).
+// `fin` non-null (the ground-state sweep): the reduce also finishes Exc from the partials, as the options say; null (the
+// response of Vxc, DFT_FxcApply): the same kernels, no energy, no publishing, nothing for the host to wait on.
+struct ExcFinish {
+    long nxb;
+    const double *partial;
+    double *exc;
+    bool want_host_exc;
+};
+
+bool vxc_stage(XCSolver *s, const SweepPlan &P, bool tiny, long ngrid, int nao, const double *ao, const double *coef,
+               double *slabs, double *vxc, const ExcFinish *fin)
+{
+    const int nblk = P.nblk, ntv = P.ntv, nslab = P.nslab, nB = P.nB, npair = P.npair;
+    const long chunk = P.chunk;
+    const bool gga = P.gga, fast = P.fast, big = P.big, vec16 = P.vec16;
+    const double *gx = P.gx, *gy = P.gy, *gz = P.gz;
+    const long nxb = fin ? fin->nxb : 0;
+    const double *partial = fin ? fin->partial : nullptr;
+    double *exc = fin ? fin->exc : nullptr;
+    const bool want_host_exc = fin && fin->want_host_exc;
+    hipStream_t st = s->stream;
+    if (!tiny) {
+        ScopedTimer t(s, fin ? "vxc" : "fxc_vxc");
+        // Option "vxc_fringe": at nao = 16 k + 1..4 (k >= 1) the one-sided kernels leave the k x k whole tiles to the matrix
+        // pipe and take the fringe lines on the vector ALU (vxc_ws_mfma_fringe) instead of padding to k + 1 tiles per side
+        const bool fringe = fast && s->type != SOLVER_B3LYP && s->vxc_fringe != 0 && nao > 16 && nao % 16 >= 1 && nao % 16 <= 4;
+        s->used_vxc_fringe = fringe;
+        auto launch = [&](auto G, auto S) { // S: B3LYP, the wave-specialised kernels write symmetrised slabs
+            if (fast)
+                with_bool(vec16, [&](auto V) { with_nt(ntv, [&](auto NT) {
+                    if constexpr (NT >= 2 && !S) {
+                        if (fringe) {
+                            hipLaunchKernelGGL((k_vxc_ws<NT, G, V, false, true>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1);
+                            return;
+                        }
+                    }
+                    hipLaunchKernelGGL((k_vxc_ws<NT, G, V, S>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1);
+                }); });
+            else if (big)
+                with_bool(vec16, [&](auto V) {
+                    hipLaunchKernelGGL((k_vxc_big<G, V>), dim3((unsigned)(nslab * npair)), dim3(BG_THREADS), 0, st, ngrid, nao, chunk, nB, npair, ao, gx, gy, gz, coef, slabs);
+                });
+            else if (s->path != 1)
+                hipLaunchKernelGGL(k_vxc_mfma<G>, dim3((unsigned)nslab, nblk, nblk), dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
+            else
+                hipLaunchKernelGGL(k_vxc_valu<G>, dim3((unsigned)nslab), dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
+        };
+        switch (s->type) { // (G, S)
+        case SOLVER_LDA: launch(std::false_type{}, std::false_type{}); break;
+        case SOLVER_GGA: launch(std::true_type{}, std::false_type{}); break;
+        case SOLVER_MIX: // GGA convention: one-sided, never symmetrised here; an LDA-class mix takes the one-plane kernels
+            if (gga) launch(std::true_type{}, std::false_type{});
+            else     launch(std::false_type{}, std::false_type{});
+            break;
+        default:         launch(std::true_type{}, std::true_type{}); break;
+        }
+    }
+    {
+        ScopedTimer t(s, fin ? "reduce_vxc" : "fxc_reduce");
+        dim3 g((unsigned)(((size_t)nao * nao + 31) / 32));
+        const bool b3 = s->type == SOLVER_B3LYP;
+        if (b3 && big) { // plain reduce into M, then tiled M + M^T
+            if (!reserve(s, s->msym, sizeof(double) * (size_t)nao * nao, "hipMalloc(M)")) return false;
+            double *M = (double *)s->msym.p;
+            hipLaunchKernelGGL(k_reduce_slabs8<false>, g, dim3(256), 0, st, nao, nslab, slabs, M);
+            const int nt = (nao + 31) / 32;
+            hipLaunchKernelGGL(k_symmetrize, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, nao, M, vxc);
+        } else if (b3 && !fast) {
+            hipLaunchKernelGGL(k_reduce_slabs8<true>, g, dim3(256), 0, st, nao, nslab, slabs, vxc);
+        } else if (!fin) { // the response of Vxc: no energy to finish (wave-specialised slabs are already symmetrised for B3LYP)
+            hipLaunchKernelGGL(k_reduce_slabs8<false>, g, dim3(256), 0, st, nao, nslab, slabs, vxc);
+        } else if (s->fuse_finish) { // wave-specialised slabs are already symmetrised for B3LYP
+            // last launch of the call: its last-ticket block also finishes Exc (device scalar + host-mapped word)
+            hipLaunchKernelGGL((k_reduce_slabs8<false, true>), g, dim3(256), 0, st, nao, nslab, slabs, vxc, nxb, partial, exc,
+                               want_host_exc ? s->h_exc_dev : nullptr);
+            return hip_ok(s, hipGetLastError(), "XC sweep launch");
+        } else {
+            // Exc is summed by the reduce kernel's highest-index block into the DEVICE scalar only; publishing it to the host
+            // is left to a one-thread kernel behind it (stream order: the whole call has completed when the word appears) --
+            // the shortest launch there is, instead of a finishing kernel that still has the partials to add up
+            // Option "publish" (where the creation-time probe passed): no publishing launch -- the reduce kernel's finishing
+            // block stores Exc to the host word, and a stream memory write behind the kernel raises the sequence word the
+            // host waits for.  Same meaning (stream order: after every store of the call), no dispatch.
+            const bool sw = want_host_exc && s->h_exc_dev && s->publish > 0 && s->publish_ok && !s->recording;
+            hipLaunchKernelGGL((k_reduce_slabs8<false, true>), g, dim3(256), 0, st, nao, nslab, slabs, vxc, nxb, partial, exc,
+                               sw ? s->h_exc_dev : (double *)nullptr);
+            if (sw) {
+                if (hipStreamWriteValue64(st, s->h_seq_dev, s->seq + 1, 0) == hipSuccess) {
+                    ++s->seq;
+                    s->wait_mode = 1;
+                } else { // refused after all: this call is waited for on the stream, later ones publish by kernel
+                    (void)hipGetLastError();
+                    s->publish_ok = false;
+                    s->wait_mode = 2;
+                }
+            } else if (want_host_exc && s->h_exc_dev) {
+                hipLaunchKernelGGL(k_publish_exc, dim3(1), dim3(1), 0, st, exc, s->h_exc_dev);
+            }
+            return hip_ok(s, hipGetLastError(), "XC sweep launch");
+        }
+        // last launch of the call: Exc to the device scalar and to host-mapped memory
+        if (fin) hipLaunchKernelGGL(k_finish_exc, dim3(1), dim3(256), 0, st, nxb, partial, exc, want_host_exc ? s->h_exc_dev : nullptr);
+    }
+    return hip_ok(s, hipGetLastError(), "XC sweep launch");
+}
+
 // The sweep: everything on s->stream, Exc left in s->exc (device).
 // `cocc` (nao, nocc) with dm = cocc cocc^T switches the density step to the occupied-orbital form where that
 // pays (xc_occ_kernels.hpp); `dm` may then be null.
@@ -293,47 +503,8 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
         launch_dm_from_cocc(s->stream, nao, nocc, cocc, (double *)s->occ_dm.p);
         dm = (const double *)s->occ_dm.p;
     }
-    const int NP = ((nao + 15) / 16) * 16;
-    const int nblk = (nao + 127) / 128;
-    // the wave-specialised kernels address a plane through ONE buffer descriptor: planes of 4 GiB or more
-    // (ngrid*nao >= 2^29) take the generic tiled kernels
-    const bool fits32 = (double)ngrid * nao * 8.0 < 4294967296.0;
-    const bool fast = s->path == 0 && nao <= 128 && fits32;
-    const bool big = s->path == 0 && nao > 128;   // nao <= 128 with planes >= 4 GiB: the generic MFMA kernels below
-    const int ntv = NP / 16;
-    int nslab;
-    long chunk = 0;
-    const int nA = (nao + BG_BM - 1) / BG_BM, nB = (nao + BG_BN - 1) / BG_BN, npair = nA * nB;
-    if (big) {
-        // split-K over grid chunks; chunks are dealt to XCDs (blockIdx % 8), so ksplit is a multiple of 8
-        // chunks per XCD: the candidate (<= 32, slabs <= 2 GB, >= 64 grid rows per chunk) whose workgroup
-        // count fills whole waves of the chip best (360 workgroups on 256 CUs lost 30 % to the tail)
-        long per_xcd = 1;
-        double best = 0.0;
-        for (long c = 1; c <= 32; ++c) {
-            const long wgs = 8L * npair * c;
-            if (8 * c * 64 > ngrid && c > 1) break;
-            if ((double)(8 * c) * nao * nao * 8.0 > 2.0e9 && c > 1) break;
-            const long rounds = (wgs + s->num_cu - 1) / s->num_cu;
-            const double eff = (double)wgs / (double)(rounds * s->num_cu);
-            if (eff > best + 1e-9) { best = eff; per_xcd = c; }
-        }
-        // a chunk of one plane stays below 4 GiB: k_vxc_big addresses it through one buffer descriptor
-        while ((double)((ngrid + 8 * per_xcd - 1) / (8 * per_xcd) + BG_BK) * nao * 8.0 >= 4294967296.0) ++per_xcd;
-        nslab = (int)(8 * per_xcd);
-        chunk = (ngrid + nslab - 1) / nslab;
-        chunk = ((chunk + BG_BK - 1) / BG_BK) * BG_BK;
-    } else if (tiny) {
-        nslab = tiny_workgroups(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid);
-    } else if (fast) {
-        const long ntile = (ngrid + WS_ROWS - 1) / WS_ROWS;
-        nslab = (int)std::min<long>(s->num_cu, ntile); // one persistent, wave-specialised workgroup per CU
-    } else {
-        const int nsplit = auto_ksplit(s, ngrid, nblk * nblk);
-        chunk = (ngrid + nsplit - 1) / nsplit;
-        chunk = ((chunk + 31) / 32) * 32;
-        nslab = (int)((ngrid + chunk - 1) / chunk);
-    }
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, tiny);
+    const int NP = P.NP, nslab = P.nslab;
     const long nxb = tiny ? nslab : (ngrid + 255) / 256; // Exc partials: one per workgroup of the kernel that evaluates the functional
     const size_t ng = (size_t)ngrid;
 
@@ -353,10 +524,8 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
            *grad = (double *)s->grad.p, *coef = (double *)s->coef.p,
            *partial = (double *)s->partial.p, *slabs = (double *)s->slabs.p,
            *exc = exc_out ? exc_out : (double *)s->exc.p;   // the asynchronous entries' caller-owned scalar: written by the finishing kernel itself
-    const double *gx = ao_grad, *gy = gga ? ao_grad + ng * nao : nullptr,
-                 *gz = gga ? ao_grad + 2 * ng * nao : nullptr;
-    // 16-byte plane loads: even nao and every plane 16-byte aligned
-    const bool vec16 = (nao % 2 == 0) && ((((uintptr_t)ao | (uintptr_t)gx | (uintptr_t)gy | (uintptr_t)gz) & 15) == 0);
+    const double *gx = P.gx, *gy = P.gy, *gz = P.gz;
+    const bool vec16 = P.vec16;
     hipStream_t st = s->stream;
 
     if (tiny) {
@@ -371,28 +540,7 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
                                       rho, grad, sigma), "occupied-orbital density launch"))
             return false;
     }
-    if (!fast && !use_occ && !tiny) { // the wave-specialised rho kernel symmetrises D in its prologue
-        ScopedTimer t(s, "sym_dm");
-        dim3 b(16, 16), g(NP / 16, NP / 16);
-        hipLaunchKernelGGL(k_sym_dm, g, b, 0, st, nao, NP, dm, Dp);
-    }
-    if (!use_occ && !tiny) {
-        ScopedTimer t(s, "rho");
-        with_bool(gga, [&](auto G) {
-            if (fast)
-                with_bool(vec16, [&](auto V) { with_nt(ntv, [&](auto NT) {
-                    hipLaunchKernelGGL((k_rho_ws<NT, G, V>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, dm, rho, grad, sigma, s->sweep_order & 1);
-                }); });
-            else if (big) // 64-row workgroups, two per CU
-                with_bool(vec16, [&](auto V) {
-                    hipLaunchKernelGGL((k_rho_big64<G, V>), dim3((unsigned)((ngrid + R6_BM - 1) / R6_BM)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-                });
-            else if (s->path != 1)
-                hipLaunchKernelGGL(k_rho_mfma<G>, dim3((unsigned)((ngrid + 63) / 64)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-            else
-                hipLaunchKernelGGL(k_rho_valu<G>, dim3((unsigned)((ngrid + 3) / 4)), dim3(256), 0, st, ngrid, nao, NP, ao, gx, gy, gz, Dp, rho, grad, sigma);
-        });
-    }
+    if (!use_occ && !tiny) launch_density(s, P, ngrid, nao, dm, ao, Dp, rho, grad, sigma);
     if (!tiny) {
         ScopedTimer t(s, "xc_points");
         dim3 g((unsigned)nxb);
@@ -402,87 +550,103 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
         else if (gga)                   hipLaunchKernelGGL(k_xc_points_mix<true>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
         else                            hipLaunchKernelGGL(k_xc_points_mix<false>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
     }
-    if (!tiny) {
-        ScopedTimer t(s, "vxc");
-        // Option "vxc_fringe": at nao = 16 k + 1..4 (k >= 1) the one-sided kernels leave the k x k whole tiles to the matrix
-        // pipe and take the fringe lines on the vector ALU (vxc_ws_mfma_fringe) instead of padding to k + 1 tiles per side
-        const bool fringe = fast && s->type != SOLVER_B3LYP && s->vxc_fringe != 0 && nao > 16 && nao % 16 >= 1 && nao % 16 <= 4;
-        s->used_vxc_fringe = fringe;
-        auto launch = [&](auto G, auto S) { // S: B3LYP, the wave-specialised kernels write symmetrised slabs
-            if (fast)
-                with_bool(vec16, [&](auto V) { with_nt(ntv, [&](auto NT) {
-                    if constexpr (NT >= 2 && !S) {
-                        if (fringe) {
-                            hipLaunchKernelGGL((k_vxc_ws<NT, G, V, false, true>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1);
-                            return;
-                        }
-                    }
-                    hipLaunchKernelGGL((k_vxc_ws<NT, G, V, S>), dim3((unsigned)nslab), dim3(WS_THREADS), 0, st, ngrid, nao, ao, gx, gy, gz, coef, slabs, (s->sweep_order >> 1) & 1);
-                }); });
-            else if (big)
-                with_bool(vec16, [&](auto V) {
-                    hipLaunchKernelGGL((k_vxc_big<G, V>), dim3((unsigned)(nslab * npair)), dim3(BG_THREADS), 0, st, ngrid, nao, chunk, nB, npair, ao, gx, gy, gz, coef, slabs);
-                });
-            else if (s->path != 1)
-                hipLaunchKernelGGL(k_vxc_mfma<G>, dim3((unsigned)nslab, nblk, nblk), dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
-            else
-                hipLaunchKernelGGL(k_vxc_valu<G>, dim3((unsigned)nslab), dim3(256), 0, st, ngrid, nao, chunk, ao, gx, gy, gz, coef, slabs);
-        };
-        switch (s->type) { // (G, S)
-        case SOLVER_LDA: launch(std::false_type{}, std::false_type{}); break;
-        case SOLVER_GGA: launch(std::true_type{}, std::false_type{}); break;
-        case SOLVER_MIX: // GGA convention: one-sided, never symmetrised here; an LDA-class mix takes the one-plane kernels
-            if (gga) launch(std::true_type{}, std::false_type{});
-            else     launch(std::false_type{}, std::false_type{});
-            break;
-        default:         launch(std::true_type{}, std::true_type{}); break;
-        }
+    const ExcFinish fin{nxb, partial, exc, want_host_exc};
+    return vxc_stage(s, P, tiny, ngrid, nao, ao, coef, slabs, vxc, &fin);
+}
+
+// Linear response of Vxc, first half: the ground-state density step of a sweep (never the one-kernel plan for small
+// bases: that one keeps no density) and the derivative table of the functional at that density.
+bool fxc_prepare(XCSolver *s, long ngrid, int nao, int nocc, const double *cocc, const double *dm, const double *ao,
+                 const double *ao_grad, const double *w)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    s->fxc_ngrid = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
+    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
+    const bool gga = s->needs_grad;
+    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
+    if (!ao || !w) { set_error(s, "DFT_FxcPrepare needs the AO values and the grid weights"); return false; }
+    if (!dm && !cocc) { set_error(s, "neither a density matrix nor occupied orbitals were given"); return false; }
+    if (cocc && nocc <= 0) { set_error(s, "occupied orbitals given with nocc=%d", nocc); return false; }
+    OccPlan oplan;
+    bool use_occ = false;
+    if (cocc && s->path == 0 && s->occ != 2) {   // the rule of xc_sweep
+        oplan = occ_plan(nao, nocc, gga);
+        use_occ = s->occ == 1 || oplan.mfma_occ <= 0.85 * oplan.mfma_full;
+    }
+    s->used_occ = use_occ;
+    if (!use_occ && !dm) {
+        if (!reserve(s, s->occ_dm, sizeof(double) * (size_t)nao * nao, "hipMalloc(dm)")) return false;
+        launch_dm_from_cocc(s->stream, nao, nocc, cocc, (double *)s->occ_dm.p);
+        dm = (const double *)s->occ_dm.p;
+    }
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const size_t ng = (size_t)ngrid;
+    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
+        !reserve(s, s->rho, sizeof(double) * ng, "hipMalloc(rho)") ||
+        !reserve(s, s->fxc_table, sizeof(double) * ng * (gga ? FXC_PLANES : 1), "hipMalloc(fxc table)"))
+        return false;
+    if (gga && (!reserve(s, s->sigma, sizeof(double) * ng, "hipMalloc(sigma)") ||
+                !reserve(s, s->fxc_g0, sizeof(double) * 3 * ng, "hipMalloc(fxc grad rho)")))
+        return false;
+    double *rho = (double *)s->rho.p, *sigma = (double *)s->sigma.p, *g0 = (double *)s->fxc_g0.p;   // grad rho goes straight to its keep
+    if (use_occ) {
+        ScopedTimer t(s, "rho_occ");
+        if (!reserve(s, s->occ_cp, sizeof(double) * oplan.cp_doubles, "hipMalloc(packed cocc)")) return false;
+        if (!hip_ok(s, launch_rho_occ(s->stream, s->num_cu, oplan, gga, P.vec16, ngrid, nao, nocc, cocc, (double *)s->occ_cp.p, ao, P.gx, P.gy,
+                                      P.gz, rho, g0, sigma), "occupied-orbital density launch"))
+            return false;
+    } else {
+        launch_density(s, P, ngrid, nao, dm, ao, (double *)s->dsym.p, rho, g0, sigma);
     }
     {
-        ScopedTimer t(s, "reduce_vxc");
-        dim3 g((unsigned)(((size_t)nao * nao + 31) / 32));
-        const bool b3 = s->type == SOLVER_B3LYP;
-        if (b3 && big) { // plain reduce into M, then tiled M + M^T
-            if (!reserve(s, s->msym, sizeof(double) * (size_t)nao * nao, "hipMalloc(M)")) return false;
-            double *M = (double *)s->msym.p;
-            hipLaunchKernelGGL(k_reduce_slabs8<false>, g, dim3(256), 0, st, nao, nslab, slabs, M);
-            const int nt = (nao + 31) / 32;
-            hipLaunchKernelGGL(k_symmetrize, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, nao, M, vxc);
-        } else if (b3 && !fast) {
-            hipLaunchKernelGGL(k_reduce_slabs8<true>, g, dim3(256), 0, st, nao, nslab, slabs, vxc);
-        } else if (s->fuse_finish) { // wave-specialised slabs are already symmetrised for B3LYP
-            // last launch of the call: its last-ticket block also finishes Exc (device scalar + host-mapped word)
-            hipLaunchKernelGGL((k_reduce_slabs8<false, true>), g, dim3(256), 0, st, nao, nslab, slabs, vxc, nxb, partial, exc,
-                               want_host_exc ? s->h_exc_dev : nullptr);
-            return hip_ok(s, hipGetLastError(), "XC sweep launch");
-        } else {
-            // Exc is summed by the reduce kernel's highest-index block into the DEVICE scalar only; publishing it to the host
-            // is left to a one-thread kernel behind it (stream order: the whole call has completed when the word appears) --
-            // the shortest launch there is, instead of a finishing kernel that still has the partials to add up
-            // Option "publish" (where the creation-time probe passed): no publishing launch -- the reduce kernel's finishing
-            // block stores Exc to the host word, and a stream memory write behind the kernel raises the sequence word the
-            // host waits for.  Same meaning (stream order: after every store of the call), no dispatch.
-            const bool sw = want_host_exc && s->h_exc_dev && s->publish > 0 && s->publish_ok && !s->recording;
-            hipLaunchKernelGGL((k_reduce_slabs8<false, true>), g, dim3(256), 0, st, nao, nslab, slabs, vxc, nxb, partial, exc,
-                               sw ? s->h_exc_dev : (double *)nullptr);
-            if (sw) {
-                if (hipStreamWriteValue64(st, s->h_seq_dev, s->seq + 1, 0) == hipSuccess) {
-                    ++s->seq;
-                    s->wait_mode = 1;
-                } else { // refused after all: this call is waited for on the stream, later ones publish by kernel
-                    (void)hipGetLastError();
-                    s->publish_ok = false;
-                    s->wait_mode = 2;
-                }
-            } else if (want_host_exc && s->h_exc_dev) {
-                hipLaunchKernelGGL(k_publish_exc, dim3(1), dim3(1), 0, st, exc, s->h_exc_dev);
-            }
-            return hip_ok(s, hipGetLastError(), "XC sweep launch");
-        }
-        // last launch of the call: Exc to the device scalar and to host-mapped memory
-        hipLaunchKernelGGL(k_finish_exc, dim3(1), dim3(256), 0, st, nxb, partial, exc, want_host_exc ? s->h_exc_dev : nullptr);
+        ScopedTimer t(s, "fxc_table");
+        const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+        if (!hip_ok(s, launch_fxc_table(s->stream, type, gga, s->mix.c, ngrid, rho, gga ? sigma : nullptr, w, (double *)s->fxc_table.p, s->quirks),
+                    "response table launch"))
+            return false;
     }
-    return hip_ok(s, hipGetLastError(), "XC sweep launch");
+    if (!hip_ok(s, hipGetLastError(), "response prepare launch")) return false;
+    s->fxc_ngrid = ngrid;
+    s->fxc_nao = nao;
+    return true;
+}
+
+// Second half: V1 of a perturbation dm1 -- its density through the same kernels (linear in the matrix), the response
+// coefficients from the table, and the sweep's contraction and reduce.  Asynchronous on the solver's stream.
+bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double *ao, const double *ao_grad, double *v1)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
+    if (s->fxc_ngrid <= 0) { set_error(s, "DFT_FxcApply before DFT_FxcPrepare (or the table was invalidated by an option change)"); return false; }
+    if (ngrid != s->fxc_ngrid || nao != s->fxc_nao) {
+        set_error(s, "DFT_FxcApply sizes ngrid=%ld nao=%d differ from DFT_FxcPrepare's ngrid=%ld nao=%d", ngrid, nao, s->fxc_ngrid, s->fxc_nao);
+        return false;
+    }
+    const bool gga = s->needs_grad;
+    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
+    if (!dm1 || !ao || !v1) { set_error(s, "DFT_FxcApply needs dm1, the AO values and the output matrix"); return false; }
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const size_t ng = (size_t)ngrid;
+    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
+        !reserve(s, s->rho, sizeof(double) * ng, "hipMalloc(rho)") ||
+        !reserve(s, s->coef, sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(coef)") ||
+        !reserve(s, s->slabs, sizeof(double) * (size_t)P.nslab * nao * nao, "hipMalloc(slabs)"))
+        return false;
+    if (gga && (!reserve(s, s->sigma, sizeof(double) * ng, "hipMalloc(sigma)") ||
+                !reserve(s, s->grad, sizeof(double) * 3 * ng, "hipMalloc(grad)")))
+        return false;
+    double *rho1 = (double *)s->rho.p, *g1 = (double *)s->grad.p, *coef = (double *)s->coef.p;
+    launch_density(s, P, ngrid, nao, dm1, ao, (double *)s->dsym.p, rho1, g1, (double *)s->sigma.p);
+    {
+        ScopedTimer t(s, "fxc_coef");
+        if (!hip_ok(s, launch_fxc_coef(s->stream, gga, ngrid, (const double *)s->fxc_table.p, (const double *)s->fxc_g0.p, rho1, g1, coef),
+                    "response coefficient launch"))
+            return false;
+    }
+    return vxc_stage(s, P, false, ngrid, nao, ao, coef, (double *)s->slabs.p, v1, nullptr);
 }
 
 // J and/or K from rows (i, j), i in [i0, i0 + ni), of the dense ERI; `eri` points at row (i0, 0).
@@ -957,7 +1121,7 @@ void DFT_DestroySolver(XCSolver *s)
         if (s->cap_stream) (void)hipStreamDestroy(s->cap_stream);
         DevBuf *bufs[] = {&s->dsym, &s->rho, &s->sigma, &s->grad, &s->coef, &s->partial,
                           &s->slabs, &s->exc, &s->jpart, &s->kpart, &s->shells, &s->msym,
-                          &s->cdy, &s->cdc, &s->cdv, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st};
+                          &s->cdy, &s->cdc, &s->cdv, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0};
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
@@ -1214,6 +1378,23 @@ int DFT_ComputeXCAsync(XCSolver *s, long long ngrid, int nao, unsigned long long
     return 0;
 }
 
+int DFT_FxcPrepare(XCSolver *s, long long ngrid, int nao, int nocc, unsigned long long d_cocc, unsigned long long d_dm0,
+                   unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_weights)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return fxc_prepare(s, (long)ngrid, nao, nocc, (const double *)d_cocc, (const double *)d_dm0, (const double *)d_ao,
+                       (const double *)d_ao_grad, (const double *)d_weights) ? 0 : -1;
+}
+
+int DFT_FxcApply(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm1, unsigned long long d_ao,
+                 unsigned long long d_ao_grad, unsigned long long d_v1)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return fxc_apply(s, (long)ngrid, nao, (const double *)d_dm1, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_v1) ? 0 : -1;
+}
+
 void DFT_ComputeCoulomb(XCSolver *s, int nao, unsigned long long d_eri, unsigned long long d_dm,
                         unsigned long long d_J)
 {
@@ -1333,7 +1514,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     }
     if (!strcmp(key, "eri_symmetric")) { s->eri_sym = value == 2.0 ? 2 : value != 0.0; return 0; }
     if (!strcmp(key, "graph")) { s->graph = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
-    if (!strcmp(key, "quirks")) { s->quirks = value != 0.0; return 0; }
+    if (!strcmp(key, "quirks")) { s->quirks = value != 0.0; s->fxc_ngrid = 0; return 0; }   // a prepared response table held the old formulas
     if (!strcmp(key, "path")) { s->path = (int)value; return 0; }
     if (!strcmp(key, "profile")) { s->profile = value != 0.0; return 0; }
     if (!strcmp(key, "spin_wait")) { s->spin_wait = value != 0.0; return 0; }

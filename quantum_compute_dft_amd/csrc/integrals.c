@@ -226,6 +226,53 @@ int qc_int1e(int nshell, const double *xyz, const int *ls, const int *nprim, con
     return 0;
 }
 
+/* ---- dipole integrals ------------------------------------------------------------------------ */
+/* D[k][mu][nu] = <mu| (r - O)_k |nu>, k = x, y, z (3, nao, nao).  In the moment's dimension the one-dimensional overlap
+ * E_0 sqrt(pi/p) becomes (E_1 + (P - O) E_0) sqrt(pi/p): r - O = (r - P) + (P - O), and the first moment about P of the
+ * Hermite Gaussian Lambda_t is sqrt(pi/p) for t = 1 and zero otherwise. */
+int qc_dipole(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+              const int *ao0, const double *ex, const double *cf, int nao, const double *origin, double *D)
+{
+    for (int s = 0; s < nshell; ++s)
+        if (ls[s] < 0 || ls[s] > LMAX) return -1;
+#pragma omp parallel for schedule(dynamic) collapse(2)
+    for (int A = 0; A < nshell; ++A)
+        for (int B = 0; B < nshell; ++B) {
+            const int la = ls[A], lb = ls[B], nca = NCART(la), ncb = NCART(lb);
+            int ax[MAXCART], ay[MAXCART], az[MAXCART], bx[MAXCART], by[MAXCART], bz[MAXCART];
+            cart_components(la, ax, ay, az);
+            cart_components(lb, bx, by, bz);
+            double cd[3][MAXCART * MAXCART] = {{0}};
+            const double *RA = xyz + 3 * A, *RB = xyz + 3 * B;
+            for (int pa = 0; pa < nprim[A]; ++pa)
+                for (int pb = 0; pb < nprim[B]; ++pb) {
+                    const double a = ex[off[A] + pa], b = ex[off[B] + pb], p = a + b;
+                    const double cc = cf[off[A] + pa] * cf[off[B] + pb];
+                    double E[3][LMAX + 3][LMAX + 3][2 * LMAX + 5];
+                    double PO[3];
+                    for (int d = 0; d < 3; ++d) {
+                        hermite_E(la, lb, a, b, RA[d] - RB[d], E[d]);
+                        PO[d] = (a * RA[d] + b * RB[d]) / p - origin[d];
+                    }
+                    const double s0 = pow(M_PI / p, 1.5);
+                    for (int ca = 0; ca < nca; ++ca)
+                        for (int cb = 0; cb < ncb; ++cb) {
+                            const int i[3] = {ax[ca], ay[ca], az[ca]}, j[3] = {bx[cb], by[cb], bz[cb]};
+                            double s1[3], m1[3];
+                            for (int d = 0; d < 3; ++d) {
+                                s1[d] = E[d][i[d]][j[d]][0];
+                                m1[d] = E[d][i[d]][j[d]][1] + PO[d] * s1[d];
+                            }
+                            cd[0][ca * ncb + cb] += cc * s0 * m1[0] * s1[1] * s1[2];
+                            cd[1][ca * ncb + cb] += cc * s0 * s1[0] * m1[1] * s1[2];
+                            cd[2][ca * ncb + cb] += cc * s0 * s1[0] * s1[1] * m1[2];
+                        }
+                }
+            for (int k = 0; k < 3; ++k) put_sph2(la, lb, cd[k], D + (size_t)k * nao * nao, nao, ao0[A], ao0[B]);
+        }
+    return 0;
+}
+
 /* ---- one-electron Coulomb integrals at arbitrary points -------------------------------------- */
 /* A[c][mu][nu] = <mu| 1/|r - R_c| |nu> (the nuclear-attraction integral of qc_int1e for a unit charge at any point,
  * positive sign), never stored: qc_point_matrix sums it over points with weights, qc_point_contract contracts it with

@@ -1,0 +1,105 @@
+// Host counterpart of xc_response.hip (lib/libqcfxc.so, built with g++): the same bodies of xc_functionals.hpp,
+// the same two dual evaluations per point.  response.fxc_apply_host() and a CPU CPKS run assemble V1 from it; the CPU
+// tests hold it against finite differences of the oracle.  type: 0 LDA, 1 GGA, 2 B3LYP, 3 mix (eight weights).
+#include "xc_functionals.hpp"
+
+using namespace qcdft;
+
+namespace {
+
+xc::MixWeights weights(const double *mix8)
+{
+    xc::MixWeights m = {};
+    if (mix8)
+        for (int k = 0; k < 8; ++k) m.c[k] = mix8[k];
+    return m;
+}
+
+bool mix_gga(const xc::MixWeights &m)
+{
+    return m.c[4] != 0.0 || m.c[5] != 0.0 || m.c[6] != 0.0 || m.c[7] != 0.0;
+}
+
+template <class T>
+xc::PQT<T> pq(int type, const xc::MixWeights &m, bool gga, T r, T s, bool quirks)
+{
+    if (type == 0) return xc::lda_pq(r, quirks);
+    if (type == 1) return xc::gga_pq(r, s, quirks);
+    if (type == 2) return xc::b3lyp_pq(r, s);
+    return gga ? xc::mix_pq<true>(m, r, s, quirks) : xc::mix_pq<false>(m, r, s, quirks);
+}
+
+} // namespace
+
+extern "C" {
+
+// out (5, n): P_rho, P_sigma, Q_rho, Q_sigma, Q (no weight).  An LDA-class functional leaves planes 1..4 zero.
+int qc_fxc_table(int type, const double *mix8, int quirks, long long n, const double *rho, const double *sigma, double *out)
+{
+    if (type < 0 || type > 3 || (type == 3 && !mix8) || n < 0 || !rho || !out) return -1;
+    const xc::MixWeights m = weights(mix8);
+    const bool gga = type == 1 || type == 2 || (type == 3 && mix_gga(m));
+    if (gga && !sigma) return -1;
+    for (long long g = 0; g < n; ++g) {
+        const double r = rho[g], s = gga ? sigma[g] : 0.0;
+        const xc::PQT<xc::Dual> a = pq(type, m, gga, xc::Dual(r, 1.0), xc::Dual(s, 0.0), quirks != 0);
+        out[g] = a.p.d;
+        out[2 * n + g] = a.q.d;
+        out[4 * n + g] = a.q.v;
+        if (gga) {
+            const xc::PQT<xc::Dual> b = pq(type, m, gga, xc::Dual(r, 0.0), xc::Dual(s, 1.0), quirks != 0);
+            out[n + g] = b.p.d;
+            out[3 * n + g] = b.q.d;
+        } else {
+            out[n + g] = 0.0;
+            out[3 * n + g] = 0.0;
+        }
+    }
+    return 0;
+}
+
+// out (2, n): P, Q evaluated in double, and the value parts of the dual evaluation in out_dual (2, n).
+int qc_fxc_pq(int type, const double *mix8, int quirks, long long n, const double *rho, const double *sigma, double *out,
+              double *out_dual)
+{
+    if (type < 0 || type > 3 || (type == 3 && !mix8) || n < 0 || !rho || !sigma || !out) return -1;
+    const xc::MixWeights m = weights(mix8);
+    const bool gga = type == 1 || type == 2 || (type == 3 && mix_gga(m));
+    for (long long g = 0; g < n; ++g) {
+        const xc::PQT<double> a = pq(type, m, gga, rho[g], sigma[g], quirks != 0);
+        out[g] = a.p;
+        out[n + g] = a.q;
+        if (out_dual) {
+            const xc::PQT<xc::Dual> d = pq(type, m, gga, xc::Dual(rho[g], 1.0), xc::Dual(sigma[g], 0.5), quirks != 0);
+            out_dual[g] = d.p.v;
+            out_dual[n + g] = d.q.v;
+        }
+    }
+    return 0;
+}
+
+// out (5, n): exc, c0..c3 of the point bodies the kernels run (lda_point / gga_point / b3lyp_point / mix_point), in double.
+int qc_xc_point(int type, const double *mix8, int quirks, long long n, const double *rho, const double *sigma,
+                const double *grad3, const double *w, double *out)
+{
+    if (type < 0 || type > 3 || (type == 3 && !mix8) || n < 0 || !rho || !sigma || !grad3 || !w || !out) return -1;
+    const xc::MixWeights m = weights(mix8);
+    const bool gga = mix_gga(m);
+    for (long long g = 0; g < n; ++g) {
+        const double gx = grad3[3 * g], gy = grad3[3 * g + 1], gz = grad3[3 * g + 2];
+        xc::PointXC p;
+        if (type == 0)      p = xc::lda_point(rho[g], w[g], quirks != 0);
+        else if (type == 1) p = xc::gga_point(rho[g], sigma[g], gx, gy, gz, w[g], quirks != 0);
+        else if (type == 2) p = xc::b3lyp_point(rho[g], sigma[g], gx, gy, gz, w[g]);
+        else if (gga)       p = xc::mix_point<true>(m, rho[g], sigma[g], gx, gy, gz, w[g], quirks != 0);
+        else                p = xc::mix_point<false>(m, rho[g], 0.0, 0.0, 0.0, 0.0, w[g], quirks != 0);
+        out[g] = p.exc;
+        out[n + g] = p.c0;
+        out[2 * n + g] = p.c1;
+        out[3 * n + g] = p.c2;
+        out[4 * n + g] = p.c3;
+    }
+    return 0;
+}
+
+} // extern "C"

@@ -4,12 +4,16 @@ other name of functionals.TABLE (PBE0, BLYP, ...) or an expression such as "0.75
 Extra flags (defaults = what the reference hard-codes): --basis sto-3g, --grid-level 3, --quirks 1.
 --point-charges FILE runs the molecule in the field of external point charges (rows `x y z q`); --esp-points FILE with
 --esp-out FILE writes the electrostatic potential of the converged density at the given points and --field-out FILE its
-electric field; --charge-forces-out FILE writes the forces of the molecule on the point charges."""
+electric field; --charge-forces-out FILE writes the forces of the molecule on the point charges.  --efield Fx Fy Fz runs
+the SCF in a uniform field (a.u.); --dipole reports the dipole moment, --polarizability the static polarizability by
+coupled-perturbed Kohn-Sham (response.py; the response of Vxc on the device)."""
 import argparse
 import importlib.util
 import os
 import sys
 import time
+
+import numpy as np
 
 from . import functionals, inputs, scf
 
@@ -123,6 +127,12 @@ def main(argv=None):
     p.add_argument("--charge-forces-out", default=None, metavar="FILE",
                    help="receives rows `x y z q Fx Fy Fz`: the force of the molecule on every charge of --point-charges in Ha/bohr "
                         "(the charges' forces on each other are not included)")
+    p.add_argument("--efield", type=float, nargs=3, default=None, metavar=("FX", "FY", "FZ"),
+                   help="uniform external electric field in a.u.: the SCF runs in it (core Hamiltonian += F.r, nuclear term -= sum Z F.R)")
+    p.add_argument("--dipole", action="store_true", help="dipole moment of the converged density (e bohr and debye)")
+    p.add_argument("--polarizability", action="store_true",
+                   help="static dipole polarizability by coupled-perturbed Kohn-Sham (the response of Vxc on the device: DFT_FxcPrepare / "
+                        "DFT_FxcApply); one rank, --ao resident")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
     args = p.parse_args(argv)
@@ -131,6 +141,8 @@ def main(argv=None):
     if args.charge_forces_out and not args.point_charges:
         p.error("--charge-forces-out needs --point-charges")
     fn = functionals.resolve(args.functional)
+    if args.polarizability and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident"):
+        p.error("--polarizability runs on one rank with --ao resident")
 
     # one process per GPU: `python -m torch.distributed.run --nproc-per-node N -m quantum_compute_dft_amd.dft ...`
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -167,7 +179,9 @@ def main(argv=None):
         args.eri = "dense" if 8.0 * _nao ** 4 <= 8.0e9 else "cholesky"
     charges = read_point_rows(args.point_charges, 4, args.point_charges_unit) if args.point_charges else None
     inp = inputs.build(atom_path, args.basis, args.grid_level, device=device, eri_mode=args.eri, chol_tol=args.chol_tol, rank=rank, world=world,
-                       point_charges=charges)
+                       point_charges=charges, efield=args.efield)
+    if args.efield is not None:
+        print(f"Uniform external field: F = ({args.efield[0]:+.6f}, {args.efield[1]:+.6f}, {args.efield[2]:+.6f}) a.u.")
     if charges is not None:
         print(f"External point charges: {len(charges)} (total {charges[:, 3].sum():+.6f} e), nuclei-charges repulsion {inp.E_nuc_ext:.8f} Ha")
     print(f"System Info: NAO={inp.shells.nao}, Grid={inp.grids.size}, Occupied={inp.nocc}")
@@ -233,6 +247,19 @@ def main(argv=None):
         if args.charge_forces_out:
             write_charge_force_rows(args.charge_forces_out, inp.point_charges, charge_forces, args.point_charges_unit)
             print(f"Forces on {len(charge_forces)} point charges written to {args.charge_forces_out}")
+    dipole = polar = None
+    if args.dipole and res["converged"] and not rank:
+        from . import properties
+        dipole = properties.dipole_moment(inp, res["dm"])
+        print("Dipole moment (e bohr): " + " ".join(f"{x:+.8f}" for x in dipole) +
+              "   (debye: " + " ".join(f"{x * properties.DEBYE_PER_AU:+.6f}" for x in dipole) + f"; |mu| = {np.linalg.norm(dipole) * properties.DEBYE_PER_AU:.6f} D)")
+    if args.polarizability and res["converged"]:
+        from . import response
+        polar = response.polarizability(inp, res, backend, args.functional, log=print)
+        print("Static polarizability (a.u.):")
+        for row in polar["alpha"]:
+            print("   " + " ".join(f"{x:+14.8f}" for x in row))
+        print(f"Isotropic polarizability: {np.trace(polar['alpha']) / 3.0:.8f} a.u.  (CPKS iterations x, y, z: {polar['cpks_iterations']})")
     import json
     record = {"functional": args.functional, "molecule": os.path.splitext(atom_file)[0], "basis": args.basis, "grid_level": args.grid_level,
               "nao": int(inp.shells.nao), "ngrid": int(inp.grids.size), "nocc": int(inp.nocc), "n_gpus": world, "eri": args.eri,
@@ -246,6 +273,13 @@ def main(argv=None):
     if charges is not None:
         record["n_point_charges"] = int(len(charges)); record["E_nuc_ext"] = float(inp.E_nuc_ext)
         record["point_charge_forces"] = charge_forces.tolist() if charge_forces is not None else None
+    if args.efield is not None:
+        record["efield"] = [float(x) for x in args.efield]
+    if args.dipole:
+        record["dipole"] = dipole.tolist() if dipole is not None else None
+    if args.polarizability:
+        record["polarizability"] = polar["alpha"].tolist() if polar is not None else None
+        record["cpks_iterations"] = [int(x) for x in polar["cpks_iterations"]] if polar is not None else None
     if other is not None:
         record["E_tot_other_quirks"] = other.get("E_tot"); record["other_quirks"] = 0 if args.quirks else 1
     line = json.dumps(record)

@@ -31,6 +31,7 @@ class SCFInputs:
     point_charges: np.ndarray = None  # (n, 4): x, y, z (bohr), q of the external point charges (build(..., point_charges=...))
     V_ext: np.ndarray = None  # (nao, nao) potential of those charges on the electrons, already part of Hcore
     E_nuc_ext: float = 0.0    # nuclei -- external charges repulsion, already part of E_nuc
+    efield: np.ndarray = None  # (3,) uniform external electric field F in a.u. (build(..., efield=...)), already part of Hcore and E_nuc
 
 
 def external_charges(symbols, atom_xyz, shells, point_charges, device="cpu"):
@@ -51,8 +52,20 @@ def external_charges(symbols, atom_xyz, shells, point_charges, device="cpu"):
     return pc, V_ext, float(np.sum(z[:, None] * pc[None, :, 3] / dist))
 
 
+def uniform_field(symbols, atom_xyz, shells, efield):
+    """(F (3,), V_F, E_nuc_F) of a uniform electric field F (a.u.):  V_F = sum_k F_k D_k (the electrons' energy +F.r, D the
+    dipole integrals about the origin of the coordinates),  E_nuc_F = -sum_A Z_A F.R_A.  The total energy then carries
+    -F.mu, so that mu = -dE/dF (properties.dipole_moment) for a variational functional."""
+    F = np.array(efield, dtype=np.float64)
+    if F.shape != (3,) or not np.all(np.isfinite(F)):
+        raise ValueError(f"efield: expected three finite numbers Fx, Fy, Fz (a.u.), got {efield!r}")
+    z = np.array([basis.atomic_number(s) for s in symbols], dtype=np.float64)
+    V_F = np.einsum("k,kij->ij", F, integrals.dipole(shells))
+    return F, V_F, -float(z @ (np.asarray(atom_xyz, dtype=np.float64) @ F))
+
+
 def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=True, eri_mode="dense",
-          chol_tol=1e-9, rank=0, world=1, group=None, point_charges=None):
+          chol_tol=1e-9, rank=0, world=1, group=None, point_charges=None, efield=None):
     """grid.py:42-67.  `atom_path`: an .xyz file (or a molecule name resolved in data/).
     eri_mode "dense": the (nao^4) tensor of grid.py:65; "cholesky": pivoted Cholesky vectors only.
     world > 1 (torch.distributed initialised): the Cholesky factorisation -- the one expensive step, host integral columns
@@ -60,7 +73,9 @@ def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=Tr
     rank receives only its slice of the vectors (grid_shard.scatter_vectors); `chol_range` records the slice.
     point_charges: (n, 4) x, y, z (bohr), q -- electrostatic embedding (external_charges): Hcore = T + V + V_ext and E_nuc
     gains the nuclei--charges repulsion, so every SCF loop runs in the field of the charges unchanged; their interaction
-    among themselves is not included.  Every rank computes V_ext itself (deterministic: nothing is broadcast)."""
+    among themselves is not included.  Every rank computes V_ext itself (deterministic: nothing is broadcast).
+    efield: (Fx, Fy, Fz) in a.u. -- a uniform external electric field (uniform_field): Hcore gains sum_k F_k D_k and E_nuc
+    -sum_A Z_A F.R_A, so every SCF loop, the fused tail included, runs in the field with no other change."""
     if not os.path.exists(atom_path):
         cand = os.path.join(DATA_DIR, atom_path if atom_path.endswith(".xyz") else atom_path + ".xyz")
         if os.path.exists(cand):
@@ -110,8 +125,15 @@ def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=Tr
     else:
         raise ValueError(f"eri_mode {eri_mode!r}: expected 'dense' or 'cholesky'")
     if point_charges is None:
-        return SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V, eri,
-                         integrals.energy_nuc(symbols, xyz), nocc, nelec, chol, chol_range)
-    pc, V_ext, E_ext = external_charges(symbols, xyz, shells, point_charges, device)
-    return SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V + V_ext, eri,
-                     integrals.energy_nuc(symbols, xyz) + E_ext, nocc, nelec, chol, chol_range, pc, V_ext, E_ext)
+        inp = SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V, eri,
+                        integrals.energy_nuc(symbols, xyz), nocc, nelec, chol, chol_range)
+    else:
+        pc, V_ext, E_ext = external_charges(symbols, xyz, shells, point_charges, device)
+        inp = SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V + V_ext, eri,
+                        integrals.energy_nuc(symbols, xyz) + E_ext, nocc, nelec, chol, chol_range, pc, V_ext, E_ext)
+    if efield is not None:
+        F, V_F, E_F = uniform_field(symbols, xyz, shells, efield)
+        inp.Hcore = inp.Hcore + V_F
+        inp.E_nuc = inp.E_nuc + E_F
+        inp.efield = F
+    return inp

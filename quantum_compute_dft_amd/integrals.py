@@ -50,6 +50,8 @@ def _load():
         dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
         L.qc_int1e.restype = ctypes.c_int
         L.qc_int1e.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp]
+        L.qc_dipole.restype = ctypes.c_int
+        L.qc_dipole.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, dp, dp]
         L.qc_int2e.restype = ctypes.c_int
         L.qc_int2e.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, dp]
         L.qc_eri_open.restype = ctypes.c_void_p
@@ -101,6 +103,18 @@ def int1e(shells, symbols, atom_xyz):
     if rc != 0:
         raise ValueError("integrals: angular momentum above f is not supported")
     return S, T, V
+
+
+def dipole(shells, origin=(0.0, 0.0, 0.0)):
+    """D[k] = <mu| (r - origin)_k |nu> as a (3, nao, nao) array (bohr), s-f shells."""
+    keep, p = _args(shells)
+    n = shells.nao
+    D = np.zeros((3, n, n))
+    o = np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+    dp = ctypes.POINTER(ctypes.c_double)
+    if _load().qc_dipole(shells.nshell, *p, n, o.ctypes.data_as(dp), D.ctypes.data_as(dp)) != 0:
+        raise ValueError("integrals: angular momentum above f is not supported")
+    return D
 
 
 def int2e(shells):

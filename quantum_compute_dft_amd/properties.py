@@ -1,9 +1,23 @@
 """Properties of a converged density.  Electrostatic potential and electric field at arbitrary points and the forces on
 the external point charges of an embedded run, on the device where one is in use (csrc/point_coulomb.hip through
-integrals.point_coulomb / integrals.point_field)."""
+integrals.point_coulomb / integrals.point_field); the dipole moment from the host dipole integrals."""
 import numpy as np
 
 from . import basis, integrals
+
+
+DEBYE_PER_AU = 2.541746473   # 1 e bohr in debye (CODATA 2018)
+
+
+def dipole_moment(inp, dm, origin=(0.0, 0.0, 0.0), debye=False):
+    """mu_k = sum_A Z_A (R_A - origin)_k - tr(dm D_k), D = integrals.dipole(shells, origin): (3,) in e bohr, or in debye.
+    Independent of the origin for a neutral molecule.  For a variational functional (option quirks = 0) and a
+    converged density mu = -dE/dF of a run in the uniform field F (inputs.build(..., efield=F))."""
+    o = np.asarray(origin, dtype=np.float64).reshape(3)
+    z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
+    D = integrals.dipole(inp.shells, o)
+    mu = z @ (np.asarray(inp.atom_xyz, dtype=np.float64) - o) - np.einsum("kij,ji->k", D, np.asarray(dm, dtype=np.float64))
+    return mu * DEBYE_PER_AU if debye else mu
 
 
 def electrostatic_potential(inp, dm, points, device="cpu", electronic_only=False):

@@ -528,6 +528,62 @@ class HipBackend:
         return self.d_J, (self.d_K if self._want_k else None)
 
 
+    # ---- linear response (response.polarizability): one rank, resident AO planes ------------------------------
+    def _response_check(self):
+        if self.world > 1:
+            raise ValueError("linear response (fxc / CPKS) runs on one rank: the grid of this backend is sharded over several")
+        if self.ao_mode != "resident":
+            raise ValueError("linear response (fxc / CPKS) needs resident AO planes (--ao resident), not --ao direct")
+
+    def ground_state_parts(self, dm, cocc, want_k):
+        """(J, K or None, Vxc_raw) of a density, as numpy arrays: the parts of its Fock matrix."""
+        self._response_check()
+        self.set_state(dm, cocc)
+        J, K, _, V, _, _ = self.fock_parts(want_k)
+        return J, K, V
+
+    def response_prepare(self, dm0, cocc=None):
+        """DFT_FxcPrepare at dm0 (through cocc, dm0 = cocc cocc^T, when given and the loop sweeps that way)."""
+        self._response_check()
+        t = self.torch
+        self._d_dm0 = t.as_tensor(np.ascontiguousarray(dm0), dtype=t.float64, device=self.dev)
+        d_c = t.as_tensor(np.ascontiguousarray(cocc), dtype=t.float64, device=self.dev) if (cocc is not None and self.xc_occ) else None
+        self.solver.fxc_prepare(self.ngrid, self.nao, self._d_dm0, self.d_ao, self.d_w, self.d_gr, d_c, 0 if d_c is None else d_c.shape[1])
+        n = self.nao
+        self._r_dm1 = t.zeros((n, n), dtype=t.float64, device=self.dev)
+        self._r_out = t.zeros((4, n, n), dtype=t.float64, device=self.dev)      # J | K | V1 | K of the second factor
+
+    def response_parts(self, dm1, want_k, factors=None):
+        """(J, K or None, V1_raw) of a symmetric perturbation dm1, as numpy arrays.  Dense ERI: DFT_ComputeJK as it
+        stands.  Cholesky vectors: J from dm1, and K by linearity from two DFT_ComputeJKFactorized calls -- with
+        dm1 = A B^T + B A^T (`factors` = (A, B), what a CPKS step has) and c+- = (A +- B)/sqrt(2),
+        K[dm1] = K[c+ c+^T] - K[c- c-^T]."""
+        self._response_check()
+        t, n = self.torch, self.nao
+        self._r_dm1.copy_(t.as_tensor(np.ascontiguousarray(dm1), dtype=t.float64))
+        d_J, d_K, d_V, d_K2 = self._r_out
+        if self.d_chol is not None:
+            naux = self.d_chol.shape[0]
+            self.solver.compute_jk_factorized(n, naux, 0, self.d_chol, self._r_dm1, None, d_J, None)
+            if want_k:
+                if factors is None:
+                    raise ValueError("response_parts: K from Cholesky vectors needs dm1 = A B^T + B A^T as factors=(A, B)")
+                A, B = (np.asarray(x, dtype=np.float64) for x in factors)
+                for sgn, out in ((1.0, d_K), (-1.0, d_K2)):
+                    c = t.as_tensor(np.ascontiguousarray((A + sgn * B) / np.sqrt(2.0)), dtype=t.float64, device=self.dev)
+                    self.solver.compute_jk_factorized(n, naux, c.shape[1], self.d_chol, None, c, None, out)
+                    t.cuda.synchronize()     # `c` is released when the loop moves on
+                d_K.sub_(d_K2)
+        elif want_k:
+            self.solver.compute_jk(n, self.d_eri, self._r_dm1, d_J, d_K)
+        else:
+            self.solver.compute_coulomb(n, self.d_eri, self._r_dm1, d_J)
+        self.solver.fxc_apply(self.ngrid, n, self._r_dm1, self.d_ao, d_V, self.d_gr)
+        self.torch.cuda.synchronize()
+        h = self._r_out.cpu().numpy()
+        return h[0], (h[1] if want_k else None), h[2]
+
+
 def run_scf(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, log=print):
     from .hostinfo import blas_threads
     # host LAPACK/BLAS never on every visible core (256 on a 16-core share: ~90 ms stalls); below 400

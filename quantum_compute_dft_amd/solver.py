@@ -129,6 +129,10 @@ class DFTSolverWrapper:
         L.DFT_CreateSolverMix.restype = ctypes.c_void_p
         L.DFT_GetMix.argtypes = [ctypes.c_void_p, dp, ctypes.c_int]
         L.DFT_GetMix.restype = ctypes.c_int
+        L.DFT_FxcPrepare.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _u64, _u64, _u64, _u64, _u64]
+        L.DFT_FxcPrepare.restype = ctypes.c_int
+        L.DFT_FxcApply.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64]
+        L.DFT_FxcApply.restype = ctypes.c_int
 
         if self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
@@ -250,6 +254,23 @@ class DFTSolverWrapper:
         keep, args = self._shell_args(shells)
         rc = self.lib.DFT_ComputeXCDirect(self.solver, int(ngrid), *args, _u64(_ptr(d_coords)), _u64(_ptr(d_weights)),
                                           _u64(_ptr(d_dm)), _u64(_ptr(d_vxc)), _u64(_ptr(d_exc)), int(chunk_points))
+        self._check()
+        return rc
+
+    def fxc_prepare(self, ngrid, nao, d_dm0, d_ao, d_weights, d_ao_grad=None, d_cocc=None, nocc=0):
+        """First half of the linear response of Vxc (DFT_FxcPrepare): the ground-state density step and the derivative
+        table of the functional, kept in the solver.  d_cocc (nao, nocc) with dm0 = cocc cocc^T takes the occupied-orbital
+        density step under compute_xc_occ's rule; d_dm0 may then be None."""
+        rc = self.lib.DFT_FxcPrepare(self.solver, int(ngrid), int(nao), int(nocc), _u64(_ptr(d_cocc)), _u64(_ptr(d_dm0)),
+                                     _u64(_ptr(d_ao)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_weights)))
+        self._check()
+        return rc
+
+    def fxc_apply(self, ngrid, nao, d_dm1, d_ao, d_v1, d_ao_grad=None):
+        """V1 = d/dt compute_xc(dm0 + t dm1).vxc at t = 0 into d_v1 (DFT_FxcApply), in the convention compute_xc writes
+        Vxc in; asynchronous on the solver's stream.  Any number of calls after one fxc_prepare."""
+        rc = self.lib.DFT_FxcApply(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm1)), _u64(_ptr(d_ao)),
+                                   _u64(_ptr(d_ao_grad)), _u64(_ptr(d_v1)))
         self._check()
         return rc
 
