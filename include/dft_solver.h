@@ -190,6 +190,27 @@ int DFT_ComputeJKFactorized(XCSolver *solver, int nao, int naux, int nocc,
                             unsigned long long d_J_ptr,
                             unsigned long long d_K_ptr);
 
+/* Response J and K from the same vectors for nvec trial densities that share their left factor,
+ *     D_k = A B_k^T + B_k A^T,   d_a_ptr: A (nao, nocc),  d_b_ptr: B (nvec, nao, nocc), f64 C-order
+ * (what an excitation or CPKS solver has: A the occupied orbitals, B_k a trial vector in the AO basis):
+ *     d_J_ptr (nvec, nao, nao) or 0:  J_k = sum_P (L_P : D_k) L_P
+ *     d_M_ptr (nvec, nao, nao) or 0:  M_k = sum_P (L_P A)(L_P B_k)^T, NOT symmetrised:
+ *         K[D]_mn = sum_ls (ml|ns) D_ls  gives  K[A B_k^T +- B_k A^T] = M_k +- M_k^T,
+ *     so the exchange response of an antisymmetric density, which no combination of
+ *     DFT_ComputeJKFactorized calls expresses, comes from the same M.
+ * Cost: A is half-transformed once per call; L_P : D_k is taken from that half transform, not from L;
+ * J of up to 8 trials takes ONE pass over L (larger nvec: groups of 8); M takes one half transform of
+ * B_k and one fp64-MFMA product per trial.  A trial's J and M are bitwise the same whether it is sent
+ * alone or in a batch.  Both outputs 0: returns 0, nothing is launched.  Asynchronous; returns 0, or -1
+ * for bad sizes (nao, naux, nocc, nvec <= 0) or a null input (DFT_GetLastError).  DFT_GetVersion is
+ * unchanged: look the symbol up. */
+int DFT_ComputeJKFactorizedResponse(XCSolver *solver, int nao, int naux, int nocc, int nvec,
+                                    unsigned long long d_chol_ptr,
+                                    unsigned long long d_a_ptr,
+                                    unsigned long long d_b_ptr,
+                                    unsigned long long d_J_ptr,
+                                    unsigned long long d_M_ptr);
+
 /* AO values (and Cartesian gradients) on the grid: replaces PySCF's
  * dft.numint.eval_ao(mol, coords, deriv=0/1) at grid.py:30,38.
  * Shell table (host pointers, copied to the device on first use / change):

@@ -23,6 +23,7 @@
 #include "ao_kernels.hpp"
 #include "jk_kernels.hpp"
 #include "cd_kernels.hpp"
+#include "cd_response_kernels.hpp"
 #include "xc_big_kernels.hpp"
 #include "xc_ws_kernels.hpp"
 #include "xc_kernels.hpp"
@@ -103,7 +104,7 @@ struct XCSolver {
     hipStream_t cap_stream = nullptr; // recording happens here (the caller's stream may be the null stream, which cannot record)
     unsigned long graph_clock = 0, graph_gen = 0;
     // workspace
-    DevBuf dsym, rho, sigma, grad, coef, partial, slabs, exc, jpart, kpart, shells, msym, cdy, cdc, cdv, ao_ws, vtmp, occ_cp, occ_dm, dmf_lt, dmf_c, dmf_st;
+    DevBuf dsym, rho, sigma, grad, coef, partial, slabs, exc, jpart, kpart, shells, msym, cdy, cdc, cdv, cdy2, cdc2, cdbt, ao_ws, vtmp, occ_cp, occ_dm, dmf_lt, dmf_c, dmf_st;
     int spin_wait = 1; // poll the host-mapped Exc instead of sleeping in hipStreamSynchronize
     int strict_sync = 0; // 1: after the Exc word, also poll the stream until it reports complete (+8-10 us per call)
     double *h_exc = nullptr;   // pinned, host-mapped: the reduce kernel writes Exc here
@@ -743,6 +744,34 @@ long chunks_per_xcd(const XCSolver *s, int npair, long rows, size_t slab_bytes)
     return best_c;
 }
 
+// Yt_P (nocc x nao, leading dimension ldy) = C^T L_P for every P: `c` (nao, nocc) is packed into cp (nao, ldp) first.
+// dot: the tiles also leave the partials of v_P = Yt_P : C^T in vpart (k_gemm_tn's DOT).
+void half_transform(hipStream_t st, int nao, int naux, int nocc, int ldp, int ldy, bool vecL, bool fused_dot,
+                    const double *c, double *cp, const double *L, double *yt, double *vpart)
+{
+    const long n2 = (long)nao * nao;
+    const int nBh = (nao + CD_BN - 1) / CD_BN;
+    hipLaunchKernelGGL(k_pack_cocc, dim3((unsigned)(((long)nao * ldp + 255) / 256)), dim3(256), 0, st, nao, nocc, ldp, c, cp);
+    // Yt_P (nocc x nao) = Cp^T L_P for every P
+#define QCDFT_HALF3(WGM, MI, VL, DOT, NW)                                                                             \
+    hipLaunchKernelGGL((k_gemm_tn<WGM, MI, true, VL, DOT, NW, (WGM == 1 ? 8 : 0), (WGM == 1 ? 4 : 0)>), g, dim3(64 * NW), 0, st, (long)nao, nocc, nao, ldp, nao, \
+                       cp, 0L, L, n2, (long)nao, nBh, npair, 0, yt, ldy, (long)nocc * ldy, 0L, vpart)
+#define QCDFT_HALF(WGM, MI, NW)                                                                                       \
+    do {                                                                                                              \
+        const int nA = (nocc + 64 * WGM - 1) / (64 * WGM), npair = nA * nBh;                                          \
+        dim3 g((unsigned)((long)npair * naux));                                                                       \
+        if (fused_dot) { if (vecL) QCDFT_HALF3(WGM, MI, true, true, NW); else QCDFT_HALF3(WGM, MI, false, true, NW); }   \
+        else           { if (vecL) QCDFT_HALF3(WGM, MI, true, false, NW); else QCDFT_HALF3(WGM, MI, false, false, NW); } \
+    } while (0)
+    if (nocc <= 16) QCDFT_HALF(1, 1, 4);
+    else if (nocc <= 32) QCDFT_HALF(1, 2, 4);
+    else if (nocc <= 48) QCDFT_HALF(1, 3, 4);
+    else if (nocc <= 64) QCDFT_HALF(1, 4, 4);
+    else QCDFT_HALF(2, 4, 8);
+#undef QCDFT_HALF
+#undef QCDFT_HALF3
+}
+
 // J and/or K from Cholesky vectors L (naux, nao, nao), D = dm, dm = cocc cocc^T with cocc (nao, nocc)
 int jk_factorized(XCSolver *s, int nao, int naux, int nocc, const double *L, const double *dm,
                   const double *cocc, double *J, double *K)
@@ -794,25 +823,7 @@ int jk_factorized(XCSolver *s, int nao, int naux, int nocc, const double *L, con
         const bool vecL = (nao % 2 == 0) && (((uintptr_t)L & 15) == 0);
         {
             ScopedTimer t(s, "cd_half");
-            hipLaunchKernelGGL(k_pack_cocc, dim3((unsigned)(((long)nao * ldp + 255) / 256)), dim3(256), 0, st, nao, nocc, ldp, cocc, cp);
-            // Yt_P (nocc x nao) = Cp^T L_P for every P
-#define QCDFT_HALF3(WGM, MI, VL, DOT, NW)                                                                             \
-    hipLaunchKernelGGL((k_gemm_tn<WGM, MI, true, VL, DOT, NW, (WGM == 1 ? 8 : 0), (WGM == 1 ? 4 : 0)>), g, dim3(64 * NW), 0, st, (long)nao, nocc, nao, ldp, nao, \
-                       cp, 0L, L, n2, (long)nao, nBh, npair, 0, yt, ldy, (long)nocc * ldy, 0L, vpart)
-#define QCDFT_HALF(WGM, MI, NW)                                                                                       \
-    do {                                                                                                              \
-        const int nA = (nocc + 64 * WGM - 1) / (64 * WGM), npair = nA * nBh;                                          \
-        dim3 g((unsigned)((long)npair * naux));                                                                       \
-        if (fused_dot) { if (vecL) QCDFT_HALF3(WGM, MI, true, true, NW); else QCDFT_HALF3(WGM, MI, false, true, NW); }   \
-        else           { if (vecL) QCDFT_HALF3(WGM, MI, true, false, NW); else QCDFT_HALF3(WGM, MI, false, false, NW); } \
-    } while (0)
-            if (nocc <= 16) QCDFT_HALF(1, 1, 4);
-            else if (nocc <= 32) QCDFT_HALF(1, 2, 4);
-            else if (nocc <= 48) QCDFT_HALF(1, 3, 4);
-            else if (nocc <= 64) QCDFT_HALF(1, 4, 4);
-            else QCDFT_HALF(2, 4, 8);
-#undef QCDFT_HALF
-#undef QCDFT_HALF3
+            half_transform(st, nao, naux, nocc, ldp, ldy, vecL, fused_dot, cocc, cp, L, yt, vpart);
         }
         {
             ScopedTimer t(s, "cd_k");
@@ -850,6 +861,114 @@ int jk_factorized(XCSolver *s, int nao, int naux, int nocc, const double *L, con
         hipLaunchKernelGGL(k_sym_from_upper, dim3((unsigned)eb), dim3(256), 0, st, nao, J);
     }
     return hip_ok(s, hipGetLastError(), "factorised J/K launch") ? 0 : -1;
+}
+
+// Response J and M of nvec trial densities that share their left factor (DFT_ComputeJKFactorizedResponse):
+//     J_k = J[A B_k^T + B_k A^T],   M_k = sum_P (L_P A)(L_P B_k)^T   (K[A B_k^T +- B_k A^T] = M_k +- M_k^T)
+// A (nao, nocc), B (nvec, nao, nocc).  Cost: ONE half transform of A per call; v[k][P] = L_P : D_k from Yt^A, not from
+// L; one pass over L per group of up to CDR_MAXV trials for J; per trial of M one half transform of B_k and one
+// Yt^A^T Yt^B_k product with every tile live.  No slicing below depends on nvec or on k: a trial's J and M are
+// bitwise the same alone or in any batch.
+int jk_factorized_response(XCSolver *s, int nao, int naux, int nocc, int nvec, const double *L, const double *A,
+                           const double *B, double *J, double *M)
+{
+    s->last_error.clear();
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return -1; }
+    if (nao <= 0 || naux <= 0 || nocc <= 0 || nvec <= 0) {
+        set_error(s, "factorised response J/K: bad sizes nao=%d naux=%d nocc=%d nvec=%d", nao, naux, nocc, nvec);
+        return -1;
+    }
+    if (!L || !A || !B) { set_error(s, "factorised response J/K needs the vectors and both factors"); return -1; }
+    if (!J && !M) return 0;
+    hipStream_t st = s->stream;
+    const long n2 = (long)nao * nao;
+    const size_t nb = (size_t)nao * nocc;                 // doubles of one factor
+    const int nB = (nao + CD_BN - 1) / CD_BN;
+    const int ldp = ((nocc + 15) / 16) * 16, ldy = (nao + 1) & ~1;
+    const long G = (long)naux * nocc;
+    const bool vecL = (nao % 2 == 0) && (((uintptr_t)L & 15) == 0);
+    const size_t ybytes = sizeof(double) * (size_t)G * ldy;
+    const bool fresh = ybytes > s->cdy.cap;
+    if (!reserve(s, s->cdc, sizeof(double) * (size_t)nao * ldp, "hipMalloc(cd cocc)") ||
+        !reserve(s, s->cdy, ybytes, "hipMalloc(cd Yt)"))
+        return -1;
+    double *cpa = (double *)s->cdc.p, *yta = (double *)s->cdy.p;
+    if (fresh && ldy != nao) // the pad column is read (into discarded outputs) but never written
+        if (!hip_ok(s, hipMemsetAsync(yta, 0, s->cdy.cap, st), "memset(cd Yt)")) return -1;
+    {
+        ScopedTimer t(s, "cdr_half");
+        half_transform(st, nao, naux, nocc, ldp, ldy, vecL, false, A, cpa, L, yta, nullptr);
+    }
+    if (J) {
+        const int gmax = std::min(nvec, CDR_MAXV);
+        const int ept = vecL ? 2 : 1;
+        const long eb = (n2 + 256 * ept - 1) / (256 * ept);
+        // slices of vectors so that the pass has >= ~4 workgroups per CU (from nao, naux and the device alone)
+        int nsl = (int)std::max<long>(1, std::min<long>(naux, (4L * s->num_cu + eb - 1) / eb));
+        const int pslice = (naux + nsl - 1) / nsl;
+        nsl = (naux + pslice - 1) / pslice;
+        if (!reserve(s, s->cdv, sizeof(double) * (size_t)naux * gmax, "hipMalloc(cd v)") ||
+            !reserve(s, s->cdbt, sizeof(double) * nb * gmax, "hipMalloc(cd B^T)") ||
+            !reserve(s, s->jpart, sizeof(double) * (size_t)gmax * nsl * n2, "hipMalloc(cd J slabs)"))
+            return -1;
+        double *v = (double *)s->cdv.p, *bt = (double *)s->cdbt.p, *jp = (double *)s->jpart.p;
+        const dim3 gdot((unsigned)naux), gax((unsigned)eb, (unsigned)nsl), gtr((unsigned)((nb + 255) / 256), 1);
+        for (int k0 = 0; k0 < nvec; k0 += CDR_MAXV) {
+            const int nv = std::min(CDR_MAXV, nvec - k0);
+            {
+                ScopedTimer t(s, "cdr_dot");
+                hipLaunchKernelGGL(k_cdr_transpose, dim3(gtr.x, (unsigned)nv), dim3(256), 0, st, nao, nocc, B + (size_t)k0 * nb, bt);
+#define QCDFT_CDR_DOT(NV) case NV: hipLaunchKernelGGL((k_cdr_dot<NV>), gdot, dim3(256), 0, st, nao, nocc, ldy, naux, yta, bt, v); break
+                switch (nv) {
+                    QCDFT_CDR_DOT(1); QCDFT_CDR_DOT(2); QCDFT_CDR_DOT(3); QCDFT_CDR_DOT(4);
+                    QCDFT_CDR_DOT(5); QCDFT_CDR_DOT(6); QCDFT_CDR_DOT(7); QCDFT_CDR_DOT(8);
+                }
+#undef QCDFT_CDR_DOT
+            }
+            ScopedTimer t(s, "cdr_j");
+#define QCDFT_CDR_AXPY(NV)                                                                                                      \
+    case NV:                                                                                                                    \
+        if (vecL) hipLaunchKernelGGL((k_cdr_axpy<NV, true>), gax, dim3(256), 0, st, n2, nao, naux, pslice, nsl, L, v, jp);       \
+        else      hipLaunchKernelGGL((k_cdr_axpy<NV, false>), gax, dim3(256), 0, st, n2, nao, naux, pslice, nsl, L, v, jp);      \
+        break
+            switch (nv) {
+                QCDFT_CDR_AXPY(1); QCDFT_CDR_AXPY(2); QCDFT_CDR_AXPY(3); QCDFT_CDR_AXPY(4);
+                QCDFT_CDR_AXPY(5); QCDFT_CDR_AXPY(6); QCDFT_CDR_AXPY(7); QCDFT_CDR_AXPY(8);
+            }
+#undef QCDFT_CDR_AXPY
+            for (int k = 0; k < nv; ++k) {
+                double *Jk = J + (size_t)(k0 + k) * n2;
+                hipLaunchKernelGGL(k_sum_slabs8, dim3((unsigned)((n2 + 31) / 32)), dim3(256), 0, st, (size_t)n2, nsl, (size_t)n2,
+                                   jp + (size_t)k * nsl * n2, Jk);
+                hipLaunchKernelGGL(k_sym_from_upper, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, nao, Jk);
+            }
+        }
+    }
+    if (M) {
+        const int npair2 = ((nao + 127) / 128) * nB;      // every tile of Yt^A^T Yt^B is live: the product is not symmetric
+        long per_xcd = s->ksplit > 0 ? s->ksplit : chunks_per_xcd(s, npair2, G, sizeof(double) * (size_t)n2);
+        while ((double)((G + 8 * per_xcd - 1) / (8 * per_xcd) + CD_BK) * ldy * 8.0 >= 4294967296.0) per_xcd *= 2; // a chunk of Yt stays below 4 GiB
+        const int nslab = (int)(8 * per_xcd);
+        long chunk = (G + nslab - 1) / nslab;
+        chunk = ((chunk + CD_BK - 1) / CD_BK) * CD_BK;
+        const bool fresh2 = ybytes > s->cdy2.cap;
+        if (!reserve(s, s->cdc2, sizeof(double) * (size_t)nao * ldp, "hipMalloc(cd right factor)") ||
+            !reserve(s, s->cdy2, ybytes, "hipMalloc(cd Yt of the right factor)") ||
+            !reserve(s, s->kpart, sizeof(double) * (size_t)nslab * n2, "hipMalloc(cd K slabs)"))
+            return -1;
+        double *cpb = (double *)s->cdc2.p, *ytb = (double *)s->cdy2.p, *kp = (double *)s->kpart.p;
+        if (fresh2 && ldy != nao)
+            if (!hip_ok(s, hipMemsetAsync(ytb, 0, s->cdy2.cap, st), "memset(cd Yt of the right factor)")) return -1;
+        ScopedTimer t(s, "cdr_m");
+        for (int k = 0; k < nvec; ++k) {
+            half_transform(st, nao, naux, nocc, ldp, ldy, vecL, false, B + (size_t)k * nb, cpb, L, ytb, nullptr);
+            hipLaunchKernelGGL((k_gemm_tn<2, 4, true, true>), dim3((unsigned)(nslab * npair2)), dim3(BG_THREADS), 0, st, G, nao, nao, ldy, ldy,
+                               yta, 0L, ytb, 0L, chunk, nB, npair2, 1, kp, nao, 0L, n2, (double *)nullptr, 0);
+            hipLaunchKernelGGL(k_sum_slabs8, dim3((unsigned)((n2 + 31) / 32)), dim3(256), 0, st, (size_t)n2, nslab, (size_t)n2, kp,
+                               M + (size_t)k * n2);
+        }
+    }
+    return hip_ok(s, hipGetLastError(), "factorised response J/K launch") ? 0 : -1;
 }
 
 // dm = L L^T on the device (dm_factor.hip): the rank (>= 1) with L (nao, rank) C-order in `out` (nao * max_rank doubles),
@@ -1121,7 +1240,7 @@ void DFT_DestroySolver(XCSolver *s)
         if (s->cap_stream) (void)hipStreamDestroy(s->cap_stream);
         DevBuf *bufs[] = {&s->dsym, &s->rho, &s->sigma, &s->grad, &s->coef, &s->partial,
                           &s->slabs, &s->exc, &s->jpart, &s->kpart, &s->shells, &s->msym,
-                          &s->cdy, &s->cdc, &s->cdv, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0};
+                          &s->cdy, &s->cdc, &s->cdv, &s->cdy2, &s->cdc2, &s->cdbt, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0};
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
@@ -1437,6 +1556,17 @@ int DFT_ComputeJKFactorized(XCSolver *s, int nao, int naux, int nocc, unsigned l
     s->n_timed = 0;
     return jk_factorized(s, nao, naux, nocc, (const double *)d_chol, (const double *)d_dm,
                          (const double *)d_cocc, (double *)d_J, (double *)d_K);
+}
+
+int DFT_ComputeJKFactorizedResponse(XCSolver *s, int nao, int naux, int nocc, int nvec, unsigned long long d_chol,
+                                    unsigned long long d_a, unsigned long long d_b, unsigned long long d_J,
+                                    unsigned long long d_M)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    s->n_timed = 0;
+    return jk_factorized_response(s, nao, naux, nocc, nvec, (const double *)d_chol, (const double *)d_a,
+                                  (const double *)d_b, (double *)d_J, (double *)d_M);
 }
 
 int DFT_FactorDensity(XCSolver *s, int nao, unsigned long long d_dm, int max_rank, double tol,

@@ -1,0 +1,177 @@
+"""Singlet excitation energies and oscillator strengths of a closed-shell state: TDDFT (the full coupled problem) and
+its Tamm-Dancoff approximation, by a reduced-space iteration on top of a response backend.
+
+Canonical orbitals Co, Cv and gaps D_ia = e_a - e_i come from one eigh(F, S) of the converged Fock matrix, as in
+response.polarizability.  For a trial Z (nocc, nvirt) with A = Co, B = 2 Cv Z^T and D+- = A B^T +- B A^T
+
+    (A+B) Z = D o Z + Co^T ( J[D+] + (V1 + V1^T)/2 [D+] - c_hf/2 K[D+] ) Cv
+    (A-B) Z = D o Z - c_hf/2 Co^T K[D-] Cv                  (= D o Z without exact exchange: no K is requested)
+    K[D]_mn = sum_ls (ml|ns) D_ls,    K[D+-] = M +- M^T,    M = K[A B^T]
+
+J, M and V1 of all trials of an iteration come from ONE backend.excitation_parts call (scf.HipBackend on the device:
+DFT_ComputeJKFactorizedResponse or DFT_ComputeJK, and DFT_FxcApply; response.HostResponse on the host).  (A+B) is the
+operator response.polarizability applies: the sum over states 2 sum_n mu_n mu_n^T / w_n of the full spectrum equals
+its alpha.  TDA solves A X = w X with A = ((A+B) + (A-B))/2 and X^T X = 1; TDDFT solves
+(A-B)(A+B)(X+Y) = w^2 (X+Y) with (X+Y)^T (X-Y) = 1.  Transition dipole mu_n = sqrt(2) sum_ia (Co^T D_k Cv)_ia (X+Y)_ia,
+oscillator strength f_n = 2/3 w_n |mu_n|^2.  With option quirks = 1 the operator is the response of the shipped
+formulas, the SCF equations the loop actually solves -- the choice the polarizability made.
+"""
+import numpy as np
+from scipy.linalg import eigh
+
+from . import functionals, integrals
+
+HARTREE_EV = 27.211386245988
+NM_PER_HARTREE = 45.56335252907954        # h c / (1 Ha) in nm
+_PBE_C = functionals.COMPONENTS.index("pbe_c")
+
+
+class ResponseOperators:
+    """(A+B) and (A-B) of a converged closed-shell state as maps on (nvec, nocc, nvirt) arrays: `apply`.  Fields: Co,
+    Cv, gap (nocc, nvirt), dip = Co^T D_k Cv (3, nocc, nvirt), c_hf, builds (trial vectors applied so far)."""
+
+    def __init__(self, inp, scf_result, backend, functional=None):
+        f = functionals.resolve(functional if functional is not None else backend.functional)
+        quirks = bool(getattr(backend, "quirks", True))
+        if quirks and f.weight_vector()[_PBE_C] != 0.0:
+            raise ValueError("excitations: with quirks = 1 the shipped PBE correlation potential is not the derivative of "
+                             "its energy and the response operator is not symmetric; run with --quirks 0")
+        self.c_hf, self.want_k = f.c_hf, f.c_hf != 0.0
+        S, nocc = inp.S, inp.nocc
+        dm0 = np.ascontiguousarray(scf_result["dm"], dtype=np.float64)
+        e0, C0 = eigh(S @ dm0 @ S, S)
+        cocc0 = np.ascontiguousarray(C0[:, ::-1][:, :nocc] * np.sqrt(np.maximum(e0[::-1][:nocc], 0.0)))
+        J, K, Vraw = backend.ground_state_parts(dm0, cocc0, self.want_k)
+        F = inp.Hcore + J + 0.5 * (Vraw + Vraw.T) - (0.5 * self.c_hf * K if self.want_k else 0.0)
+        e, C = eigh(F, S)
+        self.Co, self.Cv = np.ascontiguousarray(C[:, :nocc]), np.ascontiguousarray(C[:, nocc:])
+        self.gap = np.ascontiguousarray(e[None, nocc:] - e[:nocc, None])
+        if self.gap.size == 0 or self.gap.min() <= 1e-6:
+            raise ValueError("excitations: no gap between the occupied and the virtual orbitals")
+        backend.response_prepare(dm0, cocc0)
+        self.backend = backend
+        self.dip = np.einsum("mi,kmn,na->kia", self.Co, integrals.dipole(inp.shells), self.Cv)
+        self.builds = 0
+
+    def apply(self, Z):
+        """((A+B) Z_k, (A-B) Z_k) for Z (nvec, nocc, nvirt), through one excitation_parts call."""
+        Z = np.asarray(Z, dtype=np.float64)
+        Bs = np.ascontiguousarray(2.0 * np.einsum("na,kia->kni", self.Cv, Z))
+        J, M, V1 = self.backend.excitation_parts(self.Co, Bs, self.want_k)
+        self.builds += Z.shape[0]
+        G = J + 0.5 * (V1 + V1.transpose(0, 2, 1))
+        dz = self.gap[None] * Z
+        if not self.want_k:
+            return dz + np.einsum("mi,kmn,na->kia", self.Co, G, self.Cv), dz
+        Mt = M.transpose(0, 2, 1)
+        plus = dz + np.einsum("mi,kmn,na->kia", self.Co, G - 0.5 * self.c_hf * (M + Mt), self.Cv)
+        minus = dz - 0.5 * self.c_hf * np.einsum("mi,kmn,na->kia", self.Co, M - Mt, self.Cv)
+        return plus, minus
+
+
+def _orthonormal_additions(basis, cands, drop=1e-8):
+    """Rows of `cands`, orthogonalised against the rows of `basis` and each other (Gram-Schmidt, twice), normalised;
+    a candidate that loses all but `drop` of its norm is left out."""
+    out = []
+    for c in cands:
+        n0 = np.linalg.norm(c)
+        if n0 == 0.0:
+            continue
+        c = c / n0
+        for _ in range(2):
+            c = c - basis.T @ (basis @ c)
+            for o in out:
+                c = c - o * (o @ c)
+        n = np.linalg.norm(c)
+        if n > drop:
+            out.append(c / n)
+    return np.array(out).reshape(len(out), basis.shape[1])
+
+
+def _sqrt_spd(M, what):
+    w, U = np.linalg.eigh(M)
+    if w[0] <= 0.0:
+        raise ValueError(f"excitations: the reduced {what} is not positive definite (lowest eigenvalue {w[0]:.3e}): "
+                         "the reference state is unstable")
+    return (U * np.sqrt(w)) @ U.T, (U / np.sqrt(w)) @ U.T
+
+
+def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=None):
+    """The lowest `nroots` roots of `ops` (a ResponseOperators): the dict `excitations` returns."""
+    nocc, nvirt = ops.gap.shape
+    N = nocc * nvirt
+    if not 1 <= nroots <= N:
+        raise ValueError(f"excitations: nroots = {nroots}, but there are {N} occupied-virtual pairs")
+    gap = ops.gap.reshape(-1)
+    max_space = min(N, max_space if max_space else max(8 * nroots, 40))
+    max_space = max(max_space, min(N, 3 * nroots))           # room for a collapsed space (two vectors a root) to grow
+    b = np.zeros((0, N))
+    new = np.zeros((min(N, 2 * nroots), N))
+    new[np.arange(new.shape[0]), np.argsort(gap, kind="stable")[:new.shape[0]]] = 1.0
+    Pb, Qb = np.zeros((0, N)), np.zeros((0, N))
+    builds0 = ops.builds
+    converged, it = False, 0
+    for it in range(1, max_iter + 1):
+        P, Q = ops.apply(new.reshape(-1, nocc, nvirt))
+        b = np.vstack([b, new]); Pb = np.vstack([Pb, P.reshape(-1, N)]); Qb = np.vstack([Qb, Q.reshape(-1, N)])
+        Mp, Mm = b @ Pb.T, b @ Qb.T
+        Mp, Mm = 0.5 * (Mp + Mp.T), 0.5 * (Mm + Mm.T)
+        if tda:
+            w, T = np.linalg.eigh(0.5 * (Mp + Mm))
+            if w[0] <= 0.0:
+                raise ValueError(f"excitations: the lowest Tamm-Dancoff root is {w[0]:.3e} Ha: the reference state is unstable")
+            w, R, L = w[:nroots], T[:, :nroots], T[:, :nroots]                 # X+Y = X-Y = X
+            res1 = R.T @ (0.5 * (Pb + Qb)) - w[:, None] * (R.T @ b)
+            res2 = res1
+        else:
+            Sm, Smi = _sqrt_spd(Mm, "A-B")
+            _sqrt_spd(Mp, "A+B")
+            w2, T = np.linalg.eigh(Sm @ Mp @ Sm)
+            w = np.sqrt(w2[:nroots])
+            R = (Sm @ T[:, :nroots]) / np.sqrt(w)                               # X+Y in the basis
+            L = (Smi @ T[:, :nroots]) * np.sqrt(w)                              # X-Y
+            res1 = R.T @ Pb - w[:, None] * (L.T @ b)
+            res2 = L.T @ Qb - w[:, None] * (R.T @ b)
+        rn = np.maximum(np.linalg.norm(res1, axis=1), np.linalg.norm(res2, axis=1))
+        if log:
+            log(f"excitations iteration {it}: space {b.shape[0]}, lowest root {w[0]:.8f} Ha, largest residual {rn.max():.2e}")
+        if np.all(rn <= tol):
+            converged = True
+            break
+        if it == max_iter:
+            break
+        cands = []
+        for n in np.nonzero(rn > tol)[0]:
+            den = gap - w[n]
+            den = np.where(np.abs(den) < 1e-4, 1e-4, den)
+            cands.append(res1[n] / den)
+            if not tda:
+                cands.append(res2[n] / den)
+        if b.shape[0] + len(cands) > max_space:
+            # collapse onto the current roots: linear combinations of the basis, so the products follow without a build
+            C = np.linalg.qr(np.hstack([R, L]) if not tda else R)[0]
+            b, Pb, Qb = C.T @ b, C.T @ Pb, C.T @ Qb
+        new = _orthonormal_additions(b, cands)
+        if new.shape[0] == 0:
+            break                                                               # nothing left to add: the space is exhausted
+    xpy, xmy = R.T @ b, L.T @ b
+    mu = np.sqrt(2.0) * np.einsum("kx,nx->nk", ops.dip.reshape(3, N), xpy)
+    return {"energies": w, "oscillator_strengths": (2.0 / 3.0) * w * np.einsum("nk,nk->n", mu, mu),
+            "transition_dipoles": mu, "xpy": xpy.reshape(-1, nocc, nvirt), "xmy": xmy.reshape(-1, nocc, nvirt),
+            "residuals": rn, "iterations": it, "sigma_builds": ops.builds - builds0, "converged": converged,
+            "method": "tda" if tda else "tddft"}
+
+
+def excitations(inp, scf_result, backend, functional=None, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=None):
+    """The lowest `nroots` singlet excitations of the converged closed-shell state `scf_result` (scf.run_scf) by a
+    Davidson-type iteration on one orthonormal trial basis b: every iteration applies (A+B) and (A-B) to the new vectors
+    through one backend.excitation_parts call, solves the reduced problem M-^(1/2) M+ M-^(1/2) T = w^2 T (TDA: the
+    symmetric b^T A b), and extends b by the residuals (A+B)(X+Y) - w (X-Y) and (A-B)(X-Y) - w (X+Y) divided by
+    D - w, starting from unit vectors at the smallest gaps; a root is converged when both residual 2-norms are <= tol.
+    The space is collapsed onto the current roots when it would exceed `max_space`.
+
+    Returns {"energies" (Ha, ascending), "oscillator_strengths", "transition_dipoles" (nroots, 3), "xpy", "xmy"
+    (nroots, nocc, nvirt; equal for TDA), "residuals", "iterations", "sigma_builds", "converged", "method"}.
+    ValueError: nroots above nocc nvirt, no gap, a reduced A+B or A-B that is not positive definite (an unstable
+    reference), or quirks = 1 with PBE correlation (a non-symmetric operator; use quirks 0)."""
+    return solve(ResponseOperators(inp, scf_result, backend, functional), nroots, tda, tol, max_iter, max_space, log)

@@ -141,6 +141,7 @@ class HostResponse:
         if inp.eri is None:
             raise ValueError("HostResponse needs the dense ERI")
         self.inp, self.functional, self.scf, self.q = inp, functional, scf_backend, quirks
+        self.quirks = bool(quirks)
         self.ao, self.gr, self.fxc = ao, ao_grad, None
 
     def ground_state_parts(self, dm, cocc, want_k):
@@ -156,6 +157,16 @@ class HostResponse:
         J = np.einsum("ijkl,kl->ij", self.inp.eri, dm1)
         K = np.einsum("ikjl,kl->ij", self.inp.eri, dm1) if want_k else None
         return J, K, self.fxc.apply(dm1)
+
+    def excitation_parts(self, A, Bs, want_k):
+        """(J, M or None, V1), each (nvec, nao, nao), of the trials D_k = A B_k^T + B_k A^T: J[D_k], the unsymmetrised
+        M_k = K[A B_k^T] (K[D]_mn = sum_ls (ml|ns) D_ls, so K[A B_k^T +- B_k A^T] = M_k +- M_k^T) and V1[D_k]."""
+        A, Bs = np.asarray(A, dtype=np.float64), np.asarray(Bs, dtype=np.float64)
+        AB = np.einsum("mi,kni->kmn", A, Bs)
+        Dp = AB + AB.transpose(0, 2, 1)
+        J = np.einsum("ijkl,nkl->nij", self.inp.eri, Dp)
+        M = np.einsum("ikjl,nkl->nij", self.inp.eri, AB) if want_k else None
+        return J, M, np.stack([self.fxc.apply(d) for d in Dp])
 
 
 def _gmres(apply_a, b, tol, max_iter):

@@ -331,6 +331,7 @@ class HipBackend:
         self.functional = functional.upper()
         self.solver = DFTSolverWrapper(lib_path or library_path(), functional)   # any name or expression of functionals.resolve()
         self.solver.set_option("quirks", 1 if quirks else 0)
+        self.quirks = bool(quirks)
         t0 = time.time()
         self.rank, self.world = rank, world
         nao = inp.shells.nao
@@ -581,6 +582,37 @@ class HipBackend:
         self.solver.fxc_apply(self.ngrid, n, self._r_dm1, self.d_ao, d_V, self.d_gr)
         self.torch.cuda.synchronize()
         h = self._r_out.cpu().numpy()
+        return h[0], (h[1] if want_k else None), h[2]
+
+    def excitation_parts(self, A, Bs, want_k):
+        """(J, M or None, V1_raw), each (nvec, nao, nao) as numpy arrays, of the trials D_k = A B_k^T + B_k A^T with A
+        (nao, nocc) and Bs (nvec, nao, nocc): J[D_k], the unsymmetrised M_k = K[A B_k^T] -- K[D]_mn = sum_ls (ml|ns) D_ls,
+        so K[A B_k^T +- B_k A^T] = M_k +- M_k^T, the antisymmetric combination included -- and V1[D_k].  Cholesky
+        vectors: ONE DFT_ComputeJKFactorizedResponse call for all trials.  Dense ERI: DFT_ComputeJK per trial (its K is
+        the literal einsum, for any dm).  One DFT_FxcApply per trial either way.  After response_prepare."""
+        self._response_check()
+        t, n = self.torch, self.nao
+        f64 = t.float64
+        d_A = t.as_tensor(np.ascontiguousarray(A, dtype=np.float64), dtype=f64, device=self.dev)
+        d_B = t.as_tensor(np.ascontiguousarray(Bs, dtype=np.float64), dtype=f64, device=self.dev)
+        if d_B.dim() != 3 or d_A.dim() != 2 or d_A.shape[0] != n or tuple(d_B.shape[1:]) != tuple(d_A.shape):
+            raise ValueError(f"excitation_parts: A (nao, nocc) and Bs (nvec, nao, nocc) expected, got {tuple(d_A.shape)} and {tuple(d_B.shape)}")
+        nvec, nocc = d_B.shape[0], d_A.shape[1]
+        out = t.zeros((3, nvec, n, n), dtype=f64, device=self.dev)                   # J | M | V1
+        AB = t.matmul(d_A.unsqueeze(0), d_B.transpose(1, 2))                           # A B_k^T
+        Dp = (AB + AB.transpose(1, 2)).contiguous()
+        if self.d_chol is not None:
+            self.solver.compute_jk_factorized_response(n, self.d_chol.shape[0], nocc, nvec, self.d_chol, d_A, d_B,
+                                                       out[0], out[1] if want_k else None)
+        else:
+            for k in range(nvec):
+                self.solver.compute_coulomb(n, self.d_eri, Dp[k], out[0, k])
+                if want_k:
+                    self.solver.compute_jk(n, self.d_eri, AB[k], None, out[1, k])
+        for k in range(nvec):
+            self.solver.fxc_apply(self.ngrid, n, Dp[k], self.d_ao, out[2, k], self.d_gr)
+        t.cuda.synchronize()
+        h = out.cpu().numpy()
         return h[0], (h[1] if want_k else None), h[2]
 
 

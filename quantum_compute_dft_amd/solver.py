@@ -103,6 +103,9 @@ class DFTSolverWrapper:
         L.DFT_ComputeJKFactorized.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               _u64, _u64, _u64, _u64, _u64]
         L.DFT_ComputeJKFactorized.restype = ctypes.c_int
+        L.DFT_ComputeJKFactorizedResponse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      _u64, _u64, _u64, _u64, _u64]
+        L.DFT_ComputeJKFactorizedResponse.restype = ctypes.c_int
         L.DFT_FactorDensity.argtypes = [ctypes.c_void_p, ctypes.c_int, _u64, ctypes.c_int, ctypes.c_double, _u64,
                                         ctypes.POINTER(ctypes.c_double)]
         L.DFT_FactorDensity.restype = ctypes.c_int
@@ -208,6 +211,16 @@ class DFTSolverWrapper:
         d_J / d_K (and the input only the other one needs) may be None."""
         rc = self.lib.DFT_ComputeJKFactorized(self.solver, int(nao), int(naux), int(nocc), _u64(_ptr(d_chol)),
                                               _u64(_ptr(d_dm)), _u64(_ptr(d_cocc)), _u64(_ptr(d_J)), _u64(_ptr(d_K)))
+        self._check()
+        return rc
+
+    def compute_jk_factorized_response(self, nao, naux, nocc, nvec, d_chol, d_a, d_b, d_J, d_M):
+        """Response J and M of nvec trial densities D_k = A B_k^T + B_k A^T from Cholesky vectors
+        (DFT_ComputeJKFactorizedResponse): d_a (nao, nocc), d_b (nvec, nao, nocc); d_J (nvec, nao, nao) receives J[D_k],
+        d_M (nvec, nao, nao) the unsymmetrised M_k with K[A B_k^T +- B_k A^T] = M_k +- M_k^T.  Either output may be None.
+        One half transform of A and, for J, one pass over the vectors per eight trials, whatever nvec."""
+        rc = self.lib.DFT_ComputeJKFactorizedResponse(self.solver, int(nao), int(naux), int(nocc), int(nvec), _u64(_ptr(d_chol)),
+                                                      _u64(_ptr(d_a)), _u64(_ptr(d_b)), _u64(_ptr(d_J)), _u64(_ptr(d_M)))
         self._check()
         return rc
 
