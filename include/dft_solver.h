@@ -287,6 +287,31 @@ int DFT_FxcPrepare(XCSolver *solver, long long ngrid, int nao, int nocc, unsigne
 int DFT_FxcApply(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm1_ptr, unsigned long long d_ao_ptr,
                  unsigned long long d_ao_grad_ptr, unsigned long long d_v1_ptr);
 
+/* The same two halves for the response tables of the SPIN-RESOLVED energy bodies (csrc/xc_spin_functionals.hpp), at the
+ * closed-shell ground state dm0.  kind 1, triplet: with dm_alpha, dm_beta = dm0/2 +- t dm1/2, V1 is d/dt of the
+ * alpha-spin XC potential matrix at t = 0 -- (V1 + V1^T)/2 is that derivative of the symmetric matrix -- in the
+ * conventions of DFT_FxcApply for the solver's type (one-sided for SOLVER_GGA and SOLVER_MIX, M + M^T with the halved
+ * table for SOLVER_B3LYP, symmetric for SOLVER_LDA).  kind 2, singlet: the same bodies along dm_alpha = dm_beta =
+ * (dm0 + t dm1)/2, which is DFT_FxcApply's V1 at "quirks" = 0 to rounding.  The tables are second derivatives of the
+ * ENERGY (forward mode of second order through the energy statements): they do not depend on option "quirks", and
+ * DFT_SetOption("quirks") does not invalidate them.  At "quirks" = 1 the ground state solves the shipped potentials of
+ * vwn5_c and pbe_c, which are not the derivatives of their energies; a caller that needs the response of the equations
+ * it solved sets "quirks" = 0 for those components.
+ *
+ * DFT_FxcPrepareSpin runs the density step of DFT_FxcPrepare (same arguments, same rule for d_cocc) and fills the slot
+ * of `kind`: its own table and its own grad rho0, so the two Prepare entries and the Apply entries of every kind
+ * interleave freely, at the same or at different dm0, and a DFT_FxcPrepare table is never disturbed.
+ * DFT_FxcApplyKind is DFT_FxcApply with the table chosen: kind 0 the DFT_FxcPrepare table, 1 / 2 the slots above; the same
+ * host function, the same kernels ("fxc_coef" and the sweep's contraction and reduce).  Both return 0, or -1 with
+ * DFT_GetLastError (nothing aborts): an unknown kind, Apply before the Prepare of that kind, ngrid or nao differing from
+ * that Prepare's, a null ao_grad on a gradient solver.  Added without a change of DFT_GetVersion (it stays 5): look the
+ * symbols up. */
+int DFT_FxcPrepareSpin(XCSolver *solver, long long ngrid, int nao, int nocc, unsigned long long d_cocc_ptr,
+                       unsigned long long d_dm0_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
+                       unsigned long long d_weights_ptr, int kind);
+int DFT_FxcApplyKind(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm1_ptr, unsigned long long d_ao_ptr,
+                     unsigned long long d_ao_grad_ptr, unsigned long long d_v1_ptr, int kind);
+
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
  * reference builds the whole tensor on the host with PySCF, `mol.intor('int2e')` at grid.py:65).  Device counterpart
@@ -448,7 +473,8 @@ const char *DFT_GetLastError(XCSolver *solver);
 
 /* With option "profile"=1: durations (ms) of the kernels of the last
  * DFT_ComputeXC* call (with option "dm_factor": "dm_factor" and "dm_factor_check" in front) or of the last
- * DFT_FactorDensity, DFT_FxcPrepare ("rho" or "rho_occ", "fxc_table") or DFT_FxcApply ("rho", "fxc_coef", "fxc_vxc",
+ * DFT_FactorDensity, DFT_FxcPrepare ("rho" or "rho_occ", "fxc_table"), DFT_FxcPrepareSpin (the same with
+ * "fxc_table_spin") or DFT_FxcApply / DFT_FxcApplyKind ("rho", "fxc_coef", "fxc_vxc",
  * "fxc_reduce"), in launch order; names[i] (if non-NULL) receives a
  * static string.  Returns the number of entries written (<= max_entries). */
 int DFT_GetTimings(XCSolver *solver, double *ms, const char **names, int max_entries);

@@ -125,6 +125,11 @@ struct XCSolver {
     DevBuf fxc_table, fxc_g0;
     long fxc_ngrid = 0;   // what the table was prepared for (0: nothing prepared, or invalidated)
     int fxc_nao = 0;
+    // DFT_FxcPrepareSpin: one slot per kind (1 triplet, 2 singlet through the spin-resolved bodies), each with its own
+    // table and its own grad rho0, so that prepares at different dm0 and applies of every kind interleave freely.
+    DevBuf fxc_spin_table[2], fxc_spin_g0[2];
+    long fxc_spin_ngrid[2] = {0, 0};
+    int fxc_spin_nao[2] = {0, 0};
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -557,12 +562,19 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
 
 // Linear response of Vxc, first half: the ground-state density step of a sweep (never the one-kernel plan for small
 // bases: that one keeps no density) and the derivative table of the functional at that density.
+// kind 0: the shipped formulas differentiated (DFT_FxcPrepare); 1, 2: the tables of the spin-resolved energy bodies
+// (DFT_FxcPrepareSpin), each in its own slot.
 bool fxc_prepare(XCSolver *s, long ngrid, int nao, int nocc, const double *cocc, const double *dm, const double *ao,
-                 const double *ao_grad, const double *w)
+                 const double *ao_grad, const double *w, int kind = 0)
 {
     s->last_error.clear();
     s->n_timed = 0;
-    s->fxc_ngrid = 0;
+    if (kind < 0 || kind > 2) { set_error(s, "DFT_FxcPrepareSpin: unknown kind %d (1 triplet, 2 singlet through the spin-resolved bodies)", kind); return false; }
+    long &slot_ngrid = kind ? s->fxc_spin_ngrid[kind - 1] : s->fxc_ngrid;
+    int &slot_nao = kind ? s->fxc_spin_nao[kind - 1] : s->fxc_nao;
+    DevBuf &slot_table = kind ? s->fxc_spin_table[kind - 1] : s->fxc_table;
+    DevBuf &slot_g0 = kind ? s->fxc_spin_g0[kind - 1] : s->fxc_g0;
+    slot_ngrid = 0;
     if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
     if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
     const bool gga = s->needs_grad;
@@ -586,12 +598,12 @@ bool fxc_prepare(XCSolver *s, long ngrid, int nao, int nocc, const double *cocc,
     const size_t ng = (size_t)ngrid;
     if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
         !reserve(s, s->rho, sizeof(double) * ng, "hipMalloc(rho)") ||
-        !reserve(s, s->fxc_table, sizeof(double) * ng * (gga ? FXC_PLANES : 1), "hipMalloc(fxc table)"))
+        !reserve(s, slot_table, sizeof(double) * ng * (gga ? FXC_PLANES : 1), "hipMalloc(fxc table)"))
         return false;
     if (gga && (!reserve(s, s->sigma, sizeof(double) * ng, "hipMalloc(sigma)") ||
-                !reserve(s, s->fxc_g0, sizeof(double) * 3 * ng, "hipMalloc(fxc grad rho)")))
+                !reserve(s, slot_g0, sizeof(double) * 3 * ng, "hipMalloc(fxc grad rho)")))
         return false;
-    double *rho = (double *)s->rho.p, *sigma = (double *)s->sigma.p, *g0 = (double *)s->fxc_g0.p;   // grad rho goes straight to its keep
+    double *rho = (double *)s->rho.p, *sigma = (double *)s->sigma.p, *g0 = (double *)slot_g0.p;   // grad rho goes straight to its keep
     if (use_occ) {
         ScopedTimer t(s, "rho_occ");
         if (!reserve(s, s->occ_cp, sizeof(double) * oplan.cp_doubles, "hipMalloc(packed cocc)")) return false;
@@ -601,29 +613,40 @@ bool fxc_prepare(XCSolver *s, long ngrid, int nao, int nocc, const double *cocc,
     } else {
         launch_density(s, P, ngrid, nao, dm, ao, (double *)s->dsym.p, rho, g0, sigma);
     }
-    {
+    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+    if (kind == 0) {
         ScopedTimer t(s, "fxc_table");
-        const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
         if (!hip_ok(s, launch_fxc_table(s->stream, type, gga, s->mix.c, ngrid, rho, gga ? sigma : nullptr, w, (double *)s->fxc_table.p, s->quirks),
                     "response table launch"))
             return false;
+    } else {
+        ScopedTimer t(s, "fxc_table_spin");
+        if (!hip_ok(s, launch_fxc_table_spin(s->stream, type, gga, s->mix.c, ngrid, rho, gga ? sigma : nullptr, w, (double *)slot_table.p, kind),
+                    "spin response table launch"))
+            return false;
     }
     if (!hip_ok(s, hipGetLastError(), "response prepare launch")) return false;
-    s->fxc_ngrid = ngrid;
-    s->fxc_nao = nao;
+    slot_ngrid = ngrid;
+    slot_nao = nao;
     return true;
 }
 
 // Second half: V1 of a perturbation dm1 -- its density through the same kernels (linear in the matrix), the response
 // coefficients from the table, and the sweep's contraction and reduce.  Asynchronous on the solver's stream.
-bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double *ao, const double *ao_grad, double *v1)
+bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double *ao, const double *ao_grad, double *v1, int kind = 0)
 {
     s->last_error.clear();
     s->n_timed = 0;
     if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
-    if (s->fxc_ngrid <= 0) { set_error(s, "DFT_FxcApply before DFT_FxcPrepare (or the table was invalidated by an option change)"); return false; }
-    if (ngrid != s->fxc_ngrid || nao != s->fxc_nao) {
-        set_error(s, "DFT_FxcApply sizes ngrid=%ld nao=%d differ from DFT_FxcPrepare's ngrid=%ld nao=%d", ngrid, nao, s->fxc_ngrid, s->fxc_nao);
+    if (kind < 0 || kind > 2) { set_error(s, "DFT_FxcApplyKind: unknown kind %d (0 the DFT_FxcPrepare table, 1 triplet, 2 singlet through the spin-resolved bodies)", kind); return false; }
+    const long slot_ngrid = kind ? s->fxc_spin_ngrid[kind - 1] : s->fxc_ngrid;
+    const int slot_nao = kind ? s->fxc_spin_nao[kind - 1] : s->fxc_nao;
+    const double *slot_table = (const double *)(kind ? s->fxc_spin_table[kind - 1].p : s->fxc_table.p);
+    const double *slot_g0 = (const double *)(kind ? s->fxc_spin_g0[kind - 1].p : s->fxc_g0.p);
+    if (kind && slot_ngrid <= 0) { set_error(s, "DFT_FxcApplyKind(kind=%d) before DFT_FxcPrepareSpin of that kind", kind); return false; }
+    if (slot_ngrid <= 0) { set_error(s, "DFT_FxcApply before DFT_FxcPrepare (or the table was invalidated by an option change)"); return false; }
+    if (ngrid != slot_ngrid || nao != slot_nao) {
+        set_error(s, "DFT_FxcApply sizes ngrid=%ld nao=%d differ from DFT_FxcPrepare's ngrid=%ld nao=%d", ngrid, nao, slot_ngrid, slot_nao);
         return false;
     }
     const bool gga = s->needs_grad;
@@ -643,7 +666,7 @@ bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double
     launch_density(s, P, ngrid, nao, dm1, ao, (double *)s->dsym.p, rho1, g1, (double *)s->sigma.p);
     {
         ScopedTimer t(s, "fxc_coef");
-        if (!hip_ok(s, launch_fxc_coef(s->stream, gga, ngrid, (const double *)s->fxc_table.p, (const double *)s->fxc_g0.p, rho1, g1, coef),
+        if (!hip_ok(s, launch_fxc_coef(s->stream, gga, ngrid, slot_table, slot_g0, rho1, g1, coef),
                     "response coefficient launch"))
             return false;
     }
@@ -1240,7 +1263,8 @@ void DFT_DestroySolver(XCSolver *s)
         if (s->cap_stream) (void)hipStreamDestroy(s->cap_stream);
         DevBuf *bufs[] = {&s->dsym, &s->rho, &s->sigma, &s->grad, &s->coef, &s->partial,
                           &s->slabs, &s->exc, &s->jpart, &s->kpart, &s->shells, &s->msym,
-                          &s->cdy, &s->cdc, &s->cdv, &s->cdy2, &s->cdc2, &s->cdbt, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0};
+                          &s->cdy, &s->cdc, &s->cdv, &s->cdy2, &s->cdc2, &s->cdbt, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0,
+                          &s->fxc_spin_table[0], &s->fxc_spin_table[1], &s->fxc_spin_g0[0], &s->fxc_spin_g0[1]};
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
@@ -1504,6 +1528,28 @@ int DFT_FxcPrepare(XCSolver *s, long long ngrid, int nao, int nocc, unsigned lon
     DeviceGuard dg(s);
     return fxc_prepare(s, (long)ngrid, nao, nocc, (const double *)d_cocc, (const double *)d_dm0, (const double *)d_ao,
                        (const double *)d_ao_grad, (const double *)d_weights) ? 0 : -1;
+}
+
+int DFT_FxcPrepareSpin(XCSolver *s, long long ngrid, int nao, int nocc, unsigned long long d_cocc, unsigned long long d_dm0,
+                       unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_weights, int kind)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    if (kind != 1 && kind != 2) {
+        s->last_error.clear();
+        set_error(s, "DFT_FxcPrepareSpin: unknown kind %d (1 triplet, 2 singlet through the spin-resolved bodies)", kind);
+        return -1;
+    }
+    return fxc_prepare(s, (long)ngrid, nao, nocc, (const double *)d_cocc, (const double *)d_dm0, (const double *)d_ao,
+                       (const double *)d_ao_grad, (const double *)d_weights, kind) ? 0 : -1;
+}
+
+int DFT_FxcApplyKind(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm1, unsigned long long d_ao,
+                     unsigned long long d_ao_grad, unsigned long long d_v1, int kind)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return fxc_apply(s, (long)ngrid, nao, (const double *)d_dm1, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_v1, kind) ? 0 : -1;
 }
 
 int DFT_FxcApply(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm1, unsigned long long d_ao,

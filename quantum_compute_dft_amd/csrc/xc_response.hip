@@ -12,6 +12,7 @@
 // registers are live at a time; k_fxc_coef is the arithmetic above per perturbation.  Everything else of the
 // response (densities of dm1, contraction with the AO planes, slab reduce) is the ground-state sweep's kernels.
 #include "xc_functionals.hpp"
+#include "xc_spin_functionals.hpp"
 #include "xc_response_launch.hpp"
 
 namespace qcdft {
@@ -89,6 +90,32 @@ __global__ __launch_bounds__(256) void k_fxc_table_mix(long ngrid, const double 
     }
 }
 
+// The table of the spin-resolved energy bodies (xc_spin_functionals.hpp) in the same five planes, for k_fxc_coef as it
+// stands: kind 1 the spin-flip (triplet) response of the alpha potential, kind 2 the singlet response through the same
+// bodies (equal to k_fxc_table's at quirks = 0).  Second derivatives of the ENERGY by xc::Dual2, one evaluation live at
+// a time; WHICH (a bit per evaluation) spreads the evaluations over launches, each with its own register budget.  Built-in types arrive
+// as their component weights and `scale` (B3LYP: 1/2, its M + M^T convention).
+template <bool GGA, int WHICH>
+__global__ __launch_bounds__(256) void k_fxc_table_spin(long ngrid, const double *__restrict__ rho,
+                                                        const double *__restrict__ sigma,
+                                                        const double *__restrict__ w, double *__restrict__ table,
+                                                        int kind, double scale, xc::MixWeights m)
+{
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= ngrid) return;
+    const size_t n = (size_t)ngrid;
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0, t4 = 0.0;
+    xc::spin_table_point<GGA>(m, kind, WHICH, rho[g], GGA ? sigma[g] : 0.0, scale * w[g], &t0, &t1, &t2, &t3, &t4);
+    if (WHICH & 1) table[g] = t0;
+    if (!GGA) return;
+    if (WHICH & 2) {
+        table[2 * n + g] = t2;
+        table[4 * n + g] = t4;
+    }
+    if (WHICH & 4) table[3 * n + g] = t3;
+    if (WHICH & 8) table[n + g] = t1;
+}
+
 // Arithmetic only.  g0 / g1: three per point, interleaved (what the density kernels write).
 template <bool GGA>
 __global__ __launch_bounds__(256) void k_fxc_coef(long ngrid, const double *__restrict__ table,
@@ -127,6 +154,25 @@ hipError_t launch_fxc_table(hipStream_t st, int type, bool gga, const double *mi
         if (gga) hipLaunchKernelGGL(k_fxc_table_mix<true>, g, b, 0, st, ngrid, rho, sigma, w, table, quirks, m);
         else     hipLaunchKernelGGL(k_fxc_table_mix<false>, g, b, 0, st, ngrid, rho, sigma, w, table, quirks, m);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_fxc_table_spin(hipStream_t st, int type, bool gga, const double *mix8, long ngrid, const double *rho,
+                                 const double *sigma, const double *w, double *table, int kind)
+{
+    const dim3 g((unsigned)((ngrid + 255) / 256)), b(256);
+    xc::MixWeights m;
+    double scale = 1.0;
+    if (type == 3) for (int k = 0; k < 8; ++k) m.c[k] = mix8[k];
+    else           scale = xc::builtin_spin_mix(type, m);
+    if (!gga) {
+        hipLaunchKernelGGL((k_fxc_table_spin<false, 1>), g, b, 0, st, ngrid, rho, sigma, w, table, kind, scale, m);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_fxc_table_spin<true, 1>), g, b, 0, st, ngrid, rho, sigma, w, table, kind, scale, m);
+    hipLaunchKernelGGL((k_fxc_table_spin<true, 2>), g, b, 0, st, ngrid, rho, sigma, w, table, kind, scale, m);
+    hipLaunchKernelGGL((k_fxc_table_spin<true, 4>), g, b, 0, st, ngrid, rho, sigma, w, table, kind, scale, m);
+    hipLaunchKernelGGL((k_fxc_table_spin<true, 8>), g, b, 0, st, ngrid, rho, sigma, w, table, kind, scale, m);
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // the same two dual evaluations per point.  response.fxc_apply_host() and a CPU CPKS run assemble V1 from it; the CPU
 // tests hold it against finite differences of the oracle.  type: 0 LDA, 1 GGA, 2 B3LYP, 3 mix (eight weights).
 #include "xc_functionals.hpp"
+#include "xc_spin_functionals.hpp"
 
 using namespace qcdft;
 
@@ -99,6 +100,38 @@ int qc_xc_point(int type, const double *mix8, int quirks, long long n, const dou
         out[3 * n + g] = p.c2;
         out[4 * n + g] = p.c3;
     }
+    return 0;
+}
+
+// The table of the spin-resolved energy bodies, out (5, n) in the layout of qc_fxc_table (no weight): kind 1 the
+// spin-flip (triplet) response, kind 2 the singlet response through the same bodies.  A built-in type enters as its
+// component weights and its factor, as in launch_fxc_table_spin.  No `quirks`: a derivative of the energy.
+int qc_fxc_table_spin(int type, const double *mix8, int kind, long long n, const double *rho, const double *sigma, double *out)
+{
+    if (type < 0 || type > 3 || (type == 3 && !mix8) || (kind != 1 && kind != 2) || n < 0 || !rho || !out) return -1;
+    xc::MixWeights m = weights(mix8);
+    const double scale = type == 3 ? 1.0 : xc::builtin_spin_mix(type, m);
+    const bool gga = mix_gga(m);
+    if (gga && !sigma) return -1;
+    for (long long g = 0; g < n; ++g) {
+        double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (gga) xc::spin_table_point<true>(m, kind, 15, rho[g], sigma[g], scale, t, t + 1, t + 2, t + 3, t + 4);
+        else     xc::spin_table_point<false>(m, kind, 15, rho[g], 0.0, scale, t, t + 1, t + 2, t + 3, t + 4);
+        for (int k = 0; k < 5; ++k) out[k * n + g] = t[k];
+    }
+    return 0;
+}
+
+// out (n): the energy per volume of the eight weights at any (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb).
+int qc_spin_energy(const double *mix8, long long n, const double *ra, const double *rb, const double *saa, const double *sab,
+                   const double *sbb, double *out)
+{
+    if (!mix8 || n < 0 || !ra || !rb || !saa || !sab || !sbb || !out) return -1;
+    const xc::MixWeights m = weights(mix8);
+    const bool gga = mix_gga(m);
+    for (long long g = 0; g < n; ++g)
+        out[g] = gga ? xc::spin_mix_energy<true>(m, ra[g], rb[g], saa[g], sab[g], sbb[g])
+                     : xc::spin_mix_energy<false>(m, ra[g], rb[g], 0.0, 0.0, 0.0);
     return 0;
 }
 

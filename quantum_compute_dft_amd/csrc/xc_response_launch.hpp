@@ -14,6 +14,11 @@ constexpr int FXC_PLANES = 5;   // w P_rho, w P_sigma, w Q_rho, w Q_sigma, w Q (
 hipError_t launch_fxc_table(hipStream_t st, int type, bool gga, const double *mix8, long ngrid, const double *rho,
                             const double *sigma, const double *w, double *table, int quirks);
 
+// The same five planes from the spin-resolved energy bodies (xc_spin_functionals.hpp): kind 1 the spin-flip (triplet)
+// response, kind 2 the singlet response through those bodies.  Independent of `quirks`: a derivative of the energy.
+hipError_t launch_fxc_table_spin(hipStream_t st, int type, bool gga, const double *mix8, long ngrid, const double *rho,
+                                 const double *sigma, const double *w, double *table, int kind);
+
 // coef (c0'..c3' SoA, the layout of k_xc_points; c0' alone when !gga) from the table, the ground-state gradient g0
 // (3 per point, interleaved), and rho1 / g1 of the perturbation as the density kernels leave them.
 hipError_t launch_fxc_coef(hipStream_t st, bool gga, long ngrid, const double *table, const double *g0,

@@ -137,6 +137,9 @@ def main(argv=None):
                    help="the N lowest singlet excitation energies and oscillator strengths by TDDFT (reduced-space iteration; J and K of all "
                         "trial vectors of an iteration in one DFT_ComputeJKFactorizedResponse call with Cholesky vectors); one rank, --ao resident")
     p.add_argument("--tda", action="store_true", help="with --excitations: the Tamm-Dancoff approximation instead of the full TDDFT problem")
+    p.add_argument("--triplets", action="store_true",
+                   help="with --excitations: the N lowest TRIPLET excitations (spin-flip XC kernel on the device: DFT_FxcPrepareSpin / "
+                        "DFT_FxcApplyKind; no Coulomb response, oscillator strengths are zero); needs --quirks 0 with vwn5_c or pbe_c")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
     args = p.parse_args(argv)
@@ -149,6 +152,8 @@ def main(argv=None):
         p.error("--polarizability runs on one rank with --ao resident")
     if args.excitations < 0 or (args.tda and not args.excitations):
         p.error("--excitations takes a positive number of roots; --tda goes with it")
+    if args.triplets and not args.excitations:
+        p.error("--triplets goes with --excitations N")
     if args.excitations and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident"):
         p.error("--excitations runs on one rank with --ao resident")
 
@@ -271,14 +276,15 @@ def main(argv=None):
     excited = None
     if args.excitations and res["converged"]:
         from . import excitations as _ex
-        excited = _ex.excitations(inp, res, backend, args.functional, nroots=args.excitations, tda=args.tda, log=print)
+        excited = _ex.excitations(inp, res, backend, args.functional, nroots=args.excitations, tda=args.tda, log=print, triplet=args.triplets)
         nocc_ = inp.nocc
-        print(f"Singlet excitations ({'TDA' if args.tda else 'TDDFT'}; {excited['iterations']} iterations, {excited['sigma_builds']} trial vectors"
+        print(f"{'Triplet' if args.triplets else 'Singlet'} excitations ({'TDA' if args.tda else 'TDDFT'}; {excited['iterations']} iterations, {excited['sigma_builds']} trial vectors"
               + ("" if excited["converged"] else "; NOT converged") + "):")
         print("  state        eV         nm          f    largest |X+Y|")
+        mult = "T" if args.triplets else "S"
         for n, (w, f_n, x) in enumerate(zip(excited["energies"], excited["oscillator_strengths"], excited["xpy"]), 1):
             i, a = np.unravel_index(np.argmax(np.abs(x)), x.shape)
-            print(f"  {n:5d} {w * _ex.HARTREE_EV:9.4f} {_ex.NM_PER_HARTREE / w:10.2f} {f_n:10.6f}    {i + 1} -> {nocc_ + a + 1} ({abs(x[i, a]):.3f})")
+            print(f"  {mult}{n:<4d} {w * _ex.HARTREE_EV:9.4f} {_ex.NM_PER_HARTREE / w:10.2f} {f_n:10.6f}    {i + 1} -> {nocc_ + a + 1} ({abs(x[i, a]):.3f})")
     import json
     record = {"functional": args.functional, "molecule": os.path.splitext(atom_file)[0], "basis": args.basis, "grid_level": args.grid_level,
               "nao": int(inp.shells.nao), "ngrid": int(inp.grids.size), "nocc": int(inp.nocc), "n_gpus": world, "eri": args.eri,
@@ -300,7 +306,8 @@ def main(argv=None):
         record["polarizability"] = polar["alpha"].tolist() if polar is not None else None
         record["cpks_iterations"] = [int(x) for x in polar["cpks_iterations"]] if polar is not None else None
     if args.excitations:
-        record["excitation_method"] = "tda" if args.tda else "tddft"
+        record["excitation_method"] = ("tda" if args.tda else "tddft") + ("-triplet" if args.triplets else "")
+        record["excitation_multiplicity"] = 3 if args.triplets else 1
         record["excitation_energies"] = excited["energies"].tolist() if excited is not None else None
         record["oscillator_strengths"] = excited["oscillator_strengths"].tolist() if excited is not None else None
         record["excitation_iterations"] = int(excited["iterations"]) if excited is not None else None

@@ -1,5 +1,5 @@
-"""Singlet excitation energies and oscillator strengths of a closed-shell state: TDDFT (the full coupled problem) and
-its Tamm-Dancoff approximation, by a reduced-space iteration on top of a response backend.
+"""Singlet and triplet excitation energies of a closed-shell state, with the oscillator strengths of the singlets: TDDFT
+(the full coupled problem) and its Tamm-Dancoff approximation, by a reduced-space iteration on top of a response backend.
 
 Canonical orbitals Co, Cv and gaps D_ia = e_a - e_i come from one eigh(F, S) of the converged Fock matrix, as in
 response.polarizability.  For a trial Z (nocc, nvirt) with A = Co, B = 2 Cv Z^T and D+- = A B^T +- B A^T
@@ -15,6 +15,19 @@ its alpha.  TDA solves A X = w X with A = ((A+B) + (A-B))/2 and X^T X = 1; TDDFT
 (A-B)(A+B)(X+Y) = w^2 (X+Y) with (X+Y)^T (X-Y) = 1.  Transition dipole mu_n = sqrt(2) sum_ia (Co^T D_k Cv)_ia (X+Y)_ia,
 oscillator strength f_n = 2/3 w_n |mu_n|^2.  With option quirks = 1 the operator is the response of the shipped
 formulas, the SCF equations the loop actually solves -- the choice the polarizability made.
+
+Triplets (triplet=True): the spin-flip perturbation dm_alpha, dm_beta = dm0/2 +- t D/2 induces no Coulomb potential, and
+its XC response V1_T is the spin-flip kernel at zero polarisation (DFT_FxcPrepareSpin / DFT_FxcApplyKind, kind 1;
+csrc/xc_spin_functionals.hpp):
+
+    (A+B)_T Z = D o Z + Co^T ( (V1_T + V1_T^T)/2 [D+] - c_hf/2 K[D+] ) Cv       (no J is requested)
+    (A-B)_T Z = (A-B) Z
+
+A triplet carries no transition dipole from the singlet ground state: oscillator strengths are reported as 0.  The
+spin-flip kernel is a second derivative of the ENERGY, so with quirks = 1 and vwn5_c or pbe_c in the functional (whose
+shipped potentials are not the derivatives of their energies) the triplet operator would not belong to the ground
+state the loop solved: refused, run with --quirks 0.  A reduced (A+B)_T that is not positive definite is a triplet
+instability of the restricted reference (the classic test of a closed-shell solution) and is reported as one.
 """
 import numpy as np
 from scipy.linalg import eigh
@@ -24,15 +37,21 @@ from . import functionals, integrals
 HARTREE_EV = 27.211386245988
 NM_PER_HARTREE = 45.56335252907954        # h c / (1 Ha) in nm
 _PBE_C = functionals.COMPONENTS.index("pbe_c")
+_VWN5_C = functionals.COMPONENTS.index("vwn5_c")
 
 
 class ResponseOperators:
     """(A+B) and (A-B) of a converged closed-shell state as maps on (nvec, nocc, nvirt) arrays: `apply`.  Fields: Co,
     Cv, gap (nocc, nvirt), dip = Co^T D_k Cv (3, nocc, nvirt), c_hf, builds (trial vectors applied so far)."""
 
-    def __init__(self, inp, scf_result, backend, functional=None):
+    def __init__(self, inp, scf_result, backend, functional=None, triplet=False):
         f = functionals.resolve(functional if functional is not None else backend.functional)
         quirks = bool(getattr(backend, "quirks", True))
+        self.triplet = bool(triplet)
+        if self.triplet and quirks and (f.weight_vector()[_VWN5_C] != 0.0 or f.weight_vector()[_PBE_C] != 0.0):
+            raise ValueError("excitations: the triplet (spin-flip) kernel is the second derivative of the energy, but with quirks = 1 the "
+                             "ground state solved the shipped vwn5_c / pbe_c potentials, which are not the derivatives of their energies; "
+                             "run with --quirks 0")
         if quirks and f.weight_vector()[_PBE_C] != 0.0:
             raise ValueError("excitations: with quirks = 1 the shipped PBE correlation potential is not the derivative of "
                              "its energy and the response operator is not symmetric; run with --quirks 0")
@@ -48,7 +67,10 @@ class ResponseOperators:
         self.gap = np.ascontiguousarray(e[None, nocc:] - e[:nocc, None])
         if self.gap.size == 0 or self.gap.min() <= 1e-6:
             raise ValueError("excitations: no gap between the occupied and the virtual orbitals")
-        backend.response_prepare(dm0, cocc0)
+        if self.triplet:
+            backend.response_prepare(dm0, cocc0, kind="triplet")
+        else:
+            backend.response_prepare(dm0, cocc0)
         self.backend = backend
         self.dip = np.einsum("mi,kmn,na->kia", self.Co, integrals.dipole(inp.shells), self.Cv)
         self.builds = 0
@@ -57,9 +79,13 @@ class ResponseOperators:
         """((A+B) Z_k, (A-B) Z_k) for Z (nvec, nocc, nvirt), through one excitation_parts call."""
         Z = np.asarray(Z, dtype=np.float64)
         Bs = np.ascontiguousarray(2.0 * np.einsum("na,kia->kni", self.Cv, Z))
-        J, M, V1 = self.backend.excitation_parts(self.Co, Bs, self.want_k)
+        if self.triplet:
+            _, M, V1 = self.backend.excitation_parts(self.Co, Bs, self.want_k, kind="triplet")
+            G = 0.5 * (V1 + V1.transpose(0, 2, 1))                  # no Coulomb response to a spin flip
+        else:
+            J, M, V1 = self.backend.excitation_parts(self.Co, Bs, self.want_k)
+            G = J + 0.5 * (V1 + V1.transpose(0, 2, 1))
         self.builds += Z.shape[0]
-        G = J + 0.5 * (V1 + V1.transpose(0, 2, 1))
         dz = self.gap[None] * Z
         if not self.want_k:
             return dz + np.einsum("mi,kmn,na->kia", self.Co, G, self.Cv), dz
@@ -88,8 +114,11 @@ def _orthonormal_additions(basis, cands, drop=1e-8):
     return np.array(out).reshape(len(out), basis.shape[1])
 
 
-def _sqrt_spd(M, what):
+def _sqrt_spd(M, what, triplet=False):
     w, U = np.linalg.eigh(M)
+    if w[0] <= 0.0 and triplet and what == "A+B":
+        raise ValueError(f"excitations: the reduced triplet A+B is not positive definite (lowest eigenvalue {w[0]:.3e}): "
+                         "triplet instability of the restricted reference")
     if w[0] <= 0.0:
         raise ValueError(f"excitations: the reduced {what} is not positive definite (lowest eigenvalue {w[0]:.3e}): "
                          "the reference state is unstable")
@@ -110,6 +139,7 @@ def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=N
     new[np.arange(new.shape[0]), np.argsort(gap, kind="stable")[:new.shape[0]]] = 1.0
     Pb, Qb = np.zeros((0, N)), np.zeros((0, N))
     builds0 = ops.builds
+    triplet = bool(getattr(ops, "triplet", False))
     converged, it = False, 0
     for it in range(1, max_iter + 1):
         P, Q = ops.apply(new.reshape(-1, nocc, nvirt))
@@ -118,6 +148,9 @@ def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=N
         Mp, Mm = 0.5 * (Mp + Mp.T), 0.5 * (Mm + Mm.T)
         if tda:
             w, T = np.linalg.eigh(0.5 * (Mp + Mm))
+            if w[0] <= 0.0 and triplet:
+                raise ValueError(f"excitations: the lowest triplet Tamm-Dancoff root is {w[0]:.3e} Ha: triplet instability of the "
+                                 "restricted reference")
             if w[0] <= 0.0:
                 raise ValueError(f"excitations: the lowest Tamm-Dancoff root is {w[0]:.3e} Ha: the reference state is unstable")
             w, R, L = w[:nroots], T[:, :nroots], T[:, :nroots]                 # X+Y = X-Y = X
@@ -125,7 +158,7 @@ def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=N
             res2 = res1
         else:
             Sm, Smi = _sqrt_spd(Mm, "A-B")
-            _sqrt_spd(Mp, "A+B")
+            _sqrt_spd(Mp, "A+B", triplet)
             w2, T = np.linalg.eigh(Sm @ Mp @ Sm)
             w = np.sqrt(w2[:nroots])
             R = (Sm @ T[:, :nroots]) / np.sqrt(w)                               # X+Y in the basis
@@ -156,14 +189,17 @@ def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=N
             break                                                               # nothing left to add: the space is exhausted
     xpy, xmy = R.T @ b, L.T @ b
     mu = np.sqrt(2.0) * np.einsum("kx,nx->nk", ops.dip.reshape(3, N), xpy)
+    if triplet:
+        mu = np.zeros_like(mu)                       # spin-forbidden from the singlet ground state
     return {"energies": w, "oscillator_strengths": (2.0 / 3.0) * w * np.einsum("nk,nk->n", mu, mu),
             "transition_dipoles": mu, "xpy": xpy.reshape(-1, nocc, nvirt), "xmy": xmy.reshape(-1, nocc, nvirt),
             "residuals": rn, "iterations": it, "sigma_builds": ops.builds - builds0, "converged": converged,
-            "method": "tda" if tda else "tddft"}
+            "method": ("tda" if tda else "tddft") + ("-triplet" if triplet else ""), "multiplicity": 3 if triplet else 1}
 
 
-def excitations(inp, scf_result, backend, functional=None, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=None):
-    """The lowest `nroots` singlet excitations of the converged closed-shell state `scf_result` (scf.run_scf) by a
+def excitations(inp, scf_result, backend, functional=None, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=None,
+                triplet=False):
+    """The lowest `nroots` singlet (triplet=True: triplet) excitations of the converged closed-shell state `scf_result` (scf.run_scf) by a
     Davidson-type iteration on one orthonormal trial basis b: every iteration applies (A+B) and (A-B) to the new vectors
     through one backend.excitation_parts call, solves the reduced problem M-^(1/2) M+ M-^(1/2) T = w^2 T (TDA: the
     symmetric b^T A b), and extends b by the residuals (A+B)(X+Y) - w (X-Y) and (A-B)(X-Y) - w (X+Y) divided by
@@ -171,7 +207,9 @@ def excitations(inp, scf_result, backend, functional=None, nroots=5, tda=False, 
     The space is collapsed onto the current roots when it would exceed `max_space`.
 
     Returns {"energies" (Ha, ascending), "oscillator_strengths", "transition_dipoles" (nroots, 3), "xpy", "xmy"
-    (nroots, nocc, nvirt; equal for TDA), "residuals", "iterations", "sigma_builds", "converged", "method"}.
-    ValueError: nroots above nocc nvirt, no gap, a reduced A+B or A-B that is not positive definite (an unstable
-    reference), or quirks = 1 with PBE correlation (a non-symmetric operator; use quirks 0)."""
-    return solve(ResponseOperators(inp, scf_result, backend, functional), nroots, tda, tol, max_iter, max_space, log)
+    (nroots, nocc, nvirt; equal for TDA), "residuals", "iterations", "sigma_builds", "converged", "method" ("tddft", "tda",
+    "tddft-triplet", "tda-triplet"), "multiplicity" (1 or 3)}; a triplet's oscillator strengths and transition dipoles
+    are zero.  ValueError: nroots above nocc nvirt, no gap, a reduced A+B or A-B that is not positive definite (an
+    unstable reference; for triplets: a triplet instability of the restricted reference), quirks = 1 with PBE
+    correlation (a non-symmetric operator; use quirks 0), or triplets at quirks = 1 with vwn5_c or pbe_c."""
+    return solve(ResponseOperators(inp, scf_result, backend, functional, triplet=triplet), nroots, tda, tol, max_iter, max_space, log)

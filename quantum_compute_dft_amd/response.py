@@ -31,8 +31,29 @@ def _load():
         L.qc_fxc_pq.argtypes = [ctypes.c_int, dp, ctypes.c_int, ctypes.c_longlong, dp, dp, dp, dp]
         L.qc_xc_point.restype = ctypes.c_int
         L.qc_xc_point.argtypes = [ctypes.c_int, dp, ctypes.c_int, ctypes.c_longlong, dp, dp, dp, dp, dp]
+        L.qc_fxc_table_spin.restype = ctypes.c_int
+        L.qc_fxc_table_spin.argtypes = [ctypes.c_int, dp, ctypes.c_int, ctypes.c_longlong, dp, dp, dp]
+        L.qc_spin_energy.restype = ctypes.c_int
+        L.qc_spin_energy.argtypes = [dp, ctypes.c_longlong, dp, dp, dp, dp, dp, dp]
         _lib = L
     return _lib
+
+
+# Which response table: None the shipped vrho / vsigma formulas differentiated (DFT_FxcPrepare, the default everywhere),
+# "triplet" the spin-flip response of the spin-resolved energy bodies, "singlet-spin" the singlet response through the same
+# bodies (DFT_FxcPrepareSpin kinds 1 and 2; independent of quirks).
+SPIN_KINDS = {"triplet": 1, "singlet-spin": 2}
+
+
+def spin_kind(kind):
+    """0 for None / "singlet" (the shipped table), else the DFT_FxcPrepareSpin kind of a name or of 1 / 2 itself."""
+    if kind is None or kind == "singlet" or kind == 0:
+        return 0
+    if kind in SPIN_KINDS:
+        return SPIN_KINDS[kind]
+    if kind in (1, 2):
+        return int(kind)
+    raise ValueError(f"unknown response kind {kind!r} (singlet, {', '.join(SPIN_KINDS)})")
 
 
 def _p(a):
@@ -54,18 +75,40 @@ def _kind(functional):
     return t, w, bool(np.any(w[4:] != 0.0))
 
 
-def fxc_table_host(functional, rho, sigma=None, quirks=True):
+def fxc_table_host(functional, rho, sigma=None, quirks=True, kind=None):
     """(5, n): P_rho, P_sigma, Q_rho, Q_sigma, Q of the functional at (rho, sigma), where c0 = w P and c_k = w Q g_k are
     the coefficients the sweep contracts with the AO planes (no weight here).  Exactly zero below the density cut-off;
-    planes 1..4 are zero for an LDA-class functional."""
+    planes 1..4 are zero for an LDA-class functional.  kind "triplet" / "singlet-spin": the same five planes from the
+    spin-resolved energy bodies (csrc/xc_spin_functionals.hpp) at rho_a = rho_b -- the response of the alpha potential
+    to a spin-flip / a symmetric perturbation; `quirks` plays no part there."""
     t, w, gga = _kind(functional)
     rho = np.ascontiguousarray(np.atleast_1d(rho), dtype=np.float64)
     sigma = np.zeros_like(rho) if sigma is None else np.ascontiguousarray(np.atleast_1d(sigma), dtype=np.float64)
     if sigma.shape != rho.shape or rho.ndim != 1:
         raise ValueError("rho and sigma: one-dimensional arrays of one length")
     out = np.zeros((5, rho.size))
-    if _load().qc_fxc_table(t, _p(w), 1 if quirks else 0, rho.size, _p(rho), _p(sigma), _p(out)) != 0:
+    k = spin_kind(kind)
+    if k:
+        rc = _load().qc_fxc_table_spin(t, _p(w), k, rho.size, _p(rho), _p(sigma), _p(out))
+    else:
+        rc = _load().qc_fxc_table(t, _p(w), 1 if quirks else 0, rho.size, _p(rho), _p(sigma), _p(out))
+    if rc != 0:
         raise ValueError("fxc_table_host: bad arguments")
+    return out
+
+
+def spin_energy_host(functional, ra, rb, saa=None, sab=None, sbb=None):
+    """(n,): the energy per volume of the functional's components (no exact exchange) at the spin densities ra, rb and
+    sigma_aa = |grad ra|^2, sigma_ab = grad ra . grad rb, sigma_bb, any polarisation: the spin-resolved bodies in double."""
+    _, w, _ = _kind(functional)
+    ra = np.ascontiguousarray(np.atleast_1d(ra), dtype=np.float64)
+    a = [ra] + [np.zeros_like(ra) if x is None else np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), ra.shape))
+                for x in (rb, saa, sab, sbb)]
+    if ra.ndim != 1:
+        raise ValueError("spin_energy_host: one-dimensional arrays of one length")
+    out = np.zeros(ra.size)
+    if _load().qc_spin_energy(_p(w), ra.size, *(_p(x) for x in a), _p(out)) != 0:
+        raise ValueError("spin_energy_host: bad arguments")
     return out
 
 
@@ -103,7 +146,7 @@ def _density(dm, ao, ao_grad):
 class HostFxc:
     """fxc_prepare / fxc_apply on the host: the table at dm0 once, then V1 of any number of perturbations."""
 
-    def __init__(self, functional, dm0, ao, weights, ao_grad=None, quirks=True):
+    def __init__(self, functional, dm0, ao, weights, ao_grad=None, quirks=True, kind=None):
         self.type, self.w8, self.gga = _kind(functional)
         if self.gga and ao_grad is None:
             raise ValueError("ao_grad is needed for a gradient-corrected functional")
@@ -111,7 +154,7 @@ class HostFxc:
         self.gr = np.ascontiguousarray(ao_grad, dtype=np.float64) if self.gga else None
         rho, self.g0 = _density(np.asarray(dm0, dtype=np.float64), self.ao, self.gr)
         sigma = np.einsum("gk,gk->g", self.g0, self.g0) if self.gga else None
-        self.table = fxc_table_host(functional, rho, sigma, quirks) * np.asarray(weights, dtype=np.float64)[None, :]
+        self.table = fxc_table_host(functional, rho, sigma, quirks, kind) * np.asarray(weights, dtype=np.float64)[None, :]
 
     def apply(self, dm1):
         rho1, g1 = _density(np.asarray(dm1, dtype=np.float64), self.ao, self.gr)
@@ -127,10 +170,12 @@ class HostFxc:
         return M + M.T if self.type == 2 else M      # B3LYP: the library's M + M^T with the halved vrho
 
 
-def fxc_apply_host(functional, dm0, dm1, ao, weights, ao_grad=None, quirks=True):
+def fxc_apply_host(functional, dm0, dm1, ao, weights, ao_grad=None, quirks=True, kind=None):
     """V1 = d/dt Vxc(dm0 + t dm1) at t = 0 from AO planes, in numpy: one-sided for GGA-type functionals and mixes, M + M^T
-    with the halved vrho for B3LYP, symmetric for LDA -- element for element what DFT_FxcApply leaves."""
-    return HostFxc(functional, dm0, ao, weights, ao_grad, quirks).apply(dm1)
+    with the halved vrho for B3LYP, symmetric for LDA -- element for element what DFT_FxcApply leaves.  kind "triplet":
+    d/dt of the alpha-spin potential under dm_alpha, dm_beta = dm0/2 +- t dm1/2, in the same conventions (what
+    DFT_FxcApplyKind leaves for kind 1); "singlet-spin": the singlet V1 through the spin-resolved bodies."""
+    return HostFxc(functional, dm0, ao, weights, ao_grad, quirks, kind).apply(dm1)
 
 
 class HostResponse:
@@ -142,7 +187,7 @@ class HostResponse:
             raise ValueError("HostResponse needs the dense ERI")
         self.inp, self.functional, self.scf, self.q = inp, functional, scf_backend, quirks
         self.quirks = bool(quirks)
-        self.ao, self.gr, self.fxc = ao, ao_grad, None
+        self.ao, self.gr, self.fxc, self.fxc_spin = ao, ao_grad, None, {}
 
     def ground_state_parts(self, dm, cocc, want_k):
         self.scf.set_dm(dm)
@@ -150,23 +195,32 @@ class HostResponse:
         _, V, _ = self.scf.xc()
         return J, K, V
 
-    def response_prepare(self, dm0, cocc=None):
-        self.fxc = HostFxc(self.functional, dm0, self.ao, self.inp.grids.weights, self.gr, self.q)
+    def response_prepare(self, dm0, cocc=None, kind=None):
+        k = spin_kind(kind)
+        if k:
+            self.fxc_spin[k] = HostFxc(self.functional, dm0, self.ao, self.inp.grids.weights, self.gr, self.q, k)
+        else:
+            self.fxc = HostFxc(self.functional, dm0, self.ao, self.inp.grids.weights, self.gr, self.q)
 
     def response_parts(self, dm1, want_k, factors=None):
         J = np.einsum("ijkl,kl->ij", self.inp.eri, dm1)
         K = np.einsum("ikjl,kl->ij", self.inp.eri, dm1) if want_k else None
         return J, K, self.fxc.apply(dm1)
 
-    def excitation_parts(self, A, Bs, want_k):
+    def excitation_parts(self, A, Bs, want_k, kind=None):
         """(J, M or None, V1), each (nvec, nao, nao), of the trials D_k = A B_k^T + B_k A^T: J[D_k], the unsymmetrised
-        M_k = K[A B_k^T] (K[D]_mn = sum_ls (ml|ns) D_ls, so K[A B_k^T +- B_k A^T] = M_k +- M_k^T) and V1[D_k]."""
+        M_k = K[A B_k^T] (K[D]_mn = sum_ls (ml|ns) D_ls, so K[A B_k^T +- B_k A^T] = M_k +- M_k^T) and V1[D_k].
+        kind "triplet": V1 from the spin-flip table (response_prepare(kind="triplet") first) and no J (None)."""
         A, Bs = np.asarray(A, dtype=np.float64), np.asarray(Bs, dtype=np.float64)
         AB = np.einsum("mi,kni->kmn", A, Bs)
         Dp = AB + AB.transpose(0, 2, 1)
-        J = np.einsum("ijkl,nkl->nij", self.inp.eri, Dp)
+        k = spin_kind(kind)
+        if k and k not in self.fxc_spin:
+            raise ValueError(f"excitation_parts: response_prepare(kind={kind!r}) has not run")
+        fxc = self.fxc_spin[k] if k else self.fxc
+        J = np.einsum("ijkl,nkl->nij", self.inp.eri, Dp) if k != 1 else None
         M = np.einsum("ikjl,nkl->nij", self.inp.eri, AB) if want_k else None
-        return J, M, np.stack([self.fxc.apply(d) for d in Dp])
+        return J, M, np.stack([fxc.apply(d) for d in Dp])
 
 
 def _gmres(apply_a, b, tol, max_iter):

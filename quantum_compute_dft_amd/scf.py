@@ -543,13 +543,19 @@ class HipBackend:
         J, K, _, V, _, _ = self.fock_parts(want_k)
         return J, K, V
 
-    def response_prepare(self, dm0, cocc=None):
-        """DFT_FxcPrepare at dm0 (through cocc, dm0 = cocc cocc^T, when given and the loop sweeps that way)."""
+    def response_prepare(self, dm0, cocc=None, kind="singlet"):
+        """DFT_FxcPrepare at dm0 (through cocc, dm0 = cocc cocc^T, when given and the loop sweeps that way); kind "triplet"
+        (or "singlet-spin"): DFT_FxcPrepareSpin, the table of the spin-resolved energy bodies in its own slot."""
         self._response_check()
+        from .response import spin_kind
         t = self.torch
         self._d_dm0 = t.as_tensor(np.ascontiguousarray(dm0), dtype=t.float64, device=self.dev)
         d_c = t.as_tensor(np.ascontiguousarray(cocc), dtype=t.float64, device=self.dev) if (cocc is not None and self.xc_occ) else None
-        self.solver.fxc_prepare(self.ngrid, self.nao, self._d_dm0, self.d_ao, self.d_w, self.d_gr, d_c, 0 if d_c is None else d_c.shape[1])
+        k = spin_kind(kind)
+        if k:
+            self.solver.fxc_prepare_spin(self.ngrid, self.nao, self._d_dm0, self.d_ao, self.d_w, self.d_gr, d_c, 0 if d_c is None else d_c.shape[1], k)
+        else:
+            self.solver.fxc_prepare(self.ngrid, self.nao, self._d_dm0, self.d_ao, self.d_w, self.d_gr, d_c, 0 if d_c is None else d_c.shape[1])
         n = self.nao
         self._r_dm1 = t.zeros((n, n), dtype=t.float64, device=self.dev)
         self._r_out = t.zeros((4, n, n), dtype=t.float64, device=self.dev)      # J | K | V1 | K of the second factor
@@ -584,13 +590,18 @@ class HipBackend:
         h = self._r_out.cpu().numpy()
         return h[0], (h[1] if want_k else None), h[2]
 
-    def excitation_parts(self, A, Bs, want_k):
+    def excitation_parts(self, A, Bs, want_k, kind="singlet"):
         """(J, M or None, V1_raw), each (nvec, nao, nao) as numpy arrays, of the trials D_k = A B_k^T + B_k A^T with A
         (nao, nocc) and Bs (nvec, nao, nocc): J[D_k], the unsymmetrised M_k = K[A B_k^T] -- K[D]_mn = sum_ls (ml|ns) D_ls,
         so K[A B_k^T +- B_k A^T] = M_k +- M_k^T, the antisymmetric combination included -- and V1[D_k].  Cholesky
         vectors: ONE DFT_ComputeJKFactorizedResponse call for all trials.  Dense ERI: DFT_ComputeJK per trial (its K is
-        the literal einsum, for any dm).  One DFT_FxcApply per trial either way.  After response_prepare."""
+        the literal einsum, for any dm).  One DFT_FxcApply per trial either way.  After response_prepare.
+        kind "triplet": V1 by DFT_FxcApplyKind from the spin-flip table (after response_prepare(kind="triplet")) and no
+        J at all -- None is returned for it, no Coulomb kernel runs on either path."""
         self._response_check()
+        from .response import spin_kind
+        kd = spin_kind(kind)
+        want_j = kd != 1
         t, n = self.torch, self.nao
         f64 = t.float64
         d_A = t.as_tensor(np.ascontiguousarray(A, dtype=np.float64), dtype=f64, device=self.dev)
@@ -602,18 +613,23 @@ class HipBackend:
         AB = t.matmul(d_A.unsqueeze(0), d_B.transpose(1, 2))                           # A B_k^T
         Dp = (AB + AB.transpose(1, 2)).contiguous()
         if self.d_chol is not None:
-            self.solver.compute_jk_factorized_response(n, self.d_chol.shape[0], nocc, nvec, self.d_chol, d_A, d_B,
-                                                       out[0], out[1] if want_k else None)
+            if want_j or want_k:
+                self.solver.compute_jk_factorized_response(n, self.d_chol.shape[0], nocc, nvec, self.d_chol, d_A, d_B,
+                                                           out[0] if want_j else None, out[1] if want_k else None)
         else:
             for k in range(nvec):
-                self.solver.compute_coulomb(n, self.d_eri, Dp[k], out[0, k])
+                if want_j:
+                    self.solver.compute_coulomb(n, self.d_eri, Dp[k], out[0, k])
                 if want_k:
                     self.solver.compute_jk(n, self.d_eri, AB[k], None, out[1, k])
         for k in range(nvec):
-            self.solver.fxc_apply(self.ngrid, n, Dp[k], self.d_ao, out[2, k], self.d_gr)
+            if kd:
+                self.solver.fxc_apply_kind(self.ngrid, n, Dp[k], self.d_ao, out[2, k], self.d_gr, kd)
+            else:
+                self.solver.fxc_apply(self.ngrid, n, Dp[k], self.d_ao, out[2, k], self.d_gr)
         t.cuda.synchronize()
         h = out.cpu().numpy()
-        return h[0], (h[1] if want_k else None), h[2]
+        return (h[0] if want_j else None), (h[1] if want_k else None), h[2]
 
 
 def run_scf(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, log=print):

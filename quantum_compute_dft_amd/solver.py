@@ -136,6 +136,10 @@ class DFTSolverWrapper:
         L.DFT_FxcPrepare.restype = ctypes.c_int
         L.DFT_FxcApply.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64]
         L.DFT_FxcApply.restype = ctypes.c_int
+        L.DFT_FxcPrepareSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, ctypes.c_int]
+        L.DFT_FxcPrepareSpin.restype = ctypes.c_int
+        L.DFT_FxcApplyKind.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, ctypes.c_int]
+        L.DFT_FxcApplyKind.restype = ctypes.c_int
 
         if self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
@@ -284,6 +288,22 @@ class DFTSolverWrapper:
         Vxc in; asynchronous on the solver's stream.  Any number of calls after one fxc_prepare."""
         rc = self.lib.DFT_FxcApply(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm1)), _u64(_ptr(d_ao)),
                                    _u64(_ptr(d_ao_grad)), _u64(_ptr(d_v1)))
+        self._check()
+        return rc
+
+    def fxc_prepare_spin(self, ngrid, nao, d_dm0, d_ao, d_weights, d_ao_grad=None, d_cocc=None, nocc=0, kind=1):
+        """fxc_prepare for the tables of the spin-resolved energy bodies (DFT_FxcPrepareSpin), into the slot of `kind`:
+        1 the spin-flip (triplet) response, 2 the singlet response through the same bodies.  Independent of quirks; an
+        fxc_prepare table is left alone."""
+        rc = self.lib.DFT_FxcPrepareSpin(self.solver, int(ngrid), int(nao), int(nocc), _u64(_ptr(d_cocc)), _u64(_ptr(d_dm0)),
+                                         _u64(_ptr(d_ao)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_weights)), int(kind))
+        self._check()
+        return rc
+
+    def fxc_apply_kind(self, ngrid, nao, d_dm1, d_ao, d_v1, d_ao_grad=None, kind=1):
+        """fxc_apply with the table chosen (DFT_FxcApplyKind): 0 fxc_prepare's, 1 / 2 the slots of fxc_prepare_spin."""
+        rc = self.lib.DFT_FxcApplyKind(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm1)), _u64(_ptr(d_ao)),
+                                       _u64(_ptr(d_ao_grad)), _u64(_ptr(d_v1)), int(kind))
         self._check()
         return rc
 
