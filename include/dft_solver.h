@@ -312,6 +312,29 @@ int DFT_FxcPrepareSpin(XCSolver *solver, long long ngrid, int nao, int nocc, uns
 int DFT_FxcApplyKind(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm1_ptr, unsigned long long d_ao_ptr,
                      unsigned long long d_ao_grad_ptr, unsigned long long d_v1_ptr, int kind);
 
+/* Open-shell (spin-resolved) sweep: Exc[dm_a, dm_b] into *exc and the XC potential matrices of the two spins,
+ *     V_s = d Exc / d dm_s,   s = alpha, beta,
+ * into d_vxc_a / d_vxc_b (nao, nao), in the convention DFT_ComputeXC writes Vxc in for the solver's type (one-sided for
+ * SOLVER_GGA and SOLVER_MIX -- (V_s + V_s^T)/2 is the symmetric matrix --, M + M^T for SOLVER_B3LYP, symmetric for
+ * SOLVER_LDA).  dm_a / dm_b (nao, nao): the spin density matrices (their symmetric parts count); the other arguments
+ * as DFT_ComputeXC64.  At dm_a = dm_b = dm/2 and "quirks" = 0 the call gives DFT_ComputeXC(dm)'s Exc and Vxc, twice, to
+ * rounding.  The potentials are first derivatives of the spin-resolved ENERGY bodies (csrc/xc_spin_functionals.hpp,
+ * forward mode; nothing is differentiated by hand): at "quirks" = 1 a functional with vwn5_c or pbe_c is refused, whose
+ * shipped potentials are not those derivatives.  A point where one spin's density is below the cut-off (1e-12) is
+ * evaluated as fully polarised: that spin contributes nothing and receives no potential there, the other one gets the
+ * zeta = +-1 limit.
+ * Order of work on the solver's stream: the density kernels of the sweep on dm_a, then on dm_b, one pointwise kernel
+ * ("xc_points_spin"), the sweep's contraction and reduce for alpha, then for beta, with the sweep's choices ("path",
+ * "vxc_fringe", nao, plane size) -- never the one-kernel plan for small bases, never a recorded graph, never the
+ * occupied-orbital density step.  Synchronous: returns after Exc has been copied to *exc.  Prepared DFT_Fxc* tables and
+ * later DFT_ComputeXC* calls are not disturbed.  Returns 0, or -1 with DFT_GetLastError (nothing aborts): a null
+ * pointer, bad sizes, a null ao_grad on a gradient solver, the "quirks" case above.  Added without a change of
+ * DFT_GetVersion (it stays 5): look the symbol up. */
+int DFT_ComputeXCSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr,
+                      unsigned long long d_dm_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
+                      unsigned long long d_weights_ptr, unsigned long long d_vxc_a_ptr, unsigned long long d_vxc_b_ptr,
+                      double *exc);
+
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
  * reference builds the whole tensor on the host with PySCF, `mol.intor('int2e')` at grid.py:65).  Device counterpart
@@ -474,8 +497,9 @@ const char *DFT_GetLastError(XCSolver *solver);
 /* With option "profile"=1: durations (ms) of the kernels of the last
  * DFT_ComputeXC* call (with option "dm_factor": "dm_factor" and "dm_factor_check" in front) or of the last
  * DFT_FactorDensity, DFT_FxcPrepare ("rho" or "rho_occ", "fxc_table"), DFT_FxcPrepareSpin (the same with
- * "fxc_table_spin") or DFT_FxcApply / DFT_FxcApplyKind ("rho", "fxc_coef", "fxc_vxc",
- * "fxc_reduce"), in launch order; names[i] (if non-NULL) receives a
+ * "fxc_table_spin"), DFT_FxcApply / DFT_FxcApplyKind ("rho", "fxc_coef", "fxc_vxc",
+ * "fxc_reduce") or DFT_ComputeXCSpin ("rho" for alpha, "rho" for beta, "xc_points_spin", "fxc_vxc" and
+ * "fxc_reduce" for alpha -- the contraction without an energy --, "vxc" and "reduce_vxc" for beta), in launch order; names[i] (if non-NULL) receives a
  * static string.  Returns the number of entries written (<= max_entries). */
 int DFT_GetTimings(XCSolver *solver, double *ms, const char **names, int max_entries);
 

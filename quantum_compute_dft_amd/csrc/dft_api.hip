@@ -31,6 +31,7 @@
 #include "xc_tiny_launch.hpp"
 #include "dm_factor_launch.hpp"
 #include "xc_response_launch.hpp"
+#include "xc_spin_launch.hpp"
 
 using namespace qcdft;
 
@@ -130,6 +131,9 @@ struct XCSolver {
     DevBuf fxc_spin_table[2], fxc_spin_g0[2];
     long fxc_spin_ngrid[2] = {0, 0};
     int fxc_spin_nao[2] = {0, 0};
+    // DFT_ComputeXCSpin: densities, gradients and coefficient planes of the two spins, the partials and the scalar of its
+    // Exc -- buffers of its own, so that no recorded sweep and no prepared response table holds or reads any of them
+    DevBuf spin_rho[2], spin_grad[2], spin_sigma, spin_coef[2], spin_partial, spin_exc;
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -165,10 +169,10 @@ void drop_graphs(XCSolver *s)
     ++s->graph_gen;
 }
 
-bool reserve(XCSolver *s, DevBuf &b, size_t bytes, const char *what)
+bool reserve(XCSolver *s, DevBuf &b, size_t bytes, const char *what, bool recorded = true)
 {
     if (bytes <= b.cap) return true;
-    drop_graphs(s); // recorded launches hold the old workspace pointers
+    if (recorded) drop_graphs(s); // recorded launches hold the old workspace pointers (false: a buffer no recorded sweep touches)
     if (b.p) {
         (void)hipStreamSynchronize(s->stream);
         (void)hipFree(b.p);
@@ -558,6 +562,71 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
     }
     const ExcFinish fin{nxb, partial, exc, want_host_exc};
     return vxc_stage(s, P, tiny, ngrid, nao, ao, coef, slabs, vxc, &fin);
+}
+
+// The spin-resolved sweep (DFT_ComputeXCSpin): the closed-shell sweep's density kernels on dm_a and on dm_b (linear in
+// the matrix), one pointwise kernel (xc_spin.hip), the closed-shell contraction and reduce once per spin; the second
+// reduce finishes Exc from the pointwise kernel's partials, as xc_sweep's does.  Never the one-kernel plan for small
+// bases (it keeps no density), never recorded.  Shares Dsym, the slabs and M with the other entries (stream order), and
+// nothing else: the fxc_* tables and the workspace a recorded sweep holds are not written.
+bool xc_sweep_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
+                   const double *ao_grad, const double *w, double *vxc_a, double *vxc_b, double *exc_host)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
+    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
+    if (!dm_a || !dm_b || !ao || !w || !vxc_a || !vxc_b || !exc_host) {
+        set_error(s, "DFT_ComputeXCSpin needs both density matrices, the AO values, the grid weights, both output matrices and exc");
+        return false;
+    }
+    const bool gga = s->needs_grad;
+    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
+    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+    if (s->quirks && (type == 0 || type == 1 || (type == 3 && (s->mix.c[XC_VWN5_C] != 0.0 || s->mix.c[XC_PBE_C] != 0.0)))) {
+        set_error(s, "DFT_ComputeXCSpin: the spin-resolved potentials are the first derivatives of the energy, but with quirks = 1 the "
+                     "ground state solved the shipped vwn5_c / pbe_c potentials, which are not the derivatives of their energies; "
+                     "run with --quirks 0");
+        return false;
+    }
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const size_t ng = (size_t)ngrid;
+    const long nxb = spin_points_blocks(ngrid);
+    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
+        !reserve(s, s->slabs, sizeof(double) * (size_t)P.nslab * nao * nao, "hipMalloc(slabs)") ||
+        !reserve(s, s->spin_partial, sizeof(double) * nxb, "hipMalloc(spin partial)", false) ||
+        !reserve(s, s->spin_exc, 2 * sizeof(double), "hipMalloc(spin exc)", false))
+        return false;
+    for (int k = 0; k < 2; ++k) {
+        if (!reserve(s, s->spin_rho[k], sizeof(double) * ng, "hipMalloc(spin rho)", false) ||
+            !reserve(s, s->spin_coef[k], sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(spin coef)", false))
+            return false;
+        if (gga && !reserve(s, s->spin_grad[k], sizeof(double) * 3 * ng, "hipMalloc(spin grad)", false)) return false;
+    }
+    if (gga && !reserve(s, s->spin_sigma, sizeof(double) * ng, "hipMalloc(spin sigma)", false)) return false;
+    double *Dp = (double *)s->dsym.p, *slabs = (double *)s->slabs.p, *sigma = (double *)s->spin_sigma.p;   // sigma: what the density kernels write beside the gradient; not read
+    double *rho_a = (double *)s->spin_rho[0].p, *rho_b = (double *)s->spin_rho[1].p;
+    double *g_a = (double *)s->spin_grad[0].p, *g_b = (double *)s->spin_grad[1].p;
+    double *c_a = (double *)s->spin_coef[0].p, *c_b = (double *)s->spin_coef[1].p;
+    double *partial = (double *)s->spin_partial.p, *exc = (double *)s->spin_exc.p;
+    launch_density(s, P, ngrid, nao, dm_a, ao, Dp, rho_a, g_a, sigma);
+    launch_density(s, P, ngrid, nao, dm_b, ao, Dp, rho_b, g_b, sigma);
+    {
+        ScopedTimer t(s, "xc_points_spin");
+        if (!hip_ok(s, launch_xc_points_spin(s->stream, type, gga, s->mix.c, ngrid, rho_a, rho_b, gga ? g_a : nullptr, gga ? g_b : nullptr,
+                                             w, c_a, c_b, partial), "spin pointwise launch"))
+            return false;
+    }
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, c_a, slabs, vxc_a, nullptr)) return false;
+    const ExcFinish fin{nxb, partial, exc, false};   // no host-mapped word, no publishing: Exc is copied below
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, c_b, slabs, vxc_b, &fin)) return false;
+    double out = std::numeric_limits<double>::quiet_NaN();
+    if (!hip_ok(s, hipMemcpyAsync(&out, exc, sizeof(double), hipMemcpyDeviceToHost, s->stream), "copy Exc") ||
+        !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
+        return false;
+    *exc_host = out;
+    if (std::isnan(out)) { set_error(s, "Exc is NaN after the spin sweep completed (non-finite inputs)"); return false; }
+    return true;
 }
 
 // Linear response of Vxc, first half: the ground-state density step of a sweep (never the one-kernel plan for small
@@ -1264,7 +1333,9 @@ void DFT_DestroySolver(XCSolver *s)
         DevBuf *bufs[] = {&s->dsym, &s->rho, &s->sigma, &s->grad, &s->coef, &s->partial,
                           &s->slabs, &s->exc, &s->jpart, &s->kpart, &s->shells, &s->msym,
                           &s->cdy, &s->cdc, &s->cdv, &s->cdy2, &s->cdc2, &s->cdbt, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0,
-                          &s->fxc_spin_table[0], &s->fxc_spin_table[1], &s->fxc_spin_g0[0], &s->fxc_spin_g0[1]};
+                          &s->fxc_spin_table[0], &s->fxc_spin_table[1], &s->fxc_spin_g0[0], &s->fxc_spin_g0[1],
+                          &s->spin_rho[0], &s->spin_rho[1], &s->spin_grad[0], &s->spin_grad[1], &s->spin_sigma, &s->spin_coef[0],
+                          &s->spin_coef[1], &s->spin_partial, &s->spin_exc};
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
@@ -1558,6 +1629,16 @@ int DFT_FxcApply(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm1
     if (!s) return -1;
     DeviceGuard dg(s);
     return fxc_apply(s, (long)ngrid, nao, (const double *)d_dm1, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_v1) ? 0 : -1;
+}
+
+int DFT_ComputeXCSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                      unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_w,
+                      unsigned long long d_vxc_a, unsigned long long d_vxc_b, double *exc)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_sweep_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
+                         (const double *)d_ao_grad, (const double *)d_w, (double *)d_vxc_a, (double *)d_vxc_b, exc) ? 0 : -1;
 }
 
 void DFT_ComputeCoulomb(XCSolver *s, int nao, unsigned long long d_eri, unsigned long long d_dm,

@@ -135,4 +135,33 @@ int qc_spin_energy(const double *mix8, long long n, const double *ra, const doub
     return 0;
 }
 
+// One point of the spin-resolved sweep, xc::spin_potential_point as k_xc_points_spin runs it (a built-in type enters as
+// its component weights and its factor, as in launch_xc_points_spin).  ga3 / gb3: three per point, interleaved (may be
+// null for an LDA-class functional).  out (14, n): e (no weight); c0..c3 of alpha; c0..c3 of beta; the bare derivatives
+// of e by rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb (zero for an absent channel).
+int qc_xc_point_spin(int type, const double *mix8, long long n, const double *ra, const double *rb, const double *ga3,
+                     const double *gb3, const double *w, double *out)
+{
+    if (type < 0 || type > 3 || (type == 3 && !mix8) || n < 0 || !ra || !rb || !w || !out) return -1;
+    xc::MixWeights m = weights(mix8);
+    const double scale = type == 3 ? 1.0 : xc::builtin_spin_mix(type, m);
+    const bool gga = mix_gga(m);
+    if (gga && (!ga3 || !gb3)) return -1;
+    for (long long g = 0; g < n; ++g) {
+        xc::SpinPoint p;
+        if (gga)
+            p = xc::spin_potential_point<true>(m, ra[g], rb[g], ga3[3 * g], ga3[3 * g + 1], ga3[3 * g + 2], gb3[3 * g],
+                                               gb3[3 * g + 1], gb3[3 * g + 2], w[g], scale);
+        else
+            p = xc::spin_potential_point<false>(m, ra[g], rb[g], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, w[g], scale);
+        out[g] = p.e;
+        for (int k = 0; k < 4; ++k) {
+            out[(1 + k) * n + g] = p.a[k];
+            out[(5 + k) * n + g] = p.b[k];
+        }
+        for (int k = 0; k < 5; ++k) out[(9 + k) * n + g] = p.d[k];
+    }
+    return 0;
+}
+
 } // extern "C"

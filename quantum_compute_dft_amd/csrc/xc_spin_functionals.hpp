@@ -72,6 +72,7 @@ QCDFT_XC_FN Dual2 fabs(Dual2 a) { return a.v < 0.0 ? -a : a; }
 // sigma at or below its cut-off, as said at the top: value zero, the first direction's part only.
 QCDFT_XC_FN double sigma_at_cut(double) { return 0.0; }
 QCDFT_XC_FN Dual2 sigma_at_cut(Dual2 a) { return {0.0, a.a, 0.0, 0.0}; }
+QCDFT_XC_FN Dual sigma_at_cut(Dual a) { return {0.0, a.d}; }   // first order: the finite vsigma of that limit, as the closed-shell bodies keep it
 
 constexpr double kFpp0 = 1.709920934161365617563962776245;   // f''(0) = 4 / (9 (2^(1/3) - 1))
 constexpr double kFden = 0.5198420997897463295344212145565;  // 2^(4/3) - 2
@@ -333,6 +334,74 @@ QCDFT_XC_FN void spin_table_point(const MixWeights &m, int kind, int which, doub
                                              Dual2(q, 0.0, kind == 1 ? 0.0 : 0.25, 0.0), Dual2(q, 0.0, 0.25 * sg, 0.0));
         *t1 = scale * e.ab;
     }
+}
+
+// One ground-state point of the spin-resolved sweep (DFT_ComputeXCSpin): the energy per volume e and, per spin s (s' the
+// other one), the coefficients the Vxc kernels contract with the AO planes, in the layout and the convention of the
+// closed-shell point bodies:
+//     c0_s  = scale w e_rho_s
+//     c_s,k = 2 scale w (2 e_sigma_ss grad rho_s + e_sigma_ab grad rho_s')_k
+// one-sided like gga_point / mix_point (the caller averages V_s with its transpose); at rho_a = rho_b, grad rho_a =
+// grad rho_b these are w vrho and w 4 vsigma g_k of the closed shell.  `scale`: 1, and B3LYP's 1/2 (builtin_spin_mix), whose
+// slabs come out as M + M^T.  The five first derivatives are xc::Dual through the bodies above, one evaluation after the
+// other, so that one evaluation's registers are live at a time; d[] keeps them bare (ra, rb, saa, sab, sbb) for the tests.
+//
+// Polarised points: a channel whose density is below kRhoCut is absent -- its rho, its sigma_ss and sigma_ab count as
+// exactly 0, its coefficients are 0 and it is not differentiated (d phi / d zeta of pbe_c diverges at |zeta| = 1, and a
+// cbrt(Dual) at 0 is 0/0); the other channel gets the zeta = +-1 limit of the bodies, whose guards (p > 0, ra > 0, the
+// cut-offs of the exchange channels) never look at the absent side.  Both absent: zeros.
+struct SpinPoint {
+    double e;
+    double a[4], b[4];
+    double d[5];
+};
+
+template <bool GGA>
+QCDFT_XC_FN SpinPoint spin_potential_point(const MixWeights &m, double ra, double rb, double gax, double gay, double gaz,
+                                           double gbx, double gby, double gbz, double w, double scale)
+{
+    SpinPoint o = {};
+    const bool pa = ra >= kRhoCut, pb = rb >= kRhoCut;
+    if (!pa && !pb) return o;
+    if (!pa) ra = 0.0;
+    if (!pb) rb = 0.0;
+    double saa = 0.0, sab = 0.0, sbb = 0.0;
+    if (GGA) {
+        if (pa) saa = gax * gax + gay * gay + gaz * gaz;
+        if (pb) sbb = gbx * gbx + gby * gby + gbz * gbz;
+        if (pa && pb) sab = gax * gbx + gay * gby + gaz * gbz;
+    }
+    if (pa) {
+        const Dual e = spin_mix_energy<GGA>(m, Dual(ra, 1.0), Dual(rb), Dual(saa), Dual(sab), Dual(sbb));
+        o.e = e.v;
+        o.d[0] = e.d;
+    }
+    if (pb) {
+        const Dual e = spin_mix_energy<GGA>(m, Dual(ra), Dual(rb, 1.0), Dual(saa), Dual(sab), Dual(sbb));
+        if (!pa) o.e = e.v;
+        o.d[1] = e.d;
+    }
+    const double sw = scale * w;
+    if (pa) o.a[0] = sw * o.d[0];
+    if (pb) o.b[0] = sw * o.d[1];
+    if (!GGA) return o;
+    if (pa) o.d[2] = spin_mix_energy<GGA>(m, Dual(ra), Dual(rb), Dual(saa, 1.0), Dual(sab), Dual(sbb)).d;
+    if (pa && pb) o.d[3] = spin_mix_energy<GGA>(m, Dual(ra), Dual(rb), Dual(saa), Dual(sab, 1.0), Dual(sbb)).d;
+    if (pb) o.d[4] = spin_mix_energy<GGA>(m, Dual(ra), Dual(rb), Dual(saa), Dual(sab), Dual(sbb, 1.0)).d;
+    const double f = 2.0 * sw;
+    if (pa) {
+        const double u = 2.0 * o.d[2], v = pb ? o.d[3] : 0.0;
+        o.a[1] = f * (u * gax + (pb ? v * gbx : 0.0));
+        o.a[2] = f * (u * gay + (pb ? v * gby : 0.0));
+        o.a[3] = f * (u * gaz + (pb ? v * gbz : 0.0));
+    }
+    if (pb) {
+        const double u = 2.0 * o.d[4], v = pa ? o.d[3] : 0.0;
+        o.b[1] = f * (u * gbx + (pa ? v * gax : 0.0));
+        o.b[2] = f * (u * gby + (pa ? v * gay : 0.0));
+        o.b[3] = f * (u * gbz + (pa ? v * gaz : 0.0));
+    }
+    return o;
 }
 
 // The component weights and the factor of a built-in solver type (0 LDA, 1 GGA, 2 B3LYP), as its point body mixes

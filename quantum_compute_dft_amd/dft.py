@@ -140,6 +140,10 @@ def main(argv=None):
     p.add_argument("--triplets", action="store_true",
                    help="with --excitations: the N lowest TRIPLET excitations (spin-flip XC kernel on the device: DFT_FxcPrepareSpin / "
                         "DFT_FxcApplyKind; no Coulomb response, oscillator strengths are zero); needs --quirks 0 with vwn5_c or pbe_c")
+    p.add_argument("--spin", type=int, default=None, metavar="N",
+                   help="N = nalpha - nbeta: an unrestricted (UKS) run with the spin-resolved XC sweep (DFT_ComputeXCSpin) and the host loop "
+                        "(--spin 0 too); one rank, --ao resident; needs --quirks 0 with vwn5_c or pbe_c.  Without the flag: the closed shell")
+    p.add_argument("--charge", type=int, default=0, metavar="Q", help="charge of the molecule (electrons = sum Z - Q); an odd count needs --spin")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
     args = p.parse_args(argv)
@@ -156,6 +160,20 @@ def main(argv=None):
         p.error("--triplets goes with --excitations N")
     if args.excitations and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident"):
         p.error("--excitations runs on one rank with --ao resident")
+
+    uks = args.spin is not None
+    if uks:
+        if args.excitations or args.polarizability or args.dipole:
+            p.error("--excitations, --polarizability and --dipole take a closed-shell reference: not available after an unrestricted (--spin) run")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident" or args.dm_factor:
+            p.error("--spin (UKS) runs on one rank with --ao resident and without --dm-factor")
+        if args.fused_tail > 0 or args.device_resident > 0:
+            p.error("--spin (UKS) walks the host loop: not with --fused-tail 1 or --device-resident 1")
+        if args.both_quirks:
+            p.error("--spin (UKS) has one form of every functional (the derivatives of the energy): not with --both-quirks")
+        if args.quirks and fn.uses_quirks:
+            p.error("--spin (UKS): the spin-resolved potentials are the first derivatives of the energy, but with quirks = 1 the shipped "
+                    "vwn5_c / pbe_c potentials are not the derivatives of their energies; run with --quirks 0")
 
     # one process per GPU: `python -m torch.distributed.run --nproc-per-node N -m quantum_compute_dft_amd.dft ...`
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -191,8 +209,14 @@ def main(argv=None):
         _nao = _basis.build_shells(*_basis.parse_xyz(atom_path), args.basis).nao
         args.eri = "dense" if 8.0 * _nao ** 4 <= 8.0e9 else "cholesky"
     charges = read_point_rows(args.point_charges, 4, args.point_charges_unit) if args.point_charges else None
-    inp = inputs.build(atom_path, args.basis, args.grid_level, device=device, eri_mode=args.eri, chol_tol=args.chol_tol, rank=rank, world=world,
-                       point_charges=charges, efield=args.efield)
+    try:
+        inp = inputs.build(atom_path, args.basis, args.grid_level, device=device, eri_mode=args.eri, chol_tol=args.chol_tol, rank=rank, world=world,
+                           point_charges=charges, efield=args.efield, charge=args.charge, spin=args.spin or 0)
+    except ValueError as e:      # an odd electron count without --spin, a charge and spin that do not fit, a bad charge file
+        print(f"Error: {e}")
+        sys.exit(1)
+    if uks:
+        print(f"Unrestricted (UKS): charge {inp.charge}, spin (nalpha - nbeta) {inp.spin}: {inp.nalpha} alpha and {inp.nbeta} beta electrons")
     if args.efield is not None:
         print(f"Uniform external field: F = ({args.efield[0]:+.6f}, {args.efield[1]:+.6f}, {args.efield[2]:+.6f}) a.u.")
     if charges is not None:
@@ -202,14 +226,14 @@ def main(argv=None):
     print("Moving data to GPU...")
     try:
         backend = scf.HipBackend(inp, args.functional, args.lib, quirks=bool(args.quirks), rank=rank, world=world, device=device,
-                                 device_resident=None if args.device_resident < 0 else bool(args.device_resident),
-                                 fused_tail=None if args.fused_tail < 0 else bool(args.fused_tail),
-                                 eigensolver=args.eigensolver, ao_mode=args.ao, xc_occ=bool(args.xc_occ), dm_factor=args.dm_factor)
+                                 device_resident=False if uks else None if args.device_resident < 0 else bool(args.device_resident),
+                                 fused_tail=False if uks else None if args.fused_tail < 0 else bool(args.fused_tail),
+                                 eigensolver="exact" if uks else args.eigensolver, ao_mode=args.ao, xc_occ=bool(args.xc_occ), dm_factor=args.dm_factor)
     except Exception as e:  # dft.py:149-153
         print(e)
         sys.exit(1)
     print(f"GPU Init Time: {backend.init_time:.4f}s" + (f"  ({world} ranks: grid block + Cholesky-vector slice per GPU)" if world > 1 else ""))
-    res = scf.run_scf(inp, backend, args.functional)
+    res = scf.run_uks(inp, backend, args.functional) if uks else scf.run_scf(inp, backend, args.functional)
     eig_stats = dict(backend.occ_solver.stats) if backend.occ_solver is not None else None   # of THIS run (the second one below adds to the counters)
     other = None
     if args.both_quirks and fn.uses_quirks:   # only VWN5 and PBE-c have two forms (B3LYP's four components are derivative-correct: one answer)
@@ -225,6 +249,8 @@ def main(argv=None):
         print(f"E_xc_dft    : {res['E_xc']:.8f} Ha")
         if fn.c_hf != 0.0:
             print(f"E_ex_hf     : {res['E_ex_hf']:.8f} Ha")
+        if uks:
+            print(f"<S^2>       : {res['s_squared']:.6f}   (Sz (Sz + 1) = {0.25 * inp.spin * (inp.spin + 2):.6f})")
         print(f"Total Time  : {res['total_time']:.4f} s"); print("-" * 80)
         print("Kernel Statistics (Avg per iter):"); print(f"XC(Exc+Vxc) Time: {res['xc_ms_avg']:.4f} ms")
         print(f"Median per cycle after the first: XC {res['xc_ms']:.4f} ms, J/K {res['jk_ms']:.4f} ms ({args.eri} ERI), "
@@ -294,7 +320,12 @@ def main(argv=None):
               "E_ex_hf": res.get("E_ex_hf"), "E_nuc": float(inp.E_nuc), "total_time_s": res.get("total_time"),
               "xc_ms_avg": res.get("xc_ms_avg"), "xc_ms": res.get("xc_ms"), "jk_ms": res.get("jk_ms"), "iter_ms": res.get("iter_ms"),
               "cycle_ms": res.get("cycle_ms"), "gpu_init_s": backend.init_time, "device_resident": bool(backend.device_resident), "loop": res.get("loop", "device" if backend.device_resident else "host"), "ao": args.ao, "eigensolver": args.eigensolver,
-              "eigensolver_stats": eig_stats, "xc_occ": int(backend.xc_occ), "dm_factor": int(backend.dm_factor)}
+              "eigensolver_stats": eig_stats, "xc_occ": int(backend.xc_occ), "dm_factor": int(backend.dm_factor),
+              "charge": int(inp.charge), "spin": int(inp.spin), "uks": bool(uks)}
+    if uks:
+        record["loop"] = "host-uks"
+        record["nalpha"], record["nbeta"] = int(inp.nalpha), int(inp.nbeta)
+        record["s_squared"] = res.get("s_squared")
     if charges is not None:
         record["n_point_charges"] = int(len(charges)); record["E_nuc_ext"] = float(inp.E_nuc_ext)
         record["point_charge_forces"] = charge_forces.tolist() if charge_forces is not None else None
@@ -323,7 +354,7 @@ def main(argv=None):
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
-    pyscf_xc = {"LDA": "slater,vwn5", "GGA": "PBE,PBE", "B3LYP": "b3lyp"}.get(args.functional)
+    pyscf_xc = None if uks else {"LDA": "slater,vwn5", "GGA": "PBE,PBE", "B3LYP": "b3lyp"}.get(args.functional)
     if importlib.util.find_spec("pyscf") is None or rank or pyscf_xc is None:   # dft.py:272-297 needs PySCF; the three reference functionals only
         print("\nPySCF not importable here: reference cross-check skipped.")
         return res

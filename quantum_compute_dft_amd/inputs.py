@@ -32,6 +32,10 @@ class SCFInputs:
     V_ext: np.ndarray = None  # (nao, nao) potential of those charges on the electrons, already part of Hcore
     E_nuc_ext: float = 0.0    # nuclei -- external charges repulsion, already part of E_nuc
     efield: np.ndarray = None  # (3,) uniform external electric field F in a.u. (build(..., efield=...)), already part of Hcore and E_nuc
+    nalpha: int = None   # electrons of the two spins (build(..., charge, spin)); None: nocc each, the closed shell
+    nbeta: int = None
+    charge: int = 0
+    spin: int = 0        # nalpha - nbeta
 
 
 def external_charges(symbols, atom_xyz, shells, point_charges, device="cpu"):
@@ -65,7 +69,7 @@ def uniform_field(symbols, atom_xyz, shells, efield):
 
 
 def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=True, eri_mode="dense",
-          chol_tol=1e-9, rank=0, world=1, group=None, point_charges=None, efield=None):
+          chol_tol=1e-9, rank=0, world=1, group=None, point_charges=None, efield=None, charge=0, spin=0):
     """grid.py:42-67.  `atom_path`: an .xyz file (or a molecule name resolved in data/).
     eri_mode "dense": the (nao^4) tensor of grid.py:65; "cholesky": pivoted Cholesky vectors only.
     world > 1 (torch.distributed initialised): the Cholesky factorisation -- the one expensive step, host integral columns
@@ -75,17 +79,29 @@ def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=Tr
     gains the nuclei--charges repulsion, so every SCF loop runs in the field of the charges unchanged; their interaction
     among themselves is not included.  Every rank computes V_ext itself (deterministic: nothing is broadcast).
     efield: (Fx, Fy, Fz) in a.u. -- a uniform external electric field (uniform_field): Hcore gains sum_k F_k D_k and E_nuc
-    -sum_A Z_A F.R_A, so every SCF loop, the fused tail included, runs in the field with no other change."""
+    -sum_A Z_A F.R_A, so every SCF loop, the fused tail included, runs in the field with no other change.
+    charge, spin: the molecule's charge and nalpha - nbeta (scf.run_uks); the defaults are the neutral closed shell.
+    nelec = sum Z - charge, nalpha = (nelec + spin) / 2, nbeta = (nelec - spin) / 2, nocc = nbeta; ValueError when spin is
+    negative, exceeds the electron count or has not its parity (an odd count needs --spin), or no electron is left."""
     if not os.path.exists(atom_path):
         cand = os.path.join(DATA_DIR, atom_path if atom_path.endswith(".xyz") else atom_path + ".xyz")
         if os.path.exists(cand):
             atom_path = cand
     symbols, xyz = basis.parse_xyz(atom_path)
     shells = basis.build_shells(symbols, xyz, basis_name)
-    nelec = sum(basis.atomic_number(s) for s in symbols)
-    if nelec % 2:
-        raise ValueError("closed-shell (RKS) only: odd electron count")
-    nocc = nelec // 2
+    charge, spin = int(charge), int(spin)
+    nelec = sum(basis.atomic_number(s) for s in symbols) - charge
+    if nelec <= 0:
+        raise ValueError(f"charge {charge} leaves no electrons ({nelec})")
+    if spin < 0 or spin > nelec:
+        raise ValueError(f"spin (nalpha - nbeta) = {spin} does not fit {nelec} electrons: expected 0 <= spin <= {nelec}")
+    if (nelec - spin) % 2:
+        raise ValueError(f"{nelec} electrons (charge {charge}) and spin (nalpha - nbeta) = {spin} have different parity: "
+                         f"an {'odd' if nelec % 2 else 'even'} electron count needs an {'odd' if nelec % 2 else 'even'} --spin")
+    nalpha, nbeta = (nelec + spin) // 2, (nelec - spin) // 2
+    if nalpha > shells.nao:
+        raise ValueError(f"spin {spin}: {nalpha} alpha electrons do not fit {shells.nao} basis functions")
+    nocc = nbeta                     # the closed shell: nelec // 2 as ever
     if verbose:  # grid.py:54-56,60
         print(f"Number of basis functions: {shells.nao}")
         print(f"Number of electrons: {nelec}")
@@ -131,6 +147,7 @@ def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=Tr
         pc, V_ext, E_ext = external_charges(symbols, xyz, shells, point_charges, device)
         inp = SCFInputs(symbols, xyz, shells, grids, S, T, V, T + V + V_ext, eri,
                         integrals.energy_nuc(symbols, xyz) + E_ext, nocc, nelec, chol, chol_range, pc, V_ext, E_ext)
+    inp.nalpha, inp.nbeta, inp.charge, inp.spin = nalpha, nbeta, charge, spin
     if efield is not None:
         F, V_F, E_F = uniform_field(symbols, xyz, shells, efield)
         inp.Hcore = inp.Hcore + V_F

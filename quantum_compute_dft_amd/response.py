@@ -35,6 +35,8 @@ def _load():
         L.qc_fxc_table_spin.argtypes = [ctypes.c_int, dp, ctypes.c_int, ctypes.c_longlong, dp, dp, dp]
         L.qc_spin_energy.restype = ctypes.c_int
         L.qc_spin_energy.argtypes = [dp, ctypes.c_longlong, dp, dp, dp, dp, dp, dp]
+        L.qc_xc_point_spin.restype = ctypes.c_int
+        L.qc_xc_point_spin.argtypes = [ctypes.c_int, dp, ctypes.c_longlong, dp, dp, dp, dp, dp, dp]
         _lib = L
     return _lib
 
@@ -141,6 +143,51 @@ def _density(dm, ao, ao_grad):
     if ao_grad is None:
         return rho, None
     return rho, 2.0 * np.stack([np.einsum("gi,gi->g", x, ao_grad[k]) for k in range(3)], axis=1)
+
+
+def point_spin_host(functional, ra, rb, grad_a=None, grad_b=None, weights=None):
+    """(14, n): one point of the spin-resolved sweep as k_xc_points_spin evaluates it (xc::spin_potential_point compiled for
+    the host): row 0 the energy per volume e (no weight), rows 1..4 the alpha coefficients c0..c3, rows 5..8 the beta ones
+    (c0_s = scale w e_rho_s, c_s,k = 2 scale w (2 e_sigma_ss grad rho_s + e_sigma_ab grad rho_s')_k, scale = 1/2 for B3LYP),
+    rows 9..13 the bare derivatives of e by rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb.  grad_a / grad_b (n, 3) (zeros if
+    None), weights (n,) (ones if None).  A channel below the density cut-off is absent: zeros in its rows and columns."""
+    t, w8, gga = _kind(functional)
+    ra = np.ascontiguousarray(np.atleast_1d(ra), dtype=np.float64)
+    rb = np.ascontiguousarray(np.broadcast_to(np.asarray(rb, dtype=np.float64), ra.shape))
+    if ra.ndim != 1:
+        raise ValueError("point_spin_host: one-dimensional arrays of one length")
+    ga, gb = (np.zeros((ra.size, 3)) if g is None else np.ascontiguousarray(g, dtype=np.float64) for g in (grad_a, grad_b))
+    w = np.ones(ra.size) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if ga.shape != (ra.size, 3) or gb.shape != (ra.size, 3) or w.shape != ra.shape:
+        raise ValueError("point_spin_host: gradients (n, 3) and weights (n,) for n points")
+    out = np.zeros((14, ra.size))
+    if _load().qc_xc_point_spin(t, _p(w8), ra.size, _p(ra), _p(rb), _p(ga), _p(gb), _p(w), _p(out)) != 0:
+        raise ValueError("point_spin_host: bad arguments")
+    return out
+
+
+def xc_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad=None):
+    """(Exc, V_alpha, V_beta) of the spin density matrices from AO planes in numpy, element for element what
+    DFT_ComputeXCSpin leaves: one-sided for GGA-type functionals and mixes ((V + V^T)/2 is the potential), M + M^T with
+    the halved coefficients for B3LYP, symmetric for LDA.  The spin-resolved bodies: no `quirks`."""
+    t, _, gga = _kind(functional)
+    if gga and ao_grad is None:
+        raise ValueError("ao_grad is needed for a gradient-corrected functional")
+    ao = np.ascontiguousarray(ao, dtype=np.float64)
+    gr = np.ascontiguousarray(ao_grad, dtype=np.float64) if gga else None
+    w = np.asarray(weights, dtype=np.float64)
+    ra, ga = _density(np.asarray(dm_a, dtype=np.float64), ao, gr)
+    rb, gb = _density(np.asarray(dm_b, dtype=np.float64), ao, gr)
+    p = point_spin_host(functional, ra, rb, ga, gb, w)
+    out = []
+    for c in (p[1:5], p[5:9]):
+        B = c[0][:, None] * ao
+        if gga:
+            for k in range(3):
+                B += c[1 + k][:, None] * gr[k]
+        M = B.T @ ao
+        out.append(M + M.T if t == 2 else M)
+    return float(w @ p[0]), out[0], out[1]
 
 
 class HostFxc:

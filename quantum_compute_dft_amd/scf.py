@@ -529,6 +529,50 @@ class HipBackend:
         return self.d_J, (self.d_K if self._want_k else None)
 
 
+    # ---- open-shell (scf.run_uks): one rank, resident AO planes, the host loop -----------------------------------------
+    def _uks_check(self):
+        if self.world > 1:
+            raise ValueError("open-shell DFT (UKS) runs on one rank: the grid of this backend is sharded over several")
+        if self.ao_mode != "resident":
+            raise ValueError("open-shell DFT (UKS) needs resident AO planes (--ao resident), not --ao direct")
+        if self.dm_factor:
+            raise ValueError("open-shell DFT (UKS) does not factorise its density matrices on the device: run without dm_factor")
+        if self.fused or self.device_resident:
+            raise ValueError("open-shell DFT (UKS) walks the host loop: build the backend with fused_tail=False and "
+                             "device_resident=False (the fused and the device-resident tail are closed-shell)")
+
+    def uks_parts(self, dm_a, dm_b, cocc_a, cocc_b, want_k):
+        """(J, K_alpha or None, K_beta or None, Exc, V_alpha_raw, V_beta_raw) of the spin density matrices dm_s = cocc_s
+        cocc_s^T, as numpy arrays: J of the total density and K of each spin through the closed-shell entries (Cholesky
+        vectors: one DFT_ComputeJKFactorized call for J with the total dm alone, one per spin for K with that spin's dm and
+        orbitals), Exc and the two potentials from DFT_ComputeXCSpin.  A spin without electrons has K = 0."""
+        self._uks_check()
+        t, n = self.torch, self.nao
+        up = lambda a: t.as_tensor(np.ascontiguousarray(a), dtype=t.float64, device=self.dev)
+        d_s = [up(dm_a), up(dm_b)]
+        d_c = [up(cocc_a), up(cocc_b)]
+        self.d_dm.copy_(d_s[0] + d_s[1])
+        if getattr(self, "_uks_out", None) is None:
+            self._uks_out = t.zeros((6, n, n), dtype=t.float64, device=self.dev)      # J | K_a | K_b | V_a | V_b | scratch
+        o = self._uks_out
+        o.zero_()
+        if self.d_chol is not None:
+            naux = self.d_chol.shape[0]
+            self.solver.compute_jk_factorized(n, naux, max(d_c[0].shape[1], 1), self.d_chol, self.d_dm, None, o[0], None)
+            for k in range(2):
+                if want_k and d_c[k].shape[1]:
+                    self.solver.compute_jk_factorized(n, naux, d_c[k].shape[1], self.d_chol, d_s[k], d_c[k], None, o[1 + k])
+        else:
+            self.solver.compute_coulomb(n, self.d_eri, self.d_dm, o[0])
+            for k in range(2):
+                if want_k and d_c[k].shape[1]:
+                    self.solver.compute_exchange(n, self.d_eri, d_s[k], o[1 + k])
+        exc = self.solver.compute_xc_spin(self.ngrid, n, d_s[0], d_s[1], self.d_ao, self.d_w, o[3], o[4], self.d_gr)
+        t.cuda.synchronize()
+        h = o.cpu().numpy()
+        return h[0], (h[1] if want_k else None), (h[2] if want_k else None), exc, h[3], h[4]
+
+
     # ---- linear response (response.polarizability): one rank, resident AO planes ------------------------------
     def _response_check(self):
         if self.world > 1:
@@ -1032,3 +1076,84 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     for ev in marks:                                                                   # device-side durations: nothing waited in between
         jk_times.append(1e-3 * ev[0].elapsed_time(ev[1])); xc_times.append(1e-3 * ev[1].elapsed_time(ev[2]))
     return _finish(res, t_start, xc_times, jk_times, it_times)
+
+
+def _blockdiag(a, b):
+    n = a.shape[0]
+    out = np.zeros((2 * n, 2 * n))
+    out[:n, :n], out[n:, n:] = a, b
+    return out
+
+
+def spin_square(S, cocc_a, cocc_b):
+    """<S^2> of a single determinant: Sz (Sz + 1) + N_beta - |C_a,occ^T S C_b,occ|_F^2."""
+    na, nb = cocc_a.shape[1], cocc_b.shape[1]
+    sz = 0.5 * (na - nb)
+    return sz * (sz + 1.0) + nb - float(np.sum((cocc_a.T @ S @ cocc_b) ** 2))
+
+
+def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, log=print):
+    """Unrestricted Kohn-Sham loop on the host, for inp.nalpha / inp.nbeta electrons of the two spins (inputs.build(...,
+    charge, spin)).  `backend.uks_parts(dm_a, dm_b, cocc_a, cocc_b, want_k)` supplies (J[D_a + D_b], K[D_a], K[D_b], Exc,
+    V_a, V_b) with the potentials in the library's convention (HipBackend on the device; the tests have a numpy one).
+
+        F_s = Hcore + J[D_a + D_b] + (V_s + V_s^T)/2 - c_hf K[D_s],        D_s = C_s,occ C_s,occ^T
+        E   = tr(D Hcore) + 1/2 tr(D J) - 1/2 c_hf sum_s tr(D_s K[D_s]) + Exc + E_nuc,    D = D_a + D_b
+
+    The loop keeps run_scf's contract: core guess eigh(Hcore, S) for both spins (at spin = 0 the two stay equal: no
+    broken-symmetry guess), one DIIS with common coefficients over both spins' error vectors (CDIIS as it stands, on the
+    block-diagonal matrices diag(F_a, F_b), diag(D_a, D_b), diag(S, S): the commutator of block-diagonal matrices holds
+    both errors, their Gram matrix is the sum), eigh(F_s, S) per spin, energies from the NEW densities with J / K / Exc of
+    the old ones, convergence |dE| < conv_e and |dD_a| + |dD_b| (Frobenius) < conv_dm.  With nalpha = nbeta the loop is
+    run_scf's host loop term by term.  Returns run_scf's fields with dm the total density, and dm_a, dm_b, mo_energy_a,
+    mo_energy_b, mo_coeff_a, mo_coeff_b, s_squared (spin_square), nalpha, nbeta, uks = True."""
+    from .hostinfo import blas_threads
+    c_hf = functionals.resolve(functional).c_hf
+    want_k = c_hf != 0.0
+    Hcore, S = inp.Hcore, inp.S
+    na = int(getattr(inp, "nalpha", None) if getattr(inp, "nalpha", None) is not None else inp.nocc)
+    nb = int(getattr(inp, "nbeta", None) if getattr(inp, "nbeta", None) is not None else inp.nocc)
+    if na < nb or nb < 0 or na <= 0 or na > S.shape[0]:
+        raise ValueError(f"run_uks: nalpha = {na}, nbeta = {nb} do not fit {S.shape[0]} basis functions (nalpha >= nbeta >= 0)")
+    S2 = _blockdiag(S, S)
+    with blas_threads(1 if S.shape[0] < 400 else None):
+        e0, C0 = eigh(Hcore, S)
+        ea = eb = e0
+        Ca = Cb = C0
+        cocc = [np.ascontiguousarray(C0[:, :na]), np.ascontiguousarray(C0[:, :nb])]
+        dm = [c @ c.T for c in cocc]
+        diis = CDIIS()
+        _log_header(log)
+        E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
+        res = {"converged": False, "uks": True, "nalpha": na, "nbeta": nb}
+        per_cycle = res["per_cycle"] = []
+        for cycle in range(max_cycle):
+            t_it = time.time()
+            J, Ka, Kb, E_xc, Va, Vb = backend.uks_parts(dm[0], dm[1], cocc[0], cocc[1], want_k)
+            t_parts = time.time() - t_it
+            xc_times.append(t_parts); jk_times.append(0.0)        # one bracket: the parts are not timed apart here
+            F = [Hcore + J + 0.5 * (V + V.T) - (c_hf * K if K is not None else 0.0) for V, K in ((Va, Ka), (Vb, Kb))]
+            Fx = diis.update(S2, _blockdiag(dm[0], dm[1]), _blockdiag(F[0], F[1]))
+            n = S.shape[0]
+            ea, Ca = eigh(Fx[:n, :n], S)
+            eb, Cb = eigh(Fx[n:, n:], S)
+            cocc_new = [np.ascontiguousarray(Ca[:, :na]), np.ascontiguousarray(Cb[:, :nb])]
+            dm_new = [c @ c.T for c in cocc_new]
+            D = dm_new[0] + dm_new[1]
+            E_one, E_coul = float(np.sum(D * Hcore)), 0.5 * float(np.sum(D * J))
+            E_ex = -0.5 * c_hf * float(np.sum(dm_new[0] * Ka) + np.sum(dm_new[1] * Kb)) if want_k else 0.0
+            ddm = float(np.linalg.norm(dm_new[0] - dm[0]) + np.linalg.norm(dm_new[1] - dm[1]))
+            E_tot = E_one + E_coul + E_xc + E_ex + inp.E_nuc
+            dE = E_tot - E_old
+            it_times.append(time.time() - t_it)
+            if log:
+                log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
+            res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1, dm=D,
+                       dm_a=dm_new[0], dm_b=dm_new[1], mo_energy_a=ea, mo_energy_b=eb, mo_coeff_a=Ca, mo_coeff_b=Cb,
+                       mo_energy=ea, s_squared=spin_square(S, cocc_new[0], cocc_new[1]))
+            per_cycle.append((E_tot, ddm))
+            dm, cocc, E_old = dm_new, cocc_new, E_tot
+            if abs(dE) < conv_e and ddm < conv_dm:
+                res["converged"] = True
+                break
+        return _finish(res, t_start, xc_times, jk_times, it_times)

@@ -140,6 +140,8 @@ class DFTSolverWrapper:
         L.DFT_FxcPrepareSpin.restype = ctypes.c_int
         L.DFT_FxcApplyKind.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, ctypes.c_int]
         L.DFT_FxcApplyKind.restype = ctypes.c_int
+        L.DFT_ComputeXCSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, _u64, _u64, dp]
+        L.DFT_ComputeXCSpin.restype = ctypes.c_int
 
         if self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
@@ -306,6 +308,17 @@ class DFTSolverWrapper:
                                        _u64(_ptr(d_ao_grad)), _u64(_ptr(d_v1)), int(kind))
         self._check()
         return rc
+
+    def compute_xc_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_weights, d_vxc_a, d_vxc_b, d_ao_grad=None):
+        """Exc of the spin density matrices d_dm_a / d_dm_b (DFT_ComputeXCSpin); the potentials of the two spins go to d_vxc_a /
+        d_vxc_b in compute_xc's convention for the functional.  The first derivatives of the spin-resolved energy bodies:
+        with option quirks = 1 a functional with vwn5_c or pbe_c is refused (RuntimeError).  Synchronous."""
+        exc = ctypes.c_double(float("nan"))
+        self.lib.DFT_ComputeXCSpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)), _u64(_ptr(d_ao)),
+                                   _u64(_ptr(d_ao_grad)), _u64(_ptr(d_weights)), _u64(_ptr(d_vxc_a)), _u64(_ptr(d_vxc_b)),
+                                   ctypes.byref(exc))
+        self._check()
+        return exc.value
 
     def mix(self):
         """The solver's weights as the library reports them (DFT_GetMix; for a built-in type: its equivalent mix)."""
