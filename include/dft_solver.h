@@ -335,6 +335,43 @@ int DFT_ComputeXCSpin(XCSolver *solver, long long ngrid, int nao, unsigned long 
                       unsigned long long d_weights_ptr, unsigned long long d_vxc_a_ptr, unsigned long long d_vxc_b_ptr,
                       double *exc);
 
+/* Linear response of DFT_ComputeXCSpin, in two halves like DFT_FxcPrepare / DFT_FxcApply: V1_s (nao, nao), s = alpha,
+ * beta, is, element for element, d/dt of what DFT_ComputeXCSpin(dm0_a + t dm1_a, dm0_b + t dm1_b) writes into vxc_s at
+ * t = 0, in that call's conventions (one-sided for SOLVER_GGA and SOLVER_MIX, M + M^T with the halved table for
+ * SOLVER_B3LYP, symmetric for SOLVER_LDA).  Only the symmetric parts of dm1_a / dm1_b count.  At dm0_a = dm0_b = dm0/2,
+ * dm1_a = dm1_b = dm1/2 gives V1_a = V1_b = DFT_FxcApplyKind(kind 2)'s V1, and dm1_a = -dm1_b = dm1/2 gives V1_a = -V1_b =
+ * kind 1's.
+ * DFT_FxcPrepareSpinPol, on the solver's stream: the density kernels of the sweep on dm0_a, then on dm0_b, exactly as
+ * DFT_ComputeXCSpin runs them, and the pointwise table ("fxc_table_pol", csrc/xc_response_pol.hip): with x = (rho_a,
+ * rho_b, sigma_aa, sigma_ab, sigma_bb) the weighted second derivatives H_ij of the spin-resolved ENERGY bodies and the
+ * first derivatives by the three sigmas, forward mode of second order, nothing differentiated by hand; independent of
+ * "quirks", but at "quirks" = 1 a functional with vwn5_c or pbe_c is refused for DFT_ComputeXCSpin's reason, in its
+ * sentence.  3 planes for an LDA-class functional; 28 otherwise: the 15 of the symmetric H, 3 first derivatives, and
+ * the 10 pairs in the other order, which differ from the first 10 only at a sigma cut-off of PBE exchange or
+ * correlation (the potential's variable keeps its derivative there, the perturbation sees a constant).  A point where
+ * one spin's density is below the cut-off (1e-12): that spin neither responds nor is responded to, its rows and columns
+ * are exactly 0; nothing is NaN or Inf.  The table and grad rho0_a, grad rho0_b stay in a slot of their own: the
+ * DFT_FxcPrepare table and the kind-1 and kind-2 slots are not disturbed, and neither they nor DFT_ComputeXC* /
+ * DFT_ComputeXCSpin calls in between disturb it.
+ * DFT_FxcApplySpinPol, asynchronous on the solver's stream, no host wait: the density kernels on dm1_a, then on dm1_b,
+ * one arithmetic kernel ("fxc_coef_pol") that couples the two spins, the sweep's contraction and reduce for alpha,
+ * then for beta, with the sweep's choices ("path", "vxc_fringe", nao, plane size) -- like DFT_ComputeXCSpin never the
+ * one-kernel plan, a recorded graph or the occupied-orbital density step.  Any number of Applies after one Prepare.
+ * Both return 0, or -1 with DFT_GetLastError (nothing aborts): a null pointer, bad sizes, a null ao_grad on a gradient
+ * solver, Apply before Prepare or with another ngrid / nao, the "quirks" case.  Added without a change of DFT_GetVersion
+ * (it stays 5): look the symbols up. */
+int DFT_FxcPrepareSpinPol(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm0_a_ptr,
+                          unsigned long long d_dm0_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
+                          unsigned long long d_weights_ptr);
+int DFT_FxcApplySpinPol(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm1_a_ptr,
+                        unsigned long long d_dm1_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
+                        unsigned long long d_v1_a_ptr, unsigned long long d_v1_b_ptr);
+
+/* For the tests: copies the table DFT_FxcPrepareSpinPol left (planes as listed at the top of csrc/xc_response_pol.hip, SoA,
+ * ngrid doubles each) to d_out on the solver's stream.  Returns the number of planes (3 or 28), or -1 with
+ * DFT_GetLastError: nothing prepared, or max_doubles below planes * ngrid. */
+int DFT_FxcSpinPolTable(XCSolver *solver, unsigned long long d_out_ptr, long long max_doubles);
+
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
  * reference builds the whole tensor on the host with PySCF, `mol.intor('int2e')` at grid.py:65).  Device counterpart
@@ -499,7 +536,8 @@ const char *DFT_GetLastError(XCSolver *solver);
  * DFT_FactorDensity, DFT_FxcPrepare ("rho" or "rho_occ", "fxc_table"), DFT_FxcPrepareSpin (the same with
  * "fxc_table_spin"), DFT_FxcApply / DFT_FxcApplyKind ("rho", "fxc_coef", "fxc_vxc",
  * "fxc_reduce") or DFT_ComputeXCSpin ("rho" for alpha, "rho" for beta, "xc_points_spin", "fxc_vxc" and
- * "fxc_reduce" for alpha -- the contraction without an energy --, "vxc" and "reduce_vxc" for beta), in launch order; names[i] (if non-NULL) receives a
+ * "fxc_reduce" for alpha -- the contraction without an energy --, "vxc" and "reduce_vxc" for beta), DFT_FxcPrepareSpinPol ("rho", "rho", "fxc_table_pol") or DFT_FxcApplySpinPol ("rho", "rho",
+ * "fxc_coef_pol", then "fxc_vxc", "fxc_reduce" twice), in launch order; names[i] (if non-NULL) receives a
  * static string.  Returns the number of entries written (<= max_entries). */
 int DFT_GetTimings(XCSolver *solver, double *ms, const char **names, int max_entries);
 

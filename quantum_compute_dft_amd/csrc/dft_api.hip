@@ -31,6 +31,7 @@
 #include "xc_tiny_launch.hpp"
 #include "dm_factor_launch.hpp"
 #include "xc_response_launch.hpp"
+#include "xc_response_pol_launch.hpp"
 #include "xc_spin_launch.hpp"
 
 using namespace qcdft;
@@ -131,6 +132,11 @@ struct XCSolver {
     DevBuf fxc_spin_table[2], fxc_spin_g0[2];
     long fxc_spin_ngrid[2] = {0, 0};
     int fxc_spin_nao[2] = {0, 0};
+    // DFT_FxcPrepareSpinPol: the second-derivative table of the energy at (rho0_a, rho0_b) and the two ground-state gradients,
+    // a slot of its own again; DFT_FxcApplySpinPol works in the spin_* buffers below, which every user overwrites whole
+    DevBuf fxc_pol_table, fxc_pol_g0[2];
+    long fxc_pol_ngrid = 0;
+    int fxc_pol_nao = 0;
     // DFT_ComputeXCSpin: densities, gradients and coefficient planes of the two spins, the partials and the scalar of its
     // Exc -- buffers of its own, so that no recorded sweep and no prepared response table holds or reads any of them
     DevBuf spin_rho[2], spin_grad[2], spin_sigma, spin_coef[2], spin_partial, spin_exc;
@@ -742,6 +748,113 @@ bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double
     return vxc_stage(s, P, false, ngrid, nao, ao, coef, (double *)s->slabs.p, v1, nullptr);
 }
 
+// The refusal DFT_ComputeXCSpin and the open-shell response share: second and first derivatives of the ENERGY.
+bool spin_quirks_ok(XCSolver *s, const char *who)
+{
+    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+    if (s->quirks && (type == 0 || type == 1 || (type == 3 && (s->mix.c[XC_VWN5_C] != 0.0 || s->mix.c[XC_PBE_C] != 0.0)))) {
+        set_error(s, "%s: the spin-resolved potentials are the first derivatives of the energy, but with quirks = 1 the "
+                     "ground state solved the shipped vwn5_c / pbe_c potentials, which are not the derivatives of their energies; "
+                     "run with --quirks 0", who);
+        return false;
+    }
+    return true;
+}
+
+// Open-shell response of Vxc, first half (DFT_FxcPrepareSpinPol): the density kernels on dm0_a, then on dm0_b, as
+// xc_sweep_spin runs them, and the second-derivative table of the energy at that point (xc_response_pol.hip).  The
+// table and the two gradients stay in a slot of their own; the densities pass through the spin sweep's scratch.
+bool fxc_prepare_spinpol(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
+                         const double *ao_grad, const double *w)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    s->fxc_pol_ngrid = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
+    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
+    if (!dm_a || !dm_b || !ao || !w) {
+        set_error(s, "DFT_FxcPrepareSpinPol needs both density matrices, the AO values and the grid weights");
+        return false;
+    }
+    const bool gga = s->needs_grad;
+    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
+    if (!spin_quirks_ok(s, "DFT_FxcPrepareSpinPol")) return false;
+    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const size_t ng = (size_t)ngrid;
+    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
+        !reserve(s, s->fxc_pol_table, sizeof(double) * ng * fxc_pol_planes(gga), "hipMalloc(fxc pol table)", false))
+        return false;
+    for (int k = 0; k < 2; ++k) {
+        if (!reserve(s, s->spin_rho[k], sizeof(double) * ng, "hipMalloc(spin rho)", false)) return false;
+        if (gga && !reserve(s, s->fxc_pol_g0[k], sizeof(double) * 3 * ng, "hipMalloc(fxc pol grad rho)", false)) return false;
+    }
+    if (gga && !reserve(s, s->spin_sigma, sizeof(double) * ng, "hipMalloc(spin sigma)", false)) return false;
+    double *rho_a = (double *)s->spin_rho[0].p, *rho_b = (double *)s->spin_rho[1].p, *sigma = (double *)s->spin_sigma.p;
+    double *g_a = (double *)s->fxc_pol_g0[0].p, *g_b = (double *)s->fxc_pol_g0[1].p;   // the gradients go straight to their keep
+    launch_density(s, P, ngrid, nao, dm_a, ao, (double *)s->dsym.p, rho_a, g_a, sigma);
+    launch_density(s, P, ngrid, nao, dm_b, ao, (double *)s->dsym.p, rho_b, g_b, sigma);
+    {
+        ScopedTimer t(s, "fxc_table_pol");
+        if (!hip_ok(s, launch_fxc_table_pol(s->stream, type, gga, s->mix.c, ngrid, rho_a, rho_b, gga ? g_a : nullptr, gga ? g_b : nullptr, w,
+                                            (double *)s->fxc_pol_table.p), "open-shell response table launch"))
+            return false;
+    }
+    s->fxc_pol_ngrid = ngrid;
+    s->fxc_pol_nao = nao;
+    return true;
+}
+
+// Second half (DFT_FxcApplySpinPol): the densities of dm1_a and dm1_b, the coupled coefficients of the two spins from
+// the table, and the sweep's contraction and reduce once per spin.  Asynchronous on the solver's stream.
+bool fxc_apply_spinpol(XCSolver *s, long ngrid, int nao, const double *dm1_a, const double *dm1_b, const double *ao,
+                       const double *ao_grad, double *v1_a, double *v1_b)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
+    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
+    if (s->fxc_pol_ngrid <= 0) { set_error(s, "DFT_FxcApplySpinPol before DFT_FxcPrepareSpinPol"); return false; }
+    if (ngrid != s->fxc_pol_ngrid || nao != s->fxc_pol_nao) {
+        set_error(s, "DFT_FxcApplySpinPol sizes ngrid=%ld nao=%d differ from DFT_FxcPrepareSpinPol's ngrid=%ld nao=%d", ngrid, nao,
+                  s->fxc_pol_ngrid, s->fxc_pol_nao);
+        return false;
+    }
+    const bool gga = s->needs_grad;
+    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
+    if (!dm1_a || !dm1_b || !ao || !v1_a || !v1_b) {
+        set_error(s, "DFT_FxcApplySpinPol needs both perturbations, the AO values and both output matrices");
+        return false;
+    }
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const size_t ng = (size_t)ngrid;
+    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
+        !reserve(s, s->slabs, sizeof(double) * (size_t)P.nslab * nao * nao, "hipMalloc(slabs)"))
+        return false;
+    for (int k = 0; k < 2; ++k) {
+        if (!reserve(s, s->spin_rho[k], sizeof(double) * ng, "hipMalloc(spin rho)", false) ||
+            !reserve(s, s->spin_coef[k], sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(spin coef)", false))
+            return false;
+        if (gga && !reserve(s, s->spin_grad[k], sizeof(double) * 3 * ng, "hipMalloc(spin grad)", false)) return false;
+    }
+    if (gga && !reserve(s, s->spin_sigma, sizeof(double) * ng, "hipMalloc(spin sigma)", false)) return false;
+    double *Dp = (double *)s->dsym.p, *slabs = (double *)s->slabs.p, *sigma = (double *)s->spin_sigma.p;
+    double *r1_a = (double *)s->spin_rho[0].p, *r1_b = (double *)s->spin_rho[1].p;
+    double *g1_a = (double *)s->spin_grad[0].p, *g1_b = (double *)s->spin_grad[1].p;
+    double *c_a = (double *)s->spin_coef[0].p, *c_b = (double *)s->spin_coef[1].p;
+    launch_density(s, P, ngrid, nao, dm1_a, ao, Dp, r1_a, g1_a, sigma);
+    launch_density(s, P, ngrid, nao, dm1_b, ao, Dp, r1_b, g1_b, sigma);
+    {
+        ScopedTimer t(s, "fxc_coef_pol");
+        if (!hip_ok(s, launch_fxc_coef_pol(s->stream, gga, ngrid, (const double *)s->fxc_pol_table.p, (const double *)s->fxc_pol_g0[0].p,
+                                           (const double *)s->fxc_pol_g0[1].p, r1_a, r1_b, g1_a, g1_b, c_a, c_b),
+                    "open-shell response coefficient launch"))
+            return false;
+    }
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, c_a, slabs, v1_a, nullptr)) return false;
+    return vxc_stage(s, P, false, ngrid, nao, ao, c_b, slabs, v1_b, nullptr);
+}
+
 // J and/or K from rows (i, j), i in [i0, i0 + ni), of the dense ERI; `eri` points at row (i0, 0).
 // i0 = 0, ni = nao is the reference's whole-matrix contraction; a proper sub-range is one rank's share of
 // the row sharding: partial J over all columns, rows [i0, i0 + ni) of K, zeros elsewhere.
@@ -1334,6 +1447,7 @@ void DFT_DestroySolver(XCSolver *s)
                           &s->slabs, &s->exc, &s->jpart, &s->kpart, &s->shells, &s->msym,
                           &s->cdy, &s->cdc, &s->cdv, &s->cdy2, &s->cdc2, &s->cdbt, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0,
                           &s->fxc_spin_table[0], &s->fxc_spin_table[1], &s->fxc_spin_g0[0], &s->fxc_spin_g0[1],
+                          &s->fxc_pol_table, &s->fxc_pol_g0[0], &s->fxc_pol_g0[1],
                           &s->spin_rho[0], &s->spin_rho[1], &s->spin_grad[0], &s->spin_grad[1], &s->spin_sigma, &s->spin_coef[0],
                           &s->spin_coef[1], &s->spin_partial, &s->spin_exc};
         for (DevBuf *b : bufs)
@@ -1629,6 +1743,38 @@ int DFT_FxcApply(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm1
     if (!s) return -1;
     DeviceGuard dg(s);
     return fxc_apply(s, (long)ngrid, nao, (const double *)d_dm1, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_v1) ? 0 : -1;
+}
+
+int DFT_FxcPrepareSpinPol(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm0_a, unsigned long long d_dm0_b,
+                          unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_weights)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return fxc_prepare_spinpol(s, (long)ngrid, nao, (const double *)d_dm0_a, (const double *)d_dm0_b, (const double *)d_ao,
+                               (const double *)d_ao_grad, (const double *)d_weights) ? 0 : -1;
+}
+
+int DFT_FxcApplySpinPol(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm1_a, unsigned long long d_dm1_b,
+                        unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_v1_a, unsigned long long d_v1_b)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return fxc_apply_spinpol(s, (long)ngrid, nao, (const double *)d_dm1_a, (const double *)d_dm1_b, (const double *)d_ao,
+                             (const double *)d_ao_grad, (double *)d_v1_a, (double *)d_v1_b) ? 0 : -1;
+}
+
+int DFT_FxcSpinPolTable(XCSolver *s, unsigned long long d_out, long long max_doubles)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    s->last_error.clear();
+    if (s->fxc_pol_ngrid <= 0) { set_error(s, "DFT_FxcSpinPolTable before DFT_FxcPrepareSpinPol"); return -1; }
+    const int planes = fxc_pol_planes(s->needs_grad);
+    const long long need = (long long)planes * s->fxc_pol_ngrid;
+    if (!d_out || max_doubles < need) { set_error(s, "DFT_FxcSpinPolTable needs room for %lld doubles", need); return -1; }
+    if (!hip_ok(s, hipMemcpyAsync((void *)d_out, s->fxc_pol_table.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToDevice, s->stream), "copy table"))
+        return -1;
+    return planes;
 }
 
 int DFT_ComputeXCSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,

@@ -1,4 +1,4 @@
-// Host counterpart of xc_response.hip (lib/libqcfxc.so, built with g++): the same bodies of xc_functionals.hpp,
+// Host counterpart of xc_response.hip and xc_response_pol.hip (lib/libqcfxc.so, built with g++): the same bodies of xc_functionals.hpp,
 // the same two dual evaluations per point.  response.fxc_apply_host() and a CPU CPKS run assemble V1 from it; the CPU
 // tests hold it against finite differences of the oracle.  type: 0 LDA, 1 GGA, 2 B3LYP, 3 mix (eight weights).
 #include "xc_functionals.hpp"
@@ -118,6 +118,38 @@ int qc_fxc_table_spin(int type, const double *mix8, int kind, long long n, const
         if (gga) xc::spin_table_point<true>(m, kind, 15, rho[g], sigma[g], scale, t, t + 1, t + 2, t + 3, t + 4);
         else     xc::spin_table_point<false>(m, kind, 15, rho[g], 0.0, scale, t, t + 1, t + 2, t + 3, t + 4);
         for (int k = 0; k < 5; ++k) out[k * n + g] = t[k];
+    }
+    return 0;
+}
+
+// The table of the open-shell response (k_fxc_table_pol of xc_response_pol.hip) at any polarisation,
+// bare: no weight and no factor of the built-in type.  h (25, n): H_ij = d^2 e / dx_i dx_j at row 5 i + j, x = (ra, rb,
+// saa, sab, sbb), every ordered pair evaluated with x_i first (the two orders differ only at a sigma cut-off); g1 (5, n):
+// de / dx_i.  ga3 / gb3: three per point, interleaved (may be null for an LDA-class functional, whose sigma rows and
+// columns stay zero).  An absent channel (density below the cut-off): zeros in its rows, columns and g.
+int qc_fxc_table_pol(int type, const double *mix8, long long n, const double *ra, const double *rb, const double *ga3,
+                     const double *gb3, double *h, double *g1)
+{
+    if (type < 0 || type > 3 || (type == 3 && !mix8) || n < 0 || !ra || !rb || !h || !g1) return -1;
+    xc::MixWeights m = weights(mix8);
+    if (type != 3) (void)xc::builtin_spin_mix(type, m);
+    const bool gga = mix_gga(m);
+    if (gga && (!ga3 || !gb3)) return -1;
+    const int nv = gga ? 5 : 2;
+    for (long long k = 0; k < 25 * n; ++k) h[k] = 0.0;
+    for (long long k = 0; k < 5 * n; ++k) g1[k] = 0.0;
+    for (long long g = 0; g < n; ++g) {
+        const xc::SpinVars x = gga ? xc::spin_vars<true>(ra[g], rb[g], ga3[3 * g], ga3[3 * g + 1], ga3[3 * g + 2], gb3[3 * g],
+                                                         gb3[3 * g + 1], gb3[3 * g + 2])
+                                   : xc::spin_vars<false>(ra[g], rb[g], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0);
+        for (int i = 0; i < nv; ++i)
+            for (int j = 0; j < nv; ++j) {
+                double hij, gi;
+                if (gga) xc::spin_hessian_entry<true>(m, x, i, j, &hij, &gi);
+                else     xc::spin_hessian_entry<false>(m, x, i, j, &hij, &gi);
+                h[(5 * i + j) * n + g] = hij;
+                if (i == j) g1[i * n + g] = gi;
+            }
     }
     return 0;
 }

@@ -404,6 +404,74 @@ QCDFT_XC_FN SpinPoint spin_potential_point(const MixWeights &m, double ra, doubl
     return o;
 }
 
+// The second derivatives of the energy at ANY polarisation (DFT_FxcPrepareSpinPol): the table behind the response of the
+// two spin potentials of spin_potential_point to a perturbation of the two spin densities.  With x = (ra, rb, saa, sab,
+// sbb), g_i = de/dx_i and H_ij = d(g_i)/dx_j: one Dual2 evaluation with the first direction along x_i (the potential's
+// variable) and the second along x_j (the perturbation) yields H_ij in its mixed part and g_i in its first part.
+//
+// SpinVars is the point as spin_potential_point prepares it: a channel below kRhoCut is absent, its rho, its sigma_ss and
+// sigma_ab are exactly 0.  A variable of an absent channel (x_3 = sigma_ab belongs to both) is not differentiated: its g
+// and its rows and columns of H are exactly 0, so it neither responds nor is responded to; both absent: all zero.
+//
+// H is symmetric wherever the bodies are smooth.  At a sigma cut-off of PBE exchange or correlation (sigma_at_cut) the
+// two orders differ: the first direction keeps its part, the second sees a constant -- the rule of spin_table_point.
+// spin_sigma_cut says whether a point sits there (never for an LDA-class functional); callers keep H_ji for i < j beside
+// H_ij and evaluate it in its own order at such points.
+struct SpinVars {
+    double ra, rb, saa, sab, sbb;
+    bool pa, pb;
+};
+
+template <bool GGA>
+QCDFT_XC_FN SpinVars spin_vars(double ra, double rb, double gax, double gay, double gaz, double gbx, double gby, double gbz)
+{
+    SpinVars x = {0.0, 0.0, 0.0, 0.0, 0.0, ra >= kRhoCut, rb >= kRhoCut};
+    if (x.pa) x.ra = ra;
+    if (x.pb) x.rb = rb;
+    if (GGA) {
+        if (x.pa) x.saa = gax * gax + gay * gay + gaz * gaz;
+        if (x.pb) x.sbb = gbx * gbx + gby * gby + gbz * gbz;
+        if (x.pa && x.pb) x.sab = gax * gbx + gay * gby + gaz * gbz;
+    }
+    return x;
+}
+
+QCDFT_XC_FN bool spin_var_present(const SpinVars &x, int i)
+{
+    return i == 0 || i == 2 ? x.pa : i == 1 || i == 4 ? x.pb : (x.pa && x.pb);
+}
+
+// Generous by a factor of two: a point flagged without need is evaluated in both orders, which is always right.
+QCDFT_XC_FN bool spin_sigma_cut(const SpinVars &x)
+{
+    const double c = 2.0 * kSigmaCut;
+    return (x.pa && 4.0 * x.saa <= c) || (x.pb && 4.0 * x.sbb <= c) || (x.saa + 2.0 * x.sab + x.sbb <= c);
+}
+
+// H_ij and g_i of one ordered pair; zeros when x_i or x_j belongs to an absent channel.
+template <bool GGA>
+QCDFT_XC_FN void spin_hessian_entry(const MixWeights &m, const SpinVars &x, int i, int j, double *h, double *gi)
+{
+    *h = 0.0;
+    *gi = 0.0;
+    if (!spin_var_present(x, i) || !spin_var_present(x, j)) return;
+    const Dual2 e = spin_mix_energy<GGA>(m, Dual2(x.ra, i == 0 ? 1.0 : 0.0, j == 0 ? 1.0 : 0.0, 0.0),
+                                         Dual2(x.rb, i == 1 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, 0.0),
+                                         Dual2(x.saa, i == 2 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0, 0.0),
+                                         Dual2(x.sab, i == 3 ? 1.0 : 0.0, j == 3 ? 1.0 : 0.0, 0.0),
+                                         Dual2(x.sbb, i == 4 ? 1.0 : 0.0, j == 4 ? 1.0 : 0.0, 0.0));
+    *h = e.ab;
+    *gi = e.a;
+}
+
+// Plane numbering of the table: the upper triangle of H row by row (nv = 5: 15 planes; nv = 2 for an LDA-class
+// functional: 3), and for i < j the position of H_ji among the off-diagonal pairs in the same order (nv = 5: 0..9).
+QCDFT_XC_FN constexpr int pol_upper(int nv, int i, int j) { return i * nv - i * (i - 1) / 2 + (j - i); }
+QCDFT_XC_FN constexpr int pol_lower(int nv, int i, int j) { return pol_upper(nv, i, j) - (i + 1); }
+constexpr int kPolG = 15;       // planes 15..17: g_2, g_3, g_4
+constexpr int kPolLower = 18;   // planes 18..27: H_ji, i < j
+constexpr int kPolPlanes = 28;  // a gradient functional's table; an LDA-class one has 3
+
 // The component weights and the factor of a built-in solver type (0 LDA, 1 GGA, 2 B3LYP), as its point body mixes
 // them: B3LYP's M + M^T with the halved vrho is half the one-sided table.
 QCDFT_XC_FN double builtin_spin_mix(int type, MixWeights &m)

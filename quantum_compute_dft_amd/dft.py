@@ -143,6 +143,10 @@ def main(argv=None):
     p.add_argument("--spin", type=int, default=None, metavar="N",
                    help="N = nalpha - nbeta: an unrestricted (UKS) run with the spin-resolved XC sweep (DFT_ComputeXCSpin) and the host loop "
                         "(--spin 0 too); one rank, --ao resident; needs --quirks 0 with vwn5_c or pbe_c.  Without the flag: the closed shell")
+    p.add_argument("--open-shell-response", action="store_true",
+                   help="with --spin: allow --dipole, --polarizability (unrestricted CPKS) and --excitations (spin-conserving U-TDDFT / "
+                        "U-TDA, rows U1 ...) from the unrestricted reference (the open-shell response of Vxc on the device: "
+                        "DFT_FxcPrepareSpinPol / DFT_FxcApplySpinPol); --triplets stays refused")
     p.add_argument("--charge", type=int, default=0, metavar="Q", help="charge of the molecule (electrons = sum Z - Q); an odd count needs --spin")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
@@ -162,9 +166,15 @@ def main(argv=None):
         p.error("--excitations runs on one rank with --ao resident")
 
     uks = args.spin is not None
+    if args.open_shell_response and not uks:
+        p.error("--open-shell-response goes with --spin N")
     if uks:
-        if args.excitations or args.polarizability or args.dipole:
-            p.error("--excitations, --polarizability and --dipole take a closed-shell reference: not available after an unrestricted (--spin) run")
+        if (args.excitations or args.polarizability or args.dipole) and not args.open_shell_response:
+            p.error("--excitations, --polarizability and --dipole take a closed-shell reference: not available after an unrestricted (--spin) run "
+                    "unless --open-shell-response asks for the response of the unrestricted reference")
+        if args.triplets:
+            p.error("--triplets is the spin-flip kernel of a closed-shell reference: not available after an unrestricted (--spin) run "
+                    "(--open-shell-response gives the spin-conserving excitations only)")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident" or args.dm_factor:
             p.error("--spin (UKS) runs on one rank with --ao resident and without --dm-factor")
         if args.fused_tail > 0 or args.device_resident > 0:
@@ -304,6 +314,19 @@ def main(argv=None):
         from . import excitations as _ex
         excited = _ex.excitations(inp, res, backend, args.functional, nroots=args.excitations, tda=args.tda, log=print, triplet=args.triplets)
         nocc_ = inp.nocc
+        if uks:
+            print(f"Unrestricted excitations ({'U-TDA' if args.tda else 'U-TDDFT'}, spin-conserving; {excited['iterations']} iterations, "
+                  f"{excited['sigma_builds']} trial vectors" + ("" if excited["converged"] else "; NOT converged") + "):")
+            print("  state        eV         nm          f    largest |X+Y|")
+            nva = inp.shells.nao - inp.nalpha
+            for n, (w, f_n, x) in enumerate(zip(excited["energies"], excited["oscillator_strengths"], excited["xpy"]), 1):
+                k = int(np.argmax(np.abs(x)))
+                if k < inp.nalpha * nva:
+                    sp, (i, a), no = "alpha", divmod(k, nva), inp.nalpha
+                else:
+                    sp, (i, a), no = "beta", divmod(k - inp.nalpha * nva, inp.shells.nao - inp.nbeta), inp.nbeta
+                print(f"  U{n:<4d} {w * _ex.HARTREE_EV:9.4f} {_ex.NM_PER_HARTREE / w:10.2f} {f_n:10.6f}    {sp} {i + 1} -> {no + a + 1} ({abs(x[k]):.3f})")
+    if args.excitations and res["converged"] and not uks:
         print(f"{'Triplet' if args.triplets else 'Singlet'} excitations ({'TDA' if args.tda else 'TDDFT'}; {excited['iterations']} iterations, {excited['sigma_builds']} trial vectors"
               + ("" if excited["converged"] else "; NOT converged") + "):")
         print("  state        eV         nm          f    largest |X+Y|")
@@ -337,8 +360,8 @@ def main(argv=None):
         record["polarizability"] = polar["alpha"].tolist() if polar is not None else None
         record["cpks_iterations"] = [int(x) for x in polar["cpks_iterations"]] if polar is not None else None
     if args.excitations:
-        record["excitation_method"] = ("tda" if args.tda else "tddft") + ("-triplet" if args.triplets else "")
-        record["excitation_multiplicity"] = 3 if args.triplets else 1
+        record["excitation_method"] = ("tda" if args.tda else "tddft") + ("-uks" if uks else "-triplet" if args.triplets else "")
+        record["excitation_multiplicity"] = None if uks else 3 if args.triplets else 1
         record["excitation_energies"] = excited["energies"].tolist() if excited is not None else None
         record["oscillator_strengths"] = excited["oscillator_strengths"].tolist() if excited is not None else None
         record["excitation_iterations"] = int(excited["iterations"]) if excited is not None else None

@@ -95,6 +95,57 @@ class ResponseOperators:
         return plus, minus
 
 
+class UksResponseOperators:
+    """(A+B) and (A-B) of a converged unrestricted state (scf.run_uks) on the stacked space of the n_a nv_a + n_b nv_b
+    spin-conserving occupied-virtual pairs, as maps on flat (nvec, size) arrays: `apply`.  UKS convention: D_s = C_os
+    C_os^T with occupation 1, K enters with c_hf.  For Z = (Z_a, Z_b), A_s = C_os and B_s = C_vs Z_s^T,
+
+        [(A+B) Z]_s = gap_s o Z_s + C_os^T ( J[D+_a + D+_b] + (V1_s + V1_s^T)/2 - c_hf (M_s + M_s^T) ) C_vs
+        [(A-B) Z]_s = gap_s o Z_s - c_hf C_os^T (M_s - M_s^T) C_vs
+
+    with J, M_s and V1_s of all trials from ONE backend.uks_excitation_parts call (DFT_FxcApplySpinPol for V1).  Fields:
+    spins (per spin Co, Cv, gap), size, gap_flat, dip_flat (3, size), builds."""
+
+    flat = True
+    triplet = False
+
+    def __init__(self, inp, uks_result, backend, functional=None):
+        from . import response
+        f, self.spins = response.uks_orbitals(inp, uks_result, backend, functional)
+        self.c_hf, self.want_k = f.c_hf, f.c_hf != 0.0
+        self.backend = backend
+        self.shapes = [s["gap"].shape for s in self.spins]
+        self.na = self.shapes[0][0] * self.shapes[0][1]
+        self.size = self.na + self.shapes[1][0] * self.shapes[1][1]
+        self.gap_flat = np.concatenate([s["gap"].reshape(-1) for s in self.spins])
+        D = integrals.dipole(inp.shells)
+        self.dip_flat = np.concatenate([np.einsum("mi,kmn,na->kia", s["Co"], D, s["Cv"]).reshape(3, -1) for s in self.spins], axis=1)
+        self.builds = 0
+
+    def split(self, Z):
+        Z = np.asarray(Z, dtype=np.float64)
+        return [Z[:, :self.na].reshape((Z.shape[0],) + self.shapes[0]), Z[:, self.na:].reshape((Z.shape[0],) + self.shapes[1])]
+
+    def apply(self, Z):
+        """((A+B) Z_k, (A-B) Z_k) for Z (nvec, size)."""
+        Zs = self.split(Z)
+        Bs = [np.ascontiguousarray(np.einsum("na,kia->kni", s["Cv"], z)) for s, z in zip(self.spins, Zs)]
+        J, Ma, Mb, Va, Vb = self.backend.uks_excitation_parts(self.spins[0]["Co"], Bs[0], self.spins[1]["Co"], Bs[1], self.want_k)
+        self.builds += Zs[0].shape[0]
+        plus, minus = [], []
+        for s, z, M, V in zip(self.spins, Zs, (Ma, Mb), (Va, Vb)):
+            dz = s["gap"][None] * z
+            G = J + 0.5 * (V + V.transpose(0, 2, 1))
+            if self.want_k:
+                Mt = M.transpose(0, 2, 1)
+                G = G - self.c_hf * (M + Mt)
+                minus.append((dz - self.c_hf * np.einsum("mi,kmn,na->kia", s["Co"], M - Mt, s["Cv"])).reshape(z.shape[0], -1))
+            else:
+                minus.append(dz.reshape(z.shape[0], -1))
+            plus.append((dz + np.einsum("mi,kmn,na->kia", s["Co"], G, s["Cv"])).reshape(z.shape[0], -1))
+        return np.concatenate(plus, axis=1), np.concatenate(minus, axis=1)
+
+
 def _orthonormal_additions(basis, cands, drop=1e-8):
     """Rows of `cands`, orthogonalised against the rows of `basis` and each other (Gram-Schmidt, twice), normalised;
     a candidate that loses all but `drop` of its norm is left out."""
@@ -114,8 +165,11 @@ def _orthonormal_additions(basis, cands, drop=1e-8):
     return np.array(out).reshape(len(out), basis.shape[1])
 
 
-def _sqrt_spd(M, what, triplet=False):
+def _sqrt_spd(M, what, triplet=False, uks=False):
     w, U = np.linalg.eigh(M)
+    if w[0] <= 0.0 and uks:
+        raise ValueError(f"excitations: the reduced {what} is not positive definite (lowest eigenvalue {w[0]:.3e}): "
+                         "the unrestricted reference is unstable")
     if w[0] <= 0.0 and triplet and what == "A+B":
         raise ValueError(f"excitations: the reduced triplet A+B is not positive definite (lowest eigenvalue {w[0]:.3e}): "
                          "triplet instability of the restricted reference")
@@ -126,12 +180,18 @@ def _sqrt_spd(M, what, triplet=False):
 
 
 def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=None):
-    """The lowest `nroots` roots of `ops` (a ResponseOperators): the dict `excitations` returns."""
-    nocc, nvirt = ops.gap.shape
-    N = nocc * nvirt
+    """The lowest `nroots` roots of `ops` (a ResponseOperators, or a UksResponseOperators on its flat stacked space): the
+    dict `excitations` returns."""
+    uks = bool(getattr(ops, "flat", False))
+    if uks:
+        N, gap, dip = ops.size, ops.gap_flat, ops.dip_flat
+        to_ops, from_flat = (lambda v: v), (lambda v: v)
+    else:
+        nocc, nvirt = ops.gap.shape
+        N, gap, dip = nocc * nvirt, ops.gap.reshape(-1), ops.dip.reshape(3, nocc * nvirt)
+        to_ops, from_flat = (lambda v: v.reshape(-1, nocc, nvirt)), (lambda v: v.reshape(-1, nocc, nvirt))
     if not 1 <= nroots <= N:
         raise ValueError(f"excitations: nroots = {nroots}, but there are {N} occupied-virtual pairs")
-    gap = ops.gap.reshape(-1)
     max_space = min(N, max_space if max_space else max(8 * nroots, 40))
     max_space = max(max_space, min(N, 3 * nroots))           # room for a collapsed space (two vectors a root) to grow
     b = np.zeros((0, N))
@@ -142,12 +202,14 @@ def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=N
     triplet = bool(getattr(ops, "triplet", False))
     converged, it = False, 0
     for it in range(1, max_iter + 1):
-        P, Q = ops.apply(new.reshape(-1, nocc, nvirt))
+        P, Q = ops.apply(to_ops(new))
         b = np.vstack([b, new]); Pb = np.vstack([Pb, P.reshape(-1, N)]); Qb = np.vstack([Qb, Q.reshape(-1, N)])
         Mp, Mm = b @ Pb.T, b @ Qb.T
         Mp, Mm = 0.5 * (Mp + Mp.T), 0.5 * (Mm + Mm.T)
         if tda:
             w, T = np.linalg.eigh(0.5 * (Mp + Mm))
+            if w[0] <= 0.0 and uks:
+                raise ValueError(f"excitations: the lowest Tamm-Dancoff root is {w[0]:.3e} Ha: the unrestricted reference is unstable")
             if w[0] <= 0.0 and triplet:
                 raise ValueError(f"excitations: the lowest triplet Tamm-Dancoff root is {w[0]:.3e} Ha: triplet instability of the "
                                  "restricted reference")
@@ -157,8 +219,8 @@ def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=N
             res1 = R.T @ (0.5 * (Pb + Qb)) - w[:, None] * (R.T @ b)
             res2 = res1
         else:
-            Sm, Smi = _sqrt_spd(Mm, "A-B")
-            _sqrt_spd(Mp, "A+B", triplet)
+            Sm, Smi = _sqrt_spd(Mm, "A-B", uks=uks)
+            _sqrt_spd(Mp, "A+B", triplet, uks=uks)
             w2, T = np.linalg.eigh(Sm @ Mp @ Sm)
             w = np.sqrt(w2[:nroots])
             R = (Sm @ T[:, :nroots]) / np.sqrt(w)                               # X+Y in the basis
@@ -188,13 +250,14 @@ def solve(ops, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=N
         if new.shape[0] == 0:
             break                                                               # nothing left to add: the space is exhausted
     xpy, xmy = R.T @ b, L.T @ b
-    mu = np.sqrt(2.0) * np.einsum("kx,nx->nk", ops.dip.reshape(3, N), xpy)
+    mu = (1.0 if uks else np.sqrt(2.0)) * np.einsum("kx,nx->nk", dip, xpy)       # UKS: both spins are in the vector, no sqrt(2)
     if triplet:
         mu = np.zeros_like(mu)                       # spin-forbidden from the singlet ground state
     return {"energies": w, "oscillator_strengths": (2.0 / 3.0) * w * np.einsum("nk,nk->n", mu, mu),
-            "transition_dipoles": mu, "xpy": xpy.reshape(-1, nocc, nvirt), "xmy": xmy.reshape(-1, nocc, nvirt),
+            "transition_dipoles": mu, "xpy": from_flat(xpy), "xmy": from_flat(xmy),
             "residuals": rn, "iterations": it, "sigma_builds": ops.builds - builds0, "converged": converged,
-            "method": ("tda" if tda else "tddft") + ("-triplet" if triplet else ""), "multiplicity": 3 if triplet else 1}
+            "method": ("tda" if tda else "tddft") + ("-uks" if uks else "-triplet" if triplet else ""),
+            "multiplicity": None if uks else 3 if triplet else 1}
 
 
 def excitations(inp, scf_result, backend, functional=None, nroots=5, tda=False, tol=1e-6, max_iter=60, max_space=None, log=None,
@@ -211,5 +274,16 @@ def excitations(inp, scf_result, backend, functional=None, nroots=5, tda=False, 
     "tddft-triplet", "tda-triplet"), "multiplicity" (1 or 3)}; a triplet's oscillator strengths and transition dipoles
     are zero.  ValueError: nroots above nocc nvirt, no gap, a reduced A+B or A-B that is not positive definite (an
     unstable reference; for triplets: a triplet instability of the restricted reference), quirks = 1 with PBE
-    correlation (a non-symmetric operator; use quirks 0), or triplets at quirks = 1 with vwn5_c or pbe_c."""
+    correlation (a non-symmetric operator; use quirks 0), or triplets at quirks = 1 with vwn5_c or pbe_c.
+
+    A scf.run_uks result (uks = True): the spin-conserving excitations of the unrestricted reference on the stacked space of
+    both spins' pairs (UksResponseOperators); "method" is "tddft-uks" / "tda-uks", "multiplicity" None, xpy / xmy are flat
+    (nroots, n_a nv_a + n_b nv_b), alpha pairs first; transition dipole sum_s sum_ia (C_os^T D_k C_vs)_ia (X+Y)_s,ia (no
+    sqrt(2): the restricted singlet vector (Z, Z)/sqrt(2) recovers the closed-shell formula), f = 2/3 w |mu|^2.  A reduced
+    A+B or A-B that is not positive definite: "the unrestricted reference is unstable"; triplet=True is refused."""
+    if scf_result.get("uks"):
+        if triplet:
+            raise ValueError("excitations: triplet=True asks for the spin-flip kernel of a closed-shell reference; from an unrestricted "
+                             "reference only the spin-conserving excitations are solved (spin-flip excitations are out of scope)")
+        return solve(UksResponseOperators(inp, scf_result, backend, functional), nroots, tda, tol, max_iter, max_space, log)
     return solve(ResponseOperators(inp, scf_result, backend, functional, triplet=triplet), nroots, tda, tol, max_iter, max_space, log)

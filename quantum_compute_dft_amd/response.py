@@ -37,6 +37,8 @@ def _load():
         L.qc_spin_energy.argtypes = [dp, ctypes.c_longlong, dp, dp, dp, dp, dp, dp]
         L.qc_xc_point_spin.restype = ctypes.c_int
         L.qc_xc_point_spin.argtypes = [ctypes.c_int, dp, ctypes.c_longlong, dp, dp, dp, dp, dp, dp]
+        L.qc_fxc_table_pol.restype = ctypes.c_int
+        L.qc_fxc_table_pol.argtypes = [ctypes.c_int, dp, ctypes.c_longlong, dp, dp, dp, dp, dp, dp]
         _lib = L
     return _lib
 
@@ -190,6 +192,72 @@ def xc_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad=None):
     return float(w @ p[0]), out[0], out[1]
 
 
+def fxc_table_pol_host(functional, ra, rb, grad_a=None, grad_b=None):
+    """(H (5, 5, n), g (5, n)): the bare second and first derivatives of the energy per volume by x = (rho_a, rho_b,
+    sigma_aa, sigma_ab, sigma_bb) at any polarisation -- the table of DFT_FxcPrepareSpinPol without the weight and without
+    the factor of the built-in type, xc::spin_hessian_entry compiled for the host.  H[i, j] is evaluated with x_i as the
+    first direction (the potential's variable) and x_j as the second (the perturbation): symmetric except at a sigma
+    cut-off of PBE exchange or correlation.  grad_a / grad_b (n, 3), zeros if None.  A channel below the density cut-off is
+    absent: exact zeros in its rows, columns and g.  An LDA-class functional leaves the sigma rows and columns zero."""
+    t, w8, gga = _kind(functional)
+    ra = np.ascontiguousarray(np.atleast_1d(ra), dtype=np.float64)
+    rb = np.ascontiguousarray(np.broadcast_to(np.asarray(rb, dtype=np.float64), ra.shape))
+    if ra.ndim != 1:
+        raise ValueError("fxc_table_pol_host: one-dimensional arrays of one length")
+    ga, gb = (np.zeros((ra.size, 3)) if g is None else np.ascontiguousarray(g, dtype=np.float64) for g in (grad_a, grad_b))
+    if ga.shape != (ra.size, 3) or gb.shape != (ra.size, 3):
+        raise ValueError("fxc_table_pol_host: gradients (n, 3) for n points")
+    H, g1 = np.zeros((5, 5, ra.size)), np.zeros((5, ra.size))
+    if _load().qc_fxc_table_pol(t, _p(w8), ra.size, _p(ra), _p(rb), _p(ga), _p(gb), _p(H), _p(g1)) != 0:
+        raise ValueError("fxc_table_pol_host: bad arguments")
+    return H, g1
+
+
+class HostFxcSpin:
+    """DFT_FxcPrepareSpinPol / DFT_FxcApplySpinPol on the host: the table at (dm0_a, dm0_b) once, then (V1_a, V1_b) of any
+    number of perturbations (dm1_a, dm1_b), in numpy -- element for element what the device entries leave."""
+
+    def __init__(self, functional, dm0_a, dm0_b, ao, weights, ao_grad=None):
+        self.type, self.w8, self.gga = _kind(functional)
+        if self.gga and ao_grad is None:
+            raise ValueError("ao_grad is needed for a gradient-corrected functional")
+        self.ao = np.ascontiguousarray(ao, dtype=np.float64)
+        self.gr = np.ascontiguousarray(ao_grad, dtype=np.float64) if self.gga else None
+        self.ra, self.ga = _density(np.asarray(dm0_a, dtype=np.float64), self.ao, self.gr)
+        self.rb, self.gb = _density(np.asarray(dm0_b, dtype=np.float64), self.ao, self.gr)
+        H, g = fxc_table_pol_host(functional, self.ra, self.rb, self.ga, self.gb)
+        sw = (0.5 if self.type == 2 else 1.0) * np.asarray(weights, dtype=np.float64)      # B3LYP: the library's M + M^T
+        self.H, self.g = H * sw, g * sw
+
+    def apply(self, dm1_a, dm1_b):
+        ra1, ga1 = _density(np.asarray(dm1_a, dtype=np.float64), self.ao, self.gr)
+        rb1, gb1 = _density(np.asarray(dm1_b, dtype=np.float64), self.ao, self.gr)
+        H = self.H
+        if not self.gga:
+            c = [H[0, 0] * ra1 + H[0, 1] * rb1, H[1, 0] * ra1 + H[1, 1] * rb1]
+            return tuple((ck * self.ao.T) @ self.ao for ck in c)
+        dot = lambda u, v: np.einsum("gk,gk->g", u, v)
+        x1 = np.stack([ra1, rb1, 2.0 * dot(self.ga, ga1), dot(self.ga, gb1) + dot(self.gb, ga1), 2.0 * dot(self.gb, gb1)])
+        t = np.einsum("ijg,jg->ig", H, x1)
+        g2, g3, g4 = self.g[2], self.g[3], self.g[4]
+        ca = 2.0 * ((2.0 * t[2])[:, None] * self.ga + (2.0 * g2)[:, None] * ga1 + t[3][:, None] * self.gb + g3[:, None] * gb1)
+        cb = 2.0 * ((2.0 * t[4])[:, None] * self.gb + (2.0 * g4)[:, None] * gb1 + t[3][:, None] * self.ga + g3[:, None] * ga1)
+        out = []
+        for c0, ck in ((t[0], ca), (t[1], cb)):
+            B = c0[:, None] * self.ao
+            for k in range(3):
+                B += ck[:, k, None] * self.gr[k]
+            M = B.T @ self.ao
+            out.append(M + M.T if self.type == 2 else M)
+        return out[0], out[1]
+
+
+def fxc_apply_spinpol_host(functional, dm0_a, dm0_b, dm1_a, dm1_b, ao, weights, ao_grad=None):
+    """(V1_a, V1_b) = d/dt of xc_spin_host(dm0_a + t dm1_a, dm0_b + t dm1_b)'s potentials at t = 0, from AO planes in
+    numpy and in xc_spin_host's conventions: what DFT_FxcApplySpinPol leaves."""
+    return HostFxcSpin(functional, dm0_a, dm0_b, ao, weights, ao_grad).apply(dm1_a, dm1_b)
+
+
 class HostFxc:
     """fxc_prepare / fxc_apply on the host: the table at dm0 once, then V1 of any number of perturbations."""
 
@@ -270,6 +338,131 @@ class HostResponse:
         return J, M, np.stack([fxc.apply(d) for d in Dp])
 
 
+class HostUksResponse:
+    """Open-shell response backend on the host: uks_response_prepare / uks_excitation_parts as scf.HipBackend offers them,
+    from the dense ERI of `inp` and HostFxcSpin on the AO planes given.  `scf_backend` (uks_parts, what run_uks ran on)
+    supplies the ground-state Fock parts.  A functional without a density-functional component has V1 = 0."""
+
+    def __init__(self, inp, functional, scf_backend, ao=None, ao_grad=None, quirks=False):
+        if inp.eri is None:
+            raise ValueError("HostUksResponse needs the dense ERI")
+        self.inp, self.functional, self.scf, self.quirks = inp, functional, scf_backend, bool(quirks)
+        self.ao, self.gr, self.fxc = ao, ao_grad, None
+        self.sweep = bool(functionals.resolve(functional).weights)
+        if self.sweep and ao is None:
+            raise ValueError("HostUksResponse needs the AO planes for a functional with a density-functional component")
+
+    def uks_parts(self, dm_a, dm_b, cocc_a, cocc_b, want_k):
+        return self.scf.uks_parts(dm_a, dm_b, cocc_a, cocc_b, want_k)
+
+    def uks_response_prepare(self, dm_a, dm_b):
+        if self.sweep:
+            self.fxc = HostFxcSpin(self.functional, dm_a, dm_b, self.ao, self.inp.grids.weights, self.gr)
+
+    def uks_excitation_parts(self, A_a, Bs_a, A_b, Bs_b, want_k):
+        """(J, M_a, M_b, V1_a, V1_b), each (nvec, nao, nao) (M_s None without want_k), of the trials D_s,k = A_s B_s,k^T +
+        B_s,k A_s^T: J[D_a,k + D_b,k], the unsymmetrised M_s,k = K[A_s B_s,k^T], and the raw V1_s of the pair."""
+        AB = [np.einsum("mi,kni->kmn", np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64))
+              for A, B in ((A_a, Bs_a), (A_b, Bs_b))]
+        Dp = [x + x.transpose(0, 2, 1) for x in AB]
+        J = np.einsum("ijkl,nkl->nij", self.inp.eri, Dp[0] + Dp[1])
+        M = [np.einsum("ikjl,nkl->nij", self.inp.eri, x) if want_k else None for x in AB]
+        if self.sweep:
+            if self.fxc is None:
+                raise ValueError("uks_excitation_parts: uks_response_prepare has not run")
+            V = [self.fxc.apply(da, db) for da, db in zip(Dp[0], Dp[1])]
+            V1a, V1b = np.stack([v[0] for v in V]), np.stack([v[1] for v in V])
+        else:
+            V1a, V1b = np.zeros_like(J), np.zeros_like(J)
+        return J, M[0], M[1], V1a, V1b
+
+
+_PBE_C = functionals.COMPONENTS.index("pbe_c")
+_VWN5_C = functionals.COMPONENTS.index("vwn5_c")
+
+
+def uks_orbitals(inp, uks_result, backend, functional=None):
+    """Canonical orbitals of a converged run_uks state for the open-shell response: one eigh(F_s, S) per spin of the Fock
+    matrices of the converged densities (backend.uks_parts), then backend.uks_response_prepare.  Returns (f, spins) with
+    f the resolved functional and spins a list of two dicts {Co (nao, n_s), Cv (nao, nv_s), gap (n_s, nv_s)}."""
+    f = functionals.resolve(functional if functional is not None else backend.functional)
+    wv = f.weight_vector()
+    if bool(getattr(backend, "quirks", False)) and (wv[_VWN5_C] != 0.0 or wv[_PBE_C] != 0.0):
+        raise ValueError("open-shell response: the spin-resolved kernel is the second derivative of the energy, but with quirks = 1 the "
+                         "shipped vwn5_c / pbe_c potentials are not the derivatives of their energies; run with --quirks 0")
+    for k in ("dm_a", "dm_b", "nalpha", "nbeta"):
+        if k not in uks_result:
+            raise ValueError("open-shell response needs a scf.run_uks result (dm_a, dm_b, nalpha, nbeta)")
+    want_k = f.c_hf != 0.0
+    S = inp.S
+    dms = [np.ascontiguousarray(uks_result[k], dtype=np.float64) for k in ("dm_a", "dm_b")]
+    ns = [int(uks_result["nalpha"]), int(uks_result["nbeta"])]
+    coccs = []
+    for dm, n in zip(dms, ns):      # dm_s S is the projector on the occupied orbitals of spin s
+        e0, C0 = eigh(S @ dm @ S, S)
+        coccs.append(np.ascontiguousarray(C0[:, ::-1][:, :n] * np.sqrt(np.maximum(e0[::-1][:n], 0.0))))
+    J, Ka, Kb, _, Va, Vb = backend.uks_parts(dms[0], dms[1], coccs[0], coccs[1], want_k)
+    spins = []
+    for V, K, n in ((Va, Ka, ns[0]), (Vb, Kb, ns[1])):
+        F = inp.Hcore + J + 0.5 * (V + V.T) - (f.c_hf * K if want_k else 0.0)
+        e, C = eigh(F, S)
+        gap = np.ascontiguousarray(e[None, n:] - e[:n, None])
+        if gap.size and gap.min() <= 1e-6:
+            raise ValueError("open-shell response: no gap between the occupied and the virtual orbitals of one spin")
+        spins.append({"Co": np.ascontiguousarray(C[:, :n]), "Cv": np.ascontiguousarray(C[:, n:]), "gap": gap})
+    if not (spins[0]["gap"].size + spins[1]["gap"].size):
+        raise ValueError("open-shell response: no occupied-virtual pairs")
+    backend.uks_response_prepare(dms[0], dms[1])
+    return f, spins
+
+
+def _polarizability_uks(inp, uks_result, backend, functional, tol, max_iter, log):
+    """The unrestricted CPKS equations (occupation 1, K enters with c_hf): per spin s
+
+        (e_a - e_i) U_s,ai + [C_vs^T G_s C_os]_ai = -[C_vs^T D_k C_os]_ai,     dm1_s = C_vs U_s C_os^T + transpose
+        G_s = J[dm1_a + dm1_b] + (V1_s + V1_s^T)/2 - c_hf K[dm1_s],             alpha_kl = -tr((dm1_a + dm1_b)(l) D_k)
+
+    on the stacked unknown (U_a, U_b), every step through one backend.uks_excitation_parts call with one trial."""
+    f, sp = uks_orbitals(inp, uks_result, backend, functional)
+    c_hf, want_k = f.c_hf, f.c_hf != 0.0
+    D = integrals.dipole(inp.shells)
+    shapes = [(s["Cv"].shape[1], s["Co"].shape[1]) for s in sp]
+    na = shapes[0][0] * shapes[0][1]
+    gaps = [s["gap"].T for s in sp]                                              # (nv_s, n_s)
+
+    def split(u):
+        return [u[:na].reshape(shapes[0]), u[na:].reshape(shapes[1])]
+
+    def dms_of(u):
+        Bs = [s["Cv"] @ U for s, U in zip(sp, split(u))]                        # (nao, n_s)
+        out = []
+        for s, B in zip(sp, Bs):
+            M = B @ s["Co"].T
+            out.append(M + M.T)
+        return out, Bs
+
+    def apply_a(u):
+        _, Bs = dms_of(u)
+        J, Ma, Mb, Va, Vb = backend.uks_excitation_parts(sp[0]["Co"], Bs[0][None], sp[1]["Co"], Bs[1][None], want_k)
+        out = []
+        for s, V, M, gap in zip(sp, (Va, Vb), (Ma, Mb), gaps):
+            G = J[0] + 0.5 * (V[0] + V[0].T) - (c_hf * (M[0] + M[0].T) if want_k else 0.0)
+            out.append(((s["Cv"].T @ G @ s["Co"]) / gap).reshape(-1))
+        return np.concatenate(out)
+
+    alpha, its, ress, dm1s = np.zeros((3, 3)), [], [], []
+    for l in range(3):
+        b = -np.concatenate([((s["Cv"].T @ D[l] @ s["Co"]) / gap).reshape(-1) for s, gap in zip(sp, gaps)])
+        u, n, r = _gmres(apply_a, b, tol, max_iter)
+        d, _ = dms_of(u)
+        dm1 = d[0] + d[1]
+        alpha[:, l] = -np.einsum("kij,ji->k", D, dm1)
+        its.append(n); ress.append(r); dm1s.append(dm1)
+        if log:
+            log(f"CPKS direction {'xyz'[l]}: {n} iterations, residual {r:.2e}")
+    return {"alpha": alpha, "cpks_iterations": its, "residual": ress, "dipole_integrals": D, "dm1": dm1s}
+
+
 def _gmres(apply_a, b, tol, max_iter):
     """x with |(1 + A) x - b|_2 <= tol by GMRES without restarts: (x, matrix-vector products, final residual norm)."""
     beta = float(np.linalg.norm(b))
@@ -304,7 +497,12 @@ def polarizability(inp, scf_result, backend, functional=None, tol=1e-8, max_iter
     Canonical orbitals come from one eigh(F, S) of the Fock matrix of the converged density.  Each direction is solved
     by GMRES on the equations divided by e_a - e_i, to a residual 2-norm `tol`; every step takes J, K and V1 of one
     symmetric dm1 from `backend` (response_prepare / response_parts; ground_state_parts for the Fock matrix).  Returns
-    {"alpha", "cpks_iterations" (per direction), "residual" (per direction), "dipole_integrals", "dm1" (per direction)}."""
+    {"alpha", "cpks_iterations" (per direction), "residual" (per direction), "dipole_integrals", "dm1" (per direction)}.
+
+    A scf.run_uks result (uks = True) is solved by the unrestricted equations (_polarizability_uks) through
+    backend.uks_parts / uks_response_prepare / uks_excitation_parts; the same fields come back."""
+    if scf_result.get("uks"):
+        return _polarizability_uks(inp, scf_result, backend, functional, tol, max_iter, log)
     f = functionals.resolve(functional if functional is not None else backend.functional)
     c_hf, want_k = f.c_hf, f.c_hf != 0.0
     S, nocc = inp.S, inp.nocc

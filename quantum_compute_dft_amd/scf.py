@@ -572,6 +572,56 @@ class HipBackend:
         h = o.cpu().numpy()
         return h[0], (h[1] if want_k else None), (h[2] if want_k else None), exc, h[3], h[4]
 
+    # ---- open-shell linear response (excitations.UksResponseOperators, response.polarizability of a run_uks result) -----
+    def uks_response_prepare(self, dm_a, dm_b):
+        """DFT_FxcPrepareSpinPol at the converged spin density matrices: the table of the open-shell response of Vxc, kept
+        in the solver beside (and apart from) the closed-shell tables."""
+        self._uks_check()
+        self._response_check()
+        t = self.torch
+        self._d_dm0_s = [t.as_tensor(np.ascontiguousarray(d), dtype=t.float64, device=self.dev) for d in (dm_a, dm_b)]
+        self.solver.fxc_prepare_spinpol(self.ngrid, self.nao, self._d_dm0_s[0], self._d_dm0_s[1], self.d_ao, self.d_w, self.d_gr)
+        t.cuda.synchronize()
+
+    def uks_excitation_parts(self, A_a, Bs_a, A_b, Bs_b, want_k):
+        """(J, M_a, M_b, V1_a, V1_b), each (nvec, nao, nao) as numpy arrays (M_s None without want_k), of the trials
+        D_s,k = A_s B_s,k^T + B_s,k A_s^T with A_s (nao, n_s) and Bs_s (nvec, nao, n_s): J[D_a,k + D_b,k], the unsymmetrised
+        M_s,k = K[A_s B_s,k^T] (K[D+-] = M +- M^T) and the raw V1_s[D_a,k, D_b,k] of one DFT_FxcApplySpinPol per trial.
+        Cholesky vectors: one DFT_ComputeJKFactorizedResponse call per spin, the two J summed.  Dense ERI:
+        DFT_ComputeCoulomb on the total and DFT_ComputeJK per spin.  A spin without electrons launches nothing for J and
+        M and contributes zeros.  After uks_response_prepare."""
+        self._uks_check()
+        self._response_check()
+        t, n = self.torch, self.nao
+        f64 = t.float64
+        d_A = [t.as_tensor(np.ascontiguousarray(a, dtype=np.float64), dtype=f64, device=self.dev) for a in (A_a, A_b)]
+        d_B = [t.as_tensor(np.ascontiguousarray(b, dtype=np.float64), dtype=f64, device=self.dev) for b in (Bs_a, Bs_b)]
+        for a, b in zip(d_A, d_B):
+            if b.dim() != 3 or a.dim() != 2 or a.shape[0] != n or tuple(b.shape[1:]) != tuple(a.shape) or b.shape[0] != d_B[0].shape[0]:
+                raise ValueError(f"uks_excitation_parts: A_s (nao, n_s) and Bs_s (nvec, nao, n_s) expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+        nvec = d_B[0].shape[0]
+        out = t.zeros((6, nvec, n, n), dtype=f64, device=self.dev)                   # J | M_a | M_b | V1_a | V1_b | J of beta
+        AB = [t.matmul(a.unsqueeze(0), b.transpose(1, 2)).contiguous() for a, b in zip(d_A, d_B)]
+        Dp = [(x + x.transpose(1, 2)).contiguous() for x in AB]
+        if self.d_chol is not None:
+            for s in range(2):
+                if d_A[s].shape[1]:
+                    self.solver.compute_jk_factorized_response(n, self.d_chol.shape[0], d_A[s].shape[1], nvec, self.d_chol, d_A[s], d_B[s],
+                                                               out[0] if s == 0 else out[5], out[1 + s] if want_k else None)
+            out[0].add_(out[5])
+        else:
+            Dt = (Dp[0] + Dp[1]).contiguous()
+            for k in range(nvec):
+                self.solver.compute_coulomb(n, self.d_eri, Dt[k], out[0, k])
+                for s in range(2):
+                    if want_k and d_A[s].shape[1]:
+                        self.solver.compute_jk(n, self.d_eri, AB[s][k], None, out[1 + s, k])
+        for k in range(nvec):
+            self.solver.fxc_apply_spinpol(self.ngrid, n, Dp[0][k], Dp[1][k], self.d_ao, out[3, k], out[4, k], self.d_gr)
+        t.cuda.synchronize()
+        h = out.cpu().numpy()
+        return h[0], (h[1] if want_k else None), (h[2] if want_k else None), h[3], h[4]
+
 
     # ---- linear response (response.polarizability): one rank, resident AO planes ------------------------------
     def _response_check(self):

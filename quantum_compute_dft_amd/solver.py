@@ -142,6 +142,12 @@ class DFTSolverWrapper:
         L.DFT_FxcApplyKind.restype = ctypes.c_int
         L.DFT_ComputeXCSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, _u64, _u64, dp]
         L.DFT_ComputeXCSpin.restype = ctypes.c_int
+        L.DFT_FxcPrepareSpinPol.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64]
+        L.DFT_FxcPrepareSpinPol.restype = ctypes.c_int
+        L.DFT_FxcApplySpinPol.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, _u64]
+        L.DFT_FxcApplySpinPol.restype = ctypes.c_int
+        L.DFT_FxcSpinPolTable.argtypes = [ctypes.c_void_p, _u64, ctypes.c_longlong]
+        L.DFT_FxcSpinPolTable.restype = ctypes.c_int
 
         if self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
@@ -319,6 +325,33 @@ class DFTSolverWrapper:
                                    ctypes.byref(exc))
         self._check()
         return exc.value
+
+    def fxc_prepare_spinpol(self, ngrid, nao, d_dm0_a, d_dm0_b, d_ao, d_weights, d_ao_grad=None):
+        """First half of the open-shell response of Vxc (DFT_FxcPrepareSpinPol): the densities of the two spins and the
+        second-derivative table of the spin-resolved energy bodies at any polarisation, kept in a slot of its own.  With
+        option quirks = 1 a functional with vwn5_c or pbe_c is refused, as by compute_xc_spin."""
+        rc = self.lib.DFT_FxcPrepareSpinPol(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm0_a)), _u64(_ptr(d_dm0_b)),
+                                            _u64(_ptr(d_ao)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_weights)))
+        self._check()
+        return rc
+
+    def fxc_apply_spinpol(self, ngrid, nao, d_dm1_a, d_dm1_b, d_ao, d_v1_a, d_v1_b, d_ao_grad=None):
+        """V1_s = d/dt compute_xc_spin(dm0_a + t dm1_a, dm0_b + t dm1_b).vxc_s at t = 0 into d_v1_a / d_v1_b
+        (DFT_FxcApplySpinPol), in compute_xc_spin's conventions; asynchronous on the solver's stream.  Any number of calls
+        after one fxc_prepare_spinpol."""
+        rc = self.lib.DFT_FxcApplySpinPol(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm1_a)), _u64(_ptr(d_dm1_b)),
+                                          _u64(_ptr(d_ao)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_v1_a)), _u64(_ptr(d_v1_b)))
+        self._check()
+        return rc
+
+    def fxc_spinpol_table(self, ngrid, device):
+        """(planes, ngrid) torch tensor: a copy of the table fxc_prepare_spinpol left (DFT_FxcSpinPolTable; for the tests)."""
+        import torch
+        buf = torch.empty(28 * int(ngrid), dtype=torch.float64, device=device)
+        planes = self.lib.DFT_FxcSpinPolTable(self.solver, _u64(_ptr(buf)), buf.numel())
+        self._check()
+        torch.cuda.synchronize()
+        return buf[:planes * int(ngrid)].view(planes, int(ngrid))
 
     def mix(self):
         """The solver's weights as the library reports them (DFT_GetMix; for a built-in type: its equivalent mix)."""
