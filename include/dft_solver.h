@@ -372,6 +372,34 @@ int DFT_FxcApplySpinPol(XCSolver *solver, long long ngrid, int nao, unsigned lon
  * DFT_GetLastError: nothing prepared, or max_doubles below planes * ngrid. */
 int DFT_FxcSpinPolTable(XCSolver *solver, unsigned long long d_out_ptr, long long max_doubles);
 
+/* XC part of the analytic nuclear gradient, at fixed quadrature points and weights (csrc/xc_grad.hip).
+ * DFT_EvalAOHess: the six second-derivative planes d_hess (6, ngrid, nao), row-major fp64, in the order xx, xy, xz, yy,
+ * yz, zz, of the AOs DFT_EvalAO evaluates: the same shell table (host arrays), real solid harmonics, column order and
+ * primitive cut-off (exp(-46)), s-f.  A kernel of its own ("eval_ao_hess"); asynchronous on the solver's stream.
+ * DFT_ComputeXCGradient: d_out (nao, 3) receives G[mu, x] = d/dt of the Exc DFT_ComputeXC returns when, in column mu
+ * only, ao[:, mu] is replaced by ao[:, mu] - t ao_grad[x][:, mu] and ao_grad[k][:, mu] by ao_grad[k][:, mu] -
+ * t ao_hess[xk][:, mu], dm (symmetric) and the weights fixed: the derivative of Exc by the centre of function mu.  The
+ * XC term of dE/dR_A is the sum of G[mu, :] over the functions on atom A (taken by the caller).  With "quirks" = 1 and
+ * vwn5_c or pbe_c in the functional the shipped potentials are not the derivatives of the energy, and G is built from
+ * the shipped ones.  Linear in the grid points: a caller may sum G over slices of the grid.
+ * On the solver's stream, no host wait: the density kernels and the pointwise kernel of the sweep with the sweep's
+ * choices ("path", nao, plane size), into buffers of this entry, then "xc_grad": per tile of 16 grid rows X = AO D and
+ * Z = Q D (Q = 2 c0 AO + sum_k c_k ao_grad[k]) on the fp64 matrix pipe, contracted with ao_grad and ao_hess into one
+ * (nao, 3) slab per workgroup, and a fixed-order slab sum, so a call is bitwise reproducible.  Never the one-kernel
+ * plan, never a recorded graph; prepared DFT_Fxc* tables and later DFT_ComputeXC results are left bit for bit as they
+ * were.  d_ao_hess may be 0 for an LDA-class solver (it is not read); d_ao_grad is needed by every solver, since the
+ * displaced density is made of it.  nao is limited by the (nao, 3) accumulator and the 16-row AO and Q tiles a
+ * workgroup keeps in LDS (tiles of at most 512 columns; wider bases are staged in chunks).
+ * Both return 0, or -1 with DFT_GetLastError (nothing aborts): a null pointer, bad sizes, a null ao_grad, a null
+ * ao_hess on a gradient solver.  Added without a change of DFT_GetVersion (it stays 5): look the symbols up. */
+int DFT_EvalAOHess(XCSolver *solver, long long ngrid, int nao, int nshell,
+                   const double *shl_xyz, const int *shl_l, const int *shl_nprim, const int *shl_off, const int *shl_ao,
+                   const double *prim_exp, const double *prim_coef, int nprim_total,
+                   unsigned long long d_coords_ptr, unsigned long long d_hess_ptr);
+int DFT_ComputeXCGradient(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr,
+                          unsigned long long d_ao_ptr, unsigned long long d_weights_ptr, unsigned long long d_ao_grad_ptr,
+                          unsigned long long d_ao_hess_ptr, unsigned long long d_out_ptr);
+
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
  * reference builds the whole tensor on the host with PySCF, `mol.intor('int2e')` at grid.py:65).  Device counterpart

@@ -33,6 +33,7 @@
 #include "xc_response_launch.hpp"
 #include "xc_response_pol_launch.hpp"
 #include "xc_spin_launch.hpp"
+#include "xc_grad_launch.hpp"
 
 using namespace qcdft;
 
@@ -140,6 +141,9 @@ struct XCSolver {
     // DFT_ComputeXCSpin: densities, gradients and coefficient planes of the two spins, the partials and the scalar of its
     // Exc -- buffers of its own, so that no recorded sweep and no prepared response table holds or reads any of them
     DevBuf spin_rho[2], spin_grad[2], spin_sigma, spin_coef[2], spin_partial, spin_exc;
+    // DFT_ComputeXCGradient: density, gradient, coefficient planes, Exc partials and slabs of its own -- no recorded sweep and no
+    // prepared response table holds or reads any of them (Dsym alone is shared, in stream order)
+    DevBuf xcg_rho, xcg_grad, xcg_sigma, xcg_coef, xcg_partial, xcg_slabs;
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -1334,6 +1338,64 @@ __global__ void k_accumulate_chunk(long n2, int add, const double *__restrict__ 
     if (i == 0) *e = add ? *e + *ec : *ec;
 }
 
+// XC part of the nuclear gradient (DFT_ComputeXCGradient): the sweep's own density kernels and pointwise kernel, into
+// buffers of this entry, then k_xc_grad (xc_grad.hip) on the coefficient planes.  Never the one-kernel plan for small
+// bases (it keeps no coefficients), never recorded; asynchronous on the solver's stream.
+bool xc_gradient(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *w, const double *ao_grad,
+                 const double *ao_hess, double *out)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
+    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
+    if (!dm || !ao || !w || !out) { set_error(s, "DFT_ComputeXCGradient needs dm, the AO values, the grid weights and the output"); return false; }
+    const bool gga = s->needs_grad;
+    if (gga && (!ao_grad || !ao_hess)) {
+        set_error(s, "ao_grad or ao_hess pointer is null for a gradient-corrected functional");
+        return false;
+    }
+    if (!ao_grad) { set_error(s, "DFT_ComputeXCGradient needs ao_grad: the derivative of the density by a centre is made of it"); return false; }
+    const XcGradPlan G = xc_grad_plan(s->num_cu, gga, ngrid, nao);
+    if (G.lds > 160 * 1024) { set_error(s, "DFT_ComputeXCGradient: nao=%d needs %zu bytes of LDS per workgroup", nao, G.lds); return false; }
+    // an LDA-class solver's density kernels read ao_grad's first plane pointer only as a dummy: plan as the sweep does
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
+    const size_t ng = (size_t)ngrid;
+    const long nxb = (ngrid + 255) / 256;
+    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
+        !reserve(s, s->xcg_rho, sizeof(double) * ng, "hipMalloc(gradient rho)", false) ||
+        !reserve(s, s->xcg_coef, sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(gradient coef)", false) ||
+        !reserve(s, s->xcg_partial, sizeof(double) * nxb, "hipMalloc(gradient partial)", false) ||
+        !reserve(s, s->xcg_slabs, sizeof(double) * (size_t)G.nwg * 3 * nao, "hipMalloc(gradient slabs)", false))
+        return false;
+    if (gga && (!reserve(s, s->xcg_sigma, sizeof(double) * ng, "hipMalloc(gradient sigma)", false) ||
+                !reserve(s, s->xcg_grad, sizeof(double) * 3 * ng, "hipMalloc(gradient grad rho)", false)))
+        return false;
+    double *Dp = (double *)s->dsym.p, *rho = (double *)s->xcg_rho.p, *sigma = (double *)s->xcg_sigma.p, *grad = (double *)s->xcg_grad.p,
+           *coef = (double *)s->xcg_coef.p, *partial = (double *)s->xcg_partial.p;
+    hipStream_t st = s->stream;
+    launch_density(s, P, ngrid, nao, dm, ao, Dp, rho, grad, sigma);
+    if (P.fast) {   // the wave-specialised density kernel symmetrises dm itself: k_xc_grad reads the padded matrix
+        ScopedTimer t(s, "sym_dm");
+        dim3 b(16, 16), g(P.NP / 16, P.NP / 16);
+        hipLaunchKernelGGL(k_sym_dm, g, b, 0, st, nao, P.NP, dm, Dp);
+    }
+    {
+        ScopedTimer t(s, "xc_points");
+        dim3 g((unsigned)nxb);
+        if (s->type == SOLVER_LDA)      hipLaunchKernelGGL(k_xc_points<0>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
+        else if (s->type == SOLVER_GGA) hipLaunchKernelGGL(k_xc_points<1>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
+        else if (s->type == SOLVER_B3LYP) hipLaunchKernelGGL(k_xc_points<2>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
+        else if (gga)                   hipLaunchKernelGGL(k_xc_points_mix<true>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
+        else                            hipLaunchKernelGGL(k_xc_points_mix<false>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
+    }
+    if (!hip_ok(s, hipGetLastError(), "XC gradient density launch")) return false;
+    ScopedTimer t(s, "xc_grad");
+    // one-sided types hand over c0 = w vrho, c_k = 4 w vsigma grad_k rho; B3LYP half of each (its M + M^T)
+    const double fac = s->type == SOLVER_B3LYP ? 2.0 : 1.0;
+    return hip_ok(s, launch_xc_grad(st, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, coef, Dp, (double *)s->xcg_slabs.p, out),
+                  "XC gradient launch");
+}
+
 } // namespace
 
 extern "C" {
@@ -1449,7 +1511,8 @@ void DFT_DestroySolver(XCSolver *s)
                           &s->fxc_spin_table[0], &s->fxc_spin_table[1], &s->fxc_spin_g0[0], &s->fxc_spin_g0[1],
                           &s->fxc_pol_table, &s->fxc_pol_g0[0], &s->fxc_pol_g0[1],
                           &s->spin_rho[0], &s->spin_rho[1], &s->spin_grad[0], &s->spin_grad[1], &s->spin_sigma, &s->spin_coef[0],
-                          &s->spin_coef[1], &s->spin_partial, &s->spin_exc};
+                          &s->spin_coef[1], &s->spin_partial, &s->spin_exc,
+                          &s->xcg_rho, &s->xcg_grad, &s->xcg_sigma, &s->xcg_coef, &s->xcg_partial, &s->xcg_slabs};
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
@@ -1867,6 +1930,35 @@ int DFT_EvalAO(XCSolver *s, long long ngrid, int nao, int nshell, const double *
     ScopedTimer t(s, "eval_ao");
     launch_ao(s, tab, (long)ngrid, nao, (const double *)d_coords, (double *)d_ao, (double *)d_ao_grad);
     return hip_ok(s, hipGetLastError(), "AO launch") ? 0 : -1;
+}
+
+int DFT_EvalAOHess(XCSolver *s, long long ngrid, int nao, int nshell, const double *shl_xyz,
+                   const int *shl_l, const int *shl_nprim, const int *shl_off, const int *shl_ao,
+                   const double *prim_exp, const double *prim_coef, int nprim_total,
+                   unsigned long long d_coords, unsigned long long d_hess)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return -1; }
+    if (ngrid <= 0) { set_error(s, "bad AO sizes"); return -1; }
+    if (!d_coords || !d_hess) { set_error(s, "DFT_EvalAOHess needs the coordinates and the output planes"); return -1; }
+    AoTable tab;
+    if (!prepare_ao_table(s, nao, nshell, shl_xyz, shl_l, shl_nprim, shl_off, shl_ao, prim_exp, prim_coef, nprim_total, tab)) return -1;
+    ScopedTimer t(s, "eval_ao_hess");
+    return hip_ok(s, launch_eval_ao_hess(s->stream, (long)ngrid, nao, tab.nchunk, tab.maxcol, tab.sh, tab.exp, tab.coef, tab.chunks,
+                                         (const double *)d_coords, (double *)d_hess), "AO Hessian launch") ? 0 : -1;
+}
+
+int DFT_ComputeXCGradient(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
+                          unsigned long long d_weights, unsigned long long d_ao_grad, unsigned long long d_ao_hess,
+                          unsigned long long d_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_gradient(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_weights,
+                       (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
 }
 
 int DFT_ComputeXCDirect(XCSolver *s, long long ngrid, int nao, int nshell, const double *shl_xyz,

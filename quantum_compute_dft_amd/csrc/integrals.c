@@ -28,7 +28,7 @@
 #define NCART(l) (((l) + 1) * ((l) + 2) / 2)
 #define MAXCART 10
 #define HDIM (2 * LMAX + 1)          /* t index range of one shell pair: 0..la+lb */
-#define RDIM (4 * LMAX + 1)          /* t index range of R: 0..la+lb+lc+ld */
+#define RDIM (4 * LMAX + 2)          /* t index range of R: 0..la+lb+lc+ld, and one more for a shell raised by a centre derivative */
 
 /* ---- Cartesian component tables and real-solid-harmonic rotation ------------------------- */
 static void cart_components(int l, int cx[MAXCART], int cy[MAXCART], int cz[MAXCART])
@@ -864,6 +864,325 @@ int qc_eri_cols2(void *h, int C, int D, double screen, double *out, int lower_on
         free(cart);
         free(t1);
     }
+    return 0;
+}
+
+/* ---- nuclear gradient: derivative integrals, contracted as they are made --------------------- */
+/* A Cartesian primitive moves with its centre by  d/dA_x x^i exp(-a x_A^2) = 2 a x^(i+1) exp - i x^(i-1) exp,  so the
+ * derivative of an integral by the bra centre is the same integral over the shell raised and lowered in that dimension:
+ * E tables to la + 1 (R to L + 1), nothing else new.  Only the bra is differentiated: for symmetric D and W
+ *     sum_{mu nu} D_mu,nu d<mu|O|nu>/dR_X (basis part) = 2 sum_{mu on X, nu} D_mu,nu <d mu/dX|O|nu>,
+ * and for the two-electron energy, by the eightfold symmetry of (mu nu|lam sig),
+ *     d/dR_X [1/2 sum D D (..|..) - c_hf/4 sum D D (..|..)] = sum_{mu on X} sum_{nu lam sig} [2 D_mu,nu D_lam,sig - c_hf D_mu,lam D_nu,sig] (mu' nu|lam sig).
+ * The matrices come in over spherical functions; each shell block is rotated to Cartesian components once. */
+
+/* Cartesian block of a spherical one: Mc[ca][cb] = sum Ta[ma][ca] Tb[mb][cb] M[ia + ma][ib + mb] */
+static void block_to_cart(int la, int lb, const double *M, int ld, int ia, int ib, double *Mc)
+{
+    double Ta[7][MAXCART], Tb[7][MAXCART];
+    sph_matrix(la, Ta);
+    sph_matrix(lb, Tb);
+    const int nca = NCART(la), ncb = NCART(lb);
+    memset(Mc, 0, sizeof(double) * nca * ncb);
+    for (int ma = 0; ma < 2 * la + 1; ++ma)
+        for (int mb = 0; mb < 2 * lb + 1; ++mb) {
+            const double d = M[(size_t)(ia + ma) * ld + ib + mb];
+            for (int ca = 0; ca < nca; ++ca)
+                if (Ta[ma][ca] != 0.0)
+                    for (int cb = 0; cb < ncb; ++cb) Mc[ca * ncb + cb] += Ta[ma][ca] * Tb[mb][cb] * d;
+        }
+}
+
+/* out (3, natm, 3): [0] -tr(W dS/dR_A), [1] tr(D dT/dR_A), [2] the basis-centre part of tr(D dV/dR_A) with
+ * V = -sum_c q_c / |r - R_c| over the ncen charged centres (the nuclei, and the external charges of an embedded run); the
+ * operator part of V -- the field of the electrons at a nucleus -- is qc_point_field's.  D, W symmetric (nao, nao);
+ * shl_atom: the atom that owns each shell. */
+int qc_grad1e(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+              const int *ao0, const double *ex, const double *cf, int nao, const int *shl_atom, int natm,
+              int ncen, const double *cen_xyz, const double *cen_q, const double *D, const double *W, double *out)
+{
+    for (int s = 0; s < nshell; ++s)
+        if (ls[s] < 0 || ls[s] > LMAX || shl_atom[s] < 0 || shl_atom[s] >= natm) return -1;
+    double *acc = (double *)calloc((size_t)nshell * 9, sizeof(double));
+#pragma omp parallel for schedule(dynamic)
+    for (int A = 0; A < nshell; ++A) {
+        double gs[3] = {0, 0, 0}, gt[3] = {0, 0, 0}, gv[3] = {0, 0, 0};
+        const int la = ls[A], nca = NCART(la);
+        int ax[MAXCART], ay[MAXCART], az[MAXCART], bx[MAXCART], by[MAXCART], bz[MAXCART];
+        cart_components(la, ax, ay, az);
+        const double *RA = xyz + 3 * A;
+        for (int B = 0; B < nshell; ++B) {
+            const int lb = ls[B], ncb = NCART(lb), L = la + lb + 1;
+            cart_components(lb, bx, by, bz);
+            double Dc[MAXCART * MAXCART], Wc[MAXCART * MAXCART];
+            block_to_cart(la, lb, D, nao, ao0[A], ao0[B], Dc);
+            block_to_cart(la, lb, W, nao, ao0[A], ao0[B], Wc);
+            const double *RB = xyz + 3 * B;
+            const double R2 = dist2(RA, RB);
+            for (int pa = 0; pa < nprim[A]; ++pa)
+                for (int pb = 0; pb < nprim[B]; ++pb) {
+                    const double a = ex[off[A] + pa], b = ex[off[B] + pb], p = a + b;
+                    const double cc = cf[off[A] + pa] * cf[off[B] + pb];
+                    if (!prim_pair_kept(a, b, cc, R2)) continue;
+                    double E[3][LMAX + 3][LMAX + 3][2 * LMAX + 5];
+                    for (int d = 0; d < 3; ++d) hermite_E(la + 1, lb + 2, a, b, RA[d] - RB[d], E[d]);
+                    const double P[3] = {(a * RA[0] + b * RB[0]) / p, (a * RA[1] + b * RB[1]) / p, (a * RA[2] + b * RB[2]) / p};
+                    const double s0 = cc * pow(M_PI / p, 1.5);
+                    /* dE[x][ca][cb][t]: Hermite coefficients, in dimension x, of the bra raised and lowered */
+                    static _Thread_local double dE[3][MAXCART][MAXCART][2 * LMAX + 2];
+                    for (int ca = 0; ca < nca; ++ca)
+                        for (int cb = 0; cb < ncb; ++cb) {
+                            const int i[3] = {ax[ca], ay[ca], az[ca]}, j[3] = {bx[cb], by[cb], bz[cb]};
+                            double s1[3], k1[3], ds[3], dk[3];
+                            for (int d = 0; d < 3; ++d) {
+                                const int jd = j[d];
+                                double sv[3], kv[3]; /* the 1-D overlap and kinetic factors at i - 1, i, i + 1 */
+                                for (int m = 0; m < 3; ++m) {
+                                    const int ii = i[d] - 1 + m;
+                                    sv[m] = kv[m] = 0.0;
+                                    if (ii < 0) continue;
+                                    sv[m] = E[d][ii][jd][0];
+                                    kv[m] = -2.0 * b * b * E[d][ii][jd + 2][0] + b * (2 * jd + 1) * sv[m];
+                                    if (jd >= 2) kv[m] -= 0.5 * jd * (jd - 1) * E[d][ii][jd - 2][0];
+                                }
+                                s1[d] = sv[1]; k1[d] = kv[1];
+                                ds[d] = 2.0 * a * sv[2] - i[d] * sv[0];
+                                dk[d] = 2.0 * a * kv[2] - i[d] * kv[0];
+                                for (int t = 0; t <= i[d] + jd + 1; ++t)
+                                    dE[d][ca][cb][t] = 2.0 * a * E[d][i[d] + 1][jd][t] - (i[d] ? i[d] * E[d][i[d] - 1][jd][t] : 0.0);
+                            }
+                            const double dw = s0 * Wc[ca * ncb + cb], dd = s0 * Dc[ca * ncb + cb];
+                            for (int x = 0; x < 3; ++x) {
+                                const int y = (x + 1) % 3, z = (x + 2) % 3;
+                                gs[x] += dw * ds[x] * s1[y] * s1[z];
+                                gt[x] += dd * (dk[x] * s1[y] * s1[z] + ds[x] * k1[y] * s1[z] + ds[x] * s1[y] * k1[z]);
+                            }
+                        }
+                    for (int c = 0; c < ncen; ++c) {
+                        static _Thread_local double R[RDIM][RDIM][RDIM];
+                        const double PC[3] = {P[0] - cen_xyz[3 * c], P[1] - cen_xyz[3 * c + 1], P[2] - cen_xyz[3 * c + 2]};
+                        hermite_R(L, p, PC, R);
+                        const double pref = -cen_q[c] * 2.0 * M_PI / p * cc;
+                        for (int ca = 0; ca < nca; ++ca)
+                            for (int cb = 0; cb < ncb; ++cb) {
+                                const double dd = pref * Dc[ca * ncb + cb];
+                                if (dd == 0.0) continue;
+                                const int i[3] = {ax[ca], ay[ca], az[ca]}, j[3] = {bx[cb], by[cb], bz[cb]};
+                                for (int x = 0; x < 3; ++x) {
+                                    const double *e0 = x == 0 ? dE[0][ca][cb] : E[0][i[0]][j[0]];
+                                    const double *e1 = x == 1 ? dE[1][ca][cb] : E[1][i[1]][j[1]];
+                                    const double *e2 = x == 2 ? dE[2][ca][cb] : E[2][i[2]][j[2]];
+                                    double v = 0.0;
+                                    for (int t = 0; t <= i[0] + j[0] + (x == 0); ++t)
+                                        for (int u = 0; u <= i[1] + j[1] + (x == 1); ++u)
+                                            for (int w = 0; w <= i[2] + j[2] + (x == 2); ++w) v += e0[t] * e1[u] * e2[w] * R[t][u][w];
+                                    gv[x] += dd * v;
+                                }
+                            }
+                    }
+                }
+        }
+        for (int x = 0; x < 3; ++x) { acc[9 * A + x] = gs[x]; acc[9 * A + 3 + x] = gt[x]; acc[9 * A + 6 + x] = gv[x]; }
+    }
+    memset(out, 0, sizeof(double) * 9 * natm);
+    for (int A = 0; A < nshell; ++A)   /* in shell order: the same sum whatever the thread count */
+        for (int x = 0; x < 3; ++x) {
+            out[3 * shl_atom[A] + x] -= 2.0 * acc[9 * A + x];
+            out[3 * natm + 3 * shl_atom[A] + x] += 2.0 * acc[9 * A + 3 + x];
+            out[6 * natm + 3 * shl_atom[A] + x] += 2.0 * acc[9 * A + 6 + x];
+        }
+    free(acc);
+    return 0;
+}
+
+/* transposed rotation of one index of a 4-index block, spherical -> Cartesian components of a DENSITY:
+ * in (n0, ns, n2) -> out (n0, nc, n2), out[c] = sum_m T[m][c] in[m] */
+static void rot_axis_t(int l, int n0, int n2, const double *in, double *out)
+{
+    double T[7][MAXCART];
+    sph_matrix(l, T);
+    const int nc = NCART(l), ns = 2 * l + 1;
+    for (int i0 = 0; i0 < n0; ++i0)
+        for (int c = 0; c < nc; ++c)
+            for (int i2 = 0; i2 < n2; ++i2) {
+                double s = 0.0;
+                for (int m = 0; m < ns; ++m)
+                    if (T[m][c] != 0.0) s += T[m][c] * in[((size_t)i0 * ns + m) * n2 + i2];
+                out[((size_t)i0 * nc + c) * n2 + i2] = s;
+            }
+}
+
+/* g3[x] += sum over Cartesian components of Gc[a][b][c][d] d(ab|cd)/dA_x for shells A, B, C, D (any order).  The ket is
+ * expanded as in quartet(); the bra's Hermite lists carry the raised and lowered first shell. */
+static void grad_quartet(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off, const double *ex,
+                         const double *cf, int A, int B, int C, int D, const double *Gc, double g3[3])
+{
+    (void)nshell;
+    const int la = ls[A], lb = ls[B], lc = ls[C], ld = ls[D];
+    const int nca = NCART(la), ncb = NCART(lb), ncc = NCART(lc), ncd = NCART(ld), nkb = nca * ncb, nkc = ncc * ncd;
+    int ax[MAXCART], ay[MAXCART], az[MAXCART], bx[MAXCART], by[MAXCART], bz[MAXCART];
+    int cx[MAXCART], cy[MAXCART], cz[MAXCART], dx[MAXCART], dy[MAXCART], dz[MAXCART];
+    cart_components(la, ax, ay, az); cart_components(lb, bx, by, bz);
+    cart_components(lc, cx, cy, cz); cart_components(ld, dx, dy, dz);
+    const int Lab = la + lb + 1, L = Lab + lc + ld;
+    const double *RA = xyz + 3 * A, *RB = xyz + 3 * B, *RC = xyz + 3 * C, *RD = xyz + 3 * D;
+    const double R2ab = dist2(RA, RB), R2cd = dist2(RC, RD);
+    const double two_pi_52 = 34.986836655249725; /* 2 pi^(5/2) */
+    enum { MAXE = 27, MAXD = 48 };   /* bra terms: (i_x + j_x + 2)(i_y + j_y + 1)(i_z + j_z + 1) <= 36 at l = 3 */
+    static _Thread_local double wk[MAXCART * MAXCART][MAXE], wb[3][MAXCART * MAXCART][MAXD];
+    static _Thread_local int ok_[MAXCART * MAXCART][MAXE], ob[3][MAXCART * MAXCART][MAXD], nk[MAXCART * MAXCART], nb[3][MAXCART * MAXCART];
+    static _Thread_local double g[RDIM * RDIM * RDIM], R[RDIM][RDIM][RDIM];
+    static _Thread_local double Eab[3][LMAX + 3][LMAX + 3][2 * LMAX + 5], Ecd[3][LMAX + 3][LMAX + 3][2 * LMAX + 5];
+    const double *Rf = &R[0][0][0];
+    int tuv[(HDIM + 1) * (HDIM + 1) * (HDIM + 1)], ntuv = 0;
+    for (int t = 0; t <= Lab; ++t)
+        for (int u = 0; u <= Lab - t; ++u)
+            for (int v = 0; v <= Lab - t - u; ++v) tuv[ntuv++] = (t * RDIM + u) * RDIM + v;
+    int live[MAXCART * MAXCART];   /* ket components that meet a non-zero density */
+    for (int kc = 0; kc < nkc; ++kc) {
+        live[kc] = 0;
+        for (int kb = 0; kb < nkb && !live[kc]; ++kb) live[kc] = Gc[(size_t)kb * nkc + kc] != 0.0;
+    }
+    for (int pc = 0; pc < nprim[C]; ++pc)
+        for (int pd = 0; pd < nprim[D]; ++pd) {
+            const double c_ = ex[off[C] + pc], d_ = ex[off[D] + pd], q = c_ + d_;
+            const double ccd = cf[off[C] + pc] * cf[off[D] + pd];
+            if (!prim_pair_kept(c_, d_, ccd, R2cd)) continue;
+            double Q[3];
+            for (int d = 0; d < 3; ++d) {
+                hermite_E(lc, ld, c_, d_, RC[d] - RD[d], Ecd[d]);
+                Q[d] = (c_ * RC[d] + d_ * RD[d]) / q;
+            }
+            for (int ic = 0; ic < ncc; ++ic)
+                for (int id = 0; id < ncd; ++id) {
+                    const int k = ic * ncd + id;
+                    int n = 0;
+                    for (int a1 = 0; a1 <= cx[ic] + dx[id]; ++a1) {
+                        const double e1 = Ecd[0][cx[ic]][dx[id]][a1];
+                        for (int a2 = 0; a2 <= cy[ic] + dy[id]; ++a2) {
+                            const double e2 = e1 * Ecd[1][cy[ic]][dy[id]][a2];
+                            for (int a3 = 0; a3 <= cz[ic] + dz[id]; ++a3) {
+                                const double e3 = e2 * Ecd[2][cz[ic]][dz[id]][a3];
+                                wk[k][n] = ((a1 + a2 + a3) & 1) ? -e3 : e3;
+                                ok_[k][n] = (a1 * RDIM + a2) * RDIM + a3;
+                                ++n;
+                            }
+                        }
+                    }
+                    nk[k] = n;
+                }
+            for (int pa = 0; pa < nprim[A]; ++pa)
+                for (int pb = 0; pb < nprim[B]; ++pb) {
+                    const double a = ex[off[A] + pa], b = ex[off[B] + pb], p = a + b;
+                    const double cab = cf[off[A] + pa] * cf[off[B] + pb];
+                    if (!prim_pair_kept(a, b, cab, R2ab)) continue;
+                    double PQ[3];
+                    for (int d = 0; d < 3; ++d) {
+                        hermite_E(la + 1, lb, a, b, RA[d] - RB[d], Eab[d]);
+                        PQ[d] = (a * RA[d] + b * RB[d]) / p - Q[d];
+                    }
+                    hermite_R(L, p * q / (p + q), PQ, R);
+                    const double pref = two_pi_52 / (p * q * sqrt(p + q)) * cab * ccd;
+                    for (int ia = 0; ia < nca; ++ia)
+                        for (int ib = 0; ib < ncb; ++ib) {
+                            const int k = ia * ncb + ib;
+                            const int i[3] = {ax[ia], ay[ia], az[ia]}, j[3] = {bx[ib], by[ib], bz[ib]};
+                            for (int x = 0; x < 3; ++x) {
+                                double dEx[2 * LMAX + 2];
+                                for (int t = 0; t <= i[x] + j[x] + 1; ++t)
+                                    dEx[t] = 2.0 * a * Eab[x][i[x] + 1][j[x]][t] - (i[x] ? i[x] * Eab[x][i[x] - 1][j[x]][t] : 0.0);
+                                const double *e0 = x == 0 ? dEx : Eab[0][i[0]][j[0]];
+                                const double *e1 = x == 1 ? dEx : Eab[1][i[1]][j[1]];
+                                const double *e2 = x == 2 ? dEx : Eab[2][i[2]][j[2]];
+                                int n = 0;
+                                for (int t = 0; t <= i[0] + j[0] + (x == 0); ++t)
+                                    for (int u = 0; u <= i[1] + j[1] + (x == 1); ++u)
+                                        for (int v = 0; v <= i[2] + j[2] + (x == 2); ++v) {
+                                            wb[x][k][n] = pref * e0[t] * e1[u] * e2[v];
+                                            ob[x][k][n] = (t * RDIM + u) * RDIM + v;
+                                            ++n;
+                                        }
+                                nb[x][k] = n;
+                            }
+                        }
+                    for (int kc = 0; kc < nkc; ++kc) {
+                        if (!live[kc]) continue;
+                        const int ne = nk[kc];
+                        for (int m = 0; m < ntuv; ++m) {
+                            const double *Rm = Rf + tuv[m];
+                            double sacc = 0.0;
+                            for (int e = 0; e < ne; ++e) sacc += wk[kc][e] * Rm[ok_[kc][e]];
+                            g[tuv[m]] = sacc;
+                        }
+                        for (int kb = 0; kb < nkb; ++kb) {
+                            const double gv = Gc[(size_t)kb * nkc + kc];
+                            if (gv == 0.0) continue;
+                            for (int x = 0; x < 3; ++x) {
+                                double sacc = 0.0;
+                                for (int e = 0; e < nb[x][kb]; ++e) sacc += wb[x][kb][e] * g[ob[x][kb][e]];
+                                g3[x] += gv * sacc;
+                            }
+                        }
+                    }
+                }
+        }
+}
+
+/* out (natm, 3): the derivative of  1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum D_ac D_bd (ab|cd)  by the centres, D symmetric.
+ * Every ordered bra pair (A, B) with every ket pair C >= D: the derivative by the centre of A alone, see above.  The dense
+ * ERI is never built; primitive pairs are screened as everywhere in the engine.  OpenMP over the first shell. */
+int qc_grad2e(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+              const int *ao0, const double *ex, const double *cf, int nao, const int *shl_atom, int natm,
+              const double *Dm, double c_hf, double *out)
+{
+    for (int s = 0; s < nshell; ++s)
+        if (ls[s] < 0 || ls[s] > LMAX || shl_atom[s] < 0 || shl_atom[s] >= natm) return -1;
+    double *acc = (double *)calloc((size_t)nshell * nshell * 3, sizeof(double));
+    const size_t n = (size_t)nao;
+#pragma omp parallel
+    {
+        double *Gs = (double *)malloc(sizeof(double) * QUARTET_DOUBLES);
+        double *Gc = (double *)malloc(sizeof(double) * QUARTET_DOUBLES);
+#pragma omp for schedule(dynamic)
+        for (int AB = 0; AB < nshell * nshell; ++AB) {
+            const int A = AB / nshell, B = AB - A * nshell;
+            const int la = ls[A], lb = ls[B], nsa = 2 * la + 1, nsb = 2 * lb + 1;
+            double g3[3] = {0, 0, 0};
+            for (int C = 0; C < nshell; ++C)
+                for (int D = 0; D <= C; ++D) {
+                    const int lc = ls[C], ld = ls[D], nsc = 2 * lc + 1, nsd = 2 * ld + 1;
+                    const double f = C == D ? 1.0 : 2.0;   /* (..|lam sig) = (..|sig lam): an off-diagonal ket pair stands for both orders */
+                    double big = 0.0;
+                    for (int ma = 0; ma < nsa; ++ma)
+                        for (int mb = 0; mb < nsb; ++mb)
+                            for (int mc = 0; mc < nsc; ++mc)
+                                for (int md = 0; md < nsd; ++md) {
+                                    const size_t i = ao0[A] + ma, j = ao0[B] + mb, k = ao0[C] + mc, l = ao0[D] + md;
+                                    double v = 2.0 * f * Dm[i * n + j] * Dm[k * n + l];
+                                    if (c_hf != 0.0)
+                                        v -= c_hf * (C == D ? Dm[i * n + k] * Dm[j * n + l]
+                                                            : Dm[i * n + k] * Dm[j * n + l] + Dm[i * n + l] * Dm[j * n + k]);
+                                    Gs[((ma * nsb + mb) * nsc + mc) * nsd + md] = v;
+                                    if (fabs(v) > big) big = fabs(v);
+                                }
+                    if (big == 0.0) continue;
+                    const int ncb = NCART(lb), ncc = NCART(lc), ncd = NCART(ld);
+                    rot_axis_t(la, 1, nsb * nsc * nsd, Gs, Gc);
+                    rot_axis_t(lb, NCART(la), nsc * nsd, Gc, Gs);
+                    rot_axis_t(lc, NCART(la) * ncb, nsd, Gs, Gc);
+                    rot_axis_t(ld, NCART(la) * ncb * ncc, 1, Gc, Gs);
+                    (void)ncd;
+                    grad_quartet(nshell, xyz, ls, nprim, off, ex, cf, A, B, C, D, Gs, g3);
+                }
+            for (int x = 0; x < 3; ++x) acc[3 * (size_t)AB + x] = g3[x];
+        }
+        free(Gs);
+        free(Gc);
+    }
+    memset(out, 0, sizeof(double) * 3 * natm);
+    for (int AB = 0; AB < nshell * nshell; ++AB)   /* in pair order: the same sum whatever the thread count */
+        for (int x = 0; x < 3; ++x) out[3 * shl_atom[AB / nshell] + x] += acc[3 * (size_t)AB + x];
+    free(acc);
     return 0;
 }
 

@@ -1,0 +1,34 @@
+// Host interface of the XC part of the nuclear gradient (xc_grad.hip): the second-derivative AO planes and the
+// contraction of the sweep's coefficient planes with them.  Compiled in their own translation unit, like xc_occ.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include "ao_kernels.hpp"
+
+namespace qcdft {
+
+constexpr int XCG_ROWS = 16;      // grid rows per tile of k_xc_grad (one MFMA block of rows)
+constexpr int XCG_KC_MAX = 512;   // widest K chunk (basis functions) of the AO / Q tile a workgroup keeps in LDS
+constexpr int AOH_PT = 8;         // grid points per workgroup of k_eval_ao_hess (six planes x 8 x 127 doubles = 48 KB of LDS)
+
+// hess (6, ngrid, nao): xx, xy, xz, yy, yz, zz of every AO at every point; the shell table as launch_eval_ao takes it
+// (blocks of at most AO_CW columns, `maxcol` the widest).
+hipError_t launch_eval_ao_hess(hipStream_t st, long ngrid, int nao, int nchunk, int maxcol, const AoShell *sh,
+                               const double *pexp, const double *pcoef, const AoChunk *chunks, const double *coords,
+                               double *hess);
+
+// Workgroups of launch_xc_grad for this shape (= slabs of (nao, 3) it writes) and its K chunk.
+struct XcGradPlan {
+    int NP = 0, kc = 0, ldk = 0, nwg = 0;
+    size_t lds = 0;
+};
+XcGradPlan xc_grad_plan(int num_cu, bool gga, long ngrid, int nao);
+
+// out (nao, 3) = -fac * sum_g [ grad_x (Q D) + (sum_k c_k hess_xk) (AO D) ],  Q = 2 c0 AO + sum_k c_k grad_k, from the
+// coefficient planes coef (c0..c3 SoA, ngrid each; c0 alone when !gga), the zero-padded symmetric Dp (NP, NP) and the
+// planes; slabs: room for nwg * 3 * nao doubles.  hess may be null when !gga.  A fixed-order slab sum finishes.
+hipError_t launch_xc_grad(hipStream_t st, const XcGradPlan &p, bool gga, double fac, long ngrid, int nao, const double *ao,
+                          const double *ao_grad, const double *hess, const double *coef, const double *Dp, double *slabs,
+                          double *out);
+
+} // namespace qcdft

@@ -75,6 +75,14 @@ def write_charge_force_rows(path, charges_bohr, forces, unit="angstrom"):
             fh.write(f"{x * scale:.10f} {y * scale:.10f} {z * scale:.10f} {q:.12e} {f[0]:.12e} {f[1]:.12e} {f[2]:.12e}\n")
 
 
+def print_gradient(symbols, g):
+    """The table of atoms with dE/dR (Ha/bohr) and the net force the fixed quadrature leaves."""
+    print("Nuclear gradient dE/dR (Ha/bohr), at fixed quadrature points and weights:")
+    for k, (s, r) in enumerate(zip(symbols, g), 1):
+        print(f"  {k:3d} {s:2s} {r[0]:+16.10f} {r[1]:+16.10f} {r[2]:+16.10f}")
+    print("  sum    " + " ".join(f"{x:+16.10f}" for x in g.sum(axis=0)) + f"   max|g| = {np.abs(g).max():.2e}  rms = {np.sqrt(np.mean(g * g)):.2e}")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Run DFT (LDA/GGA/B3LYP) using the MI355X HIP backend.")
     p.add_argument("functional", type=_functional,
@@ -147,6 +155,12 @@ def main(argv=None):
                    help="with --spin: allow --dipole, --polarizability (unrestricted CPKS) and --excitations (spin-conserving U-TDDFT / "
                         "U-TDA, rows U1 ...) from the unrestricted reference (the open-shell response of Vxc on the device: "
                         "DFT_FxcPrepareSpinPol / DFT_FxcApplySpinPol); --triplets stays refused")
+    p.add_argument("--gradient", action="store_true",
+                   help="analytic nuclear gradient dE/dR of the converged closed-shell state (Ha/bohr), at fixed quadrature points and weights")
+    p.add_argument("--optimize", action="store_true",
+                   help="Cartesian BFGS geometry optimisation on that gradient (step cap 0.3 bohr; max|g| < 3e-4, rms < 2e-4 Ha/bohr); "
+                        "writes <molecule>_opt.xyz")
+    p.add_argument("--opt-max-steps", type=int, default=50, metavar="N", help="with --optimize: at most N steps")
     p.add_argument("--charge", type=int, default=0, metavar="Q", help="charge of the molecule (electrons = sum Z - Q); an odd count needs --spin")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
@@ -165,6 +179,18 @@ def main(argv=None):
     if args.excitations and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident"):
         p.error("--excitations runs on one rank with --ao resident")
 
+    if args.gradient or args.optimize:
+        if args.spin is not None:
+            p.error("--gradient / --optimize: an unrestricted (--spin) run has no analytic gradient here: the assembly is closed-shell")
+        if args.efield is not None:
+            p.error("--gradient / --optimize: a run in a uniform electric field (--efield) is not supported")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.dm_factor:
+            p.error("--gradient / --optimize run on one rank and without --dm-factor")
+        if args.quirks and fn.uses_quirks:
+            p.error("--gradient / --optimize: with quirks = 1 the shipped vwn5_c / pbe_c potentials are not the derivatives of their "
+                    "energies, so the converged state is not stationary; run with --quirks 0")
+        if args.opt_max_steps < 1:
+            p.error("--opt-max-steps takes a positive number")
     uks = args.spin is not None
     if args.open_shell_response and not uks:
         p.error("--open-shell-response goes with --spin N")
@@ -334,6 +360,27 @@ def main(argv=None):
         for n, (w, f_n, x) in enumerate(zip(excited["energies"], excited["oscillator_strengths"], excited["xpy"]), 1):
             i, a = np.unravel_index(np.argmax(np.abs(x)), x.shape)
             print(f"  {mult}{n:<4d} {w * _ex.HARTREE_EV:9.4f} {_ex.NM_PER_HARTREE / w:10.2f} {f_n:10.6f}    {i + 1} -> {nocc_ + a + 1} ({abs(x[i, a]):.3f})")
+    grad = grad_terms = opt = None
+    if (args.gradient or args.optimize) and res["converged"]:
+        from . import gradients, optimize
+        grad, grad_terms = gradients.nuclear_gradient(inp, res, backend, args.functional)
+        print_gradient(inp.symbols, grad)
+    if args.optimize and res["converged"]:
+        def energy_and_gradient(xyz):
+            inp_k = inputs.build(atom_path, args.basis, args.grid_level, device=device, verbose=False, eri_mode=args.eri, chol_tol=args.chol_tol,
+                                 point_charges=charges, charge=args.charge, atom_xyz=xyz)
+            be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, eigensolver=args.eigensolver,
+                                  ao_mode=args.ao, xc_occ=bool(args.xc_occ))
+            res_k = scf.run_scf(inp_k, be_k, args.functional, log=None)
+            if not res_k["converged"]:
+                raise RuntimeError("--optimize: the SCF did not converge at a geometry of the optimisation")
+            return res_k["E_tot"], gradients.nuclear_gradient(inp_k, res_k, be_k, args.functional)[0]
+        opt = optimize.bfgs(energy_and_gradient, inp.atom_xyz, max_steps=args.opt_max_steps, log=print)
+        opt_path = os.path.splitext(os.path.basename(atom_file))[0] + "_opt.xyz"
+        optimize.write_xyz(opt_path, inp.symbols, opt["xyz"], f"{args.functional}/{args.basis} E = {opt['energy']:.10f} Ha after {opt['steps']} steps")
+        print(f"Geometry optimisation {'converged' if opt['converged'] else 'NOT converged'} after {opt['steps']} steps "
+              f"({opt['evaluations']} energies and gradients): E = {opt['energy']:.10f} Ha; geometry written to {opt_path}")
+        print_gradient(inp.symbols, opt["gradient"])
     import json
     record = {"functional": args.functional, "molecule": os.path.splitext(atom_file)[0], "basis": args.basis, "grid_level": args.grid_level,
               "nao": int(inp.shells.nao), "ngrid": int(inp.grids.size), "nocc": int(inp.nocc), "n_gpus": world, "eri": args.eri,
@@ -365,6 +412,15 @@ def main(argv=None):
         record["excitation_energies"] = excited["energies"].tolist() if excited is not None else None
         record["oscillator_strengths"] = excited["oscillator_strengths"].tolist() if excited is not None else None
         record["excitation_iterations"] = int(excited["iterations"]) if excited is not None else None
+    if args.gradient or args.optimize:
+        record["gradient"] = grad.tolist() if grad is not None else None
+        record["gradient_terms"] = {k: v.tolist() for k, v in grad_terms.items()} if grad_terms is not None else None
+        record["net_force"] = grad.sum(axis=0).tolist() if grad is not None else None
+    if args.optimize:
+        record["opt_steps"] = int(opt["steps"]) if opt is not None else None
+        record["opt_energies"] = opt["energies"] if opt is not None else None
+        record["opt_converged"] = bool(opt["converged"]) if opt is not None else None
+        record["opt_geometry_bohr"] = opt["xyz"].tolist() if opt is not None else None
     if other is not None:
         record["E_tot_other_quirks"] = other.get("E_tot"); record["other_quirks"] = 0 if args.quirks else 1
     line = json.dumps(record)

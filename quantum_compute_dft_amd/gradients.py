@@ -1,0 +1,254 @@
+"""Analytic nuclear gradient dE/dR_A of a converged closed-shell (RKS) energy, at fixed quadrature points and weights.
+
+    g_A = -tr(W dS/dR_A) + tr(D dT/dR_A) + tr(D dV/dR_A)           integrals.grad1e (basis centres) and the field of the
+                                                                    electrons at the nucleus (integrals.point_coulomb_field)
+        + d/dR_A [1/2 sum D D (ab|cd) - c_hf/4 sum D D (ab|cd)]    integrals.grad2e
+        + g_A^xc                                                    DFT_ComputeXCGradient on the device, xc_gradient_host here
+        + dE_nuc/dR_A  (+ the external charges' terms of an embedded run)
+
+with W = 2 C_occ diag(eps_occ) C_occ^T = D F D / 2.  `nuclear_gradient` assembles it; the XC part has host counterparts of
+DFT_EvalAOHess / DFT_ComputeXCGradient (csrc/xc_grad.hip; solver.eval_ao_hess / compute_xc_gradient,
+scf.HipBackend.xc_gradient) below.
+
+    G[mu, x] = d/dt Exc  when, in column mu only,  ao[:, mu] -> ao[:, mu] - t ao_grad[x][:, mu]  and
+               ao_grad[k][:, mu] -> ao_grad[k][:, mu] - t ao_hess[xk][:, mu]          (dm and the weights fixed)
+
+is the derivative of Exc by the centre of basis function mu; the XC term of dE/dR_A is the sum of G[mu, :] over the
+functions on atom A.  The motion of the grid points with their atoms and the derivatives of the Becke weights are not
+part of it, so the term alone is not translationally invariant.
+
+Here the coefficients c0..c3 of a point come from the functional bodies the kernels run, compiled for the host
+(response.point_host), in the convention of the solver type; the rest is numpy on AO planes the caller supplies.
+"""
+import numpy as np
+
+from . import basis, functionals, integrals, response
+
+# plane index of the second derivative (x, k) in the order xx, xy, xz, yy, yz, zz
+HESS_INDEX = ((0, 1, 2), (1, 3, 4), (2, 4, 5))
+
+# Real solid harmonics of basis.py / csrc/ao_kernels.hpp as polynomials {(i, j, k): coefficient of x^i y^j z^k}
+_C1 = 0.488602511902919921
+_D = (1.092548430592079070, 0.315391565252520002, 0.546274215296039535)
+_F = (0.590043589926643510, 2.890611442640554055, 0.457045799464465739, 0.373176332590115391, 1.445305721320277020)
+_HARMONICS = {
+    0: [{(0, 0, 0): 0.282094791773878143}],
+    1: [{(1, 0, 0): _C1}, {(0, 1, 0): _C1}, {(0, 0, 1): _C1}],
+    2: [{(1, 1, 0): _D[0]}, {(0, 1, 1): _D[0]}, {(0, 0, 2): 2 * _D[1], (2, 0, 0): -_D[1], (0, 2, 0): -_D[1]},
+        {(1, 0, 1): _D[0]}, {(2, 0, 0): _D[2], (0, 2, 0): -_D[2]}],
+    3: [{(2, 1, 0): 3 * _F[0], (0, 3, 0): -_F[0]},
+        {(1, 1, 1): _F[1]},
+        {(0, 1, 2): 4 * _F[2], (2, 1, 0): -_F[2], (0, 3, 0): -_F[2]},
+        {(0, 0, 3): 2 * _F[3], (2, 0, 1): -3 * _F[3], (0, 2, 1): -3 * _F[3]},
+        {(1, 0, 2): 4 * _F[2], (3, 0, 0): -_F[2], (1, 2, 0): -_F[2]},
+        {(2, 0, 1): _F[4], (0, 2, 1): -_F[4]},
+        {(3, 0, 0): _F[0], (1, 2, 0): -3 * _F[0]}],
+}
+AO_EXP_CUT = 46.0
+
+
+def _poly_diff(poly, axis):
+    out = {}
+    for pw, c in poly.items():
+        if pw[axis]:
+            q = list(pw)
+            q[axis] -= 1
+            out[tuple(q)] = out.get(tuple(q), 0.0) + c * pw[axis]
+    return out
+
+
+def _poly_eval(poly, d):
+    v = np.zeros(d.shape[0])
+    for (i, j, k), c in poly.items():
+        v += c * d[:, 0] ** i * d[:, 1] ** j * d[:, 2] ** k
+    return v
+
+
+def ao_hessian_host(shells, coords):
+    """(6, ngrid, nao): the second derivatives xx, xy, xz, yy, yz, zz of every AO of a basis.ShellTable at coords
+    (ngrid, 3), in the conventions of DFT_EvalAO (real solid harmonics, column order, primitives cut below exp(-46)).
+    phi = R(r^2) S(x, y, z):  d_ij phi = R0 S_ij + R1 (x_i S_j + x_j S_i + delta_ij S) + R2 x_i x_j S."""
+    coords = np.ascontiguousarray(coords, dtype=np.float64)
+    out = np.zeros((6, coords.shape[0], int(shells.nao)))
+    for s in range(len(shells.l)):
+        l, n, off, col = int(shells.l[s]), int(shells.nprim[s]), int(shells.off[s]), int(shells.ao[s])
+        if l not in _HARMONICS:
+            raise ValueError(f"shell {s}: l={l} unsupported (s-f)")
+        d = coords - np.asarray(shells.xyz[s], dtype=np.float64)[None, :]
+        r2 = np.einsum("gk,gk->g", d, d)
+        a = np.asarray(shells.exp[off:off + n], dtype=np.float64)
+        t = a[None, :] * r2[:, None]
+        e = np.where(t < AO_EXP_CUT, np.asarray(shells.coef[off:off + n])[None, :] * np.exp(-np.minimum(t, AO_EXP_CUT)), 0.0)
+        R0, R1, R2 = e.sum(axis=1), (-2.0 * a * e).sum(axis=1), (4.0 * a * a * e).sum(axis=1)
+        for m, poly in enumerate(_HARMONICS[l]):
+            S = _poly_eval(poly, d)
+            d1 = [_poly_diff(poly, i) for i in range(3)]
+            S1 = [_poly_eval(p, d) for p in d1]
+            for i in range(3):
+                for j in range(i, 3):
+                    Sij = _poly_eval(_poly_diff(d1[i], j), d)
+                    v = R0 * Sij + R1 * (d[:, i] * S1[j] + d[:, j] * S1[i]) + R2 * d[:, i] * d[:, j] * S
+                    if i == j:
+                        v = v + R1 * S
+                    out[HESS_INDEX[i][j], :, col + m] = v
+    return out
+
+
+def xc_gradient_host(functional, dm, ao, weights, ao_grad, ao_hess=None, quirks=True):
+    """G (nao, 3) of DFT_ComputeXCGradient from AO planes in numpy: ao (ngrid, nao), ao_grad (3, ngrid, nao), ao_hess
+    (6, ngrid, nao) (not needed for an LDA-class functional).  The point coefficients are the sweep's own, in the
+    convention of the solver type: c0 = w vrho, c_k = 4 w vsigma grad_k rho for the one-sided types (GGA, mixes), half
+    of each for B3LYP (its M + M^T); in both
+
+        G[mu, x] = -fac sum_g [ ao_grad[x] (Q D) + (sum_k c_k ao_hess[xk]) (AO D) ][g, mu],   Q = 2 c0 AO + sum_k c_k ao_grad[k]
+
+    with fac = 1 (one-sided) or 2 (B3LYP).  With quirks and vwn5_c / pbe_c in the functional the shipped potentials
+    are not the derivatives of the energy; G is then built from the shipped ones."""
+    t, _, gga = response._kind(functional)
+    if ao_grad is None:
+        raise ValueError("ao_grad is needed: the derivative of the density by a centre is made of it")
+    if gga and ao_hess is None:
+        raise ValueError("ao_hess is needed for a gradient-corrected functional")
+    ao = np.ascontiguousarray(ao, dtype=np.float64)
+    gr = np.ascontiguousarray(ao_grad, dtype=np.float64)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    dm = np.asarray(dm, dtype=np.float64)
+    ds = 0.5 * (dm + dm.T)
+    rho, g = response._density(dm, ao, gr if gga else None)
+    if gga:
+        sigma = np.einsum("gk,gk->g", g, g)
+    else:
+        g, sigma = np.zeros((ao.shape[0], 3)), np.zeros(ao.shape[0])
+    c = response.point_host(functional, rho, sigma, g, w, quirks)[1:]
+    fac = 2.0 if t == 2 else 1.0
+    X = ao @ ds
+    G = np.zeros((ao.shape[1], 3))
+    if not gga:
+        Z = 2.0 * c[0][:, None] * X
+        for x in range(3):
+            G[:, x] = -fac * np.einsum("gm,gm->m", gr[x], Z)
+        return G
+    hs = np.ascontiguousarray(ao_hess, dtype=np.float64)
+    Q = 2.0 * c[0][:, None] * ao
+    for k in range(3):
+        Q += c[1 + k][:, None] * gr[k]
+    Z = Q @ ds
+    for x in range(3):
+        H = sum(c[1 + k][:, None] * hs[HESS_INDEX[x][k]] for k in range(3))
+        G[:, x] = -fac * (np.einsum("gm,gm->m", gr[x], Z) + np.einsum("gm,gm->m", H, X))
+    return G
+
+
+def sum_over_atoms(shells, G):
+    """(natm, 3): G (nao, 3) summed over the functions each atom owns (the shell-to-atom map of the shell table)."""
+    G = np.asarray(G, dtype=np.float64)
+    natm = int(np.max(shells.atom)) + 1
+    out = np.zeros((natm, 3))
+    for s in range(len(shells.l)):
+        c0 = int(shells.ao[s])
+        out[int(shells.atom[s])] += G[c0:c0 + 2 * int(shells.l[s]) + 1].sum(axis=0)
+    return out
+
+
+def ao_planes_host(shells, coords):
+    """(ao (ngrid, nao), ao_grad (3, ngrid, nao), ao_hess (6, ngrid, nao)) of a basis.ShellTable at coords, in numpy, in
+    DFT_EvalAO's conventions: what the host assembly of the gradient sweeps when the backend keeps no planes."""
+    coords = np.ascontiguousarray(coords, dtype=np.float64)
+    ng, nao = coords.shape[0], int(shells.nao)
+    ao, gr = np.zeros((ng, nao)), np.zeros((3, ng, nao))
+    for s in range(len(shells.l)):
+        l, n, off, col = int(shells.l[s]), int(shells.nprim[s]), int(shells.off[s]), int(shells.ao[s])
+        d = coords - np.asarray(shells.xyz[s], dtype=np.float64)[None, :]
+        r2 = np.einsum("gk,gk->g", d, d)
+        a = np.asarray(shells.exp[off:off + n], dtype=np.float64)
+        t = a[None, :] * r2[:, None]
+        e = np.where(t < AO_EXP_CUT, np.asarray(shells.coef[off:off + n])[None, :] * np.exp(-np.minimum(t, AO_EXP_CUT)), 0.0)
+        R0, R1 = e.sum(axis=1), (-2.0 * a * e).sum(axis=1)
+        for m, poly in enumerate(_HARMONICS[l]):
+            S = _poly_eval(poly, d)
+            ao[:, col + m] = R0 * S
+            for i in range(3):
+                gr[i, :, col + m] = R0 * _poly_eval(_poly_diff(poly, i), d) + R1 * d[:, i] * S
+    return ao, gr, ao_hessian_host(shells, coords)
+
+
+def _pair_repulsion_gradient(xyz, z, cen, q):
+    """(natm, 3): d/dR_A of sum_{A, c} z_A q_c / |R_A - R_c| (pairs closer than 1e-12 bohr -- an atom with itself -- skipped)."""
+    d = xyz[:, None, :] - cen[None, :, :]
+    r = np.linalg.norm(d, axis=2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.where(r > 1e-12, z[:, None] * q[None, :] / r ** 3, 0.0)
+    return -(f[:, :, None] * d).sum(axis=1)
+
+
+def _fock(inp, backend, f, dm):
+    """The Fock matrix of dm from the backend's parts: ground_state_parts (scf.HipBackend, response.HostResponse) or the
+    set_dm / jk / xc interface of the host SCF backends."""
+    want_k = f.c_hf != 0.0
+    if hasattr(backend, "ground_state_parts"):
+        from scipy.linalg import eigh
+        e0, C0 = eigh(inp.S @ dm @ inp.S, inp.S)
+        cocc = np.ascontiguousarray(C0[:, ::-1][:, :inp.nocc] * np.sqrt(np.maximum(e0[::-1][:inp.nocc], 0.0)))
+        J, K, V = backend.ground_state_parts(dm, cocc, want_k)
+    else:
+        backend.set_dm(dm)
+        J, K = backend.jk(want_k)
+        V = backend.xc()[1]
+    return inp.Hcore + J + 0.5 * (V + V.T) - (0.5 * f.c_hf * K if want_k else 0.0)
+
+
+_QUIRKY = ("vwn5_c", "pbe_c")
+
+
+def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None):
+    """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged closed-shell state `scf_result` (scf.run_scf) and its
+    breakdown {"one_electron", "two_electron", "xc", "nuclear", "external"}, each (natm, 3).  The derivative at FIXED
+    quadrature points and weights: the Becke-weight derivatives and the motion of the points with their atoms are not
+    included, so the XC term -- and with it the total -- is not translationally invariant; sum_A g_A measures what is
+    left out.  `backend`: what the SCF ran on.  scf.HipBackend sweeps the XC part on the device (xc_gradient); any other
+    backend (set_dm / jk / xc, or ground_state_parts) gets it from xc_gradient_host on planes evaluated here.  The
+    two-electron part never builds the dense ERI, so runs on Cholesky vectors are served alike.  An embedded run
+    (inp.point_charges) includes the basis term over the external charges and the nuclei--charge repulsion ("external");
+    the forces on the charges themselves are properties.point_charge_forces'.  functional / quirks default to the
+    backend's."""
+    if scf_result.get("uks"):
+        raise ValueError("nuclear_gradient: an unrestricted (UKS) result has no analytic gradient here: the assembly is closed-shell")
+    if getattr(inp, "efield", None) is not None:
+        raise ValueError("nuclear_gradient: a run in a uniform electric field (efield) is not supported")
+    if getattr(backend, "world", 1) > 1:
+        raise ValueError("nuclear_gradient runs on one rank: the grid of this backend is sharded over several")
+    f = functionals.resolve(functional if functional is not None else backend.functional)
+    if quirks is None:
+        quirks = bool(getattr(backend, "quirks", getattr(backend, "q", True)))
+    wv = f.weight_vector()
+    if quirks and any(wv[functionals.COMPONENTS.index(c)] != 0.0 for c in _QUIRKY):
+        raise ValueError("nuclear_gradient: with quirks = 1 the shipped vwn5_c / pbe_c potentials are not the derivatives of their "
+                         "energies, so the converged state is not stationary and the analytic gradient is not the energy's; "
+                         "run with --quirks 0")
+    dm = np.asarray(scf_result["dm"], dtype=np.float64)
+    dm = np.ascontiguousarray(0.5 * (dm + dm.T))
+    sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
+    z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
+    F = _fock(inp, backend, f, dm)
+    W = 0.5 * dm @ F @ dm
+    W = 0.5 * (W + W.T)
+    g1 = integrals.grad1e(sh, xyz, z, dm, W)
+    field = integrals.point_coulomb_field(sh, xyz, dm)         # sum D d<1/|r - R_A|>/dR_A: the operator part of V
+    terms = {"one_electron": g1[0] + g1[1] + g1[2] - z[:, None] * field,
+             "two_electron": integrals.grad2e(sh, dm, f.c_hf),
+             "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
+    if any(w != 0.0 for w in wv):
+        if hasattr(backend, "xc_gradient"):
+            G = backend.xc_gradient(dm)
+        else:
+            ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
+            G = xc_gradient_host(f, dm, ao, inp.grids.weights, gr, hs if f.needs_gradient else None, quirks)
+        terms["xc"] = sum_over_atoms(sh, G)
+    else:
+        terms["xc"] = np.zeros_like(xyz)
+    pc = getattr(inp, "point_charges", None)
+    if pc is not None and len(pc):
+        terms["external"] = integrals.grad1e(sh, pc[:, :3], pc[:, 3], dm, W)[2] + _pair_repulsion_gradient(xyz, z, pc[:, :3], pc[:, 3])
+    else:
+        terms["external"] = np.zeros_like(xyz)
+    return sum(terms.values()), terms

@@ -69,7 +69,7 @@ def uniform_field(symbols, atom_xyz, shells, efield):
 
 
 def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=True, eri_mode="dense",
-          chol_tol=1e-9, rank=0, world=1, group=None, point_charges=None, efield=None, charge=0, spin=0):
+          chol_tol=1e-9, rank=0, world=1, group=None, point_charges=None, efield=None, charge=0, spin=0, atom_xyz=None):
     """grid.py:42-67.  `atom_path`: an .xyz file (or a molecule name resolved in data/).
     eri_mode "dense": the (nao^4) tensor of grid.py:65; "cholesky": pivoted Cholesky vectors only.
     world > 1 (torch.distributed initialised): the Cholesky factorisation -- the one expensive step, host integral columns
@@ -82,12 +82,19 @@ def build(atom_path, basis_name="sto-3g", grid_level=3, device="cpu", verbose=Tr
     -sum_A Z_A F.R_A, so every SCF loop, the fused tail included, runs in the field with no other change.
     charge, spin: the molecule's charge and nalpha - nbeta (scf.run_uks); the defaults are the neutral closed shell.
     nelec = sum Z - charge, nalpha = (nelec + spin) / 2, nbeta = (nelec - spin) / 2, nocc = nbeta; ValueError when spin is
-    negative, exceeds the electron count or has not its parity (an odd count needs --spin), or no electron is left."""
+    negative, exceeds the electron count or has not its parity (an odd count needs --spin), or no electron is left.
+    atom_xyz: (natm, 3) coordinates in bohr that replace the file's (the elements and their order stay the file's): what a
+    geometry optimisation and a finite-difference gradient rebuild the inputs with."""
     if not os.path.exists(atom_path):
         cand = os.path.join(DATA_DIR, atom_path if atom_path.endswith(".xyz") else atom_path + ".xyz")
         if os.path.exists(cand):
             atom_path = cand
     symbols, xyz = basis.parse_xyz(atom_path)
+    if atom_xyz is not None:
+        new = np.array(atom_xyz, dtype=np.float64)
+        if new.shape != xyz.shape or not np.all(np.isfinite(new)):
+            raise ValueError(f"atom_xyz: expected finite coordinates of shape {xyz.shape} (bohr), got shape {new.shape}")
+        xyz = new
     shells = basis.build_shells(symbols, xyz, basis_name)
     charge, spin = int(charge), int(spin)
     nelec = sum(basis.atomic_number(s) for s in symbols) - charge

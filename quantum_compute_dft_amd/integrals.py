@@ -69,6 +69,10 @@ def _load():
         for f in (L.qc_point_matrix, L.qc_point_contract, L.qc_point_field, L.qc_point_field_matrix):
             f.restype = ctypes.c_int
             f.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ctypes.c_longlong, dp, dp, dp]
+        L.qc_grad1e.restype = ctypes.c_int
+        L.qc_grad1e.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ip, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp]
+        L.qc_grad2e.restype = ctypes.c_int
+        L.qc_grad2e.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ip, ctypes.c_int, dp, ctypes.c_double, dp]
         from .hostinfo import host_cpu_share
         L.qc_set_threads(host_cpu_share())
         _lib = L
@@ -126,6 +130,51 @@ def int2e(shells):
     if rc != 0:
         raise ValueError("integrals: angular momentum above f is not supported")
     return eri
+
+
+def _sym(m, what):
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1] or not np.allclose(m, m.T, rtol=0.0, atol=1e-10 * max(1.0, float(np.abs(m).max()))):
+        raise ValueError(f"{what}: a symmetric (nao, nao) matrix is expected")
+    return m
+
+
+def grad1e(shells, centres, charges, dm, w):
+    """The basis-centre derivatives of S, T and the point-Coulomb matrix V = -sum_c q_c / |r - R_c| over the charged
+    `centres` (n, 3) with `charges` (n,) (the nuclei; the external charges of an embedded run too), contracted as they are
+    made (qc_grad1e): (3, natm, 3) = [-tr(W dS/dR_A), tr(D dT/dR_A), tr(D dV/dR_A) without the operator part].  dm, w
+    symmetric.  The shell-to-atom map is the shell table's."""
+    keep, p = _args(shells)
+    dm, w = _sym(dm, "dm"), _sym(w, "w")
+    cen = np.ascontiguousarray(np.asarray(centres, dtype=np.float64).reshape(-1, 3))
+    q = np.ascontiguousarray(charges, dtype=np.float64)
+    if q.shape != (cen.shape[0],):
+        raise ValueError("grad1e: one charge per centre")
+    owner = np.ascontiguousarray(shells.atom, dtype=np.int32)
+    natm = int(owner.max()) + 1
+    out = np.zeros((3, natm, 3))
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    rc = _load().qc_grad1e(shells.nshell, *p, shells.nao, owner.ctypes.data_as(ip), natm, cen.shape[0], cen.ctypes.data_as(dp),
+                           q.ctypes.data_as(dp), dm.ctypes.data_as(dp), w.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    if rc != 0:
+        raise ValueError("grad1e: unsupported angular momentum (s-f) or a shell without an atom")
+    return out
+
+
+def grad2e(shells, dm, c_hf=0.0):
+    """(natm, 3): d/dR_A of 1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum D_ac D_bd (ab|cd) for a symmetric dm (qc_grad2e): every
+    derivative quartet contracted as it is made, the dense ERI never built, threads as set_threads says."""
+    keep, p = _args(shells)
+    dm = _sym(dm, "dm")
+    owner = np.ascontiguousarray(shells.atom, dtype=np.int32)
+    natm = int(owner.max()) + 1
+    out = np.zeros((natm, 3))
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    rc = _load().qc_grad2e(shells.nshell, *p, shells.nao, owner.ctypes.data_as(ip), natm, dm.ctypes.data_as(dp), float(c_hf),
+                           out.ctypes.data_as(dp))
+    if rc != 0:
+        raise ValueError("grad2e: unsupported angular momentum (s-f) or a shell without an atom")
+    return out
 
 
 def energy_nuc(symbols, atom_xyz):

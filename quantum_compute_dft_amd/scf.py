@@ -684,6 +684,56 @@ class HipBackend:
         h = self._r_out.cpu().numpy()
         return h[0], (h[1] if want_k else None), h[2]
 
+    # ---- XC part of the nuclear gradient (gradients.py): one rank -----------------------------------------------
+    XC_GRADIENT_HESS_BYTES = 1.0e9      # the six Hessian planes of a grid slice stay within about this
+
+    def xc_gradient(self, dm, slice_rows=None):
+        """G (nao, 3) as a numpy array: dExc / d(centre of basis function mu) at fixed points and weights
+        (DFT_ComputeXCGradient), summed over slices of the grid.  The Hessian planes of a slice are evaluated into a reused
+        buffer (DFT_EvalAOHess); the AO and gradient planes are the resident ones where the backend holds them (a slice of
+        the three gradient planes is copied together, the entry wants them back to back) and are evaluated per slice
+        otherwise (an LDA-class run keeps no gradient planes, --ao direct keeps none).  slice_rows: rows per slice (default:
+        what keeps the Hessian planes within XC_GRADIENT_HESS_BYTES)."""
+        if self.world > 1:
+            raise ValueError("the XC gradient runs on one rank: the grid of this backend is sharded over several")
+        if self.dm_factor:
+            raise ValueError("the XC gradient takes the density matrix itself: run without dm_factor")
+        t, n, ng, s = self.torch, self.nao, self.ngrid, self.solver
+        f64 = t.float64
+        rows = int(slice_rows) if slice_rows else max(16, int(self.XC_GRADIENT_HESS_BYTES // (48 * n)) // 16 * 16)
+        rows = max(1, min(rows, ng))
+        gga = s.needs_gradient
+        d_dm = t.as_tensor(np.ascontiguousarray(dm), dtype=f64, device=self.dev)
+        d_out = t.zeros((n, 3), dtype=f64, device=self.dev)
+        d_G = t.zeros((n, 3), dtype=f64, device=self.dev)
+        d_hess = t.empty(6 * rows * n, dtype=f64, device=self.dev) if gga else None
+        own_gr = self.d_gr is None
+        own_ao = self.d_ao is None or own_gr        # DFT_EvalAO writes the values along with the gradients
+        d_gr_s = t.empty(3 * rows * n, dtype=f64, device=self.dev) if (own_gr or rows < ng) else None
+        d_ao_s = t.empty(rows * n, dtype=f64, device=self.dev) if own_ao else None
+        for lo in range(0, ng, rows):
+            hi = min(lo + rows, ng)
+            m = hi - lo
+            coords = self.d_coords[lo:hi]
+            if own_gr:
+                ao, gr = d_ao_s[:m * n].view(m, n), d_gr_s[:3 * m * n].view(3, m, n)
+                s.eval_ao(self.shells, coords, m, ao, gr)
+            elif rows < ng:
+                ao, gr = self.d_ao[lo:hi], d_gr_s[:3 * m * n].view(3, m, n)
+                gr.copy_(self.d_gr[:, lo:hi])
+            else:
+                ao, gr = self.d_ao, self.d_gr
+            hs = None
+            if gga:
+                hs = d_hess[:6 * m * n].view(6, m, n)
+                s.eval_ao_hess(self.shells, coords, m, hs)
+            t.cuda.synchronize()
+            s.compute_xc_gradient(m, n, d_dm, ao, self.d_w[lo:hi], d_out, gr, hs)
+            t.cuda.synchronize()
+            d_G += d_out
+        t.cuda.synchronize()
+        return d_G.cpu().numpy()
+
     def excitation_parts(self, A, Bs, want_k, kind="singlet"):
         """(J, M or None, V1_raw), each (nvec, nao, nao) as numpy arrays, of the trials D_k = A B_k^T + B_k A^T with A
         (nao, nocc) and Bs (nvec, nao, nocc): J[D_k], the unsymmetrised M_k = K[A B_k^T] -- K[D]_mn = sum_ls (ml|ns) D_ls,

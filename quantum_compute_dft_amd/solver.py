@@ -148,6 +148,11 @@ class DFTSolverWrapper:
         L.DFT_FxcApplySpinPol.restype = ctypes.c_int
         L.DFT_FxcSpinPolTable.argtypes = [ctypes.c_void_p, _u64, ctypes.c_longlong]
         L.DFT_FxcSpinPolTable.restype = ctypes.c_int
+        L.DFT_EvalAOHess.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                     dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, _u64, _u64]
+        L.DFT_EvalAOHess.restype = ctypes.c_int
+        L.DFT_ComputeXCGradient.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, _u64]
+        L.DFT_ComputeXCGradient.restype = ctypes.c_int
 
         if self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
@@ -352,6 +357,23 @@ class DFTSolverWrapper:
         self._check()
         torch.cuda.synchronize()
         return buf[:planes * int(ngrid)].view(planes, int(ngrid))
+
+    def eval_ao_hess(self, shells, d_coords, ngrid, d_hess):
+        """The six second-derivative AO planes xx, xy, xz, yy, yz, zz into d_hess (6, ngrid, nao) (DFT_EvalAOHess), in
+        eval_ao's conventions; asynchronous on the solver's stream."""
+        keep, args = self._shell_args(shells)
+        rc = self.lib.DFT_EvalAOHess(self.solver, int(ngrid), *args, _u64(_ptr(d_coords)), _u64(_ptr(d_hess)))
+        self._check()
+        return rc
+
+    def compute_xc_gradient(self, ngrid, nao, d_dm, d_ao, d_weights, d_out, d_ao_grad=None, d_ao_hess=None):
+        """G (nao, 3) into d_out (DFT_ComputeXCGradient): the derivative of compute_xc's Exc by the centre of every basis
+        function at fixed points and weights; asynchronous on the solver's stream.  d_ao_hess may be None for an
+        LDA-class functional."""
+        rc = self.lib.DFT_ComputeXCGradient(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
+                                            _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
+        self._check()
+        return rc
 
     def mix(self):
         """The solver's weights as the library reports them (DFT_GetMix; for a built-in type: its equivalent mix)."""
