@@ -39,9 +39,19 @@ using namespace qcdft;
 
 namespace {
 
+// One device allocation, sized by reserve().  It frees itself with its owner: DFT_DestroySolver deletes the solver on the
+// solver's device after the stream has drained, so no list of the solver's buffers is kept anywhere.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    double *d() const { return (double *)p; }
 };
 
 struct Timing {
@@ -49,15 +59,42 @@ struct Timing {
     hipEvent_t t0, t1;
 };
 
+// The arguments of a sweep, and with them the key of a recorded one
+struct SweepArgs {
+    long ngrid;
+    int nao, nocc;
+    const double *dm, *ao, *grad, *w;
+    double *vxc;
+    const double *cocc;
+    bool operator==(const SweepArgs &o) const
+    {
+        return ngrid == o.ngrid && nao == o.nao && nocc == o.nocc && dm == o.dm && ao == o.ao && grad == o.grad && w == o.w &&
+               vxc == o.vxc && cocc == o.cocc;
+    }
+};
+
 // One recorded sweep (option "graph"): the launches of a call with exactly these arguments, replayed as one HIP graph.
 struct SweepGraph {
-    long ngrid = 0;
-    int nao = 0, nocc = 0;
-    const void *dm = nullptr, *ao = nullptr, *grad = nullptr, *w = nullptr, *vxc = nullptr, *cocc = nullptr;
+    SweepArgs key = {};
     hipGraphExec_t exec = nullptr;
     int seen = 0;      // calls with this key so far (the first sizes the workspace, the second is recorded)
     bool bad = false;  // recording failed once: this key runs as plain launches from then on
     unsigned long stamp = 0;
+};
+
+// The planes of one sweep, reserved together (reserve_planes): the density, its gradient (3 per point) and sigma, the
+// coefficient planes that the pointwise kernel leaves for the contraction, and that kernel's Exc partials.
+struct Planes {
+    DevBuf rho, grad, sigma, coef, partial;
+};
+
+// One prepared response of Vxc: the weighted derivative table of the functional at the ground-state density and that
+// density's gradient (g0[1]: the beta gradient, open-shell slot only), kept between a Prepare and its Applies in buffers
+// nothing else writes.
+struct FxcSlot {
+    DevBuf table, g0[2];
+    long ngrid = 0;   // what the table was prepared for (0: nothing prepared, or invalidated)
+    int nao = 0;
 };
 
 } // namespace
@@ -106,8 +143,9 @@ struct XCSolver {
     std::vector<SweepGraph> graphs;
     hipStream_t cap_stream = nullptr; // recording happens here (the caller's stream may be the null stream, which cannot record)
     unsigned long graph_clock = 0, graph_gen = 0;
-    // workspace
-    DevBuf dsym, rho, sigma, grad, coef, partial, slabs, exc, jpart, kpart, shells, msym, cdy, cdc, cdv, cdy2, cdc2, cdbt, ao_ws, vtmp, occ_cp, occ_dm, dmf_lt, dmf_c, dmf_st;
+    // workspace (`ws`: the planes of xc_sweep and of DFT_FxcPrepare / DFT_FxcApply, the set a recorded sweep holds)
+    Planes ws;
+    DevBuf dsym, slabs, exc, jpart, kpart, shells, msym, cdy, cdc, cdv, cdy2, cdc2, cdbt, ao_ws, vtmp, occ_cp, occ_dm, dmf_lt, dmf_c, dmf_st;
     int spin_wait = 1; // poll the host-mapped Exc instead of sleeping in hipStreamSynchronize
     int strict_sync = 0; // 1: after the Exc word, also poll the stream until it reports complete (+8-10 us per call)
     double *h_exc = nullptr;   // pinned, host-mapped: the reduce kernel writes Exc here
@@ -123,27 +161,22 @@ struct XCSolver {
     unsigned long long seq = 0; // value of the last stream write that was enqueued
     bool recording = false;    // xc_sweep is being recorded into a graph: stream memory operations are not recorded
     int wait_mode = 0;         // how the last sweep with want_host_exc signals completion: 0 Exc word, 1 sequence word, 2 neither (synchronise)
-    // Linear response of Vxc (DFT_FxcPrepare / DFT_FxcApply): the weighted derivative table of the functional at the ground-state
-    // density and that density's gradient, kept between the two entries in buffers nothing else writes
-    DevBuf fxc_table, fxc_g0;
-    long fxc_ngrid = 0;   // what the table was prepared for (0: nothing prepared, or invalidated)
-    int fxc_nao = 0;
-    // DFT_FxcPrepareSpin: one slot per kind (1 triplet, 2 singlet through the spin-resolved bodies), each with its own
-    // table and its own grad rho0, so that prepares at different dm0 and applies of every kind interleave freely.
-    DevBuf fxc_spin_table[2], fxc_spin_g0[2];
-    long fxc_spin_ngrid[2] = {0, 0};
-    int fxc_spin_nao[2] = {0, 0};
+    // Linear response of Vxc, one slot per kind: 0 the shipped formulas differentiated (DFT_FxcPrepare / DFT_FxcApply); 1 triplet,
+    // 2 singlet through the spin-resolved bodies (DFT_FxcPrepareSpin).  Each has its own table and its own grad rho0, so that
+    // prepares at different dm0 and applies of every kind interleave freely.
+    FxcSlot fxc[3];
     // DFT_FxcPrepareSpinPol: the second-derivative table of the energy at (rho0_a, rho0_b) and the two ground-state gradients,
-    // a slot of its own again; DFT_FxcApplySpinPol works in the spin_* buffers below, which every user overwrites whole
-    DevBuf fxc_pol_table, fxc_pol_g0[2];
-    long fxc_pol_ngrid = 0;
-    int fxc_pol_nao = 0;
-    // DFT_ComputeXCSpin: densities, gradients and coefficient planes of the two spins, the partials and the scalar of its
-    // Exc -- buffers of its own, so that no recorded sweep and no prepared response table holds or reads any of them
-    DevBuf spin_rho[2], spin_grad[2], spin_sigma, spin_coef[2], spin_partial, spin_exc;
-    // DFT_ComputeXCGradient: density, gradient, coefficient planes, Exc partials and slabs of its own -- no recorded sweep and no
-    // prepared response table holds or reads any of them (Dsym alone is shared, in stream order)
-    DevBuf xcg_rho, xcg_grad, xcg_sigma, xcg_coef, xcg_partial, xcg_slabs;
+    // a slot of its own again; DFT_FxcApplySpinPol works in the spin planes below, which every user overwrites whole
+    FxcSlot fxc_pol;
+    // DFT_ComputeXCSpin: densities, gradients and coefficient planes of the two spins (sigma and the Exc partials with
+    // spin[0] alone) and the scalar of its Exc -- buffers of its own, so that no recorded sweep and no prepared response
+    // table holds or reads any of them
+    Planes spin[2];
+    DevBuf spin_exc;
+    // DFT_ComputeXCGradient: planes and slabs of its own -- no recorded sweep and no prepared response table holds or reads
+    // any of them (Dsym alone is shared, in stream order)
+    Planes xcg;
+    DevBuf xcg_slabs;
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -192,6 +225,47 @@ bool reserve(XCSolver *s, DevBuf &b, size_t bytes, const char *what, bool record
     size_t want = bytes + bytes / 8 + 256;
     if (!hip_ok(s, hipMalloc(&b.p, want), what)) return false;
     b.cap = want;
+    return true;
+}
+
+// rho of `ngrid` points, and of the rest what the entry uses: the coefficient planes, grad rho and sigma (the last two for a
+// gradient-corrected functional only), `nxb` Exc partials.  `recorded`: the set is `ws`, which recorded sweeps hold.
+enum : unsigned { WS_COEF = 1, WS_GRAD = 2, WS_SIGMA = 4, WS_ALL = 7 };
+
+bool reserve_planes(XCSolver *s, Planes &w, bool recorded, long ngrid, unsigned parts, long nxb = 0)
+{
+    const size_t ng = sizeof(double) * (size_t)ngrid;
+    const bool gga = s->needs_grad;
+    return reserve(s, w.rho, ng, "hipMalloc(rho)", recorded) &&
+           (!(parts & WS_COEF) || reserve(s, w.coef, ng * (gga ? 4 : 1), "hipMalloc(coef)", recorded)) &&
+           (!nxb || reserve(s, w.partial, sizeof(double) * nxb, "hipMalloc(partial)", recorded)) &&
+           (!(gga && (parts & WS_SIGMA)) || reserve(s, w.sigma, ng, "hipMalloc(sigma)", recorded)) &&
+           (!(gga && (parts & WS_GRAD)) || reserve(s, w.grad, 3 * ng, "hipMalloc(grad)", recorded));
+}
+
+// 0 LDA, 1 GGA, 2 B3LYP, 3 mix: what the launchers in the other translation units take for the solver's type
+int xc_type_index(const XCSolver *s)
+{
+    return s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+}
+
+// What every XC entry does first.  `timed`: timings of the same call that stay in front of the entry's own.
+bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed = 0)
+{
+    s->last_error.clear();
+    s->n_timed = timed;
+    if (!s->device_ok) {
+        set_error(s, "no usable HIP device");
+        return false;
+    }
+    if (ngrid <= 0 || nao <= 0) {
+        set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao);
+        return false;
+    }
+    if (s->needs_grad && !ao_grad) {
+        set_error(s, "ao_grad pointer is null for a gradient-corrected functional");
+        return false;
+    }
     return true;
 }
 
@@ -267,7 +341,7 @@ void with_bool(bool b, F &&f)
 bool takes_tiny(const XCSolver *s, long ngrid, int nao)
 {
     return s->path == 0 && s->tiny != 0 && s->type != SOLVER_MIX && nao <= TINY_MAX_NAO && (double)ngrid * nao * 8.0 < 4294967296.0 &&
-           (s->tiny > 0 || tiny_pays(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid));
+           (s->tiny > 0 || tiny_pays(s->num_cu, xc_type_index(s), nao, ngrid));
 }
 
 // How a sweep over (ngrid, nao) planes is cut up: which kernel family, how many slabs, the chunk of a split-K launch.
@@ -313,7 +387,7 @@ SweepPlan plan_sweep(const XCSolver *s, long ngrid, int nao, const double *ao, c
         chunk = (ngrid + nslab - 1) / nslab;
         chunk = ((chunk + BG_BK - 1) / BG_BK) * BG_BK;
     } else if (tiny) {
-        nslab = tiny_workgroups(s->num_cu, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, nao, ngrid);
+        nslab = tiny_workgroups(s->num_cu, xc_type_index(s), nao, ngrid);   // (a mix never takes this kernel)
     } else if (fast) {
         const long ntile = (ngrid + WS_ROWS - 1) / WS_ROWS;
         nslab = (int)std::min<long>(s->num_cu, ntile); // one persistent, wave-specialised workgroup per CU
@@ -474,31 +548,44 @@ bool vxc_stage(XCSolver *s, const SweepPlan &P, bool tiny, long ngrid, int nao, 
     return hip_ok(s, hipGetLastError(), "XC sweep launch");
 }
 
-// The sweep: everything on s->stream, Exc left in s->exc (device).
-// `cocc` (nao, nocc) with dm = cocc cocc^T switches the density step to the occupied-orbital form where that
-// pays (xc_occ_kernels.hpp); `dm` may then be null.
-bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao,
-              const double *ao_grad, const double *w, double *vxc, bool want_host_exc,
-              const double *cocc = nullptr, int nocc = 0, double *exc_out = nullptr)
+// The buffers every entry shares, in stream order: the padded, symmetrised matrix and the contraction's slabs
+bool reserve_dsym(XCSolver *s, const SweepPlan &P)
 {
-    s->last_error.clear();
-    s->n_timed = s->timed_base;   // non-zero only for the sweep of a call that factorised its dm first
-    s->timed_base = 0;
-    s->wait_mode = 0;
-    s->used_vxc_fringe = 0;
-    if (!s->device_ok) {
-        set_error(s, "no usable HIP device");
-        return false;
-    }
-    if (ngrid <= 0 || nao <= 0) {
-        set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao);
-        return false;
-    }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_grad) {
-        set_error(s, "ao_grad pointer is null for a gradient-corrected functional");
-        return false;
-    }
+    return reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)");
+}
+
+bool reserve_slabs(XCSolver *s, const SweepPlan &P, int nao)
+{
+    return reserve(s, s->slabs, sizeof(double) * (size_t)P.nslab * nao * nao, "hipMalloc(slabs)");
+}
+
+// Occupied-orbital density step: 16 nch nocc_tiles MFMAs per 16 grid rows (8 for LDA) against 4 NT^2 through the
+// full matrix; taken when it does clearly fewer (the two kernels run at similar matrix-pipe efficiency), on the
+// production path only.
+bool occ_allowed(const XCSolver *s)
+{
+    return s->path == 0 && s->occ != 2;
+}
+
+bool occ_pays(const XCSolver *s, int nao, int nocc, OccPlan &plan)
+{
+    if (!occ_allowed(s)) return false;
+    plan = occ_plan(nao, nocc, s->needs_grad);
+    return s->occ == 1 || plan.mfma_occ <= 0.85 * plan.mfma_full;
+}
+
+// Where a call's density comes from, decided once (density_source) and run by run_density: the occupied-orbital kernels
+// on `cocc` (nao, nocc) with dm = cocc cocc^T, or the matrix kernels on `dm` -- the caller's, or built from cocc first.
+struct DensitySource {
+    bool use_occ = false;
+    OccPlan oplan;
+    const double *dm = nullptr, *cocc = nullptr;
+    int nocc = 0;
+};
+
+// `may_occ` false: the entry's plan has no occupied-orbital form (the one-kernel sweep for small bases)
+bool density_source(XCSolver *s, int nao, const double *dm, const double *cocc, int nocc, bool may_occ, DensitySource &d)
+{
     if (!dm && !cocc) {
         set_error(s, "neither a density matrix nor occupied orbitals were given");
         return false;
@@ -507,255 +594,88 @@ bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *
         set_error(s, "occupied orbitals given with nocc=%d", nocc);
         return false;
     }
-    // Occupied-orbital density step: 16 nch nocc_tiles MFMAs per 16 grid rows (8 for LDA) against 4 NT^2 through the
-    // full matrix; taken when it does clearly fewer (the two kernels run at similar matrix-pipe efficiency), on the
-    // production path only.
-    const bool tiny = takes_tiny(s, ngrid, nao);
-    OccPlan oplan;
-    bool use_occ = false;
-    if (cocc && s->path == 0 && s->occ != 2 && !tiny) {
-        oplan = occ_plan(nao, nocc, gga);
-        use_occ = s->occ == 1 || oplan.mfma_occ <= 0.85 * oplan.mfma_full;
-    }
-    s->used_occ = use_occ;
-    if (!use_occ && !dm) { // the dm kernels need the matrix itself
+    d.use_occ = cocc && may_occ && occ_pays(s, nao, nocc, d.oplan);
+    s->used_occ = d.use_occ;
+    if (!d.use_occ && !dm) { // the dm kernels need the matrix itself
         if (!reserve(s, s->occ_dm, sizeof(double) * (size_t)nao * nao, "hipMalloc(dm)")) return false;
-        launch_dm_from_cocc(s->stream, nao, nocc, cocc, (double *)s->occ_dm.p);
-        dm = (const double *)s->occ_dm.p;
+        launch_dm_from_cocc(s->stream, nao, nocc, cocc, s->occ_dm.d());
+        dm = s->occ_dm.d();
     }
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, tiny);
-    const int NP = P.NP, nslab = P.nslab;
-    const long nxb = tiny ? nslab : (ngrid + 255) / 256; // Exc partials: one per workgroup of the kernel that evaluates the functional
-    const size_t ng = (size_t)ngrid;
+    d.dm = dm;
+    d.cocc = cocc;
+    d.nocc = nocc;
+    return true;
+}
 
-    if (!reserve(s, s->dsym, sizeof(double) * NP * NP, "hipMalloc(Dsym)") ||
-        !reserve(s, s->rho, sizeof(double) * ng, "hipMalloc(rho)") ||
-        !reserve(s, s->coef, sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(coef)") ||
-        !reserve(s, s->partial, sizeof(double) * nxb, "hipMalloc(partial)") ||
-        !reserve(s, s->slabs, sizeof(double) * (size_t)nslab * nao * nao, "hipMalloc(slabs)") ||
-        false)
-        return false;
-    if (!reserve(s, s->exc, 2 * sizeof(double), "hipMalloc(exc)")) return false; // the device-side Exc scalar
-    if (gga && (!reserve(s, s->sigma, sizeof(double) * ng, "hipMalloc(sigma)") ||
-                !reserve(s, s->grad, sizeof(double) * 3 * ng, "hipMalloc(grad)")))
-        return false;
+bool run_density(XCSolver *s, const SweepPlan &P, const DensitySource &d, long ngrid, int nao, const double *ao, double *rho,
+                 double *grad, double *sigma)
+{
+    if (!d.use_occ) {
+        launch_density(s, P, ngrid, nao, d.dm, ao, s->dsym.d(), rho, grad, sigma);
+        return true;
+    }
+    ScopedTimer t(s, "rho_occ");
+    if (!reserve(s, s->occ_cp, sizeof(double) * d.oplan.cp_doubles, "hipMalloc(packed cocc)")) return false;
+    return hip_ok(s, launch_rho_occ(s->stream, s->num_cu, d.oplan, P.gga, P.vec16, ngrid, nao, d.nocc, d.cocc, s->occ_cp.d(), ao, P.gx, P.gy,
+                                    P.gz, rho, grad, sigma), "occupied-orbital density launch");
+}
 
-    double *Dp = (double *)s->dsym.p, *rho = (double *)s->rho.p, *sigma = (double *)s->sigma.p,
-           *grad = (double *)s->grad.p, *coef = (double *)s->coef.p,
-           *partial = (double *)s->partial.p, *slabs = (double *)s->slabs.p,
-           *exc = exc_out ? exc_out : (double *)s->exc.p;   // the asynchronous entries' caller-owned scalar: written by the finishing kernel itself
-    const double *gx = P.gx, *gy = P.gy, *gz = P.gz;
-    const bool vec16 = P.vec16;
+// The functional at the points of `p`'s density: coefficient planes for the contraction and one Exc partial per workgroup
+void launch_xc_points(XCSolver *s, long ngrid, long nxb, const double *w, const Planes &p)
+{
+    ScopedTimer t(s, "xc_points");
+    const dim3 g((unsigned)nxb), b(256);
     hipStream_t st = s->stream;
+    double *rho = p.rho.d(), *sigma = p.sigma.d(), *grad = p.grad.d(), *coef = p.coef.d(), *partial = p.partial.d();
+    switch (xc_type_index(s)) {
+    case 0: hipLaunchKernelGGL(k_xc_points<0>, g, b, 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks); break;
+    case 1: hipLaunchKernelGGL(k_xc_points<1>, g, b, 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks); break;
+    case 2: hipLaunchKernelGGL(k_xc_points<2>, g, b, 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks); break;
+    default:
+        with_bool(s->needs_grad, [&](auto G) {
+            hipLaunchKernelGGL(k_xc_points_mix<G>, g, b, 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
+        });
+    }
+}
 
+// The sweep: everything on s->stream, Exc left in s->exc (device).
+// `cocc` (nao, nocc) with dm = cocc cocc^T switches the density step to the occupied-orbital form where that
+// pays (xc_occ_kernels.hpp); `dm` may then be null.
+bool xc_sweep(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao,
+              const double *ao_grad, const double *w, double *vxc, bool want_host_exc,
+              const double *cocc = nullptr, int nocc = 0, double *exc_out = nullptr)
+{
+    const size_t timed = s->timed_base;   // non-zero only for the sweep of a call that factorised its dm first
+    s->timed_base = 0;
+    s->wait_mode = 0;
+    s->used_vxc_fringe = 0;
+    if (!enter(s, ngrid, nao, ao_grad, timed)) return false;
+    const bool tiny = takes_tiny(s, ngrid, nao);
+    DensitySource src;
+    if (!density_source(s, nao, dm, cocc, nocc, !tiny, src)) return false;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, tiny);
+    const long nxb = tiny ? P.nslab : (ngrid + 255) / 256; // Exc partials: one per workgroup of the kernel that evaluates the functional
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->ws, true, ngrid, WS_ALL, nxb) || !reserve_slabs(s, P, nao) ||
+        !reserve(s, s->exc, 2 * sizeof(double), "hipMalloc(exc)"))   // the device-side Exc scalar
+        return false;
+    const Planes &p = s->ws;
+    double *exc = exc_out ? exc_out : s->exc.d();   // the asynchronous entries' caller-owned scalar: written by the finishing kernel itself
     if (tiny) {
         ScopedTimer t(s, "sweep_tiny");
-        launch_sweep_tiny(st, nslab, s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : 2, ngrid, nao, ao, gx, gy, gz, dm, w,
-                          slabs, partial, s->quirks);
-    }
-    if (use_occ) {
-        ScopedTimer t(s, "rho_occ");
-        if (!reserve(s, s->occ_cp, sizeof(double) * oplan.cp_doubles, "hipMalloc(packed cocc)")) return false;
-        if (!hip_ok(s, launch_rho_occ(st, s->num_cu, oplan, gga, vec16, ngrid, nao, nocc, cocc, (double *)s->occ_cp.p, ao, gx, gy, gz,
-                                      rho, grad, sigma), "occupied-orbital density launch"))
-            return false;
-    }
-    if (!use_occ && !tiny) launch_density(s, P, ngrid, nao, dm, ao, Dp, rho, grad, sigma);
-    if (!tiny) {
-        ScopedTimer t(s, "xc_points");
-        dim3 g((unsigned)nxb);
-        if (s->type == SOLVER_LDA)      hipLaunchKernelGGL(k_xc_points<0>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
-        else if (s->type == SOLVER_GGA) hipLaunchKernelGGL(k_xc_points<1>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
-        else if (s->type == SOLVER_B3LYP) hipLaunchKernelGGL(k_xc_points<2>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
-        else if (gga)                   hipLaunchKernelGGL(k_xc_points_mix<true>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
-        else                            hipLaunchKernelGGL(k_xc_points_mix<false>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
-    }
-    const ExcFinish fin{nxb, partial, exc, want_host_exc};
-    return vxc_stage(s, P, tiny, ngrid, nao, ao, coef, slabs, vxc, &fin);
-}
-
-// The spin-resolved sweep (DFT_ComputeXCSpin): the closed-shell sweep's density kernels on dm_a and on dm_b (linear in
-// the matrix), one pointwise kernel (xc_spin.hip), the closed-shell contraction and reduce once per spin; the second
-// reduce finishes Exc from the pointwise kernel's partials, as xc_sweep's does.  Never the one-kernel plan for small
-// bases (it keeps no density), never recorded.  Shares Dsym, the slabs and M with the other entries (stream order), and
-// nothing else: the fxc_* tables and the workspace a recorded sweep holds are not written.
-bool xc_sweep_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
-                   const double *ao_grad, const double *w, double *vxc_a, double *vxc_b, double *exc_host)
-{
-    s->last_error.clear();
-    s->n_timed = 0;
-    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
-    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
-    if (!dm_a || !dm_b || !ao || !w || !vxc_a || !vxc_b || !exc_host) {
-        set_error(s, "DFT_ComputeXCSpin needs both density matrices, the AO values, the grid weights, both output matrices and exc");
-        return false;
-    }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
-    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
-    if (s->quirks && (type == 0 || type == 1 || (type == 3 && (s->mix.c[XC_VWN5_C] != 0.0 || s->mix.c[XC_PBE_C] != 0.0)))) {
-        set_error(s, "DFT_ComputeXCSpin: the spin-resolved potentials are the first derivatives of the energy, but with quirks = 1 the "
-                     "ground state solved the shipped vwn5_c / pbe_c potentials, which are not the derivatives of their energies; "
-                     "run with --quirks 0");
-        return false;
-    }
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const size_t ng = (size_t)ngrid;
-    const long nxb = spin_points_blocks(ngrid);
-    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
-        !reserve(s, s->slabs, sizeof(double) * (size_t)P.nslab * nao * nao, "hipMalloc(slabs)") ||
-        !reserve(s, s->spin_partial, sizeof(double) * nxb, "hipMalloc(spin partial)", false) ||
-        !reserve(s, s->spin_exc, 2 * sizeof(double), "hipMalloc(spin exc)", false))
-        return false;
-    for (int k = 0; k < 2; ++k) {
-        if (!reserve(s, s->spin_rho[k], sizeof(double) * ng, "hipMalloc(spin rho)", false) ||
-            !reserve(s, s->spin_coef[k], sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(spin coef)", false))
-            return false;
-        if (gga && !reserve(s, s->spin_grad[k], sizeof(double) * 3 * ng, "hipMalloc(spin grad)", false)) return false;
-    }
-    if (gga && !reserve(s, s->spin_sigma, sizeof(double) * ng, "hipMalloc(spin sigma)", false)) return false;
-    double *Dp = (double *)s->dsym.p, *slabs = (double *)s->slabs.p, *sigma = (double *)s->spin_sigma.p;   // sigma: what the density kernels write beside the gradient; not read
-    double *rho_a = (double *)s->spin_rho[0].p, *rho_b = (double *)s->spin_rho[1].p;
-    double *g_a = (double *)s->spin_grad[0].p, *g_b = (double *)s->spin_grad[1].p;
-    double *c_a = (double *)s->spin_coef[0].p, *c_b = (double *)s->spin_coef[1].p;
-    double *partial = (double *)s->spin_partial.p, *exc = (double *)s->spin_exc.p;
-    launch_density(s, P, ngrid, nao, dm_a, ao, Dp, rho_a, g_a, sigma);
-    launch_density(s, P, ngrid, nao, dm_b, ao, Dp, rho_b, g_b, sigma);
-    {
-        ScopedTimer t(s, "xc_points_spin");
-        if (!hip_ok(s, launch_xc_points_spin(s->stream, type, gga, s->mix.c, ngrid, rho_a, rho_b, gga ? g_a : nullptr, gga ? g_b : nullptr,
-                                             w, c_a, c_b, partial), "spin pointwise launch"))
-            return false;
-    }
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, c_a, slabs, vxc_a, nullptr)) return false;
-    const ExcFinish fin{nxb, partial, exc, false};   // no host-mapped word, no publishing: Exc is copied below
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, c_b, slabs, vxc_b, &fin)) return false;
-    double out = std::numeric_limits<double>::quiet_NaN();
-    if (!hip_ok(s, hipMemcpyAsync(&out, exc, sizeof(double), hipMemcpyDeviceToHost, s->stream), "copy Exc") ||
-        !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
-        return false;
-    *exc_host = out;
-    if (std::isnan(out)) { set_error(s, "Exc is NaN after the spin sweep completed (non-finite inputs)"); return false; }
-    return true;
-}
-
-// Linear response of Vxc, first half: the ground-state density step of a sweep (never the one-kernel plan for small
-// bases: that one keeps no density) and the derivative table of the functional at that density.
-// kind 0: the shipped formulas differentiated (DFT_FxcPrepare); 1, 2: the tables of the spin-resolved energy bodies
-// (DFT_FxcPrepareSpin), each in its own slot.
-bool fxc_prepare(XCSolver *s, long ngrid, int nao, int nocc, const double *cocc, const double *dm, const double *ao,
-                 const double *ao_grad, const double *w, int kind = 0)
-{
-    s->last_error.clear();
-    s->n_timed = 0;
-    if (kind < 0 || kind > 2) { set_error(s, "DFT_FxcPrepareSpin: unknown kind %d (1 triplet, 2 singlet through the spin-resolved bodies)", kind); return false; }
-    long &slot_ngrid = kind ? s->fxc_spin_ngrid[kind - 1] : s->fxc_ngrid;
-    int &slot_nao = kind ? s->fxc_spin_nao[kind - 1] : s->fxc_nao;
-    DevBuf &slot_table = kind ? s->fxc_spin_table[kind - 1] : s->fxc_table;
-    DevBuf &slot_g0 = kind ? s->fxc_spin_g0[kind - 1] : s->fxc_g0;
-    slot_ngrid = 0;
-    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
-    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
-    if (!ao || !w) { set_error(s, "DFT_FxcPrepare needs the AO values and the grid weights"); return false; }
-    if (!dm && !cocc) { set_error(s, "neither a density matrix nor occupied orbitals were given"); return false; }
-    if (cocc && nocc <= 0) { set_error(s, "occupied orbitals given with nocc=%d", nocc); return false; }
-    OccPlan oplan;
-    bool use_occ = false;
-    if (cocc && s->path == 0 && s->occ != 2) {   // the rule of xc_sweep
-        oplan = occ_plan(nao, nocc, gga);
-        use_occ = s->occ == 1 || oplan.mfma_occ <= 0.85 * oplan.mfma_full;
-    }
-    s->used_occ = use_occ;
-    if (!use_occ && !dm) {
-        if (!reserve(s, s->occ_dm, sizeof(double) * (size_t)nao * nao, "hipMalloc(dm)")) return false;
-        launch_dm_from_cocc(s->stream, nao, nocc, cocc, (double *)s->occ_dm.p);
-        dm = (const double *)s->occ_dm.p;
-    }
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const size_t ng = (size_t)ngrid;
-    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
-        !reserve(s, s->rho, sizeof(double) * ng, "hipMalloc(rho)") ||
-        !reserve(s, slot_table, sizeof(double) * ng * (gga ? FXC_PLANES : 1), "hipMalloc(fxc table)"))
-        return false;
-    if (gga && (!reserve(s, s->sigma, sizeof(double) * ng, "hipMalloc(sigma)") ||
-                !reserve(s, slot_g0, sizeof(double) * 3 * ng, "hipMalloc(fxc grad rho)")))
-        return false;
-    double *rho = (double *)s->rho.p, *sigma = (double *)s->sigma.p, *g0 = (double *)slot_g0.p;   // grad rho goes straight to its keep
-    if (use_occ) {
-        ScopedTimer t(s, "rho_occ");
-        if (!reserve(s, s->occ_cp, sizeof(double) * oplan.cp_doubles, "hipMalloc(packed cocc)")) return false;
-        if (!hip_ok(s, launch_rho_occ(s->stream, s->num_cu, oplan, gga, P.vec16, ngrid, nao, nocc, cocc, (double *)s->occ_cp.p, ao, P.gx, P.gy,
-                                      P.gz, rho, g0, sigma), "occupied-orbital density launch"))
-            return false;
+        launch_sweep_tiny(s->stream, P.nslab, xc_type_index(s), ngrid, nao, ao, P.gx, P.gy, P.gz, src.dm, w, s->slabs.d(), p.partial.d(),
+                          s->quirks);
     } else {
-        launch_density(s, P, ngrid, nao, dm, ao, (double *)s->dsym.p, rho, g0, sigma);
+        if (!run_density(s, P, src, ngrid, nao, ao, p.rho.d(), p.grad.d(), p.sigma.d())) return false;
+        launch_xc_points(s, ngrid, nxb, w, p);
     }
-    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
-    if (kind == 0) {
-        ScopedTimer t(s, "fxc_table");
-        if (!hip_ok(s, launch_fxc_table(s->stream, type, gga, s->mix.c, ngrid, rho, gga ? sigma : nullptr, w, (double *)s->fxc_table.p, s->quirks),
-                    "response table launch"))
-            return false;
-    } else {
-        ScopedTimer t(s, "fxc_table_spin");
-        if (!hip_ok(s, launch_fxc_table_spin(s->stream, type, gga, s->mix.c, ngrid, rho, gga ? sigma : nullptr, w, (double *)slot_table.p, kind),
-                    "spin response table launch"))
-            return false;
-    }
-    if (!hip_ok(s, hipGetLastError(), "response prepare launch")) return false;
-    slot_ngrid = ngrid;
-    slot_nao = nao;
-    return true;
-}
-
-// Second half: V1 of a perturbation dm1 -- its density through the same kernels (linear in the matrix), the response
-// coefficients from the table, and the sweep's contraction and reduce.  Asynchronous on the solver's stream.
-bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double *ao, const double *ao_grad, double *v1, int kind = 0)
-{
-    s->last_error.clear();
-    s->n_timed = 0;
-    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
-    if (kind < 0 || kind > 2) { set_error(s, "DFT_FxcApplyKind: unknown kind %d (0 the DFT_FxcPrepare table, 1 triplet, 2 singlet through the spin-resolved bodies)", kind); return false; }
-    const long slot_ngrid = kind ? s->fxc_spin_ngrid[kind - 1] : s->fxc_ngrid;
-    const int slot_nao = kind ? s->fxc_spin_nao[kind - 1] : s->fxc_nao;
-    const double *slot_table = (const double *)(kind ? s->fxc_spin_table[kind - 1].p : s->fxc_table.p);
-    const double *slot_g0 = (const double *)(kind ? s->fxc_spin_g0[kind - 1].p : s->fxc_g0.p);
-    if (kind && slot_ngrid <= 0) { set_error(s, "DFT_FxcApplyKind(kind=%d) before DFT_FxcPrepareSpin of that kind", kind); return false; }
-    if (slot_ngrid <= 0) { set_error(s, "DFT_FxcApply before DFT_FxcPrepare (or the table was invalidated by an option change)"); return false; }
-    if (ngrid != slot_ngrid || nao != slot_nao) {
-        set_error(s, "DFT_FxcApply sizes ngrid=%ld nao=%d differ from DFT_FxcPrepare's ngrid=%ld nao=%d", ngrid, nao, slot_ngrid, slot_nao);
-        return false;
-    }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
-    if (!dm1 || !ao || !v1) { set_error(s, "DFT_FxcApply needs dm1, the AO values and the output matrix"); return false; }
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const size_t ng = (size_t)ngrid;
-    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
-        !reserve(s, s->rho, sizeof(double) * ng, "hipMalloc(rho)") ||
-        !reserve(s, s->coef, sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(coef)") ||
-        !reserve(s, s->slabs, sizeof(double) * (size_t)P.nslab * nao * nao, "hipMalloc(slabs)"))
-        return false;
-    if (gga && (!reserve(s, s->sigma, sizeof(double) * ng, "hipMalloc(sigma)") ||
-                !reserve(s, s->grad, sizeof(double) * 3 * ng, "hipMalloc(grad)")))
-        return false;
-    double *rho1 = (double *)s->rho.p, *g1 = (double *)s->grad.p, *coef = (double *)s->coef.p;
-    launch_density(s, P, ngrid, nao, dm1, ao, (double *)s->dsym.p, rho1, g1, (double *)s->sigma.p);
-    {
-        ScopedTimer t(s, "fxc_coef");
-        if (!hip_ok(s, launch_fxc_coef(s->stream, gga, ngrid, slot_table, slot_g0, rho1, g1, coef),
-                    "response coefficient launch"))
-            return false;
-    }
-    return vxc_stage(s, P, false, ngrid, nao, ao, coef, (double *)s->slabs.p, v1, nullptr);
+    const ExcFinish fin{nxb, p.partial.d(), exc, want_host_exc};
+    return vxc_stage(s, P, tiny, ngrid, nao, ao, p.coef.d(), s->slabs.d(), vxc, &fin);
 }
 
 // The refusal DFT_ComputeXCSpin and the open-shell response share: second and first derivatives of the ENERGY.
 bool spin_quirks_ok(XCSolver *s, const char *who)
 {
-    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+    const int type = xc_type_index(s);
     if (s->quirks && (type == 0 || type == 1 || (type == 3 && (s->mix.c[XC_VWN5_C] != 0.0 || s->mix.c[XC_PBE_C] != 0.0)))) {
         set_error(s, "%s: the spin-resolved potentials are the first derivatives of the energy, but with quirks = 1 the "
                      "ground state solved the shipped vwn5_c / pbe_c potentials, which are not the derivatives of their energies; "
@@ -765,47 +685,167 @@ bool spin_quirks_ok(XCSolver *s, const char *who)
     return true;
 }
 
+// The density kernels on the matrix of spin alpha, then of spin beta (linear in the matrix), into the spin planes; `ga`,
+// `gb`: where the two gradients go.  sigma is what the kernels write beside the gradient; nobody reads it.
+void launch_density_spin(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
+                         double *ga, double *gb)
+{
+    double *sigma = s->spin[0].sigma.d();
+    launch_density(s, P, ngrid, nao, dm_a, ao, s->dsym.d(), s->spin[0].rho.d(), ga, sigma);
+    launch_density(s, P, ngrid, nao, dm_b, ao, s->dsym.d(), s->spin[1].rho.d(), gb, sigma);
+}
+
+// The spin-resolved sweep (DFT_ComputeXCSpin): the closed-shell sweep's density kernels on dm_a and on dm_b, one
+// pointwise kernel (xc_spin.hip), the closed-shell contraction and reduce once per spin; the second reduce finishes Exc
+// from the pointwise kernel's partials, as xc_sweep's does.  Never the one-kernel plan for small bases (it keeps no
+// density), never recorded.  Shares Dsym, the slabs and M with the other entries (stream order), and nothing else: the
+// response tables and the workspace a recorded sweep holds are not written.
+bool xc_sweep_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
+                   const double *ao_grad, const double *w, double *vxc_a, double *vxc_b, double *exc_host)
+{
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
+    if (!dm_a || !dm_b || !ao || !w || !vxc_a || !vxc_b || !exc_host) {
+        set_error(s, "DFT_ComputeXCSpin needs both density matrices, the AO values, the grid weights, both output matrices and exc");
+        return false;
+    }
+    if (!spin_quirks_ok(s, "DFT_ComputeXCSpin")) return false;
+    const bool gga = s->needs_grad;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const long nxb = spin_points_blocks(ngrid);
+    Planes &a = s->spin[0], &b = s->spin[1];
+    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, a, false, ngrid, WS_ALL, nxb) ||
+        !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD) || !reserve(s, s->spin_exc, 2 * sizeof(double), "hipMalloc(spin exc)", false))
+        return false;
+    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, a.grad.d(), b.grad.d());
+    {
+        ScopedTimer t(s, "xc_points_spin");
+        if (!hip_ok(s, launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
+                                             gga ? b.grad.d() : nullptr, w, a.coef.d(), b.coef.d(), a.partial.d()), "spin pointwise launch"))
+            return false;
+    }
+    double *exc = s->spin_exc.d();
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, a.coef.d(), s->slabs.d(), vxc_a, nullptr)) return false;
+    const ExcFinish fin{nxb, a.partial.d(), exc, false};   // no host-mapped word, no publishing: Exc is copied below
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, b.coef.d(), s->slabs.d(), vxc_b, &fin)) return false;
+    double out = std::numeric_limits<double>::quiet_NaN();
+    if (!hip_ok(s, hipMemcpyAsync(&out, exc, sizeof(double), hipMemcpyDeviceToHost, s->stream), "copy Exc") ||
+        !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
+        return false;
+    *exc_host = out;
+    if (std::isnan(out)) { set_error(s, "Exc is NaN after the spin sweep completed (non-finite inputs)"); return false; }
+    return true;
+}
+
+// What an entry that reads a response slot checks first: prepared, and for these sizes (ngrid 0: the entry has none of its own)
+bool fxc_slot_ok(XCSolver *s, const FxcSlot &f, const char *who, const char *prepare, const char *note, long ngrid, int nao)
+{
+    if (f.ngrid <= 0) {
+        set_error(s, "%s before %s%s", who, prepare, note);
+        return false;
+    }
+    if (ngrid && (ngrid != f.ngrid || nao != f.nao)) {
+        set_error(s, "%s sizes ngrid=%ld nao=%d differ from %s's ngrid=%ld nao=%d", who, ngrid, nao, prepare, f.ngrid, f.nao);
+        return false;
+    }
+    return true;
+}
+
+// Linear response of Vxc, first half: the ground-state density step of a sweep (never the one-kernel plan for small
+// bases: that one keeps no density) and the derivative table of the functional at that density.
+// kind 0: the shipped formulas differentiated (DFT_FxcPrepare); 1, 2: the tables of the spin-resolved energy bodies
+// (DFT_FxcPrepareSpin, which vouches for the kind), each in its own slot.
+bool fxc_prepare(XCSolver *s, long ngrid, int nao, int nocc, const double *cocc, const double *dm, const double *ao,
+                 const double *ao_grad, const double *w, int kind = 0)
+{
+    FxcSlot &f = s->fxc[kind];
+    f.ngrid = 0;   // a failed Prepare leaves nothing to apply
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
+    if (!ao || !w) { set_error(s, "DFT_FxcPrepare needs the AO values and the grid weights"); return false; }
+    DensitySource src;
+    if (!density_source(s, nao, dm, cocc, nocc, true, src)) return false;
+    const bool gga = s->needs_grad;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const size_t ng = (size_t)ngrid;
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->ws, true, ngrid, WS_SIGMA) ||
+        !reserve(s, f.table, sizeof(double) * ng * (gga ? FXC_PLANES : 1), "hipMalloc(fxc table)") ||
+        (gga && !reserve(s, f.g0[0], sizeof(double) * 3 * ng, "hipMalloc(fxc grad rho)")))
+        return false;
+    double *rho = s->ws.rho.d(), *sigma = s->ws.sigma.d();
+    if (!run_density(s, P, src, ngrid, nao, ao, rho, f.g0[0].d(), sigma)) return false;   // grad rho goes straight to its keep
+    if (kind == 0) {
+        ScopedTimer t(s, "fxc_table");
+        if (!hip_ok(s, launch_fxc_table(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, rho, gga ? sigma : nullptr, w, f.table.d(), s->quirks),
+                    "response table launch"))
+            return false;
+    } else {
+        ScopedTimer t(s, "fxc_table_spin");
+        if (!hip_ok(s, launch_fxc_table_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, rho, gga ? sigma : nullptr, w, f.table.d(), kind),
+                    "spin response table launch"))
+            return false;
+    }
+    if (!hip_ok(s, hipGetLastError(), "response prepare launch")) return false;
+    f.ngrid = ngrid;
+    f.nao = nao;
+    return true;
+}
+
+// Second half: V1 of a perturbation dm1 -- its density through the same kernels (linear in the matrix), the response
+// coefficients from the table, and the sweep's contraction and reduce.  Asynchronous on the solver's stream.
+bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double *ao, const double *ao_grad, double *v1, int kind = 0)
+{
+    static const char *const who[3] = {"DFT_FxcApply", "DFT_FxcApplyKind(kind=1)", "DFT_FxcApplyKind(kind=2)"};
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
+    if (kind < 0 || kind > 2) { set_error(s, "DFT_FxcApplyKind: unknown kind %d (0 the DFT_FxcPrepare table, 1 triplet, 2 singlet through the spin-resolved bodies)", kind); return false; }
+    const FxcSlot &f = s->fxc[kind];
+    if (!fxc_slot_ok(s, f, who[kind], kind ? "DFT_FxcPrepareSpin" : "DFT_FxcPrepare",
+                     kind ? " of that kind" : " (or the table was invalidated by an option change)", ngrid, nao))
+        return false;
+    if (!dm1 || !ao || !v1) { set_error(s, "DFT_FxcApply needs dm1, the AO values and the output matrix"); return false; }
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const Planes &p = s->ws;
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->ws, true, ngrid, WS_ALL) || !reserve_slabs(s, P, nao)) return false;
+    launch_density(s, P, ngrid, nao, dm1, ao, s->dsym.d(), p.rho.d(), p.grad.d(), p.sigma.d());
+    {
+        ScopedTimer t(s, "fxc_coef");
+        if (!hip_ok(s, launch_fxc_coef(s->stream, P.gga, ngrid, f.table.d(), f.g0[0].d(), p.rho.d(), p.grad.d(), p.coef.d()),
+                    "response coefficient launch"))
+            return false;
+    }
+    return vxc_stage(s, P, false, ngrid, nao, ao, p.coef.d(), s->slabs.d(), v1, nullptr);
+}
+
 // Open-shell response of Vxc, first half (DFT_FxcPrepareSpinPol): the density kernels on dm0_a, then on dm0_b, as
 // xc_sweep_spin runs them, and the second-derivative table of the energy at that point (xc_response_pol.hip).  The
 // table and the two gradients stay in a slot of their own; the densities pass through the spin sweep's scratch.
 bool fxc_prepare_spinpol(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
                          const double *ao_grad, const double *w)
 {
-    s->last_error.clear();
-    s->n_timed = 0;
-    s->fxc_pol_ngrid = 0;
-    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
-    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
+    FxcSlot &f = s->fxc_pol;
+    f.ngrid = 0;   // a failed Prepare leaves nothing to apply
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
     if (!dm_a || !dm_b || !ao || !w) {
         set_error(s, "DFT_FxcPrepareSpinPol needs both density matrices, the AO values and the grid weights");
         return false;
     }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
     if (!spin_quirks_ok(s, "DFT_FxcPrepareSpinPol")) return false;
-    const int type = s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
+    const bool gga = s->needs_grad;
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
     const size_t ng = (size_t)ngrid;
-    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
-        !reserve(s, s->fxc_pol_table, sizeof(double) * ng * fxc_pol_planes(gga), "hipMalloc(fxc pol table)", false))
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->spin[0], false, ngrid, WS_SIGMA) || !reserve_planes(s, s->spin[1], false, ngrid, 0) ||
+        !reserve(s, f.table, sizeof(double) * ng * fxc_pol_planes(gga), "hipMalloc(fxc pol table)", false))
         return false;
-    for (int k = 0; k < 2; ++k) {
-        if (!reserve(s, s->spin_rho[k], sizeof(double) * ng, "hipMalloc(spin rho)", false)) return false;
-        if (gga && !reserve(s, s->fxc_pol_g0[k], sizeof(double) * 3 * ng, "hipMalloc(fxc pol grad rho)", false)) return false;
-    }
-    if (gga && !reserve(s, s->spin_sigma, sizeof(double) * ng, "hipMalloc(spin sigma)", false)) return false;
-    double *rho_a = (double *)s->spin_rho[0].p, *rho_b = (double *)s->spin_rho[1].p, *sigma = (double *)s->spin_sigma.p;
-    double *g_a = (double *)s->fxc_pol_g0[0].p, *g_b = (double *)s->fxc_pol_g0[1].p;   // the gradients go straight to their keep
-    launch_density(s, P, ngrid, nao, dm_a, ao, (double *)s->dsym.p, rho_a, g_a, sigma);
-    launch_density(s, P, ngrid, nao, dm_b, ao, (double *)s->dsym.p, rho_b, g_b, sigma);
+    for (int k = 0; k < 2; ++k)
+        if (gga && !reserve(s, f.g0[k], sizeof(double) * 3 * ng, "hipMalloc(fxc pol grad rho)", false)) return false;
+    double *g_a = f.g0[0].d(), *g_b = f.g0[1].d();   // the gradients go straight to their keep
+    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, g_a, g_b);
     {
         ScopedTimer t(s, "fxc_table_pol");
-        if (!hip_ok(s, launch_fxc_table_pol(s->stream, type, gga, s->mix.c, ngrid, rho_a, rho_b, gga ? g_a : nullptr, gga ? g_b : nullptr, w,
-                                            (double *)s->fxc_pol_table.p), "open-shell response table launch"))
+        if (!hip_ok(s, launch_fxc_table_pol(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, s->spin[0].rho.d(), s->spin[1].rho.d(),
+                                            gga ? g_a : nullptr, gga ? g_b : nullptr, w, f.table.d()), "open-shell response table launch"))
             return false;
     }
-    s->fxc_pol_ngrid = ngrid;
-    s->fxc_pol_nao = nao;
+    f.ngrid = ngrid;
+    f.nao = nao;
     return true;
 }
 
@@ -814,49 +854,26 @@ bool fxc_prepare_spinpol(XCSolver *s, long ngrid, int nao, const double *dm_a, c
 bool fxc_apply_spinpol(XCSolver *s, long ngrid, int nao, const double *dm1_a, const double *dm1_b, const double *ao,
                        const double *ao_grad, double *v1_a, double *v1_b)
 {
-    s->last_error.clear();
-    s->n_timed = 0;
-    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
-    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
-    if (s->fxc_pol_ngrid <= 0) { set_error(s, "DFT_FxcApplySpinPol before DFT_FxcPrepareSpinPol"); return false; }
-    if (ngrid != s->fxc_pol_ngrid || nao != s->fxc_pol_nao) {
-        set_error(s, "DFT_FxcApplySpinPol sizes ngrid=%ld nao=%d differ from DFT_FxcPrepareSpinPol's ngrid=%ld nao=%d", ngrid, nao,
-                  s->fxc_pol_ngrid, s->fxc_pol_nao);
-        return false;
-    }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_grad) { set_error(s, "ao_grad pointer is null for a gradient-corrected functional"); return false; }
+    const FxcSlot &f = s->fxc_pol;
+    if (!enter(s, ngrid, nao, ao_grad) || !fxc_slot_ok(s, f, "DFT_FxcApplySpinPol", "DFT_FxcPrepareSpinPol", "", ngrid, nao)) return false;
     if (!dm1_a || !dm1_b || !ao || !v1_a || !v1_b) {
         set_error(s, "DFT_FxcApplySpinPol needs both perturbations, the AO values and both output matrices");
         return false;
     }
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const size_t ng = (size_t)ngrid;
-    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
-        !reserve(s, s->slabs, sizeof(double) * (size_t)P.nslab * nao * nao, "hipMalloc(slabs)"))
+    Planes &a = s->spin[0], &b = s->spin[1];
+    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, a, false, ngrid, WS_ALL) ||
+        !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD))
         return false;
-    for (int k = 0; k < 2; ++k) {
-        if (!reserve(s, s->spin_rho[k], sizeof(double) * ng, "hipMalloc(spin rho)", false) ||
-            !reserve(s, s->spin_coef[k], sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(spin coef)", false))
-            return false;
-        if (gga && !reserve(s, s->spin_grad[k], sizeof(double) * 3 * ng, "hipMalloc(spin grad)", false)) return false;
-    }
-    if (gga && !reserve(s, s->spin_sigma, sizeof(double) * ng, "hipMalloc(spin sigma)", false)) return false;
-    double *Dp = (double *)s->dsym.p, *slabs = (double *)s->slabs.p, *sigma = (double *)s->spin_sigma.p;
-    double *r1_a = (double *)s->spin_rho[0].p, *r1_b = (double *)s->spin_rho[1].p;
-    double *g1_a = (double *)s->spin_grad[0].p, *g1_b = (double *)s->spin_grad[1].p;
-    double *c_a = (double *)s->spin_coef[0].p, *c_b = (double *)s->spin_coef[1].p;
-    launch_density(s, P, ngrid, nao, dm1_a, ao, Dp, r1_a, g1_a, sigma);
-    launch_density(s, P, ngrid, nao, dm1_b, ao, Dp, r1_b, g1_b, sigma);
+    launch_density_spin(s, P, ngrid, nao, dm1_a, dm1_b, ao, a.grad.d(), b.grad.d());
     {
         ScopedTimer t(s, "fxc_coef_pol");
-        if (!hip_ok(s, launch_fxc_coef_pol(s->stream, gga, ngrid, (const double *)s->fxc_pol_table.p, (const double *)s->fxc_pol_g0[0].p,
-                                           (const double *)s->fxc_pol_g0[1].p, r1_a, r1_b, g1_a, g1_b, c_a, c_b),
-                    "open-shell response coefficient launch"))
+        if (!hip_ok(s, launch_fxc_coef_pol(s->stream, P.gga, ngrid, f.table.d(), f.g0[0].d(), f.g0[1].d(), a.rho.d(), b.rho.d(), a.grad.d(),
+                                           b.grad.d(), a.coef.d(), b.coef.d()), "open-shell response coefficient launch"))
             return false;
     }
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, c_a, slabs, v1_a, nullptr)) return false;
-    return vxc_stage(s, P, false, ngrid, nao, ao, c_b, slabs, v1_b, nullptr);
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, a.coef.d(), s->slabs.d(), v1_a, nullptr)) return false;
+    return vxc_stage(s, P, false, ngrid, nao, ao, b.coef.d(), s->slabs.d(), v1_b, nullptr);
 }
 
 // J and/or K from rows (i, j), i in [i0, i0 + ni), of the dense ERI; `eri` points at row (i0, 0).
@@ -1339,60 +1356,38 @@ __global__ void k_accumulate_chunk(long n2, int add, const double *__restrict__ 
 }
 
 // XC part of the nuclear gradient (DFT_ComputeXCGradient): the sweep's own density kernels and pointwise kernel, into
-// buffers of this entry, then k_xc_grad (xc_grad.hip) on the coefficient planes.  Never the one-kernel plan for small
+// planes of this entry, then k_xc_grad (xc_grad.hip) on the coefficient planes.  Never the one-kernel plan for small
 // bases (it keeps no coefficients), never recorded; asynchronous on the solver's stream.
 bool xc_gradient(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *w, const double *ao_grad,
                  const double *ao_hess, double *out)
 {
-    s->last_error.clear();
-    s->n_timed = 0;
-    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
-    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao); return false; }
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
     if (!dm || !ao || !w || !out) { set_error(s, "DFT_ComputeXCGradient needs dm, the AO values, the grid weights and the output"); return false; }
     const bool gga = s->needs_grad;
-    if (gga && (!ao_grad || !ao_hess)) {
-        set_error(s, "ao_grad or ao_hess pointer is null for a gradient-corrected functional");
-        return false;
-    }
+    if (gga && !ao_hess) { set_error(s, "ao_hess pointer is null for a gradient-corrected functional"); return false; }
     if (!ao_grad) { set_error(s, "DFT_ComputeXCGradient needs ao_grad: the derivative of the density by a centre is made of it"); return false; }
     const XcGradPlan G = xc_grad_plan(s->num_cu, gga, ngrid, nao);
     if (G.lds > 160 * 1024) { set_error(s, "DFT_ComputeXCGradient: nao=%d needs %zu bytes of LDS per workgroup", nao, G.lds); return false; }
     // an LDA-class solver's density kernels read ao_grad's first plane pointer only as a dummy: plan as the sweep does
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
-    const size_t ng = (size_t)ngrid;
     const long nxb = (ngrid + 255) / 256;
-    if (!reserve(s, s->dsym, sizeof(double) * P.NP * P.NP, "hipMalloc(Dsym)") ||
-        !reserve(s, s->xcg_rho, sizeof(double) * ng, "hipMalloc(gradient rho)", false) ||
-        !reserve(s, s->xcg_coef, sizeof(double) * ng * (gga ? 4 : 1), "hipMalloc(gradient coef)", false) ||
-        !reserve(s, s->xcg_partial, sizeof(double) * nxb, "hipMalloc(gradient partial)", false) ||
+    const Planes &p = s->xcg;
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->xcg, false, ngrid, WS_ALL, nxb) ||
         !reserve(s, s->xcg_slabs, sizeof(double) * (size_t)G.nwg * 3 * nao, "hipMalloc(gradient slabs)", false))
         return false;
-    if (gga && (!reserve(s, s->xcg_sigma, sizeof(double) * ng, "hipMalloc(gradient sigma)", false) ||
-                !reserve(s, s->xcg_grad, sizeof(double) * 3 * ng, "hipMalloc(gradient grad rho)", false)))
-        return false;
-    double *Dp = (double *)s->dsym.p, *rho = (double *)s->xcg_rho.p, *sigma = (double *)s->xcg_sigma.p, *grad = (double *)s->xcg_grad.p,
-           *coef = (double *)s->xcg_coef.p, *partial = (double *)s->xcg_partial.p;
-    hipStream_t st = s->stream;
-    launch_density(s, P, ngrid, nao, dm, ao, Dp, rho, grad, sigma);
+    double *Dp = s->dsym.d();
+    launch_density(s, P, ngrid, nao, dm, ao, Dp, p.rho.d(), p.grad.d(), p.sigma.d());
     if (P.fast) {   // the wave-specialised density kernel symmetrises dm itself: k_xc_grad reads the padded matrix
         ScopedTimer t(s, "sym_dm");
         dim3 b(16, 16), g(P.NP / 16, P.NP / 16);
-        hipLaunchKernelGGL(k_sym_dm, g, b, 0, st, nao, P.NP, dm, Dp);
+        hipLaunchKernelGGL(k_sym_dm, g, b, 0, s->stream, nao, P.NP, dm, Dp);
     }
-    {
-        ScopedTimer t(s, "xc_points");
-        dim3 g((unsigned)nxb);
-        if (s->type == SOLVER_LDA)      hipLaunchKernelGGL(k_xc_points<0>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
-        else if (s->type == SOLVER_GGA) hipLaunchKernelGGL(k_xc_points<1>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
-        else if (s->type == SOLVER_B3LYP) hipLaunchKernelGGL(k_xc_points<2>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks);
-        else if (gga)                   hipLaunchKernelGGL(k_xc_points_mix<true>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
-        else                            hipLaunchKernelGGL(k_xc_points_mix<false>, g, dim3(256), 0, st, ngrid, rho, sigma, grad, w, coef, partial, s->quirks, s->mix);
-    }
+    launch_xc_points(s, ngrid, nxb, w, p);
     if (!hip_ok(s, hipGetLastError(), "XC gradient density launch")) return false;
     ScopedTimer t(s, "xc_grad");
     // one-sided types hand over c0 = w vrho, c_k = 4 w vsigma grad_k rho; B3LYP half of each (its M + M^T)
     const double fac = s->type == SOLVER_B3LYP ? 2.0 : 1.0;
-    return hip_ok(s, launch_xc_grad(st, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, coef, Dp, (double *)s->xcg_slabs.p, out),
+    return hip_ok(s, launch_xc_grad(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), Dp, s->xcg_slabs.d(), out),
                   "XC gradient launch");
 }
 
@@ -1500,21 +1495,11 @@ int DFT_GetMix(XCSolver *s, double *weights_out, int ncomp)
 void DFT_DestroySolver(XCSolver *s)
 {
     if (!s) return;
+    DeviceGuard dg(s);   // in scope until the solver is deleted: its buffers free themselves on its device
     if (s->device_ok) {
-        DeviceGuard dg(s);
         (void)hipStreamSynchronize(s->stream);
         drop_graphs(s);
         if (s->cap_stream) (void)hipStreamDestroy(s->cap_stream);
-        DevBuf *bufs[] = {&s->dsym, &s->rho, &s->sigma, &s->grad, &s->coef, &s->partial,
-                          &s->slabs, &s->exc, &s->jpart, &s->kpart, &s->shells, &s->msym,
-                          &s->cdy, &s->cdc, &s->cdv, &s->cdy2, &s->cdc2, &s->cdbt, &s->ao_ws, &s->vtmp, &s->occ_cp, &s->occ_dm, &s->dmf_lt, &s->dmf_c, &s->dmf_st, &s->fxc_table, &s->fxc_g0,
-                          &s->fxc_spin_table[0], &s->fxc_spin_table[1], &s->fxc_spin_g0[0], &s->fxc_spin_g0[1],
-                          &s->fxc_pol_table, &s->fxc_pol_g0[0], &s->fxc_pol_g0[1],
-                          &s->spin_rho[0], &s->spin_rho[1], &s->spin_grad[0], &s->spin_grad[1], &s->spin_sigma, &s->spin_coef[0],
-                          &s->spin_coef[1], &s->spin_partial, &s->spin_exc,
-                          &s->xcg_rho, &s->xcg_grad, &s->xcg_sigma, &s->xcg_coef, &s->xcg_partial, &s->xcg_slabs};
-        for (DevBuf *b : bufs)
-            if (b->p) (void)hipFree(b->p);
         if (s->h_exc) (void)hipHostFree(s->h_exc);
         if (s->h_seq) (void)hipHostFree(s->h_seq);
         for (Timing &t : s->timings) {
@@ -1528,20 +1513,10 @@ void DFT_DestroySolver(XCSolver *s)
 // Option "graph": the launches of a synchronous call, recorded once per (pointers, sizes) and replayed as one HIP graph.
 constexpr double GRAPH_AUTO_ELEMS = 2.0e6;
 
-struct SweepArgs {
-    long ngrid;
-    int nao, nocc;
-    const double *dm, *ao, *grad, *w;
-    double *vxc;
-    const double *cocc;
-};
-
 static SweepGraph *find_sweep(XCSolver *s, const SweepArgs &a)
 {
     for (SweepGraph &g : s->graphs)
-        if (g.ngrid == a.ngrid && g.nao == a.nao && g.nocc == a.nocc && g.dm == a.dm && g.ao == a.ao && g.grad == a.grad &&
-            g.w == a.w && g.vxc == a.vxc && g.cocc == a.cocc)
-            return &g;
+        if (g.key == a) return &g;
     return nullptr;
 }
 
@@ -1616,8 +1591,7 @@ static void note_sweep(XCSolver *s, const SweepArgs &a)
         s->graphs.erase(s->graphs.begin() + (long)old);
     }
     SweepGraph g;
-    g.ngrid = a.ngrid; g.nao = a.nao; g.nocc = a.nocc;
-    g.dm = a.dm; g.ao = a.ao; g.grad = a.grad; g.w = a.w; g.vxc = a.vxc; g.cocc = a.cocc;
+    g.key = a;
     g.seen = 1;
     g.stamp = ++s->graph_clock;
     s->graphs.push_back(g);
@@ -1635,8 +1609,8 @@ static double xc_call_sync(XCSolver *s, long long ngrid, int nao, unsigned long 
     if (s->h_exc) *s->h_exc = nan; // before anything is enqueued: the last kernel overwrites it
     SweepArgs a{(long)ngrid, nao, nocc, (const double *)d_dm, (const double *)d_ao, (const double *)d_ao_grad,
                 (const double *)d_w, (double *)d_vxc, (const double *)d_cocc};
-    // Option "dm_factor": a caller that holds dm alone.  The factor of dm stands in for the occupied orbitals where the rule of
-    // xc_sweep takes the occupied form for its rank; a dm that does not factorise, or a rank at which the dm kernels do fewer
+    // Option "dm_factor": a caller that holds dm alone.  The factor of dm stands in for the occupied orbitals where occ_pays
+    // takes the occupied form for its rank; a dm that does not factorise, or a rank at which the dm kernels do fewer
     // MFMAs, leaves the call exactly as it is without the option.
     const bool dmf = s->dm_factor && d_dm && !d_cocc;
     s->used_dm_factor = 0;
@@ -1644,13 +1618,13 @@ static double xc_call_sync(XCSolver *s, long long ngrid, int nao, unsigned long 
     if (dmf) {
         s->dm_factor_rank = 0;
         s->n_timed = 0;
-        if (s->device_ok && s->path == 0 && s->occ != 2 && ngrid > 0 && nao > 0 && !takes_tiny(s, (long)ngrid, nao) &&
+        if (s->device_ok && occ_allowed(s) && ngrid > 0 && nao > 0 && !takes_tiny(s, (long)ngrid, nao) &&
             reserve(s, s->dmf_c, sizeof(double) * (size_t)nao * std::max(nao / 2, 1), "hipMalloc(dm factor, packed)")) {
             const int rank = factor_density(s, nao, a.dm, 0, 0.0, (double *)s->dmf_c.p, nullptr);
             if (rank > 0) {
                 s->dm_factor_rank = rank;
-                const OccPlan pl = occ_plan(nao, rank, s->needs_grad);
-                if (s->occ == 1 || pl.mfma_occ <= 0.85 * pl.mfma_full) {
+                OccPlan pl;
+                if (occ_pays(s, nao, rank, pl)) {
                     a.cocc = (const double *)s->dmf_c.p;
                     a.nocc = nocc = rank;
                     s->used_dm_factor = 1;
@@ -1831,11 +1805,11 @@ int DFT_FxcSpinPolTable(XCSolver *s, unsigned long long d_out, long long max_dou
     if (!s) return -1;
     DeviceGuard dg(s);
     s->last_error.clear();
-    if (s->fxc_pol_ngrid <= 0) { set_error(s, "DFT_FxcSpinPolTable before DFT_FxcPrepareSpinPol"); return -1; }
+    if (!fxc_slot_ok(s, s->fxc_pol, "DFT_FxcSpinPolTable", "DFT_FxcPrepareSpinPol", "", 0, 0)) return -1;
     const int planes = fxc_pol_planes(s->needs_grad);
-    const long long need = (long long)planes * s->fxc_pol_ngrid;
+    const long long need = (long long)planes * s->fxc_pol.ngrid;
     if (!d_out || max_doubles < need) { set_error(s, "DFT_FxcSpinPolTable needs room for %lld doubles", need); return -1; }
-    if (!hip_ok(s, hipMemcpyAsync((void *)d_out, s->fxc_pol_table.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToDevice, s->stream), "copy table"))
+    if (!hip_ok(s, hipMemcpyAsync((void *)d_out, s->fxc_pol.table.p, sizeof(double) * (size_t)need, hipMemcpyDeviceToDevice, s->stream), "copy table"))
         return -1;
     return planes;
 }
@@ -2009,7 +1983,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     }
     if (!strcmp(key, "eri_symmetric")) { s->eri_sym = value == 2.0 ? 2 : value != 0.0; return 0; }
     if (!strcmp(key, "graph")) { s->graph = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
-    if (!strcmp(key, "quirks")) { s->quirks = value != 0.0; s->fxc_ngrid = 0; return 0; }   // a prepared response table held the old formulas
+    if (!strcmp(key, "quirks")) { s->quirks = value != 0.0; s->fxc[0].ngrid = 0; return 0; }   // the prepared kind-0 table held the old formulas
     if (!strcmp(key, "path")) { s->path = (int)value; return 0; }
     if (!strcmp(key, "profile")) { s->profile = value != 0.0; return 0; }
     if (!strcmp(key, "spin_wait")) { s->spin_wait = value != 0.0; return 0; }
