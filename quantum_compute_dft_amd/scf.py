@@ -5,28 +5,56 @@ Loop contract kept exactly: core guess `eigh(Hcore, S)`; per cycle J (compute_co
 (dft.py:217-221), DIIS on (S, dm, F), `eigh(F, S)`, energies from the NEW density with J/K/Exc of
 the old one (dft.py:230-236), convergence |dE| < 1e-8 and ||d dm||_F < 1e-6 (dft.py:243),
 200 cycles.  Differences: J and K come from ONE pass over the ERI (DFT_ComputeJK), AO values
-are evaluated on the device.  Two forms of the loop body:
+are evaluated on the device.  The loop stands four times, three closed-shell forms that `run_scf` chooses between
+by two flags of the backend, and the open-shell one:
 
-* host part on the host (`_run_scf`, below `device_from` = 200 basis functions, where one LAPACK
-  thread beats everything the device offers: n = 114 0.5 ms of dsyevd against 1.9 ms for hipSOLVER and 1.4-1.6 ms
-  per cycle for the device loop with the rotation solver against 1.2): per cycle ONE pinned upload [dm | cocc]
-  and ONE pinned download [J | K | Vxc] cross PCIe;
-* device-resident (`_run_scf_device`, from 200 functions, or `HipBackend(device_resident=True)`): dm,
-  cocc, J, K, Vxc, F, the DIIS history, the eigenproblem (occupied-subspace rotation; its few full solves
-  through hipSOLVER from 400 functions, through one host LAPACK thread below) and dm = 2 C_occ C_occ^T all
-  stay in HBM; per cycle one 4-double download (E_one, E_coul, E_ex, |d dm|) besides the Exc the ABI returns.
-  Anthracene B3LYP/def2-SVP (n = 246): 4.3 against 6.0 ms per cycle for the host form.
+* fused (`_run_scf_fused`, `backend.fused`: `HipBackend(fused_tail=True)`, or by default where the rotation solver
+  is in use and scf_tail.supported(nao, nocc)): the end of the cycle -- Fock assembly, DIIS, rotation, density,
+  energy traces -- is a handful of launches of libdft.so behind the cycle's J / K / Vxc (scf_tail.py), and the host
+  waits once per cycle for the energy and convergence scalars;
+* device-resident (`_run_scf_device`, `backend.device_resident`: from `device_from` = 200 functions, or
+  `HipBackend(device_resident=True)`, where the fused form is not chosen): dm, cocc, J, K, Vxc, F, the DIIS history,
+  the eigenproblem and dm = 2 C_occ C_occ^T are torch tensors in HBM; per cycle one 4-double download (E_one,
+  E_coul, E_ex, |d dm|) besides the Exc the ABI returns.  Anthracene B3LYP/def2-SVP (n = 246): 4.3 against 6.0 ms
+  per cycle for the host form;
+* host (`_run_scf`, neither flag; also what a backend without them gets, such as the oracle backend of the tests):
+  per cycle ONE pinned upload [dm | cocc] and ONE pinned download [J | K | Vxc] cross PCIe, everything else is numpy
+  (n = 114: 0.5 ms of dsyevd on one LAPACK thread against 1.9 ms for hipSOLVER);
+* open-shell (`run_uks`): the host form for two spin densities, eigh(F_s, S) every cycle.
+
+What they share is written once: `_CycleLedger` (energy sum, dE, times, log line, `res`, the thresholds, the profile),
+`_aufbau_check` (the converged state of a rotation run against the full solver), `_rotation_tol` (how accurately a
+cycle's rotation is solved) and `FockDiagonaliser` (the full solver: S^-1/2, hipSOLVER or one host LAPACK thread).
 
 With world > 1 rank 0 is authoritative: it alone runs DIIS + eigh and broadcasts [dm | cocc | scalars]
 (grid_shard.ReplicaSync), so replicas cannot drift apart and every rank leaves the loop in the same cycle
 (the stop decision is made from the broadcast scalars).
 """
+import os
 import time
 
 import numpy as np
 from scipy.linalg import eigh
 
 from . import functionals
+
+# the full solver goes to hipSOLVER from this many basis functions; below it one host LAPACK thread is faster, for the solve
+# and for everything else left on the host (dsyevd at n = 114: 0.67 ms on one thread, 0.87 on 16), so run_scf pins the pools
+_HIPSOLVER_FROM = 400
+_FIXED_POINT_FLOOR = 1e-10     # the residual below which no rotation's fixed point is ever asked to go
+
+
+def _host(a):
+    """A numpy array or a tensor as a numpy array."""
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _rotation_tol(last_ddm, floor=_FIXED_POINT_FLOOR):
+    """The residual at which the fixed point of a cycle's occupied rotation may stop: a cycle that still moves the
+    density by `last_ddm` is solved a thousand times finer than that and no finer, never below `floor` and never
+    looser than the cap below (inexact diagonalisation; the orbitals stay exactly orthonormal, i.e. a valid trial
+    density, either way).  No previous cycle (None): `floor`."""
+    return floor if last_ddm is None else min(max(floor, 1e-3 * float(last_ddm)), 1e-5)
 
 
 class CDIIS:
@@ -105,13 +133,19 @@ class FockDiagonaliser:
     against 1.0 ms for scipy's generalised driver on 16; n = 246 3.2 against 4.9 ms).  From
     `device_from` basis functions on the problem goes to the GPU: hipSOLVER through
     torch.linalg.eigh, the only library call on the device path (n = 494: 11.4 ms against 16.5 ms on
-    16 host cores, n = 1150: 27 against 84 ms, tools/eigh_time.py)."""
+    16 host cores, n = 1150: 27 against 84 ms, tools/eigh_time.py).
 
-    def __init__(self, S, device=None, device_from=400):
+    Three ways in.  `__call__`: numpy in, numpy out, on the device from `device_from` functions (the host loop).
+    `solve_host`: numpy in, numpy out, LAPACK whatever the size.  `solve_device`: a device tensor in, eigenvectors on
+    the device out (the rotation solver's full solves and the two device loops), hipSOLVER from _HIPSOLVER_FROM
+    functions and LAPACK below, where a full solve crosses PCIe with 2 n^2 doubles (n = 246: 2.5 against ~6 ms).  It
+    needs X in HBM (`device_from=0` puts it there at any size) unless it is asked for `products="host"`."""
+
+    def __init__(self, S, device=None, device_from=_HIPSOLVER_FROM):
         self.S, self.n = S, S.shape[0]
         self.on_device = device is not None and self.n >= device_from
         s, U = np.linalg.eigh(S)
-        self.Xh = U / np.sqrt(s)
+        self.Xh = U / np.sqrt(s)                                  # S^-1/2 (columns)
         if self.on_device:
             import torch
             self.torch = torch
@@ -119,12 +153,31 @@ class FockDiagonaliser:
 
     def __call__(self, F):
         if not self.on_device:
-            e, Cp = eigh(self.Xh.T @ F @ self.Xh, driver="evd")   # run_scf pins the BLAS pool to one thread at this size
-            return e, self.Xh @ Cp
-        t = self.torch
-        Fd = t.as_tensor(F, dtype=t.float64, device=self.X.device)
-        e, Cp = t.linalg.eigh(self.X.T @ Fd @ self.X)
-        return e.cpu().numpy(), (self.X @ Cp).cpu().numpy()
+            return self.solve_host(F)
+        e, C = self._hipsolver(self.torch.as_tensor(F, dtype=self.torch.float64, device=self.X.device))
+        return e.cpu().numpy(), C.cpu().numpy()
+
+    def solve_host(self, F):
+        e, Cp = eigh(self.Xh.T @ F @ self.Xh, driver="evd")       # run_scf pins the BLAS pool to one thread at this size
+        return e, self.Xh @ Cp
+
+    def _hipsolver(self, F):
+        e, Cp = self.torch.linalg.eigh(self.X.T @ F @ self.X)
+        return e, self.X @ Cp
+
+    def solve_device(self, F, products="device"):
+        """(energies, eigenvectors as a tensor on F's device) of a device tensor F.  The energies stay where the
+        driver left them: a tensor from hipSOLVER, a numpy array from LAPACK.  `products`: where X^T F X and X C' are
+        formed on the LAPACK path -- "device" (F' goes down, C' comes up) or "host" (F goes down, C comes up).  The two
+        round differently, so each loop keeps the placement it has always had."""
+        if self.n >= _HIPSOLVER_FROM:
+            return self._hipsolver(F)
+        import torch
+        if products == "host":
+            e, C = self.solve_host(F.cpu().numpy())
+            return e, torch.from_numpy(np.ascontiguousarray(C)).to(F.device)
+        e, Cp = eigh((self.X.T @ F @ self.X).cpu().numpy(), driver="evd")
+        return e, self.X @ torch.as_tensor(Cp, device=F.device)
 
 
 class OccupiedRotation:
@@ -148,23 +201,23 @@ class OccupiedRotation:
     grows, or the aufbau order is in doubt (highest occupied level within 1e-3 Ha of the lowest virtual diagonal).
     The virtual block is never diagonalised, so that test is a necessary one only: run_scf therefore checks the
     CONVERGED state once against eigh(F, S) (which also supplies the full spectrum it reports) and resumes with the
-    full solver and a fresh DIIS history if the occupied space it followed is not the aufbau one.
+    full solver and a fresh DIIS history if the occupied space it followed is another (_aufbau_check).
 
-    Where it pays (profiles/r02_eigensolver.txt): solved to 1e-10 the fixed point needs 15-20 steps in the middle of
-    an SCF run (the Fock matrix still moves by 1e-2) and 4-6 at its end; stopped at 1e-3 x the last density change
-    (`accuracy`, inexact diagonalisation -- the orbitals stay exactly orthonormal) it needs 3-5 per cycle.  Per SCF
+    Where it pays (profiles/r02_eigensolver.txt): solved to `tol` the fixed point needs 15-20 steps in the middle of
+    an SCF run (the Fock matrix still moves by 1e-2) and 4-6 at its end; stopped where _rotation_tol puts it for the
+    last density change (`accuracy`) it needs 3-5 per cycle.  Per SCF
     cycle of the real molecules: n = 494 (device) 12.5 against 23.4 ms, n = 246 (device) 4.3 against 6.9 ms, n = 114
     (host, plain numpy: ~25 small BLAS/LAPACK calls) 0.86 against 1.23 ms; below ~80 functions dsyevd itself is
     cheaper than those calls -- `eigensolver="auto"` uses it from 80 functions.  Same converged energies (to the
     SCF's own thresholds) and cycle counts within one of the exact loop (tests/test_scf_cpu.py)."""
 
-    def __init__(self, S, nocc, device=None, tol=1e-10, max_inner=60):
+    def __init__(self, S, nocc, device=None, tol=_FIXED_POINT_FLOOR, max_inner=60, full=None):
         import torch
         self.t, self.no, self.tol, self.max_inner = torch, int(nocc), tol, max_inner
         self.dev = torch.device(device) if device is not None else torch.device("cpu")
-        s, V = np.linalg.eigh(S)
         self.host = self.dev.type == "cpu"      # host form: plain numpy (a torch-CPU operation costs 3-5 us, ~70 of them per cycle)
-        self.X = V / np.sqrt(s) if self.host else torch.as_tensor(V / np.sqrt(s), dtype=torch.float64, device=self.dev)   # S^-1/2 (columns)
+        # the full solver: the backend's FockDiagonaliser (`full`) where there is one, so that S is decomposed once
+        self.full = full if full is not None else FockDiagonaliser(S, None if self.host else self.dev, device_from=0)
         self.U = None
         self.stats = {"exact": 0, "rotated": 0, "inner_steps": 0}
 
@@ -174,32 +227,21 @@ class OccupiedRotation:
         self.stats = {"exact": 0, "rotated": 0, "inner_steps": 0}
 
     def _exact(self, F):
-        t = self.t
-        Fp = self.X.T @ F @ self.X
         if self.host:
-            e, Cp = eigh(Fp, driver="evd")
-            self.U = self.X @ Cp
-            self.stats["exact"] += 1
-            return e, self.U[:, :self.no]
-        if F.shape[0] < 400:
-            # one LAPACK thread beats hipSOLVER below ~400 functions (FockDiagonaliser: n = 246 2.5 against ~6 ms), also
-            # from the device-resident loop: the few full solves of a run cross PCIe (2 n^2 doubles), the rotations do not
-            e, Cp = eigh(Fp.cpu().numpy(), driver="evd")
-            e, Cp = t.from_numpy(e).to(self.dev), t.from_numpy(Cp).to(self.dev)
+            e, self.U = self.full.solve_host(F)
         else:
-            e, Cp = t.linalg.eigh(Fp)
-        self.U = self.X @ Cp
+            e, self.U = self.full.solve_device(F)
+            e = self.t.as_tensor(e, device=self.dev)
         self.stats["exact"] += 1
         return e, self.U[:, :self.no]
 
     def occupied(self, F, accuracy=None):
         """(orbital energies, C_occ (n, nocc)) for the Fock matrix F (numpy array or tensor on self.dev); the
         energies are exact for the occupied block, diagonal estimates for the virtual one after a rotation.
-        `accuracy`: residual at which the fixed point may stop in THIS call (never below self.tol); the SCF loop
-        passes 1e-3 x the last density change, so a cycle that still moves the density by 1e-3 is not solved to
-        1e-10 -- the returned orbitals are exactly orthonormal either way, i.e. always a valid trial density."""
+        `accuracy`: the density change of the SCF loop's last cycle, which sets the residual at which the fixed point
+        may stop in THIS call (_rotation_tol, never below self.tol); None: solve to self.tol."""
         t, no = self.t, self.no
-        tol = self.tol if accuracy is None else min(max(self.tol, float(accuracy)), 1e-5)
+        tol = _rotation_tol(accuracy, self.tol)
         if self.host:
             return self._occupied_host(np.asarray(F), tol)
         F = F if t.is_tensor(F) else t.as_tensor(F, dtype=t.float64, device=self.dev)
@@ -373,7 +415,7 @@ class HipBackend:
             rlo, rhi = eri_row_bounds(nao, world, rank)
             self.eri_rows = (rlo, rhi)
             if rhi > rlo:
-                self.d_eri = torch.as_tensor(np.ascontiguousarray(inp.eri.reshape(nao * nao, nao * nao)[rlo:rhi]), dtype=f64, device=self.dev)
+                self.d_eri = self._dev(inp.eri.reshape(nao * nao, nao * nao)[rlo:rhi])
             # (ij|kl) = (kl|ij): when the matrix in HBM really is symmetric (checked here, once) and only J is wanted, the Coulomb
             # pass streams its upper triangle alone -- half the bytes of dft_solver.cu:550-555's GEMV, which is all a J build costs
             # ... and when it is symmetric in each index pair too, (ij|kl) = (ji|kl) = (ij|lk), the unique eighth alone (k_j_sym8;
@@ -407,13 +449,13 @@ class HipBackend:
         # the full solver as first cycle and fallback; "auto": rotate where it pays -- from 80 basis functions (per
         # cycle of the real molecules: n = 24 0.23 against 0.21 ms and n = 36 0.37 against 0.34, so not there;
         # n = 114 0.86 against 1.23; n = 246 4.3 against 6.9; n = 494 12.5 against 23.4)
-        # the full solver: hipSOLVER from 400 functions whatever the loop form; the device loop needs X in HBM always
-        self.eigh = FockDiagonaliser(inp.S, self.dev, device_from=0 if self.device_resident else 400)
+        # the full solver (FockDiagonaliser keeps its threshold whatever the loop form); the device loop needs X in HBM always
+        self.eigh = FockDiagonaliser(inp.S, self.dev, device_from=0 if self.device_resident else _HIPSOLVER_FROM)
         self.occ_solver = None
         if eigensolver not in ("auto", "rotate", "exact"):
             raise ValueError(f"eigensolver {eigensolver!r}: expected 'auto', 'rotate' or 'exact'")
         if eigensolver == "rotate" or (eigensolver == "auto" and nao >= 80):
-            self.occ_solver = OccupiedRotation(inp.S, inp.nocc, self.dev if self.device_resident else None)
+            self.occ_solver = OccupiedRotation(inp.S, inp.nocc, self.dev if self.device_resident else None, full=self.eigh)
         # The end of the cycle (Fock assembly, DIIS, rotation, density, energy traces) as six launches of libdft.so behind the
         # cycle's J / K / Vxc (scf_tail.py, csrc/scf_tail.hip) where the rotation solver is in use and the sizes fit its
         # single-workgroup rotation kernel: Benzene/def2-SVP 0.44 ms of host work per cycle -> ~0.1 ms of device work.
@@ -431,7 +473,7 @@ class HipBackend:
             if not scf_tail.supported(nao, inp.nocc) or ao_mode != "resident":
                 raise ValueError(f"fused_tail: resident AO planes, nao <= {scf_tail.MAX_NAO} and nocc <= {scf_tail.MAX_NOCC} are needed")
             if self.occ_solver is None:
-                self.occ_solver = OccupiedRotation(inp.S, inp.nocc, None)      # the counters the drivers report; the rotation itself runs in the kernel
+                self.occ_solver = OccupiedRotation(inp.S, inp.nocc, None, full=self.eigh)      # the counters the drivers report; the rotation itself runs in the kernel
             if rank == 0:
                 self.tail = scf_tail.ScfTail(self.solver.lib, inp.Hcore, inp.S, inp.nocc, self.dev)
         if self.device_resident or self.diis_device is not None or self.eigh.on_device:
@@ -447,6 +489,10 @@ class HipBackend:
             del a
         torch.cuda.synchronize()
         self.init_time = time.time() - t0
+
+    def _dev(self, a):
+        """A host array as a C-contiguous float64 tensor on this backend's device."""
+        return self.torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), dtype=self.torch.float64, device=self.dev)
 
     # ---- host-loop interface ------------------------------------------------------------------
     def set_state(self, dm, cocc):
@@ -548,9 +594,8 @@ class HipBackend:
         orbitals), Exc and the two potentials from DFT_ComputeXCSpin.  A spin without electrons has K = 0."""
         self._uks_check()
         t, n = self.torch, self.nao
-        up = lambda a: t.as_tensor(np.ascontiguousarray(a), dtype=t.float64, device=self.dev)
-        d_s = [up(dm_a), up(dm_b)]
-        d_c = [up(cocc_a), up(cocc_b)]
+        d_s = [self._dev(dm_a), self._dev(dm_b)]
+        d_c = [self._dev(cocc_a), self._dev(cocc_b)]
         self.d_dm.copy_(d_s[0] + d_s[1])
         if getattr(self, "_uks_out", None) is None:
             self._uks_out = t.zeros((6, n, n), dtype=t.float64, device=self.dev)      # J | K_a | K_b | V_a | V_b | scratch
@@ -579,7 +624,7 @@ class HipBackend:
         self._uks_check()
         self._response_check()
         t = self.torch
-        self._d_dm0_s = [t.as_tensor(np.ascontiguousarray(d), dtype=t.float64, device=self.dev) for d in (dm_a, dm_b)]
+        self._d_dm0_s = [self._dev(d) for d in (dm_a, dm_b)]
         self.solver.fxc_prepare_spinpol(self.ngrid, self.nao, self._d_dm0_s[0], self._d_dm0_s[1], self.d_ao, self.d_w, self.d_gr)
         t.cuda.synchronize()
 
@@ -594,8 +639,8 @@ class HipBackend:
         self._response_check()
         t, n = self.torch, self.nao
         f64 = t.float64
-        d_A = [t.as_tensor(np.ascontiguousarray(a, dtype=np.float64), dtype=f64, device=self.dev) for a in (A_a, A_b)]
-        d_B = [t.as_tensor(np.ascontiguousarray(b, dtype=np.float64), dtype=f64, device=self.dev) for b in (Bs_a, Bs_b)]
+        d_A = [self._dev(a) for a in (A_a, A_b)]
+        d_B = [self._dev(b) for b in (Bs_a, Bs_b)]
         for a, b in zip(d_A, d_B):
             if b.dim() != 3 or a.dim() != 2 or a.shape[0] != n or tuple(b.shape[1:]) != tuple(a.shape) or b.shape[0] != d_B[0].shape[0]:
                 raise ValueError(f"uks_excitation_parts: A_s (nao, n_s) and Bs_s (nvec, nao, n_s) expected, got {tuple(a.shape)} and {tuple(b.shape)}")
@@ -643,8 +688,8 @@ class HipBackend:
         self._response_check()
         from .response import spin_kind
         t = self.torch
-        self._d_dm0 = t.as_tensor(np.ascontiguousarray(dm0), dtype=t.float64, device=self.dev)
-        d_c = t.as_tensor(np.ascontiguousarray(cocc), dtype=t.float64, device=self.dev) if (cocc is not None and self.xc_occ) else None
+        self._d_dm0 = self._dev(dm0)
+        d_c = self._dev(cocc) if (cocc is not None and self.xc_occ) else None
         k = spin_kind(kind)
         if k:
             self.solver.fxc_prepare_spin(self.ngrid, self.nao, self._d_dm0, self.d_ao, self.d_w, self.d_gr, d_c, 0 if d_c is None else d_c.shape[1], k)
@@ -671,7 +716,7 @@ class HipBackend:
                     raise ValueError("response_parts: K from Cholesky vectors needs dm1 = A B^T + B A^T as factors=(A, B)")
                 A, B = (np.asarray(x, dtype=np.float64) for x in factors)
                 for sgn, out in ((1.0, d_K), (-1.0, d_K2)):
-                    c = t.as_tensor(np.ascontiguousarray((A + sgn * B) / np.sqrt(2.0)), dtype=t.float64, device=self.dev)
+                    c = self._dev((A + sgn * B) / np.sqrt(2.0))
                     self.solver.compute_jk_factorized(n, naux, c.shape[1], self.d_chol, None, c, None, out)
                     t.cuda.synchronize()     # `c` is released when the loop moves on
                 d_K.sub_(d_K2)
@@ -703,7 +748,7 @@ class HipBackend:
         rows = int(slice_rows) if slice_rows else max(16, int(self.XC_GRADIENT_HESS_BYTES // (48 * n)) // 16 * 16)
         rows = max(1, min(rows, ng))
         gga = s.needs_gradient
-        d_dm = t.as_tensor(np.ascontiguousarray(dm), dtype=f64, device=self.dev)
+        d_dm = self._dev(dm)
         d_out = t.zeros((n, 3), dtype=f64, device=self.dev)
         d_G = t.zeros((n, 3), dtype=f64, device=self.dev)
         d_hess = t.empty(6 * rows * n, dtype=f64, device=self.dev) if gga else None
@@ -748,8 +793,7 @@ class HipBackend:
         want_j = kd != 1
         t, n = self.torch, self.nao
         f64 = t.float64
-        d_A = t.as_tensor(np.ascontiguousarray(A, dtype=np.float64), dtype=f64, device=self.dev)
-        d_B = t.as_tensor(np.ascontiguousarray(Bs, dtype=np.float64), dtype=f64, device=self.dev)
+        d_A, d_B = self._dev(A), self._dev(Bs)
         if d_B.dim() != 3 or d_A.dim() != 2 or d_A.shape[0] != n or tuple(d_B.shape[1:]) != tuple(d_A.shape):
             raise ValueError(f"excitation_parts: A (nao, nocc) and Bs (nvec, nao, nocc) expected, got {tuple(d_A.shape)} and {tuple(d_B.shape)}")
         nvec, nocc = d_B.shape[0], d_A.shape[1]
@@ -778,10 +822,9 @@ class HipBackend:
 
 def run_scf(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, log=print):
     from .hostinfo import blas_threads
-    # host LAPACK/BLAS never on every visible core (256 on a 16-core share: ~90 ms stalls); below 400
-    # functions one thread is fastest for everything left on the host (dsyevd at n = 114: 0.67 ms on one
-    # thread, 0.87 on 16), above it the pool gets the CPU share
-    with blas_threads(1 if inp.S.shape[0] < 400 else None):
+    # host LAPACK/BLAS never on every visible core (256 on a 16-core share: ~90 ms stalls): one thread where the full
+    # solver is LAPACK's (_HIPSOLVER_FROM), above it the pool gets the CPU share
+    with blas_threads(1 if inp.S.shape[0] < _HIPSOLVER_FROM else None):
         if getattr(backend, "fused", False):
             return _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log)
         if getattr(backend, "device_resident", False):
@@ -789,42 +832,99 @@ def run_scf(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, 
         return _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log)
 
 
-def _log_header(log):
+class _CycleLedger:
+    """The bookkeeping of one SCF run, the same in all four loops: the exchange weight, the log's header, the per-cycle
+    times, `res` with `per_cycle`, the energy of the last cycle, the QCDFT_SCF_PROFILE rows and the closing statistics.
+    A loop creates one where its cycles start, calls start() and cycle() once per cycle and returns finish()."""
+
+    def __init__(self, inp, functional, conv_e, conv_dm, log, **res):
+        self.c_hf = functionals.resolve(functional).c_hf     # dft.py:197 (0.2 for B3LYP, else 0) for any functional
+        self.want_k = self.c_hf != 0.0
+        self.E_nuc, self.conv_e, self.conv_dm, self.log = inp.E_nuc, conv_e, conv_dm, log
+        if log:
+            log("\nSCF started!"); log("-" * 80)
+            log(f"{'epoch':>4} {'tot energy':>15} {'Δenergy':>12} {'Δdensity':>12} {'HF_Ex':>12}"); log("-" * 80)
+        self.E_old, self.xc_times, self.jk_times, self.it_times, self.t_start = 0.0, [], [], [], time.time()
+        self.res = {"converged": False, **res}
+        self.per_cycle = self.res["per_cycle"] = []          # (E_tot, |dm' - dm|) of every cycle
+        self.prof = [] if os.environ.get("QCDFT_SCF_PROFILE") else None     # per-part times of a cycle's tail (a loop may add syncs for them)
+
+    def start(self):
+        self.t_it = time.time()
+        return self.t_it
+
+    def cycle(self, E_one, E_coul, E_xc, E_ex, ddm, **fields):
+        """Books the cycle that start() opened -- energy from the NEW density (dft.py:236), its time (taken before the log
+        line is written), the log line, `res` (with the loop's own `fields`) -- and says whether both thresholds of
+        dft.py:243 are met.  The same scalars on every rank, so the same answer."""
+        E_tot = E_one + E_coul + E_xc + E_ex + self.E_nuc
+        dE, self.E_old = E_tot - self.E_old, E_tot
+        self.it_times.append(time.time() - self.t_it)
+        if self.log:
+            self.log(f"{len(self.it_times):4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
+        self.res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=len(self.it_times), **fields)
+        self.per_cycle.append((E_tot, ddm))
+        return abs(dE) < self.conv_e and ddm < self.conv_dm
+
+    def finish(self, parts_key=None, parts=(), title=""):
+        """`res`, closed.  `parts_key`, `parts`: where the medians of the profile rows go and what their columns are."""
+        res = self.res
+        if self.prof:
+            med = np.median(np.array(self.prof[1:] if len(self.prof) > 1 else self.prof), axis=0)
+            res[parts_key] = dict(zip(parts, (float(x) for x in med)))
+            if self.log:
+                self.log(f"{title} (median ms per cycle): " + ", ".join(f"{k} {v:.3f}" for k, v in res[parts_key].items()))
+        res["total_time"] = time.time() - self.t_start
+        res["xc_ms_avg"] = 1e3 * sum(self.xc_times) / max(1, len(self.xc_times))     # dft.py:259 (includes the first call's allocations)
+        steady = lambda ts: 1e3 * float(np.median(ts[1:] if len(ts) > 1 else ts))
+        res["xc_ms"], res["jk_ms"], res["iter_ms"] = steady(self.xc_times), steady(self.jk_times), steady(self.it_times)  # medians past cycle 1
+        res["cycle_ms"] = [round(1e3 * t, 4) for t in self.it_times]          # every cycle, the first (lazy allocations) included
+        res["nelec_grid"] = None
+        return res
+
+
+def _aufbau_check(full_solve, root, flag, broadcast, log):
+    """Is the occupied space that a rotation run converged in the AUFBAU one?  The rotation solver follows the occupied
+    space continuously and never diagonalises the virtual block, so this is checked once, on the converged state, against
+    eigh(F, S) of the converged Fock matrix: `full_solve()` gives (the full spectrum, |2 C_o C_o^T - dm|_F as a float)
+    of that solve.  Rank 0 decides (`root`: this rank does), every rank hears it through `flag`, a one-element buffer of
+    the kind that `broadcast` (ReplicaSync.broadcast_numpy, ReplicaSync.broadcast or None) moves.  Returns (ok, the
+    spectrum if ok and this rank solved, else None).  After a mismatch -- an occupied/virtual level crossing that the
+    solver followed through -- the caller resumes as the reference's loop, full solver and a fresh DIIS history."""
+    spectrum = None
+    if root:
+        spectrum, gap = full_solve()
+        flag[0] = float(gap < 1e-4)
+    if broadcast:
+        broadcast([flag])
+    if float(flag[0]):
+        return True, spectrum
     if log:
-        log("\nSCF started!"); log("-" * 80)
-        log(f"{'epoch':>4} {'tot energy':>15} {'Δenergy':>12} {'Δdensity':>12} {'HF_Ex':>12}"); log("-" * 80)
-
-
-def _finish(res, t_start, xc_times, jk_times, it_times):
-    res["total_time"] = time.time() - t_start
-    res["xc_ms_avg"] = 1e3 * sum(xc_times) / max(1, len(xc_times))     # dft.py:259 (includes the first call's allocations)
-    steady = lambda ts: 1e3 * float(np.median(ts[1:] if len(ts) > 1 else ts))
-    res["xc_ms"], res["jk_ms"], res["iter_ms"] = steady(xc_times), steady(jk_times), steady(it_times)  # medians past cycle 1
-    res["cycle_ms"] = [round(1e3 * t, 4) for t in it_times]          # every cycle, the first (lazy allocations) included
-    res["nelec_grid"] = None
-    return res
+        log("     converged occupied space is not the aufbau one: continuing with eigh(F, S) every cycle")
+    return False, None
 
 
 def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     """Host form of the loop body (dft.py:199-266).  `backend` supplies either fock_parts(want_k) (HipBackend)
     or the reference-shaped pair jk(want_k) / xc() (the oracle backend of the tests)."""
-    c_hf = functionals.resolve(functional).c_hf                                        # dft.py:197 (0.2 for B3LYP, else 0) for any functional
     Hcore, S, nocc = inp.Hcore, inp.S, inp.nocc
-    root = getattr(backend, "rank", 0) == 0
     sync = getattr(backend, "replica_sync", None)
+    root = getattr(backend, "rank", 0) == 0 or sync is None   # rank 0 is authoritative: DIIS + eigh run once, replicas receive the result
     solve_full = getattr(backend, "eigh", None) or (lambda F: eigh(F, S))
     occ = getattr(backend, "occ_solver", None)
-
-    last_ddm = [None]
-
-    rot = [occ is not None]   # cleared if the converged state fails the check against the full solver (below)
+    rotate, last_ddm = occ is not None, None   # `rotate` is cleared if the converged state fails _aufbau_check
 
     def solve(F):   # (orbital energies, C_occ): the loop never uses the virtual orbitals (dft.py:182,228)
-        if rot[0]:
-            e_, co_ = occ.occupied(F, None if last_ddm[0] is None else 1e-3 * last_ddm[0])
+        if rotate:
+            e_, co_ = occ.occupied(F, last_ddm)
             return np.asarray(e_), np.asarray(co_)
         e_, C_ = solve_full(F)
         return e_, C_[:, :nocc]
+
+    def checked():   # the converged Fock matrix through the full solver, for _aufbau_check
+        e_x, C_x = solve_full(F)
+        e_x, C_x = np.asarray(e_x), np.asarray(C_x)
+        return e_x, float(np.linalg.norm(2.0 * C_x[:, :nocc] @ C_x[:, :nocc].T - dm_new))
 
     e, C = solve(Hcore)                                                                # dft.py:181
     cocc = np.ascontiguousarray(np.sqrt(2.0) * C)
@@ -832,15 +932,10 @@ def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     if sync:
         sync.broadcast_numpy([dm, cocc])                                               # replicas start from rank 0's guess
     diis = CDIIS(device=getattr(backend, "diis_device", None))
-    _log_header(log)
-    E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
-    res = {"converged": False}
-    per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
-    want_k = c_hf != 0.0
-    import os
-    prof = [] if os.environ.get("QCDFT_SCF_PROFILE") else None      # per-part times of the host side of a cycle
-    for cycle in range(max_cycle):
-        t_it = time.time()
+    led = _CycleLedger(inp, functional, conv_e, conv_dm, log)
+    c_hf, want_k = led.c_hf, led.want_k
+    for _ in range(max_cycle):
+        t_it = led.start()
         if hasattr(backend, "fock_parts"):
             backend.set_state(dm, cocc)                                                # dft.py:200
             J, K, E_xc, Vraw, t_xc, t_jk = backend.fock_parts(want_k)
@@ -849,9 +944,9 @@ def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
             J, K = backend.jk(want_k)
             t_jk = time.time() - t_it
             E_xc, Vraw, t_xc = backend.xc()
-        jk_times.append(t_jk); xc_times.append(t_xc)
+        led.jk_times.append(t_jk); led.xc_times.append(t_xc)
         dm_new, cocc_new, scal = np.empty_like(dm), np.empty_like(cocc), np.zeros(4)
-        if root or sync is None:   # rank 0 is authoritative: DIIS + eigh run once, replicas receive the result
+        if root:
             tp = [time.time()]
             Vxc = 0.5 * (Vraw + Vraw.T)                                                # dft.py:212
             F = Hcore + J + Vxc - (c_hf * 0.5 * K if K is not None else 0.0)           # dft.py:221,223
@@ -866,102 +961,60 @@ def _run_scf(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
                              -0.25 * c_hf * np.sum(dm_new * K) if K is not None else 0.0,
                              np.linalg.norm(dm_new - dm)])
             tp.append(time.time())
-            if prof is not None:
-                prof.append([1e3 * (tp[0] - t_it - t_jk - t_xc)] + [1e3 * (b - a) for a, b in zip(tp, tp[1:])])
+            if led.prof is not None:
+                led.prof.append([1e3 * (tp[0] - t_it - t_jk - t_xc)] + [1e3 * (b - a) for a, b in zip(tp, tp[1:])])
         if sync:
             sync.broadcast_numpy([dm_new, cocc_new, scal])
-        E_one, E_coul, E_ex, ddm = (float(x) for x in scal)
-        last_ddm[0] = ddm
-        E_tot = E_one + E_coul + E_xc + E_ex + inp.E_nuc                               # dft.py:236
-        dE = E_tot - E_old
-        it_times.append(time.time() - t_it)
-        if log:
-            log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
-        res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1,
-                   dm=dm_new, mo_energy=e)
-        per_cycle.append((E_tot, ddm))
-        if abs(dE) < conv_e and ddm < conv_dm:                                         # dft.py:243; same scalars on every rank
-            # The rotation solver follows the occupied space continuously; that it is still the AUFBAU one is checked
-            # once, here, against eigh(F, S) of the converged Fock matrix (which also supplies the exact orbital
-            # energies).  A mismatch (an occupied/virtual level crossing it followed through) resumes the loop with the
-            # full solver -- the reference's loop.  Rank 0 decides, every rank hears it.
-            ok = np.ones(1)
-            if rot[0]:
-                if root or sync is None:
-                    e_x, C_x = solve_full(F)
-                    e_x, C_x = np.asarray(e_x), np.asarray(C_x)
-                    ok[0] = float(np.linalg.norm(2.0 * C_x[:, :nocc] @ C_x[:, :nocc].T - dm_new) < 1e-4)
-                    if ok[0]:
-                        res["mo_energy"] = e_x
-                if sync:
-                    sync.broadcast_numpy([ok])
-            if ok[0]:
-                res["converged"] = True
+        E_one, E_coul, E_ex, last_ddm = (float(x) for x in scal)
+        if led.cycle(E_one, E_coul, E_xc, E_ex, last_ddm, dm=dm_new, mo_energy=e):
+            ok, e_x = _aufbau_check(checked, root, np.ones(1), sync and sync.broadcast_numpy, log) if rotate else (True, None)
+            led.res["mo_energy"] = e if e_x is None else e_x                           # the exact orbital energies, virtual ones included
+            if ok:
+                led.res["converged"] = True
                 break
-            rot[0] = False
+            rotate = False
             diis = CDIIS(device=getattr(backend, "diis_device", None))   # its history belongs to the other state
-            if log:
-                log("     converged occupied space is not the aufbau one: continuing with eigh(F, S) every cycle")
-        dm, cocc, E_old = dm_new, cocc_new, E_tot
-    if prof:
-        med = np.median(np.array(prof[1:] if len(prof) > 1 else prof), axis=0)
-        res["host_parts_ms"] = dict(zip(("transfers", "fock", "diis", "eigen", "density_energies"), (float(x) for x in med)))
-        if log:
-            log("host parts (median ms per cycle): " + ", ".join(f"{k} {v:.3f}" for k, v in res["host_parts_ms"].items()))
-    return _finish(res, t_start, xc_times, jk_times, it_times)
+        dm, cocc = dm_new, cocc_new
+    return led.finish("host_parts_ms", ("transfers", "fock", "diis", "eigen", "density_energies"), "host parts")
 
 
 def _run_scf_device(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     """Device-resident form of the same loop: nothing but scalars crosses PCIe per cycle."""
-    t = backend.torch
-    dev, f64 = backend.dev, backend.torch.float64
-    c_hf = functionals.resolve(functional).c_hf
-    nocc = inp.nocc
-    root, sync = backend.rank == 0, backend.replica_sync
+    t, dev, nocc, sync = backend.torch, backend.dev, inp.nocc, backend.replica_sync
+    f64, root = t.float64, backend.rank == 0 or sync is None
     H = t.as_tensor(inp.Hcore, dtype=f64, device=dev)
     S = t.as_tensor(inp.S, dtype=f64, device=dev)
-    X = backend.eigh.X                                                                # S^-1/2 (FockDiagonaliser, once per S)
+    eigh_full = backend.eigh.solve_device                                              # X^T F X and X C' on the device at every size
     sqrt2 = float(np.sqrt(2.0))
-
-    last_ddm = [None]
-
-    rot = [backend.occ_solver is not None]   # see the convergence check in _run_scf
-
-    def eigh_full(F):
-        if X.shape[0] < 400:      # as OccupiedRotation._exact: one host LAPACK thread beats hipSOLVER below ~400 functions
-            e_, Cp = eigh((X.T @ F @ X).cpu().numpy(), driver="evd")
-            return t.as_tensor(e_, device=dev), X @ t.as_tensor(Cp, device=dev)
-        e_, Cp = t.linalg.eigh(X.T @ F @ X)
-        return e_, X @ Cp
+    rotate, last_ddm = backend.occ_solver is not None, None
 
     def eigh_occ(F):                                                                   # dft.py:181,227 on the device
-        if rot[0]:
-            e, co = backend.occ_solver.occupied(F, None if last_ddm[0] is None else 1e-3 * last_ddm[0])
+        if rotate:
+            e, co = backend.occ_solver.occupied(F, last_ddm)
             return e, co * sqrt2
         e, C = eigh_full(F)
         return e, C[:, :nocc] * sqrt2
+
+    def checked():
+        e_x, C_x = eigh_full(F)
+        return e_x, float(t.linalg.norm(2.0 * C_x[:, :nocc] @ C_x[:, :nocc].T - dm_new))
 
     e, cocc = eigh_occ(H)
     dm = cocc @ cocc.T
     if sync:
         sync.broadcast([dm, cocc])
     diis = CDIIS(device=dev)
-    _log_header(log)
-    E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
-    res = {"converged": False}
-    per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
-    want_k = c_hf != 0.0
+    led = _CycleLedger(inp, functional, conv_e, conv_dm, log)
+    c_hf, want_k, prof = led.c_hf, led.want_k, led.prof
     scal = t.zeros(4, dtype=f64, device=dev)
-    import os
-    prof = [] if os.environ.get("QCDFT_SCF_PROFILE") else None      # per-part times of the host-side-of-the-cycle (adds syncs)
-    for cycle in range(max_cycle):
-        t_it = time.time()
+    for _ in range(max_cycle):
+        t_it = led.start()
         backend.d_dm.copy_(dm); backend.d_cocc.copy_(cocc)                             # device to device
         E_xc, t_xc = backend._device_parts(want_k)
         t.cuda.synchronize()
-        xc_times.append(t_xc); jk_times.append(time.time() - t_it - t_xc)
+        led.xc_times.append(t_xc); led.jk_times.append(time.time() - t_it - t_xc)
         J, K, V = backend.d_J, backend.d_K, backend.d_v
-        if root or sync is None:
+        if root:
             tp = [time.time()]
             mark = (lambda: (t.cuda.synchronize(), tp.append(time.time()))) if prof is not None else (lambda: None)
             F = H + J + 0.5 * (V + V.T)                                                # dft.py:212,223
@@ -984,73 +1037,48 @@ def _run_scf_device(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
             dm_new, cocc_new = t.empty_like(dm), t.empty_like(cocc)
         if sync:
             sync.broadcast([dm_new, cocc_new, scal])
-        E_one, E_coul, E_ex, ddm = scal.tolist()                                       # the cycle's only download
-        last_ddm[0] = ddm
-        E_tot = E_one + E_coul + E_xc + E_ex + inp.E_nuc
-        dE = E_tot - E_old
-        it_times.append(time.time() - t_it)
-        if log:
-            log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
-        res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1)
-        per_cycle.append((E_tot, ddm))
-        if abs(dE) < conv_e and ddm < conv_dm:
-            ok = t.ones(1, dtype=f64, device=dev)
-            if rot[0]:                                                                 # as in _run_scf
-                if root or sync is None:
-                    e_x, C_x = eigh_full(F)
-                    ok[0] = float(float(t.linalg.norm(2.0 * C_x[:, :nocc] @ C_x[:, :nocc].T - dm_new)) < 1e-4)
-                    if float(ok[0]):
-                        e = e_x
-                if sync:
-                    sync.broadcast([ok])
-            if float(ok[0]):
-                res["converged"] = True
+        E_one, E_coul, E_ex, last_ddm = scal.tolist()                                  # the cycle's only download
+        if led.cycle(E_one, E_coul, E_xc, E_ex, last_ddm):
+            ok, e_x = _aufbau_check(checked, root, t.ones(1, dtype=f64, device=dev), sync and sync.broadcast, log) if rotate else (True, None)
+            e = e if e_x is None else e_x
+            if ok:
+                led.res["converged"] = True
                 dm = dm_new
                 break
-            rot[0] = False
+            rotate = False
             diis = CDIIS(device=dev)
-            if log:
-                log("     converged occupied space is not the aufbau one: continuing with eigh(F, S) every cycle")
-        dm, cocc, E_old = dm_new, cocc_new, E_tot
-    res["dm"] = dm.cpu().numpy()
-    res["mo_energy"] = e.cpu().numpy()
-    if prof:
-        med = np.median(np.array(prof[1:] if len(prof) > 1 else prof), axis=0)
-        res["device_parts_ms"] = dict(zip(("fock", "diis", "eigen", "density_energies"), (float(x) for x in med)))
-        if log:
-            log("device-resident parts (median ms per cycle): " + ", ".join(f"{k} {v:.3f}" for k, v in res["device_parts_ms"].items()))
-    return _finish(res, t_start, xc_times, jk_times, it_times)
+        dm, cocc = dm_new, cocc_new
+    led.res["dm"] = dm.cpu().numpy()
+    led.res["mo_energy"] = _host(e)
+    return led.finish("device_parts_ms", ("fock", "diis", "eigen", "density_energies"), "device-resident parts")
 
 
 def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     """The loop with its host part on the device (scf_tail.ScfTail): per cycle the J / K and XC kernels, then the tail's
     launches for dft.py:212-236, then ONE wait on host-mapped memory for the energy / convergence scalars.  The few full
-    diagonalisations of a run (first cycle, refused rotations, the final aufbau check) are LAPACK calls on the host below
-    400 functions and hipSOLVER above, as in the other two loops.  With several ranks the cycle's device work is the sharded
+    diagonalisations of a run (first cycle, refused rotations, the final aufbau check) go through the backend's
+    FockDiagonaliser, as in the other two loops.  With several ranks the cycle's device work is the sharded
     one (grid_shard.ShardedFock: local sweep + local J/K + one all-reduce), rank 0 alone runs the tail, and
     [dm | cocc | scalars] reach the other ranks in one broadcast."""
     t = backend.torch
     tail, rot_stats = backend.tail, backend.occ_solver.stats
     root, sync, world = backend.rank == 0, backend.replica_sync, backend.world
-    c_hf = functionals.resolve(functional).c_hf
-    want_k = c_hf != 0.0
-    nocc, Xh = inp.nocc, backend.eigh.Xh
+    nocc = inp.nocc
     sqrt2 = float(np.sqrt(2.0))
-    on_dev = inp.S.shape[0] >= 400          # hipSOLVER from 400 functions, one LAPACK thread below (FockDiagonaliser)
-    Xd = t.as_tensor(Xh, dtype=t.float64, device=backend.dev) if (on_dev and root) else None
 
     def full_solve(F_dev):                                                             # dft.py:181,227: (energies, eigenvectors on the device)
-        if on_dev:
-            e_, Cp = t.linalg.eigh(Xd.T @ F_dev @ Xd)
-            return e_.cpu().numpy(), Xd @ Cp
-        e_, Cp = eigh(Xh.T @ F_dev.cpu().numpy() @ Xh, driver="evd")
-        return e_, t.from_numpy(np.ascontiguousarray(Xh @ Cp)).to(backend.dev)
+        e_, U = backend.eigh.solve_device(F_dev, products="host")                      # where LAPACK solves, this loop forms X^T F X and X C' on the host
+        return _host(e_), U
 
     def diagonalise_into_basis(F_dev):
         e_, U = full_solve(F_dev)
         tail.basis.copy_(U)
         rot_stats["exact"] += 1
         return e_
+
+    def checked():
+        e_x, C_x = full_solve(tail.fock)
+        return e_x, float(t.linalg.norm(2.0 * C_x[:, :nocc] @ C_x[:, :nocc].T - backend.d_dm))
 
     e = None
     if root:
@@ -1060,10 +1088,8 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     scal = t.zeros(8, dtype=t.float64, device=backend.dev)                           # what travels with [dm | cocc] when there are replicas
     if sync:
         sync.broadcast([backend._up])                                                  # [dm | cocc] is one flat buffer (HipBackend)
-    _log_header(log)
-    E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
-    res = {"converged": False}
-    per_cycle = res["per_cycle"] = []                                                  # (E_tot, |dm' - dm|) of every cycle
+    led = _CycleLedger(inp, functional, conv_e, conv_dm, log)
+    res, c_hf, want_k, xc_times, jk_times = led.res, led.c_hf, led.want_k, led.xc_times, led.jk_times
     rotate, last_ddm = True, None
     d_K = backend.d_K if want_k else None
     marks, tail_log = [], []      # (start, J/K done, XC done) events; (status, fixed-point steps, Jacobi sweeps, continued, queued ahead)
@@ -1101,7 +1127,7 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
 
     queued, last_status = -1, None
     for cycle in range(max_cycle):
-        t_it = time.time()
+        t_it = led.start()
         if world == 1:
             if queued < cycle:
                 enqueue_parts(cycle); queued = cycle
@@ -1113,7 +1139,7 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
             E_xc, t_xc = backend._device_parts(want_k)                                 # sharded: ends in the all-reduce of [Vxc | J | K | Exc]
             xc_times.append(t_xc); jk_times.append(time.time() - t_it - t_xc)
         if root:
-            tol = 1e-10 if last_ddm is None else min(max(1e-10, 1e-3 * last_ddm), 1e-5)    # as OccupiedRotation.occupied(accuracy)
+            tol = _rotation_tol(last_ddm)
             tail.step(rotate, c_hf, tol, d_J, d_K, d_V, backend.d_dm, backend.d_cocc, d_exc=d_excs[cycle % 2] if world == 1 else None)
             if ahead and last_status == 0 and rotate:                                  # the last rotation went through: expect this one to
                 enqueue_parts(cycle + 1); queued = cycle + 1
@@ -1142,32 +1168,16 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
             sync.broadcast([backend._up, scal])
             E_one, E_coul, E_ex, ddm = scal[:4].tolist()
         last_ddm = ddm
-        E_tot = E_one + E_coul + E_xc + E_ex + inp.E_nuc
-        dE = E_tot - E_old
-        it_times.append(time.time() - t_it)
-        if log:
-            log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
-        res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1)
-        per_cycle.append((E_tot, ddm))
-        if abs(dE) < conv_e and ddm < conv_dm:                                         # the same scalars on every rank
-            ok = t.ones(1, dtype=t.float64, device=backend.dev)
-            if rotate:                                                                 # as in _run_scf: the followed space against eigh(F, S)
-                if root:
-                    e_x, C_x = full_solve(tail.fock)
-                    ok[0] = float(float(t.linalg.norm(2.0 * C_x[:, :nocc] @ C_x[:, :nocc].T - backend.d_dm)) < 1e-4)
-                    if float(ok[0]):
-                        e = e_x
-                if sync:
-                    sync.broadcast([ok])
-            if float(ok[0]):
+        if led.cycle(E_one, E_coul, E_xc, E_ex, ddm):
+            flag = t.ones(1, dtype=t.float64, device=backend.dev)
+            ok, e_x = _aufbau_check(checked, root, flag, sync and sync.broadcast, log) if rotate else (True, None)
+            e = e if e_x is None else e_x
+            if ok:
                 res["converged"] = True
                 break
             rotate = False
             if root:
                 tail.reset()
-            if log:
-                log("     converged occupied space is not the aufbau one: continuing with eigh(F, S) every cycle")
-        E_old = E_tot
     backend.d_J, backend.d_K, backend.d_v = sets[0]
     res["dm"] = backend.d_dm.cpu().numpy()                                             # (waits for anything still queued ahead)
     res["mo_energy"] = None if e is None else np.asarray(e)
@@ -1175,7 +1185,7 @@ def _run_scf_fused(inp, backend, functional, max_cycle, conv_e, conv_dm, log):
     res["tail_log"] = tail_log
     for ev in marks:                                                                   # device-side durations: nothing waited in between
         jk_times.append(1e-3 * ev[0].elapsed_time(ev[1])); xc_times.append(1e-3 * ev[1].elapsed_time(ev[2]))
-    return _finish(res, t_start, xc_times, jk_times, it_times)
+    return led.finish()
 
 
 def _blockdiag(a, b):
@@ -1208,30 +1218,23 @@ def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, 
     run_scf's host loop term by term.  Returns run_scf's fields with dm the total density, and dm_a, dm_b, mo_energy_a,
     mo_energy_b, mo_coeff_a, mo_coeff_b, s_squared (spin_square), nalpha, nbeta, uks = True."""
     from .hostinfo import blas_threads
-    c_hf = functionals.resolve(functional).c_hf
-    want_k = c_hf != 0.0
     Hcore, S = inp.Hcore, inp.S
     na = int(getattr(inp, "nalpha", None) if getattr(inp, "nalpha", None) is not None else inp.nocc)
     nb = int(getattr(inp, "nbeta", None) if getattr(inp, "nbeta", None) is not None else inp.nocc)
     if na < nb or nb < 0 or na <= 0 or na > S.shape[0]:
         raise ValueError(f"run_uks: nalpha = {na}, nbeta = {nb} do not fit {S.shape[0]} basis functions (nalpha >= nbeta >= 0)")
     S2 = _blockdiag(S, S)
-    with blas_threads(1 if S.shape[0] < 400 else None):
-        e0, C0 = eigh(Hcore, S)
-        ea = eb = e0
-        Ca = Cb = C0
+    with blas_threads(1 if S.shape[0] < _HIPSOLVER_FROM else None):
+        C0 = eigh(Hcore, S)[1]
         cocc = [np.ascontiguousarray(C0[:, :na]), np.ascontiguousarray(C0[:, :nb])]
         dm = [c @ c.T for c in cocc]
         diis = CDIIS()
-        _log_header(log)
-        E_old, xc_times, jk_times, it_times, t_start = 0.0, [], [], [], time.time()
-        res = {"converged": False, "uks": True, "nalpha": na, "nbeta": nb}
-        per_cycle = res["per_cycle"] = []
-        for cycle in range(max_cycle):
-            t_it = time.time()
+        led = _CycleLedger(inp, functional, conv_e, conv_dm, log, uks=True, nalpha=na, nbeta=nb)
+        c_hf, want_k = led.c_hf, led.want_k
+        for _ in range(max_cycle):
+            t_it = led.start()
             J, Ka, Kb, E_xc, Va, Vb = backend.uks_parts(dm[0], dm[1], cocc[0], cocc[1], want_k)
-            t_parts = time.time() - t_it
-            xc_times.append(t_parts); jk_times.append(0.0)        # one bracket: the parts are not timed apart here
+            led.xc_times.append(time.time() - t_it); led.jk_times.append(0.0)        # one bracket: the parts are not timed apart here
             F = [Hcore + J + 0.5 * (V + V.T) - (c_hf * K if K is not None else 0.0) for V, K in ((Va, Ka), (Vb, Kb))]
             Fx = diis.update(S2, _blockdiag(dm[0], dm[1]), _blockdiag(F[0], F[1]))
             n = S.shape[0]
@@ -1243,17 +1246,10 @@ def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, 
             E_one, E_coul = float(np.sum(D * Hcore)), 0.5 * float(np.sum(D * J))
             E_ex = -0.5 * c_hf * float(np.sum(dm_new[0] * Ka) + np.sum(dm_new[1] * Kb)) if want_k else 0.0
             ddm = float(np.linalg.norm(dm_new[0] - dm[0]) + np.linalg.norm(dm_new[1] - dm[1]))
-            E_tot = E_one + E_coul + E_xc + E_ex + inp.E_nuc
-            dE = E_tot - E_old
-            it_times.append(time.time() - t_it)
-            if log:
-                log(f"{cycle + 1:4d} {E_tot:18.8f} {dE:15.6e} {ddm:15.6e} {E_ex:12.6f}")
-            res.update(E_tot=E_tot, E_one=E_one, E_coul=E_coul, E_xc=E_xc, E_ex_hf=E_ex, cycles=cycle + 1, dm=D,
-                       dm_a=dm_new[0], dm_b=dm_new[1], mo_energy_a=ea, mo_energy_b=eb, mo_coeff_a=Ca, mo_coeff_b=Cb,
-                       mo_energy=ea, s_squared=spin_square(S, cocc_new[0], cocc_new[1]))
-            per_cycle.append((E_tot, ddm))
-            dm, cocc, E_old = dm_new, cocc_new, E_tot
-            if abs(dE) < conv_e and ddm < conv_dm:
-                res["converged"] = True
+            done = led.cycle(E_one, E_coul, E_xc, E_ex, ddm, dm=D, dm_a=dm_new[0], dm_b=dm_new[1], mo_energy_a=ea, mo_energy_b=eb,
+                             mo_coeff_a=Ca, mo_coeff_b=Cb, mo_energy=ea, s_squared=spin_square(S, cocc_new[0], cocc_new[1]))
+            dm, cocc = dm_new, cocc_new
+            if done:
+                led.res["converged"] = True
                 break
-        return _finish(res, t_start, xc_times, jk_times, it_times)
+        return led.finish()

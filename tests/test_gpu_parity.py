@@ -371,6 +371,25 @@ def test_device_resident_scf_matches_the_host_loop(dev, fn, eri_mode):
     assert np.abs(r_d["dm"] - r_h["dm"]).max() < 1e-7
 
 
+def test_the_three_closed_shell_loops_return_the_same_fields(dev):
+    """What scf._CycleLedger books for the host, the device-resident and the fused loop, from one `inp` (H2O/STO-3G, GGA,
+    dense ERI, the rotation solver forced on): the fields a caller reads and their shapes.  No numerical bound here: the
+    energy agreement between the loops is test_device_resident_scf_matches_the_host_loop's and test_gpu_scf_tail's."""
+    from quantum_compute_dft_amd import inputs, scf
+    inp = inputs.build("H2O", "sto-3g", 3, verbose=False)
+    res = {name: scf.run_scf(inp, scf.HipBackend(inp, "GGA", eigensolver="rotate", **kw), "GGA", log=None)
+           for name, kw in (("host", dict(device_resident=False, fused_tail=False)),
+                            ("device", dict(device_resident=True, fused_tail=False)), ("fused", dict(fused_tail=True)))}
+    for name, r in res.items():
+        assert r["converged"] is True and len(r["per_cycle"]) == r["cycles"] > 1, name
+        assert isinstance(r["dm"], np.ndarray) and r["dm"].shape == (7, 7), name
+        assert isinstance(r["mo_energy"], np.ndarray) and r["mo_energy"].shape == (7,), name
+        assert len(r["cycle_ms"]) == r["cycles"], name
+        assert all(np.isfinite(r[k]) for k in ("xc_ms", "jk_ms", "iter_ms")), name
+        assert ("loop" in r, "tail_log" in r) == ((True, True) if name == "fused" else (False, False)), name
+    assert res["fused"]["loop"] == "fused" and len(res["fused"]["tail_log"]) == res["fused"]["cycles"]
+
+
 def test_host_loop_with_the_rotation_solver_on_benzene(dev):
     """Benzene PBE/def2-SVP (nao 114: "auto" selects the occupied-subspace rotation, host form): same energy, density
     and cycle count (within one) as eigh(F, S) every cycle, and most cycles are rotations."""

@@ -83,6 +83,76 @@ def test_occupied_rotation_falls_back_when_the_fock_matrix_jumps():
     assert sol.stats["exact"] == 2 and sol.stats["rotated"] == 1   # first call and the jump: full solver
 
 
+def test_rotation_tolerance_rule_and_where_the_fixed_point_stops():
+    """scf._rotation_tol, the one rule for how accurately a cycle's rotation is solved, and that
+    OccupiedRotation.occupied(F, accuracy) stops its fixed point exactly there."""
+    assert scf._rotation_tol(None) == scf._rotation_tol(None, 1e-10) == 1e-10        # no previous cycle: the floor
+    assert scf._rotation_tol(None, 1e-8) == 1e-8
+    assert scf._rotation_tol(1e-9, 1e-10) == 1e-10 and scf._rotation_tol(1e-6, 1e-8) == 1e-8   # clamped below
+    assert scf._rotation_tol(2e-4, 1e-10) == 1e-3 * 2e-4                              # between the clamps
+    assert scf._rotation_tol(1e-2, 1e-10) == 1e-5 and scf._rotation_tol(7.0, 1e-10) == 1e-5    # clamped above
+    # the Fock matrices of an SCF run on water, as the loop hands them to the solver
+    inp = inputs.build("H2O", "def2-svp", 1, verbose=False)
+    seq = []
+
+    class Recording(scf.OccupiedRotation):
+        def occupied(self, F, accuracy=None):
+            seq.append(np.array(F))
+            return super().occupied(F, accuracy)
+
+    be = OracleBackend(inp, "B3LYP")
+    be.occ_solver = Recording(inp.S, inp.nocc)
+    assert scf.run_scf(inp, be, "B3LYP", log=None)["converged"] and len(seq) > 8
+
+    def steps(F0, F1, accuracy, tol=1e-10):     # fixed-point steps for F1 from the exact basis of F0; None if it was not a rotation
+        sol = scf.OccupiedRotation(inp.S, inp.nocc, tol=tol)
+        sol.occupied(F0)
+        e, C = sol.occupied(F1, accuracy)
+        return (sol.stats["inner_steps"] if sol.stats["rotated"] == 1 else None), C
+
+    loose = tight = 0
+    for F0, F1 in zip(seq[2:], seq[3:]):
+        (a, Ca), (b, _) = steps(F0, F1, 1e-2), steps(F0, F1, None)
+        if b is None:
+            continue
+        assert a is not None and a <= b                       # from the same state the looser call takes no more steps
+        c, Cc = steps(F0, F1, None, tol=scf._rotation_tol(1e-2))
+        assert c == a and np.array_equal(Cc, Ca)              # ... and stops where a solver with that tolerance does
+        loose, tight = loose + a, tight + b
+    assert 0 < loose < tight
+
+
+def test_aufbau_check_decides_on_rank_0_and_every_rank_hears_it():
+    """scf._aufbau_check, the rule the three closed-shell loops run on their converged state, with numpy values (the
+    host loop) and torch tensors (the two device loops): the bound on |2 C_o C_o^T - dm|_F, the flag that travels, the
+    spectrum that is adopted only on success, the message on a mismatch."""
+    import torch
+    kinds = {"numpy": (np.array, lambda: np.ones(1), np.linalg.norm),
+             "torch": (lambda v: torch.tensor(v, dtype=torch.float64), lambda: torch.ones(1, dtype=torch.float64), torch.linalg.norm)}
+    for kind, (mk, new_flag, norm) in kinds.items():
+        spectrum = mk([-20.0, -1.0, 0.5])
+        for gap, want in ((0.99e-4, True), (1.01e-4, False)):                      # either side of the bound
+            solve = lambda: (spectrum, float(norm(mk([0.6 * gap, 0.8 * gap]))))
+            for with_broadcast in (False, True):
+                sent, lines, flag = [], [], new_flag()
+                got, e = scf._aufbau_check(solve, True, flag, (lambda bufs: sent.append([float(b[0]) for b in bufs])) if with_broadcast else None,
+                                           lines.append)
+                assert got is want and (e is spectrum if want else e is None), (kind, gap)
+                assert sent == ([[float(want)]] if with_broadcast else []) and type(flag) is type(new_flag())
+                assert len(lines) == (0 if want else 1) and all("not the aufbau one" in l for l in lines)
+            # a replica: it does not solve, it takes what rank 0 sent
+            for answer in (1.0, 0.0):
+                lines, flag = [], new_flag()
+
+                def receive(bufs):
+                    bufs[0][0] = answer
+
+                got, e = scf._aufbau_check(lambda: pytest.fail("a replica must not solve"), False, flag, receive, lines.append)
+                assert got is bool(answer) and e is None and len(lines) == (0 if answer else 1), (kind, answer)
+        # no log, no message; the decision is the same
+        assert scf._aufbau_check(lambda: (spectrum, 1.0), True, new_flag(), None, None) == (False, None)
+
+
 def _drift_worker(rank, world, port, out_dir):
     """Two replicas of the host SCF loop under gloo; rank 1's LOCAL view of the device results is off by
     an ulp-scale perturbation every cycle (what different BLAS thread counts or different GPUs behind the
