@@ -452,6 +452,29 @@ int DFT_PointCoulombSetStream(void *handle, unsigned long long hip_stream);
 const char *DFT_PointCoulombLastError(void *handle);
 void DFT_PointCoulombClose(void *handle);
 
+/* The two-electron term of the nuclear gradient, contracted on the device as the derivative integrals are made
+ * (csrc/grad2e.hip; device counterpart of the host engine's qc_grad2e / grad_quartet, s-f shells, the dense ERI never
+ * built).  Shell table as for DFT_EvalAO (host arrays, copied once).  Open returns NULL without a device, for a shell
+ * with l > 3 or a shell table that does not fit nao / nprim_total.
+ *   d_dm   (nao, nao) f64 on the device, symmetric (only then is the result the derivative below).
+ *   d_out  (nshell, 3) f64 on the device, overwritten:
+ *            out[A][x] = d/dR_A,x of  1/2 sum_abcd D_ab D_cd (ab|cd) - c_hf/4 sum_abcd D_ac D_bd (ab|cd),
+ *          the derivative acting on the functions of shell A in the FIRST index only, times the 4 equivalent positions
+ *          -- element-wise: sum over shells B and ket pairs C >= D of
+ *            sum_{a in A, b in B, c in C, d in D} [2 f D_ab D_cd - c_hf (D_ac D_bd + (C != D) D_ad D_bc)] d(ab|cd)/dA_x,
+ *          f = 1 for C == D and 2 otherwise.  The rows of an atom's shells add up to the atom's gradient term.
+ * Every primitive pair with |c_a c_b| exp(-mu R^2) < 1e-18 is dropped, as on the host; nothing else is screened.  Partial
+ * sums are added in a fixed order, no floating-point atomics: the same call twice gives the same bits.  Asynchronous on
+ * the handle's stream (default: the null stream).  DFT_Grad2e and SetStream return 0, or -1 for a null handle or
+ * pointer, a refused LDS request or a failed launch (DFT_Grad2eLastError); nothing aborts.  Added without a change of
+ * DFT_GetVersion (it stays 5): look the symbols up. */
+void *DFT_Grad2eOpen(int nshell, const double *shl_xyz, const int *shl_l, const int *shl_nprim, const int *shl_off,
+                     const int *shl_ao, const double *prim_exp, const double *prim_coef, int nao, int nprim_total);
+int DFT_Grad2e(void *handle, unsigned long long d_dm, double c_hf, unsigned long long d_out);
+int DFT_Grad2eSetStream(void *handle, unsigned long long hip_stream);
+const char *DFT_Grad2eLastError(void *handle);
+void DFT_Grad2eClose(void *handle);
+
 /* The rest of an SCF cycle on the device: between the cycle's J / K / Vxc and the next density the
  * reference's loop runs on the host -- Fock assembly (dft.py:212-223), Pulay DIIS (dft.py:225), eigh(F, S) (dft.py:227),
  * dm = 2 C_occ C_occ^T (dft.py:228) and the energy traces (dft.py:231-234).  DFT_ScfTailStep queues all of it behind

@@ -1,5 +1,6 @@
 // McMurchie-Davidson building blocks on the device, shared by the translation units that evaluate Coulomb-type Gaussian
-// integrals (eri_cols.hip: two-electron columns; point_coulomb.hip: one-electron integrals at a point): the Boys
+// integrals (eri_cols.hip: two-electron columns; point_coulomb.hip: one-electron integrals at a point; grad2e.hip: the
+// two-electron derivative quartets): the Boys
 // function, the Hermite expansion coefficients of one Cartesian direction, the Cartesian component tables and the
 // rotation to real solid harmonics.  Device counterparts of integrals.c::boys / hermite_E / cart_components /
 // sph_matrix, term for term.  Everything has internal linkage: every unit that includes this header owns its copy of
@@ -79,6 +80,25 @@ __device__ void hermite_E(int la, int lb, double a, double b, double XAB, double
     for (int i = 0; i < EC_ED; ++i) E[i] = 0.0;
     auto at = [&](int i, int j, int t) -> double & { return E[(i * 4 + j) * 7 + t]; };
     auto get = [&](int i, int j, int t) -> double { return (t < 0 || t > i + j) ? 0.0 : E[(i * 4 + j) * 7 + t]; };
+    at(0, 0, 0) = exp(-mu * XAB * XAB);
+    for (int i = 0; i <= la; ++i) {
+        if (i > 0)
+            for (int t = 0; t <= i; ++t) at(i, 0, t) = XPA * get(i - 1, 0, t) + get(i - 1, 0, t - 1) / (2 * p) + (t + 1) * get(i - 1, 0, t + 1);
+        for (int j = 1; j <= lb; ++j)
+            for (int t = 0; t <= i + j; ++t) at(i, j, t) = XPB * get(i, j - 1, t) + get(i, j - 1, t - 1) / (2 * p) + (t + 1) * get(i, j - 1, t + 1);
+    }
+}
+
+// The same recurrence into a table dimensioned by the caller, E[NI][NJ][NT] (la < NI, lb < NJ, la + lb < NT): a shell
+// raised by a centre derivative needs i <= 4, t <= 7 (grad2e.hip).  Rows i <= la, j <= lb are written, zero at t > i + j;
+// the others are not touched.
+template <int NI, int NJ, int NT> __device__ void hermite_E_dim(int la, int lb, double a, double b, double XAB, double *E)
+{
+    const double p = a + b, mu = a * b / p, XPA = -b / p * XAB, XPB = a / p * XAB;
+    for (int i = 0; i <= la; ++i)
+        for (int k = 0; k < (lb + 1) * NT; ++k) E[i * NJ * NT + k] = 0.0;
+    auto at = [&](int i, int j, int t) -> double & { return E[(i * NJ + j) * NT + t]; };
+    auto get = [&](int i, int j, int t) -> double { return (t < 0 || t > i + j) ? 0.0 : E[(i * NJ + j) * NT + t]; };
     at(0, 0, 0) = exp(-mu * XAB * XAB);
     for (int i = 0; i <= la; ++i) {
         if (i > 0)

@@ -83,7 +83,8 @@ def print_gradient(symbols, g):
     print("  sum    " + " ".join(f"{x:+16.10f}" for x in g.sum(axis=0)) + f"   max|g| = {np.abs(g).max():.2e}  rms = {np.sqrt(np.mean(g * g)):.2e}")
 
 
-def main(argv=None):
+def build_parser():
+    """The driver's command line (main() adds the checks that span several options)."""
     p = argparse.ArgumentParser(description="Run DFT (LDA/GGA/B3LYP) using the MI355X HIP backend.")
     p.add_argument("functional", type=_functional,
                    help="Functional: LDA, GGA, B3LYP (the reference's three), another name of the table (" +
@@ -161,9 +162,17 @@ def main(argv=None):
                    help="Cartesian BFGS geometry optimisation on that gradient (step cap 0.3 bohr; max|g| < 3e-4, rms < 2e-4 Ha/bohr); "
                         "writes <molecule>_opt.xyz")
     p.add_argument("--opt-max-steps", type=int, default=50, metavar="N", help="with --optimize: at most N steps")
+    p.add_argument("--grad2e", default="host", choices=["host", "device"],
+                   help="with --gradient / --optimize: where the two-electron term of the gradient is computed; host (default): "
+                        "integrals.c::qc_grad2e on the CPU share; device: DFT_Grad2e (csrc/grad2e.hip), in every step of --optimize too")
     p.add_argument("--charge", type=int, default=0, metavar="Q", help="charge of the molecule (electrons = sum Z - Q); an odd count needs --spin")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
     args = p.parse_args(argv)
     if bool(args.esp_points) != bool(args.esp_out or args.field_out):
         p.error("--esp-points goes with --esp-out and / or --field-out")
@@ -363,7 +372,7 @@ def main(argv=None):
     grad = grad_terms = opt = None
     if (args.gradient or args.optimize) and res["converged"]:
         from . import gradients, optimize
-        grad, grad_terms = gradients.nuclear_gradient(inp, res, backend, args.functional)
+        grad, grad_terms = gradients.nuclear_gradient(inp, res, backend, args.functional, two_electron=args.grad2e)
         print_gradient(inp.symbols, grad)
     if args.optimize and res["converged"]:
         def energy_and_gradient(xyz):
@@ -374,7 +383,9 @@ def main(argv=None):
             res_k = scf.run_scf(inp_k, be_k, args.functional, log=None)
             if not res_k["converged"]:
                 raise RuntimeError("--optimize: the SCF did not converge at a geometry of the optimisation")
-            return res_k["E_tot"], gradients.nuclear_gradient(inp_k, res_k, be_k, args.functional)[0]
+            g_k = gradients.nuclear_gradient(inp_k, res_k, be_k, args.functional, two_electron=args.grad2e)[0]
+            be_k.close()
+            return res_k["E_tot"], g_k
         opt = optimize.bfgs(energy_and_gradient, inp.atom_xyz, max_steps=args.opt_max_steps, log=print)
         opt_path = os.path.splitext(os.path.basename(atom_file))[0] + "_opt.xyz"
         optimize.write_xyz(opt_path, inp.symbols, opt["xyz"], f"{args.functional}/{args.basis} E = {opt['energy']:.10f} Ha after {opt['steps']} steps")
@@ -416,6 +427,7 @@ def main(argv=None):
         record["gradient"] = grad.tolist() if grad is not None else None
         record["gradient_terms"] = {k: v.tolist() for k, v in grad_terms.items()} if grad_terms is not None else None
         record["net_force"] = grad.sum(axis=0).tolist() if grad is not None else None
+        record["grad2e_engine"] = args.grad2e
     if args.optimize:
         record["opt_steps"] = int(opt["steps"]) if opt is not None else None
         record["opt_energies"] = opt["energies"] if opt is not None else None

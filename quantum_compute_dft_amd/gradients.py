@@ -200,7 +200,7 @@ def _fock(inp, backend, f, dm):
 _QUIRKY = ("vwn5_c", "pbe_c")
 
 
-def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None):
+def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two_electron="host"):
     """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged closed-shell state `scf_result` (scf.run_scf) and its
     breakdown {"one_electron", "two_electron", "xc", "nuclear", "external"}, each (natm, 3).  The derivative at FIXED
     quadrature points and weights: the Becke-weight derivatives and the motion of the points with their atoms are not
@@ -210,7 +210,13 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None):
     two-electron part never builds the dense ERI, so runs on Cholesky vectors are served alike.  An embedded run
     (inp.point_charges) includes the basis term over the external charges and the nuclei--charge repulsion ("external");
     the forces on the charges themselves are properties.point_charge_forces'.  functional / quirks default to the
-    backend's."""
+    backend's.  `two_electron`: "host" (integrals.grad2e, the default) or "device" (backend.grad2e: the derivative quartets
+    made and contracted on the device, csrc/grad2e.hip); every other term is the same either way."""
+    if two_electron not in ("host", "device"):
+        raise ValueError(f"nuclear_gradient: two_electron must be 'host' or 'device', not {two_electron!r}")
+    if two_electron == "device" and not hasattr(backend, "grad2e"):
+        raise ValueError("nuclear_gradient: two_electron='device' needs a backend with a device two-electron gradient "
+                         "(scf.HipBackend); this backend has none")
     if scf_result.get("uks"):
         raise ValueError("nuclear_gradient: an unrestricted (UKS) result has no analytic gradient here: the assembly is closed-shell")
     if getattr(inp, "efield", None) is not None:
@@ -235,7 +241,7 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None):
     g1 = integrals.grad1e(sh, xyz, z, dm, W)
     field = integrals.point_coulomb_field(sh, xyz, dm)         # sum D d<1/|r - R_A|>/dR_A: the operator part of V
     terms = {"one_electron": g1[0] + g1[1] + g1[2] - z[:, None] * field,
-             "two_electron": integrals.grad2e(sh, dm, f.c_hf),
+             "two_electron": backend.grad2e(dm, f.c_hf) if two_electron == "device" else integrals.grad2e(sh, dm, f.c_hf),
              "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
     if any(w != 0.0 for w in wv):
         if hasattr(backend, "xc_gradient"):

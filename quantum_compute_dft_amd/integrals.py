@@ -161,12 +161,17 @@ def grad1e(shells, centres, charges, dm, w):
     return out
 
 
-def grad2e(shells, dm, c_hf=0.0):
+def grad2e(shells, dm, c_hf=0.0, per_shell=False):
     """(natm, 3): d/dR_A of 1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum D_ac D_bd (ab|cd) for a symmetric dm (qc_grad2e): every
-    derivative quartet contracted as it is made, the dense ERI never built, threads as set_threads says."""
+    derivative quartet contracted as it is made, the dense ERI never built, threads as set_threads says.
+    `per_shell`: (nshell, 3) instead, the term of every shell's own centre (the same routine with every shell its own
+    "atom"); the rows of an atom's shells add up to the atom's row."""
     keep, p = _args(shells)
     dm = _sym(dm, "dm")
-    owner = np.ascontiguousarray(shells.atom, dtype=np.int32)
+    if per_shell:
+        owner = np.arange(shells.nshell, dtype=np.int32)
+    else:
+        owner = np.ascontiguousarray(shells.atom, dtype=np.int32)
     natm = int(owner.max()) + 1
     out = np.zeros((natm, 3))
     dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
@@ -292,6 +297,77 @@ class DeviceEriColumns:
         if self.lib.DFT_EriColumnsMany(self._h, len(pairs), Cs, Ds, float(screen), ctypes.c_uint64(out.data_ptr()), of) != 0:
             raise RuntimeError("libdft: " + (self.lib.DFT_EriColumnsLastError(self._h) or b"").decode())
         return out.view(-1)[:tot * n2].view(tot, self.nao, self.nao)
+
+
+class DeviceGrad2e:
+    """grad2e ON THE DEVICE (libdft.so: csrc/grad2e.hip, DFT_Grad2e): the derivative quartets are made and contracted with
+    the density there; (nshell, 3) doubles come back.  `per_shell(d_dm, c_hf)` works on torch tensors and is asynchronous
+    on the null stream (or the one given to set_stream); `grad(dm, c_hf)` is the drop-in for grad2e()."""
+
+    def __init__(self, shells, lib_path=None):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeviceGrad2e: no GPU device is available (the two-electron gradient kernel runs on the device only; "
+                               "integrals.grad2e is the host engine)")
+        from .build import library_path
+        from .solver import load_library
+        self.lib = load_library(lib_path or library_path())
+        L = self.lib
+        dp, ip, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.c_uint64
+        L.DFT_Grad2eOpen.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ctypes.c_int]
+        L.DFT_Grad2eOpen.restype = ctypes.c_void_p
+        L.DFT_Grad2e.argtypes = [ctypes.c_void_p, u64, ctypes.c_double, u64]
+        L.DFT_Grad2e.restype = ctypes.c_int
+        L.DFT_Grad2eSetStream.argtypes = [ctypes.c_void_p, u64]
+        L.DFT_Grad2eSetStream.restype = ctypes.c_int
+        L.DFT_Grad2eLastError.argtypes = [ctypes.c_void_p]
+        L.DFT_Grad2eLastError.restype = ctypes.c_char_p
+        L.DFT_Grad2eClose.argtypes = [ctypes.c_void_p]
+        L.DFT_Grad2eClose.restype = None
+        keep, p = _args(shells)
+        self.shells, self.nao, self.nshell = shells, shells.nao, shells.nshell
+        self._h = L.DFT_Grad2eOpen(shells.nshell, *p, shells.nao, len(shells.exp))
+        if not self._h:
+            raise RuntimeError("DFT_Grad2eOpen failed (no GPU device, or angular momentum above f)")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.DFT_Grad2eClose(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_stream(self, stream):
+        """`stream`: a torch.cuda.Stream, or None for the null stream."""
+        self.lib.DFT_Grad2eSetStream(self._h, ctypes.c_uint64(stream.cuda_stream if stream is not None else 0))
+
+    def per_shell(self, d_dm, c_hf=0.0, out=None):
+        """(nshell, 3) torch tensor: the term of every shell's centre, for the symmetric (nao, nao) device tensor `d_dm`
+        (its symmetry is the caller's business here: nothing crosses to the host).  Asynchronous."""
+        import torch
+        PointCoulomb._check(d_dm, (self.nao, self.nao), "dm")
+        if out is None:
+            out = torch.empty((self.nshell, 3), dtype=torch.float64, device=d_dm.device)
+        PointCoulomb._check(out, (self.nshell, 3), "out")
+        if self.lib.DFT_Grad2e(self._h, ctypes.c_uint64(d_dm.data_ptr()), float(c_hf), ctypes.c_uint64(out.data_ptr())) != 0:
+            raise RuntimeError("libdft: " + (self.lib.DFT_Grad2eLastError(self._h) or b"").decode())
+        return out
+
+    def grad(self, dm, c_hf=0.0):
+        """numpy (natm, 3), what grad2e(shells, dm, c_hf) returns: `dm` a symmetric host array or device tensor; the shells'
+        rows are added per atom on the host, in shell order."""
+        import torch
+        if torch.is_tensor(dm):
+            d_dm = dm.to(dtype=torch.float64).contiguous()
+            _sym(d_dm.cpu().numpy(), "dm")
+        else:
+            d_dm = torch.as_tensor(_sym(dm, "dm"), device="cuda")
+        rows = self.per_shell(d_dm, c_hf).cpu().numpy()
+        owner = np.asarray(self.shells.atom, dtype=np.int64)
+        out = np.zeros((int(owner.max()) + 1, 3))
+        for s in range(self.nshell):
+            out[owner[s]] += rows[s]
+        return out
 
 
 

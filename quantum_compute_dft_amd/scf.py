@@ -374,6 +374,7 @@ class HipBackend:
         self.solver = DFTSolverWrapper(lib_path or library_path(), functional)   # any name or expression of functionals.resolve()
         self.solver.set_option("quirks", 1 if quirks else 0)
         self.quirks = bool(quirks)
+        self._lib_path, self._grad2e = lib_path, None       # the device two-electron gradient: opened by the first grad2e()
         t0 = time.time()
         self.rank, self.world = rank, world
         nao = inp.shells.nao
@@ -778,6 +779,26 @@ class HipBackend:
             d_G += d_out
         t.cuda.synchronize()
         return d_G.cpu().numpy()
+
+    # ---- two-electron part of the nuclear gradient on the device (integrals.DeviceGrad2e): one rank ----------------
+    def grad2e(self, dm, c_hf):
+        """(natm, 3) as a numpy array: what integrals.grad2e(shells, dm, c_hf) computes on the host, from DFT_Grad2e.  The
+        handle is opened by the first call and lives until close()."""
+        if self.world > 1:
+            raise ValueError("the device two-electron gradient runs on one rank: this backend is one of several")
+        if self._grad2e is None:
+            from .integrals import DeviceGrad2e
+            self._grad2e = DeviceGrad2e(self.shells, self._lib_path)
+        with self.torch.cuda.device(self.dev):
+            return self._grad2e.grad(dm, c_hf)
+
+    def close(self):
+        """Releases the handles this backend opened on demand (the buffers go with the object)."""
+        g, self._grad2e = getattr(self, "_grad2e", None), None
+        if g is not None:
+            g.close()
+
+    __del__ = close
 
     def excitation_parts(self, A, Bs, want_k, kind="singlet"):
         """(J, M or None, V1_raw), each (nvec, nao, nao) as numpy arrays, of the trials D_k = A B_k^T + B_k A^T with A
