@@ -399,6 +399,27 @@ int DFT_EvalAOHess(XCSolver *solver, long long ngrid, int nao, int nshell,
 int DFT_ComputeXCGradient(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr,
                           unsigned long long d_ao_ptr, unsigned long long d_weights_ptr, unsigned long long d_ao_grad_ptr,
                           unsigned long long d_ao_hess_ptr, unsigned long long d_out_ptr);
+/* The same for an open-shell state: d_out (nao, 3) receives G[mu, x] = d/dt of the Exc DFT_ComputeXCSpin(dm_a, dm_b)
+ * returns under DFT_ComputeXCGradient's column replacement, both matrices (symmetric) and the weights fixed.  With the
+ * per-spin coefficients c_s0..c_s3 of the spin-resolved pointwise kernel (closed-shell conventions)
+ *   G[mu, x] = -fac sum_s sum_g [ d_x phi_mu Z_s + (sum_k c_sk d_xk phi_mu) X_s ][g, mu],  X_s = AO D_s,  Z_s = Q_s D_s,
+ * Q_s = 2 c_s0 AO + sum_k c_sk ao_grad[k], fac = 1 (one-sided types) or 2 (B3LYP): the closed-shell formula once per spin.
+ * On the solver's stream, no host wait: the density kernels on dm_a and on dm_b and the spin-resolved pointwise kernel
+ * exactly as DFT_ComputeXCSpin runs them, into buffers of this entry, then "xc_grad_spin": k_xc_grad_spin stages the AO
+ * rows of a tile once beside the Q rows of both spins, forms X_a, X_b, Z_a, Z_b of a column tile together and reads each
+ * gradient and Hessian plane element once, for d_x phi (Z_a + Z_b) + sum_k d_xk phi (c_ak X_a + c_bk X_b), into one
+ * (nao, 3) slab per workgroup; a fixed-order slab sum finishes, so a call is bitwise reproducible.  Option
+ * "xcg_spin_fused" = 0 runs k_xc_grad once per spin into two slab sets and one sum over both instead (the same numbers to
+ * rounding; 1.6 x / 1.2 x the time at 143 556 x 114 / 60 000 x 494).  Three 16-row tiles: K chunks of at most 320 columns.
+ * Linear in the grid points: a caller may sum G over slices.  Never the one-kernel plan, never a recorded graph; prepared DFT_Fxc* tables (all slots)
+ * and later DFT_ComputeXC* results are left bit for bit.  d_ao_hess may be 0 for an LDA-class solver.
+ * Returns 0, or -1 with DFT_GetLastError: a null pointer, bad sizes, a null ao_hess on a gradient solver, and "quirks" = 1
+ * with vwn5_c or pbe_c in the functional (DFT_ComputeXCSpin's refusal: the potentials are derivatives of the energy).
+ * Added without a change of DFT_GetVersion (it stays 5): look the symbol up. */
+int DFT_ComputeXCGradientSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr,
+                              unsigned long long d_dm_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_weights_ptr,
+                              unsigned long long d_ao_grad_ptr, unsigned long long d_ao_hess_ptr,
+                              unsigned long long d_out_ptr);
 
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
@@ -471,6 +492,15 @@ void DFT_PointCoulombClose(void *handle);
 void *DFT_Grad2eOpen(int nshell, const double *shl_xyz, const int *shl_l, const int *shl_nprim, const int *shl_off,
                      const int *shl_ao, const double *prim_exp, const double *prim_coef, int nao, int nprim_total);
 int DFT_Grad2e(void *handle, unsigned long long d_dm, double c_hf, unsigned long long d_out);
+/* The same for an open-shell state, in one pass over the derivative integrals: d_dm the total density D = D_a + D_b,
+ * d_ms the spin density M = D_a - D_b (both (nao, nao) f64 on the device, symmetric), and
+ *   out[A][x] = d/dR_A,x of  1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum (D_ac D_bd + M_ac M_bd) (ab|cd)
+ * in DFT_Grad2e's element-wise conventions: the density quartet is
+ *   2 f D_ab D_cd - c_hf [D_ac D_bd + M_ac M_bd + (C != D)(D_ad D_bc + M_ad M_bc)].
+ * Only the gather of the density quartet differs from DFT_Grad2e; the handle's tables, streams and partial sums are
+ * shared, so the two entries may alternate on one handle and each stays bitwise reproducible.  Asynchronous on the
+ * handle's stream.  Returns 0, or -1 (DFT_Grad2eLastError) under DFT_Grad2e's conditions and for a null d_ms. */
+int DFT_Grad2eSpin(void *handle, unsigned long long d_dm, unsigned long long d_ms, double c_hf, unsigned long long d_out);
 int DFT_Grad2eSetStream(void *handle, unsigned long long hip_stream);
 const char *DFT_Grad2eLastError(void *handle);
 void DFT_Grad2eClose(void *handle);
@@ -562,7 +592,9 @@ void DFT_ScfTailClose(void *handle);
  * stores Exc there itself and a stream memory write (hipStreamWriteValue64) behind it raises a per-call sequence word
  * the host waits for -- same contract, no launch; taken only where a probe at DFT_CreateSolver found the runtime
  * performs the operation, else the kernel stays; -1 = auto, default: the kernel, which measured 1-2 us faster per call.
- * A recorded graph always ends with the kernel).  Returns 0 if the key is known. */
+ * A recorded graph always ends with the kernel), "xcg_spin_fused" (DFT_ComputeXCGradientSpin: 1, default = both spins in
+ * one kernel, k_xc_grad_spin; 0 = k_xc_grad once per spin, the plain form the tests hold it to).  Returns 0 if the key is
+ * known. */
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
 
 /* Read-back of "publish", "vxc_fringe", "fuse_finish", "strict_sync", "spin_wait", "graph", "tiny", "sweep_order", "path",

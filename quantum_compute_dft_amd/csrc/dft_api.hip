@@ -177,6 +177,12 @@ struct XCSolver {
     // any of them (Dsym alone is shared, in stream order)
     Planes xcg;
     DevBuf xcg_slabs;
+    // DFT_ComputeXCGradientSpin: the planes of the two spins, their padded matrices and two slab sets, its own again
+    Planes xcgs[2];
+    // 1 (default): k_xc_grad_spin, one kernel for both spins (0.64 x / 0.82 x of the two launches at 143 556 x 114 / 60 000 x 494,
+    // GGA: profiles/xc_gradient_spin_time.txt); 0: k_xc_grad once per spin into two slab sets, what the tests hold the kernel to
+    int xcg_spin_fused = 1;
+    DevBuf xcgs_dp[2], xcgs_slabs;
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -687,12 +693,20 @@ bool spin_quirks_ok(XCSolver *s, const char *who)
 
 // The density kernels on the matrix of spin alpha, then of spin beta (linear in the matrix), into the spin planes; `ga`,
 // `gb`: where the two gradients go.  sigma is what the kernels write beside the gradient; nobody reads it.
+// `pa`, `pb`: the planes that take the densities (the spin planes, or those of the open-shell gradient); `Dp_a`, `Dp_b`: where
+// the kernels that symmetrise on the host side of the launch leave the padded matrices (Dsym twice where nobody reads them after).
+void launch_density_spin(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
+                         const Planes &pa, const Planes &pb, double *Dp_a, double *Dp_b, double *ga, double *gb)
+{
+    double *sigma = pa.sigma.d();
+    launch_density(s, P, ngrid, nao, dm_a, ao, Dp_a, pa.rho.d(), ga, sigma);
+    launch_density(s, P, ngrid, nao, dm_b, ao, Dp_b, pb.rho.d(), gb, sigma);
+}
+
 void launch_density_spin(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
                          double *ga, double *gb)
 {
-    double *sigma = s->spin[0].sigma.d();
-    launch_density(s, P, ngrid, nao, dm_a, ao, s->dsym.d(), s->spin[0].rho.d(), ga, sigma);
-    launch_density(s, P, ngrid, nao, dm_b, ao, s->dsym.d(), s->spin[1].rho.d(), gb, sigma);
+    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, s->spin[0], s->spin[1], s->dsym.d(), s->dsym.d(), ga, gb);
 }
 
 // The spin-resolved sweep (DFT_ComputeXCSpin): the closed-shell sweep's density kernels on dm_a and on dm_b, one
@@ -1391,6 +1405,57 @@ bool xc_gradient(XCSolver *s, long ngrid, int nao, const double *dm, const doubl
                   "XC gradient launch");
 }
 
+// XC part of the open-shell nuclear gradient (DFT_ComputeXCGradientSpin): the density kernels on dm_a and dm_b and the
+// spin-resolved pointwise kernel exactly as DFT_ComputeXCSpin runs them, into planes of this entry; then k_xc_grad_spin on
+// (D_a, c_a, D_b, c_b) and the fixed-order slab sum -- or, with option "xcg_spin_fused" = 0, k_xc_grad once per spin with
+// (D_s, c_s) into two slab sets and one fixed-order sum over both.  Never the one-kernel plan, never recorded;
+// asynchronous on the solver's stream.  The padded matrices are this entry's too: both are read after both are written.
+bool xc_gradient_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao, const double *w,
+                      const double *ao_grad, const double *ao_hess, double *out)
+{
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
+    if (!dm_a || !dm_b || !ao || !w || !out) {
+        set_error(s, "DFT_ComputeXCGradientSpin needs both density matrices, the AO values, the grid weights and the output");
+        return false;
+    }
+    const bool gga = s->needs_grad;
+    if (gga && !ao_hess) { set_error(s, "ao_hess pointer is null for a gradient-corrected functional"); return false; }
+    if (!ao_grad) { set_error(s, "DFT_ComputeXCGradientSpin needs ao_grad: the derivative of the density by a centre is made of it"); return false; }
+    if (!spin_quirks_ok(s, "DFT_ComputeXCGradientSpin")) return false;
+    const bool fused = s->xcg_spin_fused != 0;
+    const XcGradPlan G = fused ? xc_grad_spin_fused_plan(s->num_cu, gga, ngrid, nao) : xc_grad_plan(s->num_cu, gga, ngrid, nao);
+    if (G.lds > 160 * 1024) { set_error(s, "DFT_ComputeXCGradientSpin: nao=%d needs %zu bytes of LDS per workgroup", nao, G.lds); return false; }
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
+    const long nxb = spin_points_blocks(ngrid);
+    Planes &a = s->xcgs[0], &b = s->xcgs[1];
+    const size_t dpb = sizeof(double) * P.NP * P.NP;
+    if (!reserve_planes(s, a, false, ngrid, WS_ALL, nxb) || !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD) ||
+        !reserve(s, s->xcgs_dp[0], dpb, "hipMalloc(Dsym alpha)", false) || !reserve(s, s->xcgs_dp[1], dpb, "hipMalloc(Dsym beta)", false) ||
+        !reserve(s, s->xcgs_slabs, sizeof(double) * (fused ? 1 : 2) * (size_t)G.nwg * 3 * nao, "hipMalloc(spin gradient slabs)", false))
+        return false;
+    double *Dp_a = s->xcgs_dp[0].d(), *Dp_b = s->xcgs_dp[1].d();
+    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, a, b, Dp_a, Dp_b, a.grad.d(), b.grad.d());
+    if (P.fast) {   // the wave-specialised density kernel symmetrises dm itself: k_xc_grad reads the padded matrices
+        ScopedTimer t(s, "sym_dm");
+        dim3 bl(16, 16), g(P.NP / 16, P.NP / 16);
+        hipLaunchKernelGGL(k_sym_dm, g, bl, 0, s->stream, nao, P.NP, dm_a, Dp_a);
+        hipLaunchKernelGGL(k_sym_dm, g, bl, 0, s->stream, nao, P.NP, dm_b, Dp_b);
+    }
+    {
+        ScopedTimer t(s, "xc_points_spin");
+        if (!hip_ok(s, launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
+                                             gga ? b.grad.d() : nullptr, w, a.coef.d(), b.coef.d(), a.partial.d()), "spin pointwise launch"))
+            return false;
+    }
+    ScopedTimer t(s, "xc_grad_spin");
+    const double fac = s->type == SOLVER_B3LYP ? 2.0 : 1.0;
+    if (fused)
+        return hip_ok(s, launch_xc_grad_spin_fused(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp_a, Dp_b,
+                                                   s->xcgs_slabs.d(), out), "XC spin gradient launch (fused)");
+    return hip_ok(s, launch_xc_grad_spin(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp_a, Dp_b,
+                                         s->xcgs_slabs.d(), out), "XC spin gradient launch");
+}
+
 } // namespace
 
 extern "C" {
@@ -1935,6 +2000,16 @@ int DFT_ComputeXCGradient(XCSolver *s, long long ngrid, int nao, unsigned long l
                        (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
 }
 
+int DFT_ComputeXCGradientSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                              unsigned long long d_ao, unsigned long long d_weights, unsigned long long d_ao_grad,
+                              unsigned long long d_ao_hess, unsigned long long d_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_gradient_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
+                            (const double *)d_weights, (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+}
+
 int DFT_ComputeXCDirect(XCSolver *s, long long ngrid, int nao, int nshell, const double *shl_xyz,
                         const int *shl_l, const int *shl_nprim, const int *shl_off, const int *shl_ao,
                         const double *prim_exp, const double *prim_coef, int nprim_total,
@@ -1997,6 +2072,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "tiny")) { s->tiny = value > 0.0 ? 1 : value < 0.0 ? -1 : 0; return 0; }
     if (!strcmp(key, "ao_pt")) { s->ao_pt = value == 16.0 ? 16 : value == 8.0 ? 8 : 0; return 0; }
     if (!strcmp(key, "ksplit")) { s->ksplit = value > 0 ? (int)value : 0; return 0; }
+    if (!strcmp(key, "xcg_spin_fused")) { s->xcg_spin_fused = value != 0.0; return 0; }
     return -1;
 }
 
@@ -2022,6 +2098,7 @@ double DFT_GetOption(XCSolver *s, const char *key)
     if (!strcmp(key, "used_occ")) return s->used_occ;                                          // what the last sweep's density step was
     if (!strcmp(key, "dm_factor")) return s->dm_factor;
     if (!strcmp(key, "used_dm_factor")) return s->used_dm_factor;                              // the last synchronous call swept with the factor of dm
+    if (!strcmp(key, "xcg_spin_fused")) return s->xcg_spin_fused;
     if (!strcmp(key, "dm_factor_rank")) return s->dm_factor_rank;                              // the rank its attempt found (0: rejected / not attempted)
     return unknown;
 }

@@ -19,6 +19,8 @@
 // A thread owns one (component pair, direction) sum for the whole workgroup's life; at the end the workgroup adds them in
 // component order and writes three doubles to part[(A, B)][slice][chunk].  A second kernel adds the partial sums of a
 // shell in a fixed order: no floating-point atomics anywhere, the same call twice gives the same bits.
+// DFT_Grad2eSpin (an open-shell state) is the same pass with the spin density M = D_a - D_b beside D in the exchange part of
+// the gather, -c_hf (D_ac D_bd + M_ac M_bd [+ D_ad D_bc + M_ad M_bc]): the SPIN instantiations of the kernel.
 // Not here: Schwarz or density screening (the host has none either, the two agree to rounding).
 #include <hip/hip_runtime.h>
 
@@ -86,14 +88,19 @@ struct Grad2eDev {
 // T threads: 256, or 64 for s and p on the bra (at most 9 component pairs: a wave has the whole chunk, its barriers cost
 // nothing and four times as many workgroups share a CU -- the contracted shells, whose primitive quartets are the bulk of
 // the work, are of this kind).  Every sum is taken by one thread in a fixed order: the result does not depend on T.
-template <int T>
+//
+// SPIN: the open-shell quartet (DFT_Grad2eSpin).  With D = D_a + D_b (`dm`) and M = D_a - D_b (`ms`) the exchange part of
+// the gather is D_ac D_bd + M_ac M_bd [+ D_ad D_bc + M_ad M_bc]; everything behind the gather is the same code.  `ms` is the
+// last parameter and is not read without SPIN, so the SPIN = false instantiations are instruction for instruction the
+// kernels that had no such parameter (same registers, same LDS; the build's resource report shows it).
+template <int T, bool SPIN>
 __global__ __launch_bounds__(T) void k_grad2e(int nao, int nshell, const double *__restrict__ xyz, const int *__restrict__ ls,
                                                  const int *__restrict__ nprim, const int *__restrict__ off,
                                                  const int *__restrict__ ao0, const double *__restrict__ ex,
                                                  const double *__restrict__ cf, const double *__restrict__ dm, double c_hf,
                                                  const int *__restrict__ pairs, const int *__restrict__ kC,
                                                  const int *__restrict__ kD, int nket, int nslice, int nch, int kbc, int lmaxk,
-                                                 int hbox, double *__restrict__ part)
+                                                 int hbox, double *__restrict__ part, const double *__restrict__ ms)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
@@ -140,8 +147,14 @@ __global__ __launch_bounds__(T) void k_grad2e(int nao, int nshell, const double 
             const int md = e % nsd, mc = (e / nsd) % nsc, mb = (e / (nsd * nsc)) % nsb, ma = e / (nsd * nsc * nsb);
             const size_t i = ao0[A] + ma, j = ao0[B] + mb, k = ao0[C] + mc, l = ao0[D] + md;
             double v = 2.0 * f * dm[i * n + j] * dm[k * n + l];
-            if (c_hf != 0.0)
-                v -= c_hf * (C == D ? dm[i * n + k] * dm[j * n + l] : dm[i * n + k] * dm[j * n + l] + dm[i * n + l] * dm[j * n + k]);
+            if (c_hf != 0.0) {
+                if (SPIN)
+                    v -= c_hf * (C == D ? dm[i * n + k] * dm[j * n + l] + ms[i * n + k] * ms[j * n + l]
+                                        : dm[i * n + k] * dm[j * n + l] + ms[i * n + k] * ms[j * n + l] + dm[i * n + l] * dm[j * n + k] +
+                                              ms[i * n + l] * ms[j * n + k]);
+                else
+                    v -= c_hf * (C == D ? dm[i * n + k] * dm[j * n + l] : dm[i * n + k] * dm[j * n + l] + dm[i * n + l] * dm[j * n + k]);
+            }
             Gq[((ma * nsb + mb) * ncc + mc) * ncd + md] = v;
             nz |= v != 0.0;
         }
@@ -337,6 +350,58 @@ template <class T> bool upload(T *&dst, const T *src, size_t n)
     return hipMemcpy(dst, src, sizeof(T) * n, hipMemcpyHostToDevice) == hipSuccess;
 }
 
+// Both entries: `d_ms` null is DFT_Grad2e (the closed-shell kernels), otherwise DFT_Grad2eSpin's kernels on the same tables,
+// streams and partial sums.  `who` names the entry in the error sentences.
+int grad2e_run(Grad2eDev *c, const char *who, const double *d_dm, const double *d_ms, double c_hf, double *d_out)
+{
+    const bool spin = d_ms != nullptr;
+    if (hipMemsetAsync(c->part, 0, sizeof(double) * c->part_doubles, c->stream) != hipSuccess) {
+        snprintf(c->err, sizeof c->err, "%s: clearing the partial sums failed", who);
+        (void)hipGetLastError();
+        return -1;
+    }
+    // fork: the side streams start behind the clear (and whatever the caller queued before it on the handle's stream)
+    (void)hipEventRecord(c->fork, c->stream);
+    for (int i = 0; i < 4; ++i) (void)hipStreamWaitEvent(c->side[i], c->fork, 0);
+    int nlaunch = 0, rc = 0;
+    // the heaviest classes first
+    for (int cls = 15; cls >= 0 && rc == 0; --cls) {
+        const int cnt = c->cls_off[cls + 1] - c->cls_off[cls];
+        if (!cnt) continue;
+        const int la = cls / 4, lb = cls % 4, nkb = g2_ncart(la) * g2_ncart(lb);
+        const int nch = (nkb + G2_KBC - 1) / G2_KBC, kbc = (nkb + nch - 1) / nch, hbox = box_max(la + lb);
+        const size_t bytes = ((size_t)g2_layout(la, lb, c->lmax, kbc, hbox).total * 8 + 15) & ~(size_t)15;
+        const bool small = la <= 1 && lb <= 1;   // 3 nkb <= 27 sums: one wave
+        static size_t allowed_all[2][2] = {{48 * 1024, 48 * 1024}, {48 * 1024, 48 * 1024}};   // per instantiation
+        size_t *allowed = allowed_all[spin];
+        auto kern = spin ? (small ? k_grad2e<64, true> : k_grad2e<G2_T, true>) : (small ? k_grad2e<64, false> : k_grad2e<G2_T, false>);
+        if (bytes > allowed[small]) {
+            if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+                snprintf(c->err, sizeof c->err, "%s: LDS request of %zu bytes refused", who, bytes);
+                (void)hipGetLastError();
+                rc = -1;
+                break;
+            }
+            allowed[small] = bytes;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)cnt * c->nslice * nch), dim3(small ? 64 : G2_T), bytes, c->side[nlaunch++ & 3], c->nao, c->nshell,
+                           c->xyz, c->ls, c->nprim, c->off, c->ao0, c->ex, c->cf, d_dm, c_hf, c->cls_pairs + c->cls_off[cls],
+                           c->kC, c->kD, c->nket, c->nslice, nch, kbc, c->lmax, hbox, c->part, d_ms);
+    }
+    for (int i = 0; i < 4; ++i) { // join, also after a refusal: the handle's stream continues behind what was launched
+        (void)hipEventRecord(c->join[i], c->side[i]);
+        (void)hipStreamWaitEvent(c->stream, c->join[i], 0);
+    }
+    if (rc != 0) return -1;
+    hipLaunchKernelGGL(k_grad2e_sum, dim3((3 * c->nshell + 63) / 64), dim3(64), 0, c->stream, c->nshell, c->nslice, c->part, d_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(c->err, sizeof c->err, "%s: launch failed: %s", who, hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -435,50 +500,19 @@ int DFT_Grad2e(void *h, unsigned long long d_dm, double c_hf, unsigned long long
         snprintf(c->err, sizeof c->err, "DFT_Grad2e: null %s pointer", d_dm ? "output" : "density");
         return -1;
     }
-    if (hipMemsetAsync(c->part, 0, sizeof(double) * c->part_doubles, c->stream) != hipSuccess) {
-        snprintf(c->err, sizeof c->err, "DFT_Grad2e: clearing the partial sums failed");
-        (void)hipGetLastError();
+    return grad2e_run(c, "DFT_Grad2e", (const double *)d_dm, nullptr, c_hf, (double *)d_out);
+}
+
+int DFT_Grad2eSpin(void *h, unsigned long long d_dm, unsigned long long d_ms, double c_hf, unsigned long long d_out)
+{
+    Grad2eDev *c = (Grad2eDev *)h;
+    if (!c) return -1;
+    c->err[0] = 0;
+    if (!d_dm || !d_ms || !d_out) {
+        snprintf(c->err, sizeof c->err, "DFT_Grad2eSpin: null %s pointer", !d_dm ? "density" : !d_ms ? "spin density" : "output");
         return -1;
     }
-    // fork: the side streams start behind the clear (and whatever the caller queued before it on the handle's stream)
-    (void)hipEventRecord(c->fork, c->stream);
-    for (int i = 0; i < 4; ++i) (void)hipStreamWaitEvent(c->side[i], c->fork, 0);
-    int nlaunch = 0, rc = 0;
-    // the heaviest classes first
-    for (int cls = 15; cls >= 0 && rc == 0; --cls) {
-        const int cnt = c->cls_off[cls + 1] - c->cls_off[cls];
-        if (!cnt) continue;
-        const int la = cls / 4, lb = cls % 4, nkb = g2_ncart(la) * g2_ncart(lb);
-        const int nch = (nkb + G2_KBC - 1) / G2_KBC, kbc = (nkb + nch - 1) / nch, hbox = box_max(la + lb);
-        const size_t bytes = ((size_t)g2_layout(la, lb, c->lmax, kbc, hbox).total * 8 + 15) & ~(size_t)15;
-        const bool small = la <= 1 && lb <= 1;   // 3 nkb <= 27 sums: one wave
-        auto kern = small ? k_grad2e<64> : k_grad2e<G2_T>;
-        static size_t allowed[2] = {48 * 1024, 48 * 1024};
-        if (bytes > allowed[small]) {
-            if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-                snprintf(c->err, sizeof c->err, "DFT_Grad2e: LDS request of %zu bytes refused", bytes);
-                (void)hipGetLastError();
-                rc = -1;
-                break;
-            }
-            allowed[small] = bytes;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)cnt * c->nslice * nch), dim3(small ? 64 : G2_T), bytes, c->side[nlaunch++ & 3], c->nao, c->nshell,
-                           c->xyz, c->ls, c->nprim, c->off, c->ao0, c->ex, c->cf, (const double *)d_dm, c_hf, c->cls_pairs + c->cls_off[cls],
-                           c->kC, c->kD, c->nket, c->nslice, nch, kbc, c->lmax, hbox, c->part);
-    }
-    for (int i = 0; i < 4; ++i) { // join, also after a refusal: the handle's stream continues behind what was launched
-        (void)hipEventRecord(c->join[i], c->side[i]);
-        (void)hipStreamWaitEvent(c->stream, c->join[i], 0);
-    }
-    if (rc != 0) return -1;
-    hipLaunchKernelGGL(k_grad2e_sum, dim3((3 * c->nshell + 63) / 64), dim3(64), 0, c->stream, c->nshell, c->nslice, c->part, (double *)d_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(c->err, sizeof c->err, "DFT_Grad2e: launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return grad2e_run(c, "DFT_Grad2eSpin", (const double *)d_dm, (const double *)d_ms, c_hf, (double *)d_out);
 }
 
 } // extern "C"

@@ -1128,12 +1128,13 @@ static void grad_quartet(int nshell, const double *xyz, const int *ls, const int
         }
 }
 
-/* out (natm, 3): the derivative of  1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum D_ac D_bd (ab|cd)  by the centres, D symmetric.
+/* out (natm, 3): the derivative of  1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum D_ac D_bd (ab|cd)  by the centres, D symmetric
+ * (Ms null: qc_grad2e), or with the spin density Ms the open-shell quartet of qc_grad2e_spin below.
  * Every ordered bra pair (A, B) with every ket pair C >= D: the derivative by the centre of A alone, see above.  The dense
  * ERI is never built; primitive pairs are screened as everywhere in the engine.  OpenMP over the first shell. */
-int qc_grad2e(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
-              const int *ao0, const double *ex, const double *cf, int nao, const int *shl_atom, int natm,
-              const double *Dm, double c_hf, double *out)
+static int grad2e_loop(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                       const int *ao0, const double *ex, const double *cf, int nao, const int *shl_atom, int natm,
+                       const double *Dm, const double *Ms, double c_hf, double *out)
 {
     for (int s = 0; s < nshell; ++s)
         if (ls[s] < 0 || ls[s] > LMAX || shl_atom[s] < 0 || shl_atom[s] >= natm) return -1;
@@ -1159,9 +1160,13 @@ int qc_grad2e(int nshell, const double *xyz, const int *ls, const int *nprim, co
                                 for (int md = 0; md < nsd; ++md) {
                                     const size_t i = ao0[A] + ma, j = ao0[B] + mb, k = ao0[C] + mc, l = ao0[D] + md;
                                     double v = 2.0 * f * Dm[i * n + j] * Dm[k * n + l];
-                                    if (c_hf != 0.0)
+                                    if (c_hf != 0.0 && !Ms)
                                         v -= c_hf * (C == D ? Dm[i * n + k] * Dm[j * n + l]
                                                             : Dm[i * n + k] * Dm[j * n + l] + Dm[i * n + l] * Dm[j * n + k]);
+                                    else if (c_hf != 0.0)
+                                        v -= c_hf * (C == D ? Dm[i * n + k] * Dm[j * n + l] + Ms[i * n + k] * Ms[j * n + l]
+                                                            : Dm[i * n + k] * Dm[j * n + l] + Ms[i * n + k] * Ms[j * n + l] +
+                                                                  Dm[i * n + l] * Dm[j * n + k] + Ms[i * n + l] * Ms[j * n + k]);
                                     Gs[((ma * nsb + mb) * nsc + mc) * nsd + md] = v;
                                     if (fabs(v) > big) big = fabs(v);
                                 }
@@ -1184,6 +1189,23 @@ int qc_grad2e(int nshell, const double *xyz, const int *ls, const int *nprim, co
         for (int x = 0; x < 3; ++x) out[3 * shl_atom[AB / nshell] + x] += acc[3 * (size_t)AB + x];
     free(acc);
     return 0;
+}
+
+int qc_grad2e(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+              const int *ao0, const double *ex, const double *cf, int nao, const int *shl_atom, int natm,
+              const double *Dm, double c_hf, double *out)
+{
+    return grad2e_loop(nshell, xyz, ls, nprim, off, ao0, ex, cf, nao, shl_atom, natm, Dm, NULL, c_hf, out);
+}
+
+/* The same for an open-shell state, Dm = D_a + D_b and Ms = D_a - D_b (both symmetric): the derivative of
+ * 1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum (D_ac D_bd + M_ac M_bd) (ab|cd), one pass with the extended density quartet. */
+int qc_grad2e_spin(int nshell, const double *xyz, const int *ls, const int *nprim, const int *off,
+                   const int *ao0, const double *ex, const double *cf, int nao, const int *shl_atom, int natm,
+                   const double *Dm, const double *Ms, double c_hf, double *out)
+{
+    if (!Ms) return -1;
+    return grad2e_loop(nshell, xyz, ls, nprim, off, ao0, ex, cf, nao, shl_atom, natm, Dm, Ms, c_hf, out);
 }
 
 /* worker threads of the OpenMP regions above (default: every visible core, which oversubscribes a

@@ -9,6 +9,7 @@ namespace qcdft {
 
 constexpr int XCG_ROWS = 16;      // grid rows per tile of k_xc_grad (one MFMA block of rows)
 constexpr int XCG_KC_MAX = 512;   // widest K chunk (basis functions) of the AO / Q tile a workgroup keeps in LDS
+constexpr int XCGS_KC_MAX = 320;  // the same for k_xc_grad_spin, which keeps three tiles (AO, Q of either spin)
 constexpr int AOH_PT = 8;         // grid points per workgroup of k_eval_ao_hess (six planes x 8 x 127 doubles = 48 KB of LDS)
 
 // hess (6, ngrid, nao): xx, xy, xz, yy, yz, zz of every AO at every point; the shell table as launch_eval_ao takes it
@@ -30,5 +31,18 @@ XcGradPlan xc_grad_plan(int num_cu, bool gga, long ngrid, int nao);
 hipError_t launch_xc_grad(hipStream_t st, const XcGradPlan &p, bool gga, double fac, long ngrid, int nao, const double *ao,
                           const double *ao_grad, const double *hess, const double *coef, const double *Dp, double *slabs,
                           double *out);
+
+// The same once per spin, summed: out = G(coef_a, Dp_a) + G(coef_b, Dp_b).  slabs: room for 2 * nwg * 3 * nao doubles (alpha's
+// slabs, then beta's); one fixed-order sum over both sets finishes.
+hipError_t launch_xc_grad_spin(hipStream_t st, const XcGradPlan &p, bool gga, double fac, long ngrid, int nao, const double *ao,
+                               const double *ao_grad, const double *hess, const double *coef_a, const double *coef_b,
+                               const double *Dp_a, const double *Dp_b, double *slabs, double *out);
+
+// The two launches in one kernel (k_xc_grad_spin): its own plan (three tiles in LDS, K chunk capped at XCGS_KC_MAX),
+// slabs: room for nwg * 3 * nao doubles.  Refuses an LDS request above 160 KB.
+XcGradPlan xc_grad_spin_fused_plan(int num_cu, bool gga, long ngrid, int nao);
+hipError_t launch_xc_grad_spin_fused(hipStream_t st, const XcGradPlan &p, bool gga, double fac, long ngrid, int nao, const double *ao,
+                                     const double *ao_grad, const double *hess, const double *coef_a, const double *coef_b,
+                                     const double *Dp_a, const double *Dp_b, double *slabs, double *out);
 
 } // namespace qcdft

@@ -156,6 +156,10 @@ def build_parser():
                    help="with --spin: allow --dipole, --polarizability (unrestricted CPKS) and --excitations (spin-conserving U-TDDFT / "
                         "U-TDA, rows U1 ...) from the unrestricted reference (the open-shell response of Vxc on the device: "
                         "DFT_FxcPrepareSpinPol / DFT_FxcApplySpinPol); --triplets stays refused")
+    p.add_argument("--open-shell-gradient", action="store_true",
+                   help="with --spin: let --gradient and --optimize run on the unrestricted state (gradients.nuclear_gradient_uks: the XC "
+                        "term per spin by DFT_ComputeXCGradientSpin, the two-electron term with the spin density, DFT_Grad2eSpin under "
+                        "--grad2e device); every step of --optimize goes through the unrestricted loop")
     p.add_argument("--gradient", action="store_true",
                    help="analytic nuclear gradient dE/dR of the converged closed-shell state (Ha/bohr), at fixed quadrature points and weights")
     p.add_argument("--optimize", action="store_true",
@@ -164,7 +168,7 @@ def build_parser():
     p.add_argument("--opt-max-steps", type=int, default=50, metavar="N", help="with --optimize: at most N steps")
     p.add_argument("--grad2e", default="host", choices=["host", "device"],
                    help="with --gradient / --optimize: where the two-electron term of the gradient is computed; host (default): "
-                        "integrals.c::qc_grad2e on the CPU share; device: DFT_Grad2e (csrc/grad2e.hip), in every step of --optimize too")
+                        "integrals.c::qc_grad2e on the CPU share; device: DFT_Grad2e (csrc/grad2e.hip; DFT_Grad2eSpin with --open-shell-gradient), in every step of --optimize too")
     p.add_argument("--charge", type=int, default=0, metavar="Q", help="charge of the molecule (electrons = sum Z - Q); an odd count needs --spin")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
@@ -189,8 +193,9 @@ def main(argv=None):
         p.error("--excitations runs on one rank with --ao resident")
 
     if args.gradient or args.optimize:
-        if args.spin is not None:
-            p.error("--gradient / --optimize: an unrestricted (--spin) run has no analytic gradient here: the assembly is closed-shell")
+        if args.spin is not None and not args.open_shell_gradient:
+            p.error("--gradient / --optimize: an unrestricted (--spin) run has no analytic gradient here: the assembly is closed-shell "
+                    "unless --open-shell-gradient asks for the gradient of the unrestricted state")
         if args.efield is not None:
             p.error("--gradient / --optimize: a run in a uniform electric field (--efield) is not supported")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.dm_factor:
@@ -203,6 +208,10 @@ def main(argv=None):
     uks = args.spin is not None
     if args.open_shell_response and not uks:
         p.error("--open-shell-response goes with --spin N")
+    if args.open_shell_gradient and not uks:
+        p.error("--open-shell-gradient goes with --spin N")
+    if args.open_shell_gradient and not (args.gradient or args.optimize):
+        p.error("--open-shell-gradient goes with --gradient or --optimize")
     if uks:
         if (args.excitations or args.polarizability or args.dipole) and not args.open_shell_response:
             p.error("--excitations, --polarizability and --dipole take a closed-shell reference: not available after an unrestricted (--spin) run "
@@ -372,18 +381,24 @@ def main(argv=None):
     grad = grad_terms = opt = None
     if (args.gradient or args.optimize) and res["converged"]:
         from . import gradients, optimize
-        grad, grad_terms = gradients.nuclear_gradient(inp, res, backend, args.functional, two_electron=args.grad2e)
+        nuclear_gradient = gradients.nuclear_gradient_uks if uks else gradients.nuclear_gradient
+        grad, grad_terms = nuclear_gradient(inp, res, backend, args.functional, two_electron=args.grad2e)
         print_gradient(inp.symbols, grad)
     if args.optimize and res["converged"]:
         def energy_and_gradient(xyz):
             inp_k = inputs.build(atom_path, args.basis, args.grid_level, device=device, verbose=False, eri_mode=args.eri, chol_tol=args.chol_tol,
-                                 point_charges=charges, charge=args.charge, atom_xyz=xyz)
-            be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, eigensolver=args.eigensolver,
-                                  ao_mode=args.ao, xc_occ=bool(args.xc_occ))
-            res_k = scf.run_scf(inp_k, be_k, args.functional, log=None)
+                                 point_charges=charges, charge=args.charge, spin=args.spin or 0, atom_xyz=xyz)
+            if uks:
+                be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, device_resident=False,
+                                      fused_tail=False, eigensolver="exact", ao_mode=args.ao, xc_occ=bool(args.xc_occ))
+                res_k = scf.run_uks(inp_k, be_k, args.functional, log=None)
+            else:
+                be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, eigensolver=args.eigensolver,
+                                      ao_mode=args.ao, xc_occ=bool(args.xc_occ))
+                res_k = scf.run_scf(inp_k, be_k, args.functional, log=None)
             if not res_k["converged"]:
                 raise RuntimeError("--optimize: the SCF did not converge at a geometry of the optimisation")
-            g_k = gradients.nuclear_gradient(inp_k, res_k, be_k, args.functional, two_electron=args.grad2e)[0]
+            g_k = nuclear_gradient(inp_k, res_k, be_k, args.functional, two_electron=args.grad2e)[0]
             be_k.close()
             return res_k["E_tot"], g_k
         opt = optimize.bfgs(energy_and_gradient, inp.atom_xyz, max_steps=args.opt_max_steps, log=print)

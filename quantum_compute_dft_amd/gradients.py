@@ -1,4 +1,5 @@
-"""Analytic nuclear gradient dE/dR_A of a converged closed-shell (RKS) energy, at fixed quadrature points and weights.
+"""Analytic nuclear gradient dE/dR_A of a converged closed-shell (RKS) or unrestricted (UKS) energy, at fixed quadrature
+points and weights.
 
     g_A = -tr(W dS/dR_A) + tr(D dT/dR_A) + tr(D dV/dR_A)           integrals.grad1e (basis centres) and the field of the
                                                                     electrons at the nucleus (integrals.point_coulomb_field)
@@ -8,7 +9,9 @@
 
 with W = 2 C_occ diag(eps_occ) C_occ^T = D F D / 2.  `nuclear_gradient` assembles it; the XC part has host counterparts of
 DFT_EvalAOHess / DFT_ComputeXCGradient (csrc/xc_grad.hip; solver.eval_ao_hess / compute_xc_gradient,
-scf.HipBackend.xc_gradient) below.
+scf.HipBackend.xc_gradient) below.  `nuclear_gradient_uks` is the same assembly for a run_uks state: W = sum_s D_s F_s D_s, the
+two-electron term with the spin density beside the total one (integrals.grad2e_spin / DFT_Grad2eSpin), the XC term once
+per spin (xc_gradient_spin_host / DFT_ComputeXCGradientSpin).
 
     G[mu, x] = d/dt Exc  when, in column mu only,  ao[:, mu] -> ao[:, mu] - t ao_grad[x][:, mu]  and
                ao_grad[k][:, mu] -> ao_grad[k][:, mu] - t ao_hess[xk][:, mu]          (dm and the weights fixed)
@@ -139,6 +142,46 @@ def xc_gradient_host(functional, dm, ao, weights, ao_grad, ao_hess=None, quirks=
     return G
 
 
+def xc_gradient_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad, ao_hess=None):
+    """G (nao, 3) of DFT_ComputeXCGradientSpin from AO planes in numpy: the derivative of xc_spin_host's Exc under the
+    column replacement above, both spin density matrices and the weights fixed.  The per-spin coefficients c_s0..c_s3 are
+    the spin-resolved sweep's own (response.point_spin_host, closed-shell conventions), and
+
+        G[mu, x] = -fac sum_s sum_g [ ao_grad[x] (Q_s D_s) + (sum_k c_sk ao_hess[xk]) (AO D_s) ][g, mu],   Q_s = 2 c_s0 AO + sum_k c_sk ao_grad[k]
+
+    with fac = 1 (one-sided types) or 2 (B3LYP): xc_gradient_host's formula once per spin.  The spin-resolved bodies are the
+    derivatives of the energy: no `quirks`."""
+    t, _, gga = response._kind(functional)
+    if ao_grad is None:
+        raise ValueError("ao_grad is needed: the derivative of the density by a centre is made of it")
+    if gga and ao_hess is None:
+        raise ValueError("ao_hess is needed for a gradient-corrected functional")
+    ao = np.ascontiguousarray(ao, dtype=np.float64)
+    gr = np.ascontiguousarray(ao_grad, dtype=np.float64)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    dms = [np.asarray(d, dtype=np.float64) for d in (dm_a, dm_b)]
+    (ra, ga), (rb, gb) = (response._density(d, ao, gr if gga else None) for d in dms)
+    p = response.point_spin_host(functional, ra, rb, ga, gb, w)
+    hs = np.ascontiguousarray(ao_hess, dtype=np.float64) if gga else None
+    fac = 2.0 if t == 2 else 1.0
+    G = np.zeros((ao.shape[1], 3))
+    for dm, c in zip(dms, (p[1:5], p[5:9])):
+        X = ao @ (0.5 * (dm + dm.T))
+        if not gga:
+            Z = 2.0 * c[0][:, None] * X
+            for x in range(3):
+                G[:, x] -= fac * np.einsum("gm,gm->m", gr[x], Z)
+            continue
+        Q = 2.0 * c[0][:, None] * ao
+        for k in range(3):
+            Q += c[1 + k][:, None] * gr[k]
+        Z = Q @ (0.5 * (dm + dm.T))
+        for x in range(3):
+            H = sum(c[1 + k][:, None] * hs[HESS_INDEX[x][k]] for k in range(3))
+            G[:, x] -= fac * (np.einsum("gm,gm->m", gr[x], Z) + np.einsum("gm,gm->m", H, X))
+    return G
+
+
 def sum_over_atoms(shells, G):
     """(natm, 3): G (nao, 3) summed over the functions each atom owns (the shell-to-atom map of the shell table)."""
     G = np.asarray(G, dtype=np.float64)
@@ -218,7 +261,8 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
         raise ValueError("nuclear_gradient: two_electron='device' needs a backend with a device two-electron gradient "
                          "(scf.HipBackend); this backend has none")
     if scf_result.get("uks"):
-        raise ValueError("nuclear_gradient: an unrestricted (UKS) result has no analytic gradient here: the assembly is closed-shell")
+        raise ValueError("nuclear_gradient: an unrestricted (UKS) result has no analytic gradient here: the assembly is closed-shell "
+                         "(nuclear_gradient_uks assembles the open-shell one)")
     if getattr(inp, "efield", None) is not None:
         raise ValueError("nuclear_gradient: a run in a uniform electric field (efield) is not supported")
     if getattr(backend, "world", 1) > 1:
@@ -249,6 +293,78 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
         else:
             ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
             G = xc_gradient_host(f, dm, ao, inp.grids.weights, gr, hs if f.needs_gradient else None, quirks)
+        terms["xc"] = sum_over_atoms(sh, G)
+    else:
+        terms["xc"] = np.zeros_like(xyz)
+    pc = getattr(inp, "point_charges", None)
+    if pc is not None and len(pc):
+        terms["external"] = integrals.grad1e(sh, pc[:, :3], pc[:, 3], dm, W)[2] + _pair_repulsion_gradient(xyz, z, pc[:, :3], pc[:, 3])
+    else:
+        terms["external"] = np.zeros_like(xyz)
+    return sum(terms.values()), terms
+
+
+def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron="host"):
+    """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged unrestricted state `uks_result` (scf.run_uks), with
+    nuclear_gradient's five terms and its conventions (fixed quadrature points and weights).  With D = D_a + D_b:
+
+        one_electron   grad1e with D and W = sym(sum_s D_s F_s D_s), F_s from backend.uks_parts as run_uks assembles it,
+                       and the Hellmann-Feynman field of D at the nuclei
+        two_electron   d/dR_A [1/2 sum D D (ab|cd) - c_hf/4 sum (D D + M M) (ab|cd)], M = D_a - D_b: integrals.grad2e_spin, or
+                       backend.grad2e_spin (DFT_Grad2eSpin: one pass over the derivative integrals) with two_electron="device"
+        xc             backend.xc_gradient_spin (DFT_ComputeXCGradientSpin) where the backend has it, xc_gradient_spin_host on
+                       planes evaluated here otherwise
+
+    A spin without electrons has D_s = 0 and contributes nothing.  Point charges are served through "external"."""
+    if two_electron not in ("host", "device"):
+        raise ValueError(f"nuclear_gradient_uks: two_electron must be 'host' or 'device', not {two_electron!r}")
+    if two_electron == "device" and not hasattr(backend, "grad2e_spin"):
+        raise ValueError("nuclear_gradient_uks: two_electron='device' needs a backend with a device two-electron gradient "
+                         "(scf.HipBackend); this backend has none")
+    if "dm_a" not in uks_result or "dm_b" not in uks_result:
+        raise ValueError("nuclear_gradient_uks needs a scf.run_uks result (dm_a, dm_b); nuclear_gradient serves the closed shell")
+    if getattr(inp, "efield", None) is not None:
+        raise ValueError("nuclear_gradient_uks: a run in a uniform electric field (efield) is not supported")
+    if getattr(backend, "world", 1) > 1:
+        raise ValueError("nuclear_gradient_uks runs on one rank: the grid of this backend is sharded over several")
+    if getattr(backend, "dm_factor", False):
+        raise ValueError("nuclear_gradient_uks takes the density matrices themselves: run without dm_factor")
+    f = functionals.resolve(functional if functional is not None else backend.functional)
+    wv = f.weight_vector()
+    if bool(getattr(backend, "quirks", getattr(backend, "q", False))) and any(wv[functionals.COMPONENTS.index(c)] != 0.0 for c in _QUIRKY):
+        raise ValueError("nuclear_gradient_uks: the spin-resolved potentials are the derivatives of the energy, but with quirks = 1 the "
+                         "ground state solved the shipped vwn5_c / pbe_c potentials, which are not; run with --quirks 0")
+    from scipy.linalg import eigh
+    S = inp.S
+    dms = [np.asarray(uks_result[k], dtype=np.float64) for k in ("dm_a", "dm_b")]
+    dms = [np.ascontiguousarray(0.5 * (d + d.T)) for d in dms]
+    coccs = []
+    for d, key in zip(dms, ("nalpha", "nbeta")):       # D_s S is the projector on the occupied orbitals of spin s; an empty spin has no columns
+        e0, C0 = eigh(S @ d @ S, S)
+        n = int(uks_result[key]) if key in uks_result else int(round(float(np.sum(d * S))))
+        coccs.append(np.ascontiguousarray(C0[:, ::-1][:, :n] * np.sqrt(np.maximum(e0[::-1][:n], 0.0))))
+    want_k = f.c_hf != 0.0
+    J, Ka, Kb, _, Va, Vb = backend.uks_parts(dms[0], dms[1], coccs[0], coccs[1], want_k)
+    W = np.zeros_like(S)
+    for d, V, K in ((dms[0], Va, Ka), (dms[1], Vb, Kb)):
+        F = inp.Hcore + J + 0.5 * (V + V.T) - (f.c_hf * K if (want_k and K is not None) else 0.0)
+        W += d @ F @ d
+    W = 0.5 * (W + W.T)
+    dm, ms = np.ascontiguousarray(dms[0] + dms[1]), np.ascontiguousarray(dms[0] - dms[1])
+    sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
+    z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
+    g1 = integrals.grad1e(sh, xyz, z, dm, W)
+    field = integrals.point_coulomb_field(sh, xyz, dm)
+    terms = {"one_electron": g1[0] + g1[1] + g1[2] - z[:, None] * field,
+             "two_electron": backend.grad2e_spin(dms[0], dms[1], f.c_hf) if two_electron == "device"
+                             else integrals.grad2e_spin(sh, dm, ms, f.c_hf),
+             "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
+    if any(w != 0.0 for w in wv):
+        if hasattr(backend, "xc_gradient_spin"):
+            G = backend.xc_gradient_spin(dms[0], dms[1])
+        else:
+            ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
+            G = xc_gradient_spin_host(f, dms[0], dms[1], ao, inp.grids.weights, gr, hs if f.needs_gradient else None)
         terms["xc"] = sum_over_atoms(sh, G)
     else:
         terms["xc"] = np.zeros_like(xyz)

@@ -73,6 +73,8 @@ def _load():
         L.qc_grad1e.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ip, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp, dp]
         L.qc_grad2e.restype = ctypes.c_int
         L.qc_grad2e.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ip, ctypes.c_int, dp, ctypes.c_double, dp]
+        L.qc_grad2e_spin.restype = ctypes.c_int
+        L.qc_grad2e_spin.argtypes = [ctypes.c_int, dp, ip, ip, ip, ip, dp, dp, ctypes.c_int, ip, ctypes.c_int, dp, dp, ctypes.c_double, dp]
         from .hostinfo import host_cpu_share
         L.qc_set_threads(host_cpu_share())
         _lib = L
@@ -179,6 +181,29 @@ def grad2e(shells, dm, c_hf=0.0, per_shell=False):
                            out.ctypes.data_as(dp))
     if rc != 0:
         raise ValueError("grad2e: unsupported angular momentum (s-f) or a shell without an atom")
+    return out
+
+
+def grad2e_spin(shells, dm, ms, c_hf=0.0, per_shell=False):
+    """(natm, 3): d/dR_A of 1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum (D_ac D_bd + M_ac M_bd) (ab|cd), the two-electron energy of
+    an open-shell state with the total density dm = D_a + D_b and the spin density ms = D_a - D_b, both symmetric
+    (qc_grad2e_spin): grad2e's pass over the derivative quartets with the extended density quartet.  `per_shell` as in
+    grad2e."""
+    keep, p = _args(shells)
+    dm, ms = _sym(dm, "dm"), _sym(ms, "ms")
+    if ms.shape != dm.shape:
+        raise ValueError("grad2e_spin: dm and ms must have the same shape")
+    if per_shell:
+        owner = np.arange(shells.nshell, dtype=np.int32)
+    else:
+        owner = np.ascontiguousarray(shells.atom, dtype=np.int32)
+    natm = int(owner.max()) + 1
+    out = np.zeros((natm, 3))
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    rc = _load().qc_grad2e_spin(shells.nshell, *p, shells.nao, owner.ctypes.data_as(ip), natm, dm.ctypes.data_as(dp),
+                                ms.ctypes.data_as(dp), float(c_hf), out.ctypes.data_as(dp))
+    if rc != 0:
+        raise ValueError("grad2e_spin: unsupported angular momentum (s-f) or a shell without an atom")
     return out
 
 
@@ -318,6 +343,8 @@ class DeviceGrad2e:
         L.DFT_Grad2eOpen.restype = ctypes.c_void_p
         L.DFT_Grad2e.argtypes = [ctypes.c_void_p, u64, ctypes.c_double, u64]
         L.DFT_Grad2e.restype = ctypes.c_int
+        L.DFT_Grad2eSpin.argtypes = [ctypes.c_void_p, u64, u64, ctypes.c_double, u64]
+        L.DFT_Grad2eSpin.restype = ctypes.c_int
         L.DFT_Grad2eSetStream.argtypes = [ctypes.c_void_p, u64]
         L.DFT_Grad2eSetStream.restype = ctypes.c_int
         L.DFT_Grad2eLastError.argtypes = [ctypes.c_void_p]
@@ -353,21 +380,43 @@ class DeviceGrad2e:
             raise RuntimeError("libdft: " + (self.lib.DFT_Grad2eLastError(self._h) or b"").decode())
         return out
 
-    def grad(self, dm, c_hf=0.0):
-        """numpy (natm, 3), what grad2e(shells, dm, c_hf) returns: `dm` a symmetric host array or device tensor; the shells'
-        rows are added per atom on the host, in shell order."""
+    def per_shell_spin(self, d_dm, d_ms, c_hf=0.0, out=None):
+        """per_shell for an open-shell state (DFT_Grad2eSpin): `d_dm` the total density D_a + D_b, `d_ms` the spin density
+        D_a - D_b, both symmetric (nao, nao) device tensors; one pass over the derivative integrals.  Asynchronous."""
         import torch
-        if torch.is_tensor(dm):
-            d_dm = dm.to(dtype=torch.float64).contiguous()
-            _sym(d_dm.cpu().numpy(), "dm")
-        else:
-            d_dm = torch.as_tensor(_sym(dm, "dm"), device="cuda")
-        rows = self.per_shell(d_dm, c_hf).cpu().numpy()
+        PointCoulomb._check(d_dm, (self.nao, self.nao), "dm")
+        PointCoulomb._check(d_ms, (self.nao, self.nao), "ms")
+        if out is None:
+            out = torch.empty((self.nshell, 3), dtype=torch.float64, device=d_dm.device)
+        PointCoulomb._check(out, (self.nshell, 3), "out")
+        if self.lib.DFT_Grad2eSpin(self._h, ctypes.c_uint64(d_dm.data_ptr()), ctypes.c_uint64(d_ms.data_ptr()), float(c_hf),
+                                   ctypes.c_uint64(out.data_ptr())) != 0:
+            raise RuntimeError("libdft: " + (self.lib.DFT_Grad2eLastError(self._h) or b"").decode())
+        return out
+
+    def _on_device(self, m, what):
+        import torch
+        if torch.is_tensor(m):
+            d = m.to(dtype=torch.float64).contiguous()
+            _sym(d.cpu().numpy(), what)
+            return d
+        return torch.as_tensor(_sym(m, what), device="cuda")
+
+    def _per_atom(self, rows):
         owner = np.asarray(self.shells.atom, dtype=np.int64)
         out = np.zeros((int(owner.max()) + 1, 3))
         for s in range(self.nshell):
             out[owner[s]] += rows[s]
         return out
+
+    def grad_spin(self, dm, ms, c_hf=0.0):
+        """numpy (natm, 3), what grad2e_spin(shells, dm, ms, c_hf) returns: symmetric host arrays or device tensors."""
+        return self._per_atom(self.per_shell_spin(self._on_device(dm, "dm"), self._on_device(ms, "ms"), c_hf).cpu().numpy())
+
+    def grad(self, dm, c_hf=0.0):
+        """numpy (natm, 3), what grad2e(shells, dm, c_hf) returns: `dm` a symmetric host array or device tensor; the shells'
+        rows are added per atom on the host, in shell order."""
+        return self._per_atom(self.per_shell(self._on_device(dm, "dm"), c_hf).cpu().numpy())
 
 
 

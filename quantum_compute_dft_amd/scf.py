@@ -740,6 +740,18 @@ class HipBackend:
         the three gradient planes is copied together, the entry wants them back to back) and are evaluated per slice
         otherwise (an LDA-class run keeps no gradient planes, --ao direct keeps none).  slice_rows: rows per slice (default:
         what keeps the Hessian planes within XC_GRADIENT_HESS_BYTES)."""
+        d_dm = self._dev(dm)
+        return self._xc_gradient_slices(slice_rows, lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient(m, self.nao, d_dm, ao, w, out, gr, hs))
+
+    def xc_gradient_spin(self, dm_a, dm_b, slice_rows=None):
+        """G (nao, 3) as a numpy array for an open-shell state: dExc[dm_a, dm_b] / d(centre of basis function mu) at fixed
+        points and weights (DFT_ComputeXCGradientSpin), summed over slices of the grid exactly as xc_gradient does."""
+        self._uks_check()
+        d_a, d_b = self._dev(dm_a), self._dev(dm_b)
+        return self._xc_gradient_slices(slice_rows, lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient_spin(m, self.nao, d_a, d_b, ao, w, out, gr, hs))
+
+    def _xc_gradient_slices(self, slice_rows, entry):
+        """The slicing xc_gradient and xc_gradient_spin share: entry(m, ao, w, d_out, gr, hs) is the library call of a slice."""
         if self.world > 1:
             raise ValueError("the XC gradient runs on one rank: the grid of this backend is sharded over several")
         if self.dm_factor:
@@ -749,7 +761,6 @@ class HipBackend:
         rows = int(slice_rows) if slice_rows else max(16, int(self.XC_GRADIENT_HESS_BYTES // (48 * n)) // 16 * 16)
         rows = max(1, min(rows, ng))
         gga = s.needs_gradient
-        d_dm = self._dev(dm)
         d_out = t.zeros((n, 3), dtype=f64, device=self.dev)
         d_G = t.zeros((n, 3), dtype=f64, device=self.dev)
         d_hess = t.empty(6 * rows * n, dtype=f64, device=self.dev) if gga else None
@@ -774,7 +785,7 @@ class HipBackend:
                 hs = d_hess[:6 * m * n].view(6, m, n)
                 s.eval_ao_hess(self.shells, coords, m, hs)
             t.cuda.synchronize()
-            s.compute_xc_gradient(m, n, d_dm, ao, self.d_w[lo:hi], d_out, gr, hs)
+            entry(m, ao, self.d_w[lo:hi], d_out, gr, hs)
             t.cuda.synchronize()
             d_G += d_out
         t.cuda.synchronize()
@@ -791,6 +802,18 @@ class HipBackend:
             self._grad2e = DeviceGrad2e(self.shells, self._lib_path)
         with self.torch.cuda.device(self.dev):
             return self._grad2e.grad(dm, c_hf)
+
+    def grad2e_spin(self, dm_a, dm_b, c_hf):
+        """(natm, 3) as a numpy array: what integrals.grad2e_spin(shells, dm_a + dm_b, dm_a - dm_b, c_hf) computes on the
+        host, from DFT_Grad2eSpin on grad2e's handle: one pass over the derivative integrals for both spins."""
+        if self.world > 1:
+            raise ValueError("the device two-electron gradient runs on one rank: this backend is one of several")
+        if self._grad2e is None:
+            from .integrals import DeviceGrad2e
+            self._grad2e = DeviceGrad2e(self.shells, self._lib_path)
+        dm_a, dm_b = np.asarray(dm_a, dtype=np.float64), np.asarray(dm_b, dtype=np.float64)
+        with self.torch.cuda.device(self.dev):
+            return self._grad2e.grad_spin(dm_a + dm_b, dm_a - dm_b, c_hf)
 
     def close(self):
         """Releases the handles this backend opened on demand (the buffers go with the object)."""

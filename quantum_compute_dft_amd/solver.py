@@ -153,6 +153,8 @@ class DFTSolverWrapper:
         L.DFT_EvalAOHess.restype = ctypes.c_int
         L.DFT_ComputeXCGradient.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, _u64]
         L.DFT_ComputeXCGradient.restype = ctypes.c_int
+        L.DFT_ComputeXCGradientSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, _u64, _u64]
+        L.DFT_ComputeXCGradientSpin.restype = ctypes.c_int
 
         if self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
@@ -372,6 +374,15 @@ class DFTSolverWrapper:
         LDA-class functional."""
         rc = self.lib.DFT_ComputeXCGradient(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
                                             _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
+        self._check()
+        return rc
+
+    def compute_xc_gradient_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_weights, d_out, d_ao_grad=None, d_ao_hess=None):
+        """G (nao, 3) into d_out (DFT_ComputeXCGradientSpin): the derivative of compute_xc_spin's Exc by the centre of every
+        basis function at fixed points and weights; asynchronous on the solver's stream.  d_ao_hess may be None for an
+        LDA-class functional.  With option quirks = 1 a functional with vwn5_c or pbe_c is refused, as by compute_xc_spin."""
+        rc = self.lib.DFT_ComputeXCGradientSpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)), _u64(_ptr(d_ao)),
+                                                _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
         self._check()
         return rc
 

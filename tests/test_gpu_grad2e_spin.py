@@ -1,0 +1,119 @@
+"""The open-shell two-electron gradient term on the device (csrc/grad2e.hip: DFT_Grad2eSpin, DeviceGrad2e.per_shell_spin /
+grad_spin, HipBackend.grad2e_spin) against the host engine (integrals.c::qc_grad2e_spin), which tests/test_grad2e_spin_cpu.py
+holds against the closed-shell routine by linearity.
+
+Yardstick (grad2e_helper): bar = the HOST's own spread between the two orders of the atoms; a comparison passes when
+10 bar <= 1e-11 and |device - host| <= max(10 bar, 1e-13) max|host|."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import grad2e_helper as gh
+from quantum_compute_dft_amd import integrals
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev(a):
+    return torch.as_tensor(np.array(a, dtype=np.float64, order="C"), device="cuda")      # a copy: the shared cases are read-only
+
+
+def spin_density(c, blocked=False):
+    """A random symmetric M for the case `c` (gh.ch_case), from a generator of its own; per-atom blocks only if `blocked`."""
+    M = gh.random_density(c["shells"].nao, seed=23)
+    return np.ascontiguousarray(gh.block_diagonal(c["shells"], M) if blocked else M)
+
+
+@pytest.fixture(scope="module")
+def ch_engines():
+    eng = {sw: integrals.DeviceGrad2e(gh.ch_case(0.0, sw)["shells"]) for sw in (False, True)}
+    yield eng
+    for e in eng.values():
+        e.close()
+
+
+@pytest.mark.parametrize("swapped", [False, True])
+@pytest.mark.parametrize("c_hf", [0.0, 0.25])
+def test_every_class(ch_engines, c_hf, swapped):
+    """CH/def2-TZVP: s-f on bra and ket, both orders of the atoms."""
+    c = gh.ch_case(c_hf, swapped)
+    M = spin_density(c)
+    eng = ch_engines[swapped]
+    ref = integrals.grad2e_spin(c["shells"], c["D"], M, c_hf, per_shell=True)
+    rows = eng.per_shell_spin(_dev(c["D"]), _dev(M), c_hf).cpu().numpy()
+    label = f"spin CH/def2-TZVP{' atoms swapped' if swapped else ''} c_hf {c_hf}"
+    gh.check(label + " per shell", rows, ref, c["bar"])
+    gh.check(label + " per atom", eng.grad_spin(c["D"], M, c_hf), integrals.grad2e_spin(c["shells"], c["D"], M, c_hf), c["bar"])
+
+
+def test_exactly_zero_quartets(ch_engines):
+    """D and M block-diagonal per atom: every density quartet with an odd mix of centres is exactly zero and is skipped."""
+    c = gh.ch_case(0.25, False, True)
+    M = spin_density(c, blocked=True)
+    assert np.count_nonzero(c["D"]) < c["D"].size and np.count_nonzero(M) < M.size
+    rows = ch_engines[False].per_shell_spin(_dev(c["D"]), _dev(M), 0.25).cpu().numpy()
+    gh.check("spin CH/def2-TZVP block-diagonal D, M c_hf 0.25 per shell", rows,
+             integrals.grad2e_spin(c["shells"], c["D"], M, 0.25, per_shell=True), c["bar"])
+
+
+def test_contracted_s_and_p():
+    sh = gh.molecule(gh.H2O_STO)[2]
+    D, M = gh.random_density(sh.nao), gh.random_density(sh.nao, seed=23)
+    bar = gh.reorder_bar(gh.H2O_STO, D, 0.25, integrals.grad2e(sh, D, 0.25))
+    eng = integrals.DeviceGrad2e(sh)
+    gh.check("spin H2O/STO-3G c_hf 0.25 per shell", eng.per_shell_spin(_dev(D), _dev(M), 0.25).cpu().numpy(),
+             integrals.grad2e_spin(sh, D, M, 0.25, per_shell=True), bar)
+    eng.close()
+
+
+def test_without_a_spin_density_it_is_the_closed_shell_entry(ch_engines):
+    c = gh.ch_case(0.25)
+    d_D = _dev(c["D"])
+    eng = ch_engines[False]
+    a = eng.per_shell(d_D, 0.25).cpu().numpy()
+    b = eng.per_shell_spin(d_D, torch.zeros_like(d_D), 0.25).cpu().numpy()
+    err = np.abs(a - b).max() / np.abs(a).max()
+    print(f"gpu DFT_Grad2eSpin(D, 0, c) against DFT_Grad2e(D, c): {err:.2e}")
+    assert err <= 1e-14
+
+
+def test_reproducible_and_the_closed_shell_entry_is_left_alone(ch_engines):
+    c = gh.ch_case(0.25)
+    eng = ch_engines[False]
+    d_D, d_M = _dev(c["D"]), _dev(spin_density(c))
+    before = eng.per_shell(d_D, 0.25).clone()
+    a = eng.per_shell_spin(d_D, d_M, 0.25).clone()
+    after = eng.per_shell(d_D, 0.25).clone()
+    b = eng.per_shell_spin(d_D, d_M, 0.25).clone()
+    out = torch.full((c["shells"].nshell, 3), 7.0, dtype=torch.float64, device="cuda")
+    assert eng.per_shell_spin(d_D, d_M, 0.25, out=out) is out
+    assert torch.equal(a, b) and torch.equal(a, out)
+    assert torch.equal(before, after)
+    assert not torch.equal(a, before)
+
+
+def test_translational_invariance_on_the_device(ch_engines):
+    c = gh.ch_case(0.25)
+    rows = ch_engines[False].per_shell_spin(_dev(c["D"]), _dev(spin_density(c)), 0.25).cpu().numpy()
+    net = np.abs(rows.sum(axis=0)).max() / np.abs(rows).max()
+    print(f"gpu grad2e spin CH/def2-TZVP c_hf 0.25: |sum over shells| / max|row| {net:.2e}")
+    assert net <= 1e-10
+
+
+def test_refusals(ch_engines):
+    c = gh.ch_case(0.0)
+    eng = ch_engines[False]
+    d_D = _dev(c["D"])
+    out = torch.zeros((c["shells"].nshell, 3), dtype=torch.float64, device="cuda")
+    u64 = ctypes.c_uint64
+    p, o = u64(d_D.data_ptr()), u64(out.data_ptr())
+    for args, word in (((u64(0), p, 0.0, o), b"density"), ((p, u64(0), 0.0, o), b"spin density"), ((p, p, 0.0, u64(0)), b"output")):
+        assert eng.lib.DFT_Grad2eSpin(eng._h, *args) == -1
+        assert word in eng.lib.DFT_Grad2eLastError(eng._h)
+    assert eng.lib.DFT_Grad2eSpin(None, p, p, 0.0, o) == -1
+    skew = np.array(c["D"])
+    skew[0, 1] += 1e-3
+    with pytest.raises(ValueError, match="symmetric"):
+        eng.grad_spin(c["D"], skew, 0.0)
