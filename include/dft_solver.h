@@ -421,6 +421,43 @@ int DFT_ComputeXCGradientSpin(XCSolver *solver, long long ngrid, int nao, unsign
                               unsigned long long d_ao_grad_ptr, unsigned long long d_ao_hess_ptr,
                               unsigned long long d_out_ptr);
 
+/* Grid response of the nuclear gradient (csrc/becke.hip): what the derivative at fixed points and weights leaves out.
+ * With Exc = sum_g w0_g cell_g e_g -- w0 the atomic radial x angular weight, cell_g = P_own(r_g) / sum_C P_C(r_g) the
+ * Becke cell function of the point's own atom (three smoothing iterations, radius adjustment a_CD clipped to +-1/2),
+ * e_g the energy per volume -- the entries below give e_g and sum_g f_g D_B cell_g for the caller's f_g = w0_g e_g.
+ * DFT_ComputeXCEnergyDensity: d_e_out (ngrid) receives e_g of the density of dm, WITHOUT the weight: sum_g w_g e_g is the
+ * Exc DFT_ComputeXC returns.  The density kernels of the sweep with the sweep's choices ("path", nao, plane size) into
+ * planes of this entry, then "xc_edens": the body the sweep's pointwise kernel runs for the solver's type with unit
+ * weight, so the density cut-off, "quirks" and the mix weights are the sweep's.
+ * DFT_ComputeXCEnergyDensitySpin: the same of DFT_ComputeXCSpin(dm_a, dm_b): the density kernels on dm_a and on dm_b and
+ * the spin-resolved body; it refuses what DFT_ComputeXCSpin refuses ("quirks" = 1 with vwn5_c / pbe_c).
+ * Both are asynchronous on the solver's stream, never the one-kernel plan, never a recorded graph; prepared DFT_Fxc*
+ * tables (all slots) and later DFT_ComputeXC* results are left bit for bit as they were.  d_ao_grad may be 0 for an
+ * LDA-class solver.
+ * DFT_BeckeWeightGradient: d_out (natm, 3) receives sum_g f_g D_B cell_g, where D_B cell_g is the derivative of cell_g by
+ * R_B at FIXED r_g for B other than the point's owner, and minus the sum of those for the owner (the point moves with its
+ * owner and the cell function is translationally invariant), so the rows of d_out sum to zero.  atom_xyz (natm, 3) bohr
+ * and atom_radius (natm; the Bragg radius in bohr: a_CD is made of sqrt(radius) as grid_gen.becke_weights makes it) are
+ * HOST arrays; d_coords (ngrid, 3) fp64, d_owner (ngrid) int32 in [0, natm) (values outside are clamped, the caller
+ * vouches for them), d_f (ngrid) fp64; d_cell_out (ngrid) receives cell_g, or is 0.  "becke_wgrad": a workgroup keeps the
+ * distances and the cell functions of a tile of points in LDS -- 64 points up to 60 atoms, 32 up to 120, 16 up to 240, 8
+ * beyond -- and every (point, B) pair walks the atoms C once (fp64 vector ALU, O(natm^2) per point, no screening of
+ * distant atoms); one (natm, 3) slab per workgroup and a fixed-order slab sum: no floating-point atomics, a call is
+ * bitwise reproducible.  No formula divides by a cell function or a switching factor that can be zero; a point on a
+ * nucleus is served.  natm above 1005 is refused (the tile no longer fits 160 KB of LDS).  Asynchronous on the solver's
+ * stream, except that a call with other atoms than the last one uploads its tables and waits for that.
+ * All return 0, or -1 with DFT_GetLastError (nothing aborts): a null pointer, bad sizes, a null ao_grad on a gradient
+ * solver, the "quirks" case, a radius that is not positive, coinciding atoms, natm too large.  Added without a change of
+ * DFT_GetVersion (it stays 5): look the symbols up. */
+int DFT_ComputeXCEnergyDensity(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr,
+                               unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr, unsigned long long d_e_out_ptr);
+int DFT_ComputeXCEnergyDensitySpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr,
+                                   unsigned long long d_dm_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
+                                   unsigned long long d_e_out_ptr);
+int DFT_BeckeWeightGradient(XCSolver *solver, long long ngrid, int natm, const double *atom_xyz, const double *atom_radius,
+                            unsigned long long d_coords_ptr, unsigned long long d_owner_ptr, unsigned long long d_f_ptr,
+                            unsigned long long d_cell_out_ptr, unsigned long long d_out_ptr);
+
 /* Columns of the electron-repulsion matrix on the device: all (ij|kl) with k in shell C and l in shell D, for every
  * i >= j -- what the integral-direct pivoted Cholesky factorisation of the ERI asks for per pivot (cholesky.py; the
  * reference builds the whole tensor on the host with PySCF, `mol.intor('int2e')` at grid.py:65).  Device counterpart

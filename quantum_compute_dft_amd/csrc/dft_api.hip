@@ -34,6 +34,7 @@
 #include "xc_response_pol_launch.hpp"
 #include "xc_spin_launch.hpp"
 #include "xc_grad_launch.hpp"
+#include "becke_launch.hpp"
 
 using namespace qcdft;
 
@@ -183,6 +184,12 @@ struct XCSolver {
     // GGA: profiles/xc_gradient_spin_time.txt); 0: k_xc_grad once per spin into two slab sets, what the tests hold the kernel to
     int xcg_spin_fused = 1;
     DevBuf xcgs_dp[2], xcgs_slabs;
+    // DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin: the density planes of the entry (of the two spins), its own again
+    Planes xce[2];
+    // DFT_BeckeWeightGradient: [atoms (natm, 3) | a_CD (natm, natm) | 1 / R_CD (natm, natm)] on the device and the host copy they
+    // were made from (uploaded again only when the atoms change), and the slabs of the kernel
+    DevBuf becke_tab, becke_slabs;
+    std::vector<double> becke_tab_host;
     std::string last_error;
     std::vector<Timing> timings;
     size_t n_timed = 0;
@@ -1456,6 +1463,106 @@ bool xc_gradient_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, cons
                                          s->xcgs_slabs.d(), out), "XC spin gradient launch");
 }
 
+// The energy per volume of the functional at the density of dm (DFT_ComputeXCEnergyDensity): the density kernels of the
+// sweep with the sweep's choices and k_xc_edens, the body of the sweep's pointwise kernel with unit weight, into planes of
+// this entry.  Never the one-kernel plan, never recorded; asynchronous on the solver's stream.
+bool xc_energy_density(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *ao_grad, double *e_out)
+{
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
+    if (!dm || !ao || !e_out) { set_error(s, "DFT_ComputeXCEnergyDensity needs dm, the AO values and the output"); return false; }
+    const bool gga = s->needs_grad;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
+    const Planes &p = s->xce[0];
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->xce[0], false, ngrid, WS_GRAD | WS_SIGMA)) return false;
+    launch_density(s, P, ngrid, nao, dm, ao, s->dsym.d(), p.rho.d(), p.grad.d(), p.sigma.d());
+    if (!hip_ok(s, hipGetLastError(), "energy density: density launch")) return false;
+    ScopedTimer t(s, "xc_edens");
+    return hip_ok(s, launch_xc_edens(s->stream, xc_type_index(s), gga, s->mix.c, s->quirks, ngrid, p.rho.d(), p.sigma.d(), p.grad.d(), e_out),
+                  "energy density launch");
+}
+
+// The same of an open-shell state (DFT_ComputeXCEnergyDensitySpin): the density kernels on dm_a and dm_b as
+// DFT_ComputeXCSpin runs them and the spin-resolved body with unit weight; DFT_ComputeXCSpin's refusal.
+bool xc_energy_density_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
+                            const double *ao_grad, double *e_out)
+{
+    if (!enter(s, ngrid, nao, ao_grad)) return false;
+    if (!dm_a || !dm_b || !ao || !e_out) {
+        set_error(s, "DFT_ComputeXCEnergyDensitySpin needs both density matrices, the AO values and the output");
+        return false;
+    }
+    if (!spin_quirks_ok(s, "DFT_ComputeXCEnergyDensitySpin")) return false;
+    const bool gga = s->needs_grad;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
+    Planes &a = s->xce[0], &b = s->xce[1];
+    if (!reserve_dsym(s, P) || !reserve_planes(s, a, false, ngrid, WS_GRAD | WS_SIGMA) || !reserve_planes(s, b, false, ngrid, WS_GRAD))
+        return false;
+    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, a, b, s->dsym.d(), s->dsym.d(), a.grad.d(), b.grad.d());
+    if (!hip_ok(s, hipGetLastError(), "spin energy density: density launch")) return false;
+    ScopedTimer t(s, "xc_edens_spin");
+    return hip_ok(s, launch_xc_edens_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
+                                          gga ? b.grad.d() : nullptr, e_out), "spin energy density launch");
+}
+
+// sum_g f_g D_B cell_g (DFT_BeckeWeightGradient, becke.hip).  The tables a_CD = clamp((rad_D / rad_C - rad_C / rad_D) / 4,
+// +-1/2) with rad = sqrt(radius) + 1e-200 (grid_gen.becke_weights, operation for operation) and 1 / R_CD are made here and
+// kept on the device until the atoms change; only then does the call wait for the stream.
+bool becke_weight_gradient(XCSolver *s, long ngrid, int natm, const double *atom_xyz, const double *atom_radius, const double *coords,
+                           const int *owner, const double *f, double *cell_out, double *out)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return false; }
+    if (ngrid <= 0 || natm <= 0) { set_error(s, "DFT_BeckeWeightGradient: bad sizes ngrid=%ld natm=%d", ngrid, natm); return false; }
+    if (!atom_xyz || !atom_radius || !coords || !owner || !f || !out) {
+        set_error(s, "DFT_BeckeWeightGradient needs the atom positions and radii, the coordinates, the owners, f and the output");
+        return false;
+    }
+    const BeckePlan B = becke_plan(s->num_cu, ngrid, natm);
+    if (B.lds > BECKE_LDS_MAX) {
+        set_error(s, "DFT_BeckeWeightGradient: natm=%d needs %zu bytes of LDS per workgroup for a tile of %d points, above the %zu a "
+                     "workgroup has; distant atoms are not screened", natm, B.lds, B.tp, BECKE_LDS_MAX);
+        return false;
+    }
+    const size_t n2 = (size_t)natm * natm;
+    std::vector<double> tab(3 * (size_t)natm + 2 * n2);
+    double *xyz = tab.data(), *at = xyz + 3 * natm, *rt = at + n2;
+    std::vector<double> rad(natm);
+    for (int i = 0; i < natm; ++i) {
+        if (!(atom_radius[i] > 0.0) || !std::isfinite(atom_radius[i])) {
+            set_error(s, "DFT_BeckeWeightGradient: radius %g of atom %d is not positive", atom_radius[i], i);
+            return false;
+        }
+        rad[i] = std::sqrt(atom_radius[i]) + 1e-200;
+        for (int k = 0; k < 3; ++k) xyz[3 * i + k] = atom_xyz[3 * i + k];
+    }
+    for (int i = 0; i < natm; ++i)
+        for (int j = 0; j < natm; ++j) {
+            const double a = 0.25 * (rad[j] / rad[i] - rad[i] / rad[j]);
+            at[(size_t)i * natm + j] = std::min(0.5, std::max(-0.5, a));
+            const double dx = xyz[3 * i] - xyz[3 * j], dy = xyz[3 * i + 1] - xyz[3 * j + 1], dz = xyz[3 * i + 2] - xyz[3 * j + 2];
+            const double R = std::sqrt(dx * dx + dy * dy + dz * dz);
+            if (i != j && !(R > 0.0 && std::isfinite(R))) {
+                set_error(s, "DFT_BeckeWeightGradient: atoms %d and %d coincide (or a position is not finite)", i, j);
+                return false;
+            }
+            rt[(size_t)i * natm + j] = i == j ? 1.0 : 1.0 / R;
+        }
+    if (!reserve(s, s->becke_slabs, sizeof(double) * (size_t)B.nwg * 3 * natm, "hipMalloc(Becke slabs)", false)) return false;
+    if (tab != s->becke_tab_host) {
+        s->becke_tab_host.clear();
+        if (!reserve(s, s->becke_tab, sizeof(double) * tab.size(), "hipMalloc(Becke tables)", false) ||
+            !hip_ok(s, hipMemcpyAsync(s->becke_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s->stream), "upload Becke tables") ||
+            !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
+            return false;
+        s->becke_tab_host.swap(tab);
+    }
+    const double *d_xyz = s->becke_tab.d(), *d_at = d_xyz + 3 * natm, *d_rt = d_at + n2;
+    ScopedTimer t(s, "becke_wgrad");
+    return hip_ok(s, launch_becke_wgrad(s->stream, B, ngrid, natm, d_xyz, d_at, d_rt, coords, owner, f, cell_out, s->becke_slabs.d(), out),
+                  "Becke weight gradient launch");
+}
+
 } // namespace
 
 extern "C" {
@@ -2008,6 +2115,34 @@ int DFT_ComputeXCGradientSpin(XCSolver *s, long long ngrid, int nao, unsigned lo
     DeviceGuard dg(s);
     return xc_gradient_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
                             (const double *)d_weights, (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+}
+
+int DFT_ComputeXCEnergyDensity(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
+                               unsigned long long d_ao_grad, unsigned long long d_e_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_energy_density(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_ao_grad,
+                             (double *)d_e_out) ? 0 : -1;
+}
+
+int DFT_ComputeXCEnergyDensitySpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                                   unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_e_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_energy_density_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
+                                  (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
+}
+
+int DFT_BeckeWeightGradient(XCSolver *s, long long ngrid, int natm, const double *atom_xyz, const double *atom_radius,
+                            unsigned long long d_coords, unsigned long long d_owner, unsigned long long d_f,
+                            unsigned long long d_cell_out, unsigned long long d_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return becke_weight_gradient(s, (long)ngrid, natm, atom_xyz, atom_radius, (const double *)d_coords, (const int *)d_owner,
+                                 (const double *)d_f, (double *)d_cell_out, (double *)d_out) ? 0 : -1;
 }
 
 int DFT_ComputeXCDirect(XCSolver *s, long long ngrid, int nao, int nshell, const double *shl_xyz,

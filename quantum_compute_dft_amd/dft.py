@@ -75,9 +75,12 @@ def write_charge_force_rows(path, charges_bohr, forces, unit="angstrom"):
             fh.write(f"{x * scale:.10f} {y * scale:.10f} {z * scale:.10f} {q:.12e} {f[0]:.12e} {f[1]:.12e} {f[2]:.12e}\n")
 
 
-def print_gradient(symbols, g):
-    """The table of atoms with dE/dR (Ha/bohr) and the net force the fixed quadrature leaves."""
-    print("Nuclear gradient dE/dR (Ha/bohr), at fixed quadrature points and weights:")
+def print_gradient(symbols, g, grid_response=False):
+    """The table of atoms with dE/dR (Ha/bohr) and the net force the fixed quadrature leaves (none with the grid response)."""
+    if grid_response:
+        print("Nuclear gradient dE/dR (Ha/bohr), the derivative includes the grid (points and Becke weights follow the atoms):")
+    else:
+        print("Nuclear gradient dE/dR (Ha/bohr), at fixed quadrature points and weights:")
     for k, (s, r) in enumerate(zip(symbols, g), 1):
         print(f"  {k:3d} {s:2s} {r[0]:+16.10f} {r[1]:+16.10f} {r[2]:+16.10f}")
     print("  sum    " + " ".join(f"{x:+16.10f}" for x in g.sum(axis=0)) + f"   max|g| = {np.abs(g).max():.2e}  rms = {np.sqrt(np.mean(g * g)):.2e}")
@@ -169,6 +172,11 @@ def build_parser():
     p.add_argument("--grad2e", default="host", choices=["host", "device"],
                    help="with --gradient / --optimize: where the two-electron term of the gradient is computed; host (default): "
                         "integrals.c::qc_grad2e on the CPU share; device: DFT_Grad2e (csrc/grad2e.hip; DFT_Grad2eSpin with --open-shell-gradient), in every step of --optimize too")
+    p.add_argument("--grid-response", action="store_true",
+                   help="with --gradient / --optimize: add the grid response to the gradient (term xc_grid: the motion of the quadrature "
+                        "points with their atoms and the derivatives of the Becke weights, DFT_ComputeXCEnergyDensity and "
+                        "DFT_BeckeWeightGradient), in every step of --optimize too; the gradient then sums to zero over the atoms at "
+                        "any grid level.  Works with --open-shell-gradient and either --grad2e; one rank, no --efield")
     p.add_argument("--charge", type=int, default=0, metavar="Q", help="charge of the molecule (electrons = sum Z - Q); an odd count needs --spin")
     p.add_argument("--json", default=None, help="also append the run's one-line JSON record to this file")
     p.add_argument("--dist-backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 (nccl = RCCL)")
@@ -212,6 +220,8 @@ def main(argv=None):
         p.error("--open-shell-gradient goes with --spin N")
     if args.open_shell_gradient and not (args.gradient or args.optimize):
         p.error("--open-shell-gradient goes with --gradient or --optimize")
+    if args.grid_response and not (args.gradient or args.optimize):
+        p.error("--grid-response goes with --gradient or --optimize")
     if uks:
         if (args.excitations or args.polarizability or args.dipole) and not args.open_shell_response:
             p.error("--excitations, --polarizability and --dipole take a closed-shell reference: not available after an unrestricted (--spin) run "
@@ -382,8 +392,9 @@ def main(argv=None):
     if (args.gradient or args.optimize) and res["converged"]:
         from . import gradients, optimize
         nuclear_gradient = gradients.nuclear_gradient_uks if uks else gradients.nuclear_gradient
-        grad, grad_terms = nuclear_gradient(inp, res, backend, args.functional, two_electron=args.grad2e)
-        print_gradient(inp.symbols, grad)
+        grad_kw = dict(two_electron=args.grad2e, grid_response=True) if args.grid_response else dict(two_electron=args.grad2e)
+        grad, grad_terms = nuclear_gradient(inp, res, backend, args.functional, **grad_kw)
+        print_gradient(inp.symbols, grad, args.grid_response)
     if args.optimize and res["converged"]:
         def energy_and_gradient(xyz):
             inp_k = inputs.build(atom_path, args.basis, args.grid_level, device=device, verbose=False, eri_mode=args.eri, chol_tol=args.chol_tol,
@@ -398,7 +409,7 @@ def main(argv=None):
                 res_k = scf.run_scf(inp_k, be_k, args.functional, log=None)
             if not res_k["converged"]:
                 raise RuntimeError("--optimize: the SCF did not converge at a geometry of the optimisation")
-            g_k = nuclear_gradient(inp_k, res_k, be_k, args.functional, two_electron=args.grad2e)[0]
+            g_k = nuclear_gradient(inp_k, res_k, be_k, args.functional, **grad_kw)[0]
             be_k.close()
             return res_k["E_tot"], g_k
         opt = optimize.bfgs(energy_and_gradient, inp.atom_xyz, max_steps=args.opt_max_steps, log=print)
@@ -406,7 +417,7 @@ def main(argv=None):
         optimize.write_xyz(opt_path, inp.symbols, opt["xyz"], f"{args.functional}/{args.basis} E = {opt['energy']:.10f} Ha after {opt['steps']} steps")
         print(f"Geometry optimisation {'converged' if opt['converged'] else 'NOT converged'} after {opt['steps']} steps "
               f"({opt['evaluations']} energies and gradients): E = {opt['energy']:.10f} Ha; geometry written to {opt_path}")
-        print_gradient(inp.symbols, opt["gradient"])
+        print_gradient(inp.symbols, opt["gradient"], args.grid_response)
     import json
     record = {"functional": args.functional, "molecule": os.path.splitext(atom_file)[0], "basis": args.basis, "grid_level": args.grid_level,
               "nao": int(inp.shells.nao), "ngrid": int(inp.grids.size), "nocc": int(inp.nocc), "n_gpus": world, "eri": args.eri,
@@ -443,6 +454,8 @@ def main(argv=None):
         record["gradient_terms"] = {k: v.tolist() for k, v in grad_terms.items()} if grad_terms is not None else None
         record["net_force"] = grad.sum(axis=0).tolist() if grad is not None else None
         record["grad2e_engine"] = args.grad2e
+        if args.grid_response:
+            record["grid_response"] = True
     if args.optimize:
         record["opt_steps"] = int(opt["steps"]) if opt is not None else None
         record["opt_energies"] = opt["energies"] if opt is not None else None

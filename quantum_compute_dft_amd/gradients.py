@@ -182,6 +182,92 @@ def xc_gradient_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad, ao_hess=
     return G
 
 
+def xc_energy_density_host(functional, dm, ao, ao_grad=None, quirks=True):
+    """e_g (ngrid,) of DFT_ComputeXCEnergyDensity from AO planes in numpy: the energy per volume of the sweep's point body at the
+    density of dm, without the weight (response.point_host with unit weights)."""
+    _, _, gga = response._kind(functional)
+    if gga and ao_grad is None:
+        raise ValueError("ao_grad is needed for a gradient-corrected functional")
+    ao = np.ascontiguousarray(ao, dtype=np.float64)
+    rho, g = response._density(np.asarray(dm, dtype=np.float64), ao, np.ascontiguousarray(ao_grad, dtype=np.float64) if gga else None)
+    if gga:
+        sigma = np.einsum("gk,gk->g", g, g)
+    else:
+        g, sigma = np.zeros((ao.shape[0], 3)), np.zeros(ao.shape[0])
+    return response.point_host(functional, rho, sigma, g, np.ones(ao.shape[0]), quirks)[0]
+
+
+def xc_energy_density_spin_host(functional, dm_a, dm_b, ao, ao_grad=None):
+    """e_g (ngrid,) of DFT_ComputeXCEnergyDensitySpin from AO planes in numpy (response.point_spin_host, row 0)."""
+    _, _, gga = response._kind(functional)
+    if gga and ao_grad is None:
+        raise ValueError("ao_grad is needed for a gradient-corrected functional")
+    ao = np.ascontiguousarray(ao, dtype=np.float64)
+    gr = np.ascontiguousarray(ao_grad, dtype=np.float64) if gga else None
+    (ra, ga), (rb, gb) = (response._density(np.asarray(d, dtype=np.float64), ao, gr) for d in (dm_a, dm_b))
+    return response.point_spin_host(functional, ra, rb, ga, gb)[0]
+
+
+def _grid_of(grids, symbols, atom_xyz, who):
+    """(owner, atomic weights, charges) of a grid that says which atom each point moves with, checked against the atoms."""
+    own, w0 = getattr(grids, "atom_index", None), getattr(grids, "atomic_weights", None)
+    if own is None or w0 is None:
+        raise ValueError(f"{who}: the grid carries no atom_index / atomic_weights (grid_gen.Grids keeps both): it does not say which "
+                         "atom a point moves with")
+    own, w0 = np.asarray(own), np.asarray(w0, dtype=np.float64)
+    natm, ng = np.asarray(atom_xyz).reshape(-1, 3).shape[0], np.asarray(grids.coords).reshape(-1, 3).shape[0]
+    if len(symbols) != natm or own.shape != (ng,) or w0.shape != (ng,) or (ng and (own.min() < 0 or own.max() >= natm)):
+        raise ValueError(f"{who}: the grid's atom_index / atomic_weights do not match the {natm} atoms and {ng} points")
+    return own.astype(np.int64), w0, [basis.atomic_number(s) for s in symbols]
+
+
+def _xc_grid_response_host(grids, symbols, atom_xyz, gradient, edens, who):
+    """-sum_mu G^(A)[mu] + sum_g w0_g e_g D_A cell_g: gradient(rows) and edens(rows) evaluate G and e on a block of rows."""
+    from . import grid_gen
+    own, w0, charges = _grid_of(grids, symbols, atom_xyz, who)
+    xyz = np.asarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros_like(xyz)
+    e = np.zeros(own.shape[0])
+    cut = np.flatnonzero(np.diff(own)) + 1
+    for lo, hi in zip(np.concatenate([[0], cut]), np.concatenate([cut, [own.shape[0]]])):
+        if hi > lo:
+            rows = slice(int(lo), int(hi))
+            out[own[lo]] -= gradient(rows).sum(axis=0)
+            e[rows] = edens(rows)
+    return out + grid_gen.becke_weight_gradient_host(grids.coords, own, xyz, charges, w0 * e)
+
+
+def xc_grid_response_host(functional, dm, shells, grids, symbols, atom_xyz, quirks=True, planes=None):
+    """(natm, 3): the grid response of the XC term of dE/dR_A, the host counterpart of scf.HipBackend.xc_grid_response.  With
+    Exc = sum_g w0_g cell_g e_g, the points r_g = R_own(g) + t_g moving rigidly with their owners:
+
+        xc_grid[A] = -sum_mu G^(A)[mu] + sum_g w0_g e_g D_A cell_g,
+
+    G^(A) = xc_gradient_host on the rows atom A owns (the motion of A's points: grad_r e = -sum_B de/dR_B at fixed r), e_g
+    the energy per volume (response.point_host with unit weights) and the last sum grid_gen.becke_weight_gradient_host.
+    planes: (ao, ao_grad, ao_hess) at grids.coords when the caller has them (evaluated here otherwise)."""
+    f = functionals.resolve(functional)
+    ao, gr, hs = planes if planes is not None else ao_planes_host(shells, grids.coords)
+    w = np.asarray(grids.weights, dtype=np.float64)
+    gga = f.needs_gradient
+    return _xc_grid_response_host(
+        grids, symbols, atom_xyz,
+        lambda r: xc_gradient_host(f, dm, ao[r], w[r], gr[:, r], hs[:, r] if gga else None, quirks),
+        lambda r: xc_energy_density_host(f, dm, ao[r], gr[:, r] if gga else None, quirks), "xc_grid_response_host")
+
+
+def xc_grid_response_spin_host(functional, dm_a, dm_b, shells, grids, symbols, atom_xyz, planes=None):
+    """xc_grid_response_host for an open-shell state: xc_gradient_spin_host per atom block and response.point_spin_host's e."""
+    f = functionals.resolve(functional)
+    ao, gr, hs = planes if planes is not None else ao_planes_host(shells, grids.coords)
+    w = np.asarray(grids.weights, dtype=np.float64)
+    gga = f.needs_gradient
+    return _xc_grid_response_host(
+        grids, symbols, atom_xyz,
+        lambda r: xc_gradient_spin_host(f, dm_a, dm_b, ao[r], w[r], gr[:, r], hs[:, r] if gga else None),
+        lambda r: xc_energy_density_spin_host(f, dm_a, dm_b, ao[r], gr[:, r] if gga else None), "xc_grid_response_spin_host")
+
+
 def sum_over_atoms(shells, G):
     """(natm, 3): G (nao, 3) summed over the functions each atom owns (the shell-to-atom map of the shell table)."""
     G = np.asarray(G, dtype=np.float64)
@@ -243,9 +329,9 @@ def _fock(inp, backend, f, dm):
 _QUIRKY = ("vwn5_c", "pbe_c")
 
 
-def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two_electron="host"):
+def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two_electron="host", grid_response=False):
     """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged closed-shell state `scf_result` (scf.run_scf) and its
-    breakdown {"one_electron", "two_electron", "xc", "nuclear", "external"}, each (natm, 3).  The derivative at FIXED
+    breakdown {"one_electron", "two_electron", "xc", "nuclear", "external"}, each (natm, 3).  By default the derivative at FIXED
     quadrature points and weights: the Becke-weight derivatives and the motion of the points with their atoms are not
     included, so the XC term -- and with it the total -- is not translationally invariant; sum_A g_A measures what is
     left out.  `backend`: what the SCF ran on.  scf.HipBackend sweeps the XC part on the device (xc_gradient); any other
@@ -254,7 +340,10 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
     (inp.point_charges) includes the basis term over the external charges and the nuclei--charge repulsion ("external");
     the forces on the charges themselves are properties.point_charge_forces'.  functional / quirks default to the
     backend's.  `two_electron`: "host" (integrals.grad2e, the default) or "device" (backend.grad2e: the derivative quartets
-    made and contracted on the device, csrc/grad2e.hip); every other term is the same either way."""
+    made and contracted on the device, csrc/grad2e.hip); every other term is the same either way.  `grid_response` = True adds
+    the term "xc_grid": the motion of the quadrature points with their atoms and the derivatives of the Becke weights
+    (backend.xc_grid_response on scf.HipBackend, xc_grid_response_host otherwise); g is then the derivative of the energy as the
+    grid follows the atoms, and sums to zero over the atoms.  Without it everything is as it was."""
     if two_electron not in ("host", "device"):
         raise ValueError(f"nuclear_gradient: two_electron must be 'host' or 'device', not {two_electron!r}")
     if two_electron == "device" and not hasattr(backend, "grad2e"):
@@ -275,6 +364,8 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
         raise ValueError("nuclear_gradient: with quirks = 1 the shipped vwn5_c / pbe_c potentials are not the derivatives of their "
                          "energies, so the converged state is not stationary and the analytic gradient is not the energy's; "
                          "run with --quirks 0")
+    if grid_response:
+        _grid_of(inp.grids, inp.symbols, inp.atom_xyz, "nuclear_gradient")          # refuses a grid that does not say which atom a point moves with
     dm = np.asarray(scf_result["dm"], dtype=np.float64)
     dm = np.ascontiguousarray(0.5 * (dm + dm.T))
     sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
@@ -288,14 +379,22 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
              "two_electron": backend.grad2e(dm, f.c_hf) if two_electron == "device" else integrals.grad2e(sh, dm, f.c_hf),
              "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
     if any(w != 0.0 for w in wv):
+        planes = None
         if hasattr(backend, "xc_gradient"):
             G = backend.xc_gradient(dm)
         else:
-            ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
+            planes = ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
             G = xc_gradient_host(f, dm, ao, inp.grids.weights, gr, hs if f.needs_gradient else None, quirks)
         terms["xc"] = sum_over_atoms(sh, G)
+        if grid_response:
+            if hasattr(backend, "xc_grid_response"):
+                terms["xc_grid"] = backend.xc_grid_response(dm)
+            else:
+                terms["xc_grid"] = xc_grid_response_host(f, dm, sh, inp.grids, inp.symbols, xyz, quirks, planes=planes)
     else:
         terms["xc"] = np.zeros_like(xyz)
+        if grid_response:
+            terms["xc_grid"] = np.zeros_like(xyz)
     pc = getattr(inp, "point_charges", None)
     if pc is not None and len(pc):
         terms["external"] = integrals.grad1e(sh, pc[:, :3], pc[:, 3], dm, W)[2] + _pair_repulsion_gradient(xyz, z, pc[:, :3], pc[:, 3])
@@ -304,7 +403,7 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
     return sum(terms.values()), terms
 
 
-def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron="host"):
+def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron="host", grid_response=False):
     """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged unrestricted state `uks_result` (scf.run_uks), with
     nuclear_gradient's five terms and its conventions (fixed quadrature points and weights).  With D = D_a + D_b:
 
@@ -315,7 +414,8 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
         xc             backend.xc_gradient_spin (DFT_ComputeXCGradientSpin) where the backend has it, xc_gradient_spin_host on
                        planes evaluated here otherwise
 
-    A spin without electrons has D_s = 0 and contributes nothing.  Point charges are served through "external"."""
+    A spin without electrons has D_s = 0 and contributes nothing.  Point charges are served through "external".
+    `grid_response` = True adds "xc_grid" as in nuclear_gradient (backend.xc_grid_response_spin / xc_grid_response_spin_host)."""
     if two_electron not in ("host", "device"):
         raise ValueError(f"nuclear_gradient_uks: two_electron must be 'host' or 'device', not {two_electron!r}")
     if two_electron == "device" and not hasattr(backend, "grad2e_spin"):
@@ -334,6 +434,8 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
     if bool(getattr(backend, "quirks", getattr(backend, "q", False))) and any(wv[functionals.COMPONENTS.index(c)] != 0.0 for c in _QUIRKY):
         raise ValueError("nuclear_gradient_uks: the spin-resolved potentials are the derivatives of the energy, but with quirks = 1 the "
                          "ground state solved the shipped vwn5_c / pbe_c potentials, which are not; run with --quirks 0")
+    if grid_response:
+        _grid_of(inp.grids, inp.symbols, inp.atom_xyz, "nuclear_gradient_uks")
     from scipy.linalg import eigh
     S = inp.S
     dms = [np.asarray(uks_result[k], dtype=np.float64) for k in ("dm_a", "dm_b")]
@@ -360,14 +462,22 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
                              else integrals.grad2e_spin(sh, dm, ms, f.c_hf),
              "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
     if any(w != 0.0 for w in wv):
+        planes = None
         if hasattr(backend, "xc_gradient_spin"):
             G = backend.xc_gradient_spin(dms[0], dms[1])
         else:
-            ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
+            planes = ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
             G = xc_gradient_spin_host(f, dms[0], dms[1], ao, inp.grids.weights, gr, hs if f.needs_gradient else None)
         terms["xc"] = sum_over_atoms(sh, G)
+        if grid_response:
+            if hasattr(backend, "xc_grid_response_spin"):
+                terms["xc_grid"] = backend.xc_grid_response_spin(dms[0], dms[1])
+            else:
+                terms["xc_grid"] = xc_grid_response_spin_host(f, dms[0], dms[1], sh, inp.grids, inp.symbols, xyz, planes=planes)
     else:
         terms["xc"] = np.zeros_like(xyz)
+        if grid_response:
+            terms["xc_grid"] = np.zeros_like(xyz)
     pc = getattr(inp, "point_charges", None)
     if pc is not None and len(pc):
         terms["external"] = integrals.grad1e(sh, pc[:, :3], pc[:, 3], dm, W)[2] + _pair_repulsion_gradient(xyz, z, pc[:, :3], pc[:, 3])

@@ -122,8 +122,87 @@ def becke_weights(coords, atom_index, atom_xyz, charges, device="cpu", block=655
     return out
 
 
+def bragg_radii_bohr(charges):
+    """The Bragg-Slater radius of every atom in bohr: what becke_weights makes the radius adjustment a_ij of."""
+    return np.array([_BRAGG[int(z)] / BOHR for z in charges], dtype=np.float64)
+
+
+def becke_weight_gradient_host(coords, owner, atom_xyz, charges, f, block=None):
+    """(natm, 3): sum_g f_g D_B cell_g, cell_g = becke_weights' cell function of point g's owner.  D_B cell_g is the
+    derivative by R_B at FIXED r_g for B != owner(g) and minus the sum of those for B = owner(g): the point moves rigidly
+    with its owner and the cell function is translationally invariant, so the rows sum to zero.  The host counterpart of
+    DFT_BeckeWeightGradient (csrc/becke.hip), from the analytic formulas in numpy.  With d_C = |r - R_C|, u_C = (r - R_C) / d_C
+    (0 on the nucleus), n_CD = (R_C - R_D) / R_CD, mu_CD = (d_C - d_D) / R_CD, nu = mu + a_CD (1 - mu^2), p(x) = (3 x - x^3) / 2,
+    s_CD = (1 - p(p(p(nu)))) / 2, P_C = prod_{D != C} s_CD and t_CD = ds_CD / dmu_CD:
+
+        dP_C/dR_B = q_CB (u_B + mu_CB n_CB)  (B != C),   dP_C/dR_C = -sum_D q_CD (u_C + mu_CD n_CD),   q_CD = (prod_{D' != C, D} s_CD') t_CD / R_CD,
+        dcell/dR_B = (dP_own/dR_B - cell sum_C dP_C/dR_B) / Z,   Z = sum_C P_C.
+
+    "The product without one factor" is formed from prefix and suffix products: nothing is divided by a cell function or a
+    switching factor (both are exactly 0 at points of ordinary grids)."""
+    R = np.ascontiguousarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+    C = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1, 3)
+    own = np.asarray(owner).astype(np.int64).reshape(-1)
+    f = np.asarray(f, dtype=np.float64).reshape(-1)
+    natm, ng = R.shape[0], C.shape[0]
+    if len(charges) != natm or own.shape[0] != ng or f.shape[0] != ng:
+        raise ValueError("becke_weight_gradient_host: coords, owner and f must have one entry per point, charges one per atom")
+    if ng and (own.min() < 0 or own.max() >= natm):
+        raise ValueError("becke_weight_gradient_host: an owner index is outside the atoms")
+    out = np.zeros((natm, 3))
+    if natm < 2 or ng == 0:
+        return out
+    rad = np.sqrt(bragg_radii_bohr(charges)) + 1e-200
+    rr = rad[:, None] / rad[None, :]
+    a = np.clip(0.25 * (rr.T - rr), -0.5, 0.5)
+    dR = R[:, None, :] - R[None, :, :]
+    Rij = np.sqrt(np.einsum("cdk,cdk->cd", dR, dR))
+    off = ~np.eye(natm, dtype=bool)
+    if np.any(Rij[off] == 0.0):
+        raise ValueError("becke_weight_gradient_host: two atoms coincide")
+    np.fill_diagonal(Rij, 1.0)
+    n = dR / Rij[:, :, None]                                        # n_CD, zero on the diagonal
+    nb = int(block) if block else max(1, min(4096, 2_000_000 // (natm * natm)))
+    for lo in range(0, ng, nb):
+        c, o, fb = C[lo:lo + nb], own[lo:lo + nb], f[lo:lo + nb]
+        m = c.shape[0]
+        rv = c[:, None, :] - R[None, :, :]                          # (m, natm, 3)
+        d = np.sqrt(np.einsum("gck,gck->gc", rv, rv))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = np.where(d[:, :, None] > 0.0, rv / d[:, :, None], 0.0)
+        mu = (d[:, :, None] - d[:, None, :]) / Rij[None]            # (m, C, D)
+        nu = mu + a[None] * (1.0 - mu * mu)
+        p1 = (3.0 - nu * nu) * nu * 0.5
+        p2 = (3.0 - p1 * p1) * p1 * 0.5
+        p3 = (3.0 - p2 * p2) * p2 * 0.5
+        s = np.where(off[None], 0.5 * (1.0 - p3), 1.0)
+        t = -0.5 * (1.5 * (1.0 - p2 * p2)) * (1.5 * (1.0 - p1 * p1)) * (1.5 * (1.0 - nu * nu)) * (1.0 - 2.0 * a[None] * mu)
+        t = np.where(off[None], t, 0.0)
+        pre = np.ones_like(s)                                       # pre[.., D] = prod_{D' < D} s, suf[.., D] = prod_{D' > D} s
+        suf = np.ones_like(s)
+        pre[:, :, 1:] = np.cumprod(s[:, :, :-1], axis=2)
+        suf[:, :, :-1] = np.cumprod(s[:, :, :0:-1], axis=2)[:, :, ::-1]
+        P = pre[:, :, -1] * s[:, :, -1]
+        Z = P.sum(axis=1)
+        rows = np.arange(m)
+        cell = P[rows, o] / Z
+        q = pre * suf * t / Rij[None]                               # (m, C, D)
+        cc = -cell[:, None] / Z[:, None] * np.ones((1, natm))
+        cc[rows, o] += 1.0 / Z                                      # c_C = (delta_{C, own} - cell) / Z
+        cq = cc[:, :, None] * q                                     # c_C q_CB
+        W = cq - np.swapaxes(cq, 1, 2)                              # W_CB = c_C q_CB - c_B q_BC: dcell/dR_B = u_B sum_C W_CB + sum_C W_CB mu_CB n_CB
+        v = u * W.sum(axis=1)[:, :, None] + np.einsum("gcb,cbk->gbk", W * mu, n)
+        v[rows, o] = 0.0
+        v *= fb[:, None, None]
+        out += v.sum(axis=0)
+        np.subtract.at(out, o, v.sum(axis=1))
+    return out
+
+
 class Grids:
-    """`coords` (ngrid,3) bohr and `weights` (ngrid,), like PySCF's Grids after build()."""
+    """`coords` (ngrid,3) bohr and `weights` (ngrid,), like PySCF's Grids after build(); `atom_index` (ngrid,) the atom
+    each point belongs to and moves with, `atomic_weights` (ngrid,) its radial x angular weight before the Becke
+    partition (weights = atomic_weights x cell function)."""
 
     def __init__(self, symbols, coords_bohr, level=3, device="cpu"):
         self.symbols, self.atom_xyz, self.level = list(symbols), np.asarray(coords_bohr, dtype=np.float64), level
@@ -140,6 +219,7 @@ class Grids:
         self.coords = np.concatenate(pts)
         own = np.concatenate(own)
         w0 = np.concatenate(wts)
+        self.atomic_weights = w0
         if len(charges) > 1:
             w0 = w0 * becke_weights(self.coords, own, self.atom_xyz, charges, device=device)
         self.weights = w0

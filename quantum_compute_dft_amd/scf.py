@@ -393,6 +393,8 @@ class HipBackend:
         if ao_mode not in ("resident", "direct"):
             raise ValueError(f"ao_mode {ao_mode!r}: expected 'resident' or 'direct'")
         self.ao_mode, self.ao_chunk, self.shells, self.d_coords = ao_mode, int(ao_chunk), inp.shells, d_coords
+        # what the grid response of the nuclear gradient reads (xc_grid_response): the atoms and the grid's own bookkeeping
+        self._atoms, self._grids = (getattr(inp, "symbols", None), getattr(inp, "atom_xyz", None)), inp.grids
         # the sweep's density step through the occupied orbitals (DFT_ComputeXCOcc: the loop holds cocc with
         # dm = cocc cocc^T in every cycle, dft.py:181-182); False = the reference's call with the full matrix
         self.xc_occ = bool(xc_occ)
@@ -750,13 +752,18 @@ class HipBackend:
         d_a, d_b = self._dev(dm_a), self._dev(dm_b)
         return self._xc_gradient_slices(slice_rows, lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient_spin(m, self.nao, d_a, d_b, ao, w, out, gr, hs))
 
-    def _xc_gradient_slices(self, slice_rows, entry):
-        """The slicing xc_gradient and xc_gradient_spin share: entry(m, ao, w, d_out, gr, hs) is the library call of a slice."""
+    def _xc_gradient_slices(self, slice_rows, entry, block=None, after=None):
+        """The slicing xc_gradient and xc_gradient_spin share: entry(m, ao, w, d_out, gr, hs) is the library call of a slice.
+        block = (lo, hi): the rows of the grid to sweep (default: all of it); after(lo, hi, ao, gr), when given, runs behind
+        the entry of every slice on the same planes (the grid response takes the energy density there)."""
         if self.world > 1:
             raise ValueError("the XC gradient runs on one rank: the grid of this backend is sharded over several")
         if self.dm_factor:
             raise ValueError("the XC gradient takes the density matrix itself: run without dm_factor")
-        t, n, ng, s = self.torch, self.nao, self.ngrid, self.solver
+        t, n, s = self.torch, self.nao, self.solver
+        b_lo, b_hi = (0, self.ngrid) if block is None else (int(block[0]), int(block[1]))
+        ng = b_hi - b_lo
+        whole = ng == self.ngrid
         f64 = t.float64
         rows = int(slice_rows) if slice_rows else max(16, int(self.XC_GRADIENT_HESS_BYTES // (48 * n)) // 16 * 16)
         rows = max(1, min(rows, ng))
@@ -766,16 +773,16 @@ class HipBackend:
         d_hess = t.empty(6 * rows * n, dtype=f64, device=self.dev) if gga else None
         own_gr = self.d_gr is None
         own_ao = self.d_ao is None or own_gr        # DFT_EvalAO writes the values along with the gradients
-        d_gr_s = t.empty(3 * rows * n, dtype=f64, device=self.dev) if (own_gr or rows < ng) else None
+        d_gr_s = t.empty(3 * rows * n, dtype=f64, device=self.dev) if (own_gr or rows < ng or not whole) else None
         d_ao_s = t.empty(rows * n, dtype=f64, device=self.dev) if own_ao else None
-        for lo in range(0, ng, rows):
-            hi = min(lo + rows, ng)
+        for lo in range(b_lo, b_hi, rows):
+            hi = min(lo + rows, b_hi)
             m = hi - lo
             coords = self.d_coords[lo:hi]
             if own_gr:
                 ao, gr = d_ao_s[:m * n].view(m, n), d_gr_s[:3 * m * n].view(3, m, n)
                 s.eval_ao(self.shells, coords, m, ao, gr)
-            elif rows < ng:
+            elif rows < ng or not whole:
                 ao, gr = self.d_ao[lo:hi], d_gr_s[:3 * m * n].view(3, m, n)
                 gr.copy_(self.d_gr[:, lo:hi])
             else:
@@ -788,8 +795,73 @@ class HipBackend:
             entry(m, ao, self.d_w[lo:hi], d_out, gr, hs)
             t.cuda.synchronize()
             d_G += d_out
+            if after is not None:
+                after(lo, hi, ao, gr)
+                t.cuda.synchronize()
         t.cuda.synchronize()
         return d_G.cpu().numpy()
+
+    # ---- grid response of the nuclear gradient (gradients.py): one rank ---------------------------------------------
+    def xc_grid_response(self, dm, slice_rows=None):
+        """(natm, 3) as a numpy array: what the motion of the grid with the atoms adds to the XC term of dE/dR_A,
+
+            xc_grid[A] = -sum_mu G^(A)[mu] + sum_g w0_g e_g D_A cell_g,
+
+        G^(A) = xc_gradient's G on the rows of the grid atom A owns (the existing slicing per atom block: a block is cut
+        further when its Hessian planes exceed XC_GRADIENT_HESS_BYTES), e_g from DFT_ComputeXCEnergyDensity on the planes
+        of each slice, the second sum from DFT_BeckeWeightGradient."""
+        d_dm = self._dev(dm)
+        return self._xc_grid_response(slice_rows,
+                                      lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient(m, self.nao, d_dm, ao, w, out, gr, hs),
+                                      lambda m, ao, gr, e: self.solver.compute_xc_energy_density(m, self.nao, d_dm, ao, e, gr))
+
+    def xc_grid_response_spin(self, dm_a, dm_b, slice_rows=None):
+        """xc_grid_response for an open-shell state: DFT_ComputeXCGradientSpin and DFT_ComputeXCEnergyDensitySpin per block."""
+        self._uks_check()
+        d_a, d_b = self._dev(dm_a), self._dev(dm_b)
+        return self._xc_grid_response(slice_rows,
+                                      lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient_spin(m, self.nao, d_a, d_b, ao, w, out, gr, hs),
+                                      lambda m, ao, gr, e: self.solver.compute_xc_energy_density_spin(m, self.nao, d_a, d_b, ao, e, gr))
+
+    def _xc_grid_response(self, slice_rows, entry, edens):
+        from . import basis, grid_gen
+        if self.world > 1:
+            raise ValueError("the grid response runs on one rank: the grid of this backend is sharded over several")
+        if self.dm_factor:
+            raise ValueError("the grid response takes the density matrix itself: run without dm_factor")
+        symbols, xyz = self._atoms
+        own, w0 = getattr(self._grids, "atom_index", None), getattr(self._grids, "atomic_weights", None)
+        if own is None or w0 is None or symbols is None or xyz is None:
+            raise ValueError("the grid response needs the grid's atom_index and atomic_weights (grid_gen.Grids) and the atoms of the input: "
+                             "this grid does not say which atom a point moves with")
+        xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+        own, w0 = np.asarray(own), np.asarray(w0, dtype=np.float64)
+        natm = xyz.shape[0]
+        if len(symbols) != natm or own.shape != (self.ngrid,) or w0.shape != (self.ngrid,) or \
+                (self.ngrid and (own.min() < 0 or own.max() >= natm)):
+            raise ValueError(f"the grid response: the grid's atom_index / atomic_weights do not match the {natm} atoms and {self.ngrid} points of this backend")
+        t, n = self.torch, self.nao
+        # the blocks of consecutive rows one atom owns (grid_gen.Grids: one per atom)
+        cut = np.flatnonzero(np.diff(own)) + 1
+        los, his = np.concatenate([[0], cut]), np.concatenate([cut, [self.ngrid]])
+        d_e = t.zeros(max(self.ngrid, 1), dtype=t.float64, device=self.dev)
+        out = np.zeros((natm, 3))
+
+        def after(lo, hi, ao, gr):
+            edens(hi - lo, ao, gr if self.solver.needs_gradient else None, d_e[lo:hi])
+
+        for lo, hi in zip(los, his):
+            if hi > lo:
+                G = self._xc_gradient_slices(slice_rows, entry, block=(int(lo), int(hi)), after=after)
+                out[int(own[lo])] -= G.sum(axis=0)
+        d_f = d_e[:self.ngrid] * t.as_tensor(w0, dtype=t.float64, device=self.dev)
+        d_own = t.as_tensor(own.astype(np.int32), dtype=t.int32, device=self.dev)
+        d_out = t.zeros((natm, 3), dtype=t.float64, device=self.dev)
+        radii = grid_gen.bragg_radii_bohr([basis.atomic_number(sy) for sy in symbols])
+        t.cuda.synchronize()
+        self.solver.becke_weight_gradient(self.ngrid, xyz, radii, self.d_coords, d_own, d_f, d_out)
+        t.cuda.synchronize()
+        return out + d_out.cpu().numpy()
 
     # ---- two-electron part of the nuclear gradient on the device (integrals.DeviceGrad2e): one rank ----------------
     def grad2e(self, dm, c_hf):

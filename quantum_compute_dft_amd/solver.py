@@ -155,6 +155,12 @@ class DFTSolverWrapper:
         L.DFT_ComputeXCGradient.restype = ctypes.c_int
         L.DFT_ComputeXCGradientSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, _u64, _u64]
         L.DFT_ComputeXCGradientSpin.restype = ctypes.c_int
+        L.DFT_ComputeXCEnergyDensity.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64]
+        L.DFT_ComputeXCEnergyDensity.restype = ctypes.c_int
+        L.DFT_ComputeXCEnergyDensitySpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64]
+        L.DFT_ComputeXCEnergyDensitySpin.restype = ctypes.c_int
+        L.DFT_BeckeWeightGradient.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, dp, dp, _u64, _u64, _u64, _u64, _u64]
+        L.DFT_BeckeWeightGradient.restype = ctypes.c_int
 
         if self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
@@ -383,6 +389,40 @@ class DFTSolverWrapper:
         LDA-class functional.  With option quirks = 1 a functional with vwn5_c or pbe_c is refused, as by compute_xc_spin."""
         rc = self.lib.DFT_ComputeXCGradientSpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)), _u64(_ptr(d_ao)),
                                                 _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
+        self._check()
+        return rc
+
+    def compute_xc_energy_density(self, ngrid, nao, d_dm, d_ao, d_e_out, d_ao_grad=None):
+        """e_g, the energy per volume of the functional at the density of d_dm, into d_e_out (ngrid) without the weight
+        (DFT_ComputeXCEnergyDensity): sum_g w_g e_g is compute_xc's Exc.  The body, cut-offs, quirks and mix weights of the
+        sweep's pointwise kernel; asynchronous on the solver's stream."""
+        rc = self.lib.DFT_ComputeXCEnergyDensity(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
+                                                 _u64(_ptr(d_ao_grad)), _u64(_ptr(d_e_out)))
+        self._check()
+        return rc
+
+    def compute_xc_energy_density_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_e_out, d_ao_grad=None):
+        """e_g of the spin density matrices d_dm_a / d_dm_b into d_e_out (DFT_ComputeXCEnergyDensitySpin): sum_g w_g e_g is
+        compute_xc_spin's Exc.  With option quirks = 1 a functional with vwn5_c or pbe_c is refused, as by compute_xc_spin."""
+        rc = self.lib.DFT_ComputeXCEnergyDensitySpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)),
+                                                     _u64(_ptr(d_ao)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_e_out)))
+        self._check()
+        return rc
+
+    def becke_weight_gradient(self, ngrid, atom_xyz, atom_radius, d_coords, d_owner, d_f, d_out, d_cell_out=None):
+        """sum_g f_g D_B cell_g into d_out (natm, 3) (DFT_BeckeWeightGradient; grid_gen.becke_weight_gradient_host is its
+        host counterpart): atom_xyz (natm, 3) and atom_radius (natm; grid_gen.bragg_radii_bohr) are host arrays, d_coords
+        (ngrid, 3) fp64, d_owner (ngrid) int32 in [0, natm), d_f (ngrid) fp64 device arrays; d_cell_out (ngrid) receives the
+        cell function when given.  Asynchronous on the solver's stream."""
+        import numpy as np
+        dp = ctypes.POINTER(ctypes.c_double)
+        xyz = np.ascontiguousarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+        rad = np.ascontiguousarray(atom_radius, dtype=np.float64).reshape(-1)
+        if rad.shape[0] != xyz.shape[0]:
+            raise ValueError(f"becke_weight_gradient: {xyz.shape[0]} atoms but {rad.shape[0]} radii")
+        rc = self.lib.DFT_BeckeWeightGradient(self.solver, int(ngrid), int(xyz.shape[0]), xyz.ctypes.data_as(dp), rad.ctypes.data_as(dp),
+                                              _u64(_ptr(d_coords)), _u64(_ptr(d_owner)), _u64(_ptr(d_f)), _u64(_ptr(d_cell_out)),
+                                              _u64(_ptr(d_out)))
         self._check()
         return rc
 
