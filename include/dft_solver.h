@@ -405,7 +405,7 @@ int DFT_ComputeXCGradient(XCSolver *solver, long long ngrid, int nao, unsigned l
  *   G[mu, x] = -fac sum_s sum_g [ d_x phi_mu Z_s + (sum_k c_sk d_xk phi_mu) X_s ][g, mu],  X_s = AO D_s,  Z_s = Q_s D_s,
  * Q_s = 2 c_s0 AO + sum_k c_sk ao_grad[k], fac = 1 (one-sided types) or 2 (B3LYP): the closed-shell formula once per spin.
  * On the solver's stream, no host wait: the density kernels on dm_a and on dm_b and the spin-resolved pointwise kernel
- * exactly as DFT_ComputeXCSpin runs them, into buffers of this entry, then "xc_grad_spin": k_xc_grad_spin stages the AO
+ * exactly as DFT_ComputeXCSpin runs them, into buffers of this entry, then "xc_grad_spin": k_xc_grad on both spins stages the AO
  * rows of a tile once beside the Q rows of both spins, forms X_a, X_b, Z_a, Z_b of a column tile together and reads each
  * gradient and Hessian plane element once, for d_x phi (Z_a + Z_b) + sum_k d_xk phi (c_ak X_a + c_bk X_b), into one
  * (nao, 3) slab per workgroup; a fixed-order slab sum finishes, so a call is bitwise reproducible.  Option
@@ -630,7 +630,7 @@ void DFT_ScfTailClose(void *handle);
  * the host waits for -- same contract, no launch; taken only where a probe at DFT_CreateSolver found the runtime
  * performs the operation, else the kernel stays; -1 = auto, default: the kernel, which measured 1-2 us faster per call.
  * A recorded graph always ends with the kernel), "xcg_spin_fused" (DFT_ComputeXCGradientSpin: 1, default = both spins in
- * one kernel, k_xc_grad_spin; 0 = k_xc_grad once per spin, the plain form the tests hold it to).  Returns 0 if the key is
+ * one k_xc_grad launch; 0 = k_xc_grad once per spin, the plain form the tests hold it to).  Returns 0 if the key is
  * known. */
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
 

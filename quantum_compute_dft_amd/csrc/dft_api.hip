@@ -174,18 +174,17 @@ struct XCSolver {
     // table holds or reads any of them
     Planes spin[2];
     DevBuf spin_exc;
-    // DFT_ComputeXCGradient: planes and slabs of its own -- no recorded sweep and no prepared response table holds or reads
-    // any of them (Dsym alone is shared, in stream order)
-    Planes xcg;
-    DevBuf xcg_slabs;
-    // DFT_ComputeXCGradientSpin: the planes of the two spins, their padded matrices and two slab sets, its own again
-    Planes xcgs[2];
-    // 1 (default): k_xc_grad_spin, one kernel for both spins (0.64 x / 0.82 x of the two launches at 143 556 x 114 / 60 000 x 494,
-    // GGA: profiles/xc_gradient_spin_time.txt); 0: k_xc_grad once per spin into two slab sets, what the tests hold the kernel to
+    // DFT_ComputeXCGradient / DFT_ComputeXCGradientSpin and DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin: one set
+    // of their own -- the planes of each spin (a closed-shell call uses [0]), the padded matrix of each spin that k_xc_grad reads
+    // (the closed-shell entry's too: it no longer takes the shared Dsym) and the slabs (two sets with "xcg_spin_fused" = 0).  No
+    // recorded sweep and no prepared response table holds or reads any of them; the four entries share them in stream order, and
+    // every call overwrites whole what it reads.  The energy-density entries, which read no matrix back, symmetrise into Dsym.
+    Planes xcg[2];
+    DevBuf xcg_dp[2], xcg_slabs;
+    // DFT_ComputeXCGradientSpin.  1 (default): k_xc_grad on both spins' (coef, D) pairs in one launch (0.64 x / 0.82 x of the two
+    // launches at 143 556 x 114 / 60 000 x 494, GGA: profiles/xc_gradient_spin_time.txt); 0: k_xc_grad once per spin into two slab
+    // sets, what the tests hold the two-spin instantiation to
     int xcg_spin_fused = 1;
-    DevBuf xcgs_dp[2], xcgs_slabs;
-    // DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin: the density planes of the entry (of the two spins), its own again
-    Planes xce[2];
     // DFT_BeckeWeightGradient: [atoms (natm, 3) | a_CD (natm, natm) | 1 / R_CD (natm, natm)] on the device and the host copy they
     // were made from (uploaded again only when the atoms change), and the slabs of the kernel
     DevBuf becke_tab, becke_slabs;
@@ -700,20 +699,12 @@ bool spin_quirks_ok(XCSolver *s, const char *who)
 
 // The density kernels on the matrix of spin alpha, then of spin beta (linear in the matrix), into the spin planes; `ga`,
 // `gb`: where the two gradients go.  sigma is what the kernels write beside the gradient; nobody reads it.
-// `pa`, `pb`: the planes that take the densities (the spin planes, or those of the open-shell gradient); `Dp_a`, `Dp_b`: where
-// the kernels that symmetrise on the host side of the launch leave the padded matrices (Dsym twice where nobody reads them after).
-void launch_density_spin(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
-                         const Planes &pa, const Planes &pb, double *Dp_a, double *Dp_b, double *ga, double *gb)
-{
-    double *sigma = pa.sigma.d();
-    launch_density(s, P, ngrid, nao, dm_a, ao, Dp_a, pa.rho.d(), ga, sigma);
-    launch_density(s, P, ngrid, nao, dm_b, ao, Dp_b, pb.rho.d(), gb, sigma);
-}
-
 void launch_density_spin(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
                          double *ga, double *gb)
 {
-    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, s->spin[0], s->spin[1], s->dsym.d(), s->dsym.d(), ga, gb);
+    double *sigma = s->spin[0].sigma.d(), *Dp = s->dsym.d();
+    launch_density(s, P, ngrid, nao, dm_a, ao, Dp, s->spin[0].rho.d(), ga, sigma);
+    launch_density(s, P, ngrid, nao, dm_b, ao, Dp, s->spin[1].rho.d(), gb, sigma);
 }
 
 // The spin-resolved sweep (DFT_ComputeXCSpin): the closed-shell sweep's density kernels on dm_a and on dm_b, one
@@ -1376,130 +1367,102 @@ __global__ void k_accumulate_chunk(long n2, int add, const double *__restrict__ 
     if (i == 0) *e = add ? *e + *ec : *ec;
 }
 
-// XC part of the nuclear gradient (DFT_ComputeXCGradient): the sweep's own density kernels and pointwise kernel, into
-// planes of this entry, then k_xc_grad (xc_grad.hip) on the coefficient planes.  Never the one-kernel plan for small
-// bases (it keeps no coefficients), never recorded; asynchronous on the solver's stream.
-bool xc_gradient(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *w, const double *ao_grad,
-                 const double *ao_hess, double *out)
+// XC part of the nuclear gradient, closed shell (DFT_ComputeXCGradient: nspin = 1, dm_b unused) and open shell
+// (DFT_ComputeXCGradientSpin: nspin = 2).  The sweep's own density kernels on each matrix and its pointwise kernel -- the
+// spin-resolved one exactly as DFT_ComputeXCSpin runs it for two spins -- into planes of these entries (XCSolver::xcg), then
+// k_xc_grad (xc_grad.hip) on the (coefficient planes, padded matrix) pair of every spin and the fixed-order slab sum: both
+// spins' pairs in one launch, or, with option "xcg_spin_fused" = 0, one launch per spin into two slab sets.  Never the
+// one-kernel plan for small bases (it keeps no coefficients), never recorded; asynchronous on the solver's stream.  The
+// padded matrices are these entries' too: both are read after both are written.
+bool xc_gradient(XCSolver *s, int nspin, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao, const double *w,
+                 const double *ao_grad, const double *ao_hess, double *out)
 {
+    const bool spin = nspin == 2;
+    const char *who = spin ? "DFT_ComputeXCGradientSpin" : "DFT_ComputeXCGradient";
     if (!enter(s, ngrid, nao, ao_grad)) return false;
-    if (!dm || !ao || !w || !out) { set_error(s, "DFT_ComputeXCGradient needs dm, the AO values, the grid weights and the output"); return false; }
+    if (!dm_a || (spin && !dm_b) || !ao || !w || !out) {
+        set_error(s, "%s needs %s, the AO values, the grid weights and the output", who, spin ? "both density matrices" : "dm");
+        return false;
+    }
     const bool gga = s->needs_grad;
     if (gga && !ao_hess) { set_error(s, "ao_hess pointer is null for a gradient-corrected functional"); return false; }
-    if (!ao_grad) { set_error(s, "DFT_ComputeXCGradient needs ao_grad: the derivative of the density by a centre is made of it"); return false; }
-    const XcGradPlan G = xc_grad_plan(s->num_cu, gga, ngrid, nao);
-    if (G.lds > 160 * 1024) { set_error(s, "DFT_ComputeXCGradient: nao=%d needs %zu bytes of LDS per workgroup", nao, G.lds); return false; }
+    if (!ao_grad) { set_error(s, "%s needs ao_grad: the derivative of the density by a centre is made of it", who); return false; }
+    if (spin && !spin_quirks_ok(s, who)) return false;
+    const bool fused = spin && s->xcg_spin_fused != 0;
+    const XcGradPlan G = xc_grad_plan(s->num_cu, gga, fused ? 2 : 1, ngrid, nao);
+    if (G.lds > 160 * 1024) { set_error(s, "%s: nao=%d needs %zu bytes of LDS per workgroup", who, nao, G.lds); return false; }
     // an LDA-class solver's density kernels read ao_grad's first plane pointer only as a dummy: plan as the sweep does
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
-    const long nxb = (ngrid + 255) / 256;
-    const Planes &p = s->xcg;
-    if (!reserve_dsym(s, P) || !reserve_planes(s, s->xcg, false, ngrid, WS_ALL, nxb) ||
-        !reserve(s, s->xcg_slabs, sizeof(double) * (size_t)G.nwg * 3 * nao, "hipMalloc(gradient slabs)", false))
+    const long nxb = spin ? spin_points_blocks(ngrid) : (ngrid + 255) / 256;
+    const Planes &a = s->xcg[0], &b = s->xcg[1];   // sigma and the Exc partials with [0] alone
+    const size_t dpb = sizeof(double) * P.NP * P.NP, slab = sizeof(double) * (size_t)G.nwg * 3 * nao;
+    if (!reserve_planes(s, s->xcg[0], false, ngrid, WS_ALL, nxb) || (spin && !reserve_planes(s, s->xcg[1], false, ngrid, WS_COEF | WS_GRAD)) ||
+        !reserve(s, s->xcg_dp[0], dpb, spin ? "hipMalloc(Dsym alpha)" : "hipMalloc(Dsym)", false) ||
+        (spin && !reserve(s, s->xcg_dp[1], dpb, "hipMalloc(Dsym beta)", false)) ||
+        !reserve(s, s->xcg_slabs, (spin && !fused ? 2 : 1) * slab, spin ? "hipMalloc(spin gradient slabs)" : "hipMalloc(gradient slabs)", false))
         return false;
-    double *Dp = s->dsym.d();
-    launch_density(s, P, ngrid, nao, dm, ao, Dp, p.rho.d(), p.grad.d(), p.sigma.d());
-    if (P.fast) {   // the wave-specialised density kernel symmetrises dm itself: k_xc_grad reads the padded matrix
-        ScopedTimer t(s, "sym_dm");
-        dim3 b(16, 16), g(P.NP / 16, P.NP / 16);
-        hipLaunchKernelGGL(k_sym_dm, g, b, 0, s->stream, nao, P.NP, dm, Dp);
-    }
-    launch_xc_points(s, ngrid, nxb, w, p);
-    if (!hip_ok(s, hipGetLastError(), "XC gradient density launch")) return false;
-    ScopedTimer t(s, "xc_grad");
-    // one-sided types hand over c0 = w vrho, c_k = 4 w vsigma grad_k rho; B3LYP half of each (its M + M^T)
-    const double fac = s->type == SOLVER_B3LYP ? 2.0 : 1.0;
-    return hip_ok(s, launch_xc_grad(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), Dp, s->xcg_slabs.d(), out),
-                  "XC gradient launch");
-}
-
-// XC part of the open-shell nuclear gradient (DFT_ComputeXCGradientSpin): the density kernels on dm_a and dm_b and the
-// spin-resolved pointwise kernel exactly as DFT_ComputeXCSpin runs them, into planes of this entry; then k_xc_grad_spin on
-// (D_a, c_a, D_b, c_b) and the fixed-order slab sum -- or, with option "xcg_spin_fused" = 0, k_xc_grad once per spin with
-// (D_s, c_s) into two slab sets and one fixed-order sum over both.  Never the one-kernel plan, never recorded;
-// asynchronous on the solver's stream.  The padded matrices are this entry's too: both are read after both are written.
-bool xc_gradient_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao, const double *w,
-                      const double *ao_grad, const double *ao_hess, double *out)
-{
-    if (!enter(s, ngrid, nao, ao_grad)) return false;
-    if (!dm_a || !dm_b || !ao || !w || !out) {
-        set_error(s, "DFT_ComputeXCGradientSpin needs both density matrices, the AO values, the grid weights and the output");
-        return false;
-    }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_hess) { set_error(s, "ao_hess pointer is null for a gradient-corrected functional"); return false; }
-    if (!ao_grad) { set_error(s, "DFT_ComputeXCGradientSpin needs ao_grad: the derivative of the density by a centre is made of it"); return false; }
-    if (!spin_quirks_ok(s, "DFT_ComputeXCGradientSpin")) return false;
-    const bool fused = s->xcg_spin_fused != 0;
-    const XcGradPlan G = fused ? xc_grad_spin_fused_plan(s->num_cu, gga, ngrid, nao) : xc_grad_plan(s->num_cu, gga, ngrid, nao);
-    if (G.lds > 160 * 1024) { set_error(s, "DFT_ComputeXCGradientSpin: nao=%d needs %zu bytes of LDS per workgroup", nao, G.lds); return false; }
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
-    const long nxb = spin_points_blocks(ngrid);
-    Planes &a = s->xcgs[0], &b = s->xcgs[1];
-    const size_t dpb = sizeof(double) * P.NP * P.NP;
-    if (!reserve_planes(s, a, false, ngrid, WS_ALL, nxb) || !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD) ||
-        !reserve(s, s->xcgs_dp[0], dpb, "hipMalloc(Dsym alpha)", false) || !reserve(s, s->xcgs_dp[1], dpb, "hipMalloc(Dsym beta)", false) ||
-        !reserve(s, s->xcgs_slabs, sizeof(double) * (fused ? 1 : 2) * (size_t)G.nwg * 3 * nao, "hipMalloc(spin gradient slabs)", false))
-        return false;
-    double *Dp_a = s->xcgs_dp[0].d(), *Dp_b = s->xcgs_dp[1].d();
-    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, a, b, Dp_a, Dp_b, a.grad.d(), b.grad.d());
+    const double *dm[2] = {dm_a, dm_b};
+    double *Dp[2] = {s->xcg_dp[0].d(), s->xcg_dp[1].d()};
+    for (int sp = 0; sp < nspin; ++sp)
+        launch_density(s, P, ngrid, nao, dm[sp], ao, Dp[sp], s->xcg[sp].rho.d(), s->xcg[sp].grad.d(), a.sigma.d());
     if (P.fast) {   // the wave-specialised density kernel symmetrises dm itself: k_xc_grad reads the padded matrices
         ScopedTimer t(s, "sym_dm");
         dim3 bl(16, 16), g(P.NP / 16, P.NP / 16);
-        hipLaunchKernelGGL(k_sym_dm, g, bl, 0, s->stream, nao, P.NP, dm_a, Dp_a);
-        hipLaunchKernelGGL(k_sym_dm, g, bl, 0, s->stream, nao, P.NP, dm_b, Dp_b);
+        for (int sp = 0; sp < nspin; ++sp) hipLaunchKernelGGL(k_sym_dm, g, bl, 0, s->stream, nao, P.NP, dm[sp], Dp[sp]);
     }
-    {
+    if (!spin) {
+        launch_xc_points(s, ngrid, nxb, w, a);
+        if (!hip_ok(s, hipGetLastError(), "XC gradient density launch")) return false;
+    } else {
         ScopedTimer t(s, "xc_points_spin");
         if (!hip_ok(s, launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
                                              gga ? b.grad.d() : nullptr, w, a.coef.d(), b.coef.d(), a.partial.d()), "spin pointwise launch"))
             return false;
     }
-    ScopedTimer t(s, "xc_grad_spin");
+    ScopedTimer t(s, spin ? "xc_grad_spin" : "xc_grad");
+    // one-sided types hand over c0 = w vrho, c_k = 4 w vsigma grad_k rho; B3LYP half of each (its M + M^T)
     const double fac = s->type == SOLVER_B3LYP ? 2.0 : 1.0;
+    double *slabs = s->xcg_slabs.d();
+    if (!spin)
+        return hip_ok(s, launch_xc_grad(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), Dp[0], slabs, out),
+                      "XC gradient launch");
     if (fused)
-        return hip_ok(s, launch_xc_grad_spin_fused(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp_a, Dp_b,
-                                                   s->xcgs_slabs.d(), out), "XC spin gradient launch (fused)");
-    return hip_ok(s, launch_xc_grad_spin(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp_a, Dp_b,
-                                         s->xcgs_slabs.d(), out), "XC spin gradient launch");
+        return hip_ok(s, launch_xc_grad_spin_fused(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp[0], Dp[1],
+                                                   slabs, out), "XC spin gradient launch (fused)");
+    return hip_ok(s, launch_xc_grad_spin(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp[0], Dp[1], slabs, out),
+                  "XC spin gradient launch");
 }
 
-// The energy per volume of the functional at the density of dm (DFT_ComputeXCEnergyDensity): the density kernels of the
-// sweep with the sweep's choices and k_xc_edens, the body of the sweep's pointwise kernel with unit weight, into planes of
-// this entry.  Never the one-kernel plan, never recorded; asynchronous on the solver's stream.
-bool xc_energy_density(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *ao_grad, double *e_out)
+// The energy per volume of the functional at the density of dm (DFT_ComputeXCEnergyDensity: nspin = 1, dm_b unused) or of
+// an open-shell state (DFT_ComputeXCEnergyDensitySpin: nspin = 2, with DFT_ComputeXCSpin's refusal): the density kernels of
+// the sweep with the sweep's choices, then the body of the sweep's pointwise kernel with unit weight (k_xc_edens, or the
+// spin-resolved body), into the planes of the gradient entries.  Never the one-kernel plan, never recorded; asynchronous on
+// the solver's stream.
+bool xc_energy_density(XCSolver *s, int nspin, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
+                       const double *ao_grad, double *e_out)
 {
+    const bool spin = nspin == 2;
+    const char *who = spin ? "DFT_ComputeXCEnergyDensitySpin" : "DFT_ComputeXCEnergyDensity";
     if (!enter(s, ngrid, nao, ao_grad)) return false;
-    if (!dm || !ao || !e_out) { set_error(s, "DFT_ComputeXCEnergyDensity needs dm, the AO values and the output"); return false; }
-    const bool gga = s->needs_grad;
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
-    const Planes &p = s->xce[0];
-    if (!reserve_dsym(s, P) || !reserve_planes(s, s->xce[0], false, ngrid, WS_GRAD | WS_SIGMA)) return false;
-    launch_density(s, P, ngrid, nao, dm, ao, s->dsym.d(), p.rho.d(), p.grad.d(), p.sigma.d());
-    if (!hip_ok(s, hipGetLastError(), "energy density: density launch")) return false;
-    ScopedTimer t(s, "xc_edens");
-    return hip_ok(s, launch_xc_edens(s->stream, xc_type_index(s), gga, s->mix.c, s->quirks, ngrid, p.rho.d(), p.sigma.d(), p.grad.d(), e_out),
-                  "energy density launch");
-}
-
-// The same of an open-shell state (DFT_ComputeXCEnergyDensitySpin): the density kernels on dm_a and dm_b as
-// DFT_ComputeXCSpin runs them and the spin-resolved body with unit weight; DFT_ComputeXCSpin's refusal.
-bool xc_energy_density_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
-                            const double *ao_grad, double *e_out)
-{
-    if (!enter(s, ngrid, nao, ao_grad)) return false;
-    if (!dm_a || !dm_b || !ao || !e_out) {
-        set_error(s, "DFT_ComputeXCEnergyDensitySpin needs both density matrices, the AO values and the output");
+    if (!dm_a || (spin && !dm_b) || !ao || !e_out) {
+        set_error(s, "%s needs %s, the AO values and the output", who, spin ? "both density matrices" : "dm");
         return false;
     }
-    if (!spin_quirks_ok(s, "DFT_ComputeXCEnergyDensitySpin")) return false;
+    if (spin && !spin_quirks_ok(s, who)) return false;
     const bool gga = s->needs_grad;
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
-    Planes &a = s->xce[0], &b = s->xce[1];
-    if (!reserve_dsym(s, P) || !reserve_planes(s, a, false, ngrid, WS_GRAD | WS_SIGMA) || !reserve_planes(s, b, false, ngrid, WS_GRAD))
+    const Planes &a = s->xcg[0], &b = s->xcg[1];
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->xcg[0], false, ngrid, WS_GRAD | WS_SIGMA) ||
+        (spin && !reserve_planes(s, s->xcg[1], false, ngrid, WS_GRAD)))
         return false;
-    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, a, b, s->dsym.d(), s->dsym.d(), a.grad.d(), b.grad.d());
-    if (!hip_ok(s, hipGetLastError(), "spin energy density: density launch")) return false;
-    ScopedTimer t(s, "xc_edens_spin");
+    const double *dm[2] = {dm_a, dm_b};
+    for (int sp = 0; sp < nspin; ++sp)
+        launch_density(s, P, ngrid, nao, dm[sp], ao, s->dsym.d(), s->xcg[sp].rho.d(), s->xcg[sp].grad.d(), a.sigma.d());
+    if (!hip_ok(s, hipGetLastError(), spin ? "spin energy density: density launch" : "energy density: density launch")) return false;
+    ScopedTimer t(s, spin ? "xc_edens_spin" : "xc_edens");
+    if (!spin)
+        return hip_ok(s, launch_xc_edens(s->stream, xc_type_index(s), gga, s->mix.c, s->quirks, ngrid, a.rho.d(), a.sigma.d(), a.grad.d(), e_out),
+                      "energy density launch");
     return hip_ok(s, launch_xc_edens_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
                                           gga ? b.grad.d() : nullptr, e_out), "spin energy density launch");
 }
@@ -2103,7 +2066,7 @@ int DFT_ComputeXCGradient(XCSolver *s, long long ngrid, int nao, unsigned long l
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_gradient(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_weights,
+    return xc_gradient(s, 1, (long)ngrid, nao, (const double *)d_dm, nullptr, (const double *)d_ao, (const double *)d_weights,
                        (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
 }
 
@@ -2113,8 +2076,8 @@ int DFT_ComputeXCGradientSpin(XCSolver *s, long long ngrid, int nao, unsigned lo
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_gradient_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
-                            (const double *)d_weights, (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+    return xc_gradient(s, 2, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
+                       (const double *)d_weights, (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
 }
 
 int DFT_ComputeXCEnergyDensity(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
@@ -2122,7 +2085,7 @@ int DFT_ComputeXCEnergyDensity(XCSolver *s, long long ngrid, int nao, unsigned l
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_energy_density(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_ao_grad,
+    return xc_energy_density(s, 1, (long)ngrid, nao, (const double *)d_dm, nullptr, (const double *)d_ao, (const double *)d_ao_grad,
                              (double *)d_e_out) ? 0 : -1;
 }
 
@@ -2131,8 +2094,8 @@ int DFT_ComputeXCEnergyDensitySpin(XCSolver *s, long long ngrid, int nao, unsign
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_energy_density_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
-                                  (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
+    return xc_energy_density(s, 2, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
+                             (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
 }
 
 int DFT_BeckeWeightGradient(XCSolver *s, long long ngrid, int natm, const double *atom_xyz, const double *atom_radius,

@@ -20,9 +20,11 @@
 // zero-padded to NP = 16 ceil(nao / 16)) straight from L2.  The epilogue reads the three gradient and six Hessian planes
 // at the positions of the result layout -- each plane element once -- and adds into a per-workgroup (nao, 3) in LDS,
 // which leaves as one slab; k_xc_grad_reduce sums the slabs in a fixed order, so a call is bitwise reproducible.
-// The open-shell gradient (DFT_ComputeXCGradientSpin) is the same formula once per spin with (D_s, c_s).  k_xc_grad_spin
-// does both spins in one pass over the planes (below); launch_xc_grad_spin is the plain form it is tested against:
-// k_xc_grad twice into two slab sets and one reduce over both, alpha's slabs first.
+// The open-shell gradient (DFT_ComputeXCGradientSpin) is the same formula once per spin with (D_s, c_s).  The kernel is one
+// template over the number of (c, D) pairs, k_xc_grad<GGA, NS>: NS = 1 is the closed shell, NS = 2 does both spins in one
+// pass over the planes (launch_xc_grad_spin_fused).  launch_xc_grad_spin is the plain form that one is tested against:
+// k_xc_grad<GGA, 1> twice into two slab sets and one reduce over both, alpha's slabs first.  One plan function sizes all
+// of them (xc_grad_plan, by the number of pairs per launch) and one launch core sets them off (launch_xc_grad_slabs).
 // Rows past the grid and columns past nao are staged as zeros and masked in the epilogue: no out-of-range read.
 //
 // k_eval_ao_hess: the six second-derivative planes in k_eval_ao's conventions (same harmonics, column order and
@@ -137,19 +139,27 @@ __global__ __launch_bounds__(256) void k_eval_ao_hess(long ngrid, int nao, int n
     }
 }
 
-// Dynamic LDS: As[16 * ldk], (GGA) Qs[16 * ldk], Gs[3 * NP], cs[4 * 16].  kc: K chunk, a multiple of 16; ldk = kc | 1.
-template <bool GGA>
+// One (coef, D) pair (NS = 1: the closed shell, or one spin of an open-shell state) or both spins' pairs in one pass over the
+// planes (NS = 2): the AO rows of a tile are staged once, beside the Q rows of every spin; X_s, Z_s of a column tile are formed
+// together, and the epilogue reads each plane element once for
+//     d_x phi sum_s Z_s + sum_k d_xk phi sum_s c_sk X_s.
+// Two spins keep three 16-row tiles, so their K chunk is capped lower (XCGS_KC_MAX).  coef_b and Dp_b are not read when NS = 1.
+// Dynamic LDS: As[16 * ldk], (GGA) Qs[NS][16 * ldk], Gs[3 * NP], cs[NS][4 * 16].  kc: K chunk, a multiple of 16; ldk = kc | 1.
+template <bool GGA, int NS>
 __global__ __launch_bounds__(256) void k_xc_grad(long ngrid, int nao, int NP, int kc, int ldk, double fac,
                                                  const double *__restrict__ ao, const double *__restrict__ gx,
                                                  const double *__restrict__ gy, const double *__restrict__ gz,
-                                                 const double *__restrict__ hess, const double *__restrict__ coef,
-                                                 const double *__restrict__ Dp, double *__restrict__ slabs)
+                                                 const double *__restrict__ hess, const double *__restrict__ coef_a,
+                                                 const double *__restrict__ coef_b, const double *__restrict__ Dp_a,
+                                                 const double *__restrict__ Dp_b, double *__restrict__ slabs)
 {
+    static_assert(NS == 1 || NS == 2, "one (coef, D) pair or two");
     extern __shared__ double lds[];
+    const int qsz = XCG_ROWS * ldk;   // one staged tile
     double *As = lds;
-    double *Qs = As + (GGA ? XCG_ROWS * ldk : 0);
-    double *Gs = Qs + XCG_ROWS * ldk;
-    double *cs = Gs + 3 * NP;
+    double *Qs = As + qsz;            // spin s at Qs + s * qsz (GGA only)
+    double *Gs = Qs + (GGA ? NS * qsz : 0);
+    double *cs = Gs + 3 * NP;         // c0..c3 of the 16 rows, spin s at cs + 64 s
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const size_t ng = (size_t)ngrid, plane = ng * nao;
@@ -161,126 +171,19 @@ __global__ __launch_bounds__(256) void k_xc_grad(long ngrid, int nao, int NP, in
     for (long tl = blockIdx.x; tl < ntile; tl += gridDim.x) {
         const long g0 = tl * XCG_ROWS;
         __syncthreads();   // the previous tile's readers of cs and of the staged rows are done
-        if (tid < 64) {
-            const int k = tid >> 4, r = tid & 15;
+        if (tid < 64 * NS) {
+            const int k = (tid >> 4) & 3, r = tid & 15;
             const long g = g0 + r;
-            cs[k * 16 + r] = (g < ngrid && (GGA || k == 0)) ? coef[k * ng + g] : 0.0;
+            const double *coef = (NS == 2 && tid >= 64) ? coef_b : coef_a;
+            cs[tid] = (g < ngrid && (GGA || k == 0)) ? coef[k * ng + g] : 0.0;
         }
         __syncthreads();
         for (int rd = 0; rd < nround; ++rd) {
             const int j = rd * 4 + wave;
             const bool active = j < nct;   // wave-uniform
-            d4 accX = (d4){0.0, 0.0, 0.0, 0.0}, accZ = (d4){0.0, 0.0, 0.0, 0.0};
-            for (int c = 0; c < nchunk; ++c) {
-                const int k0 = c * kc, kw = min(kc, NP - k0);
-                if (nchunk > 1 || rd == 0) {   // block-uniform: one staging per tile while the whole row fits
-                    if (nchunk > 1 || rd > 0) __syncthreads();
-                    for (int idx = tid; idx < XCG_ROWS * kw; idx += 256) {
-                        const int r = idx / kw, k = idx - r * kw;
-                        const long g = g0 + r;
-                        const int col = k0 + k;
-                        double a = 0.0, qv = 0.0;
-                        if (g < ngrid && col < nao) {
-                            const size_t o = (size_t)g * nao + col;
-                            a = ao[o];
-                            if (GGA) qv = 2.0 * cs[r] * a + cs[16 + r] * gx[o] + cs[32 + r] * gy[o] + cs[48 + r] * gz[o];
-                        }
-                        As[r * ldk + k] = a;
-                        if (GGA) Qs[r * ldk + k] = qv;
-                    }
-                    __syncthreads();
-                }
-                if (active) {
-                    const double *arow = As + li * ldk + lk, *qrow = Qs + li * ldk + lk;
-                    const double *bcol = Dp + (size_t)(k0 + lk) * NP + 16 * j + li;
-                    for (int ks = 0; ks < kw; ks += 4) {
-                        const double b = bcol[(size_t)ks * NP];
-                        accX = mfma_f64(arow[ks], b, accX);
-                        if (GGA) accZ = mfma_f64(qrow[ks], b, accZ);
-                    }
-                }
-            }
-            const int mu = 16 * j + li;
-            double sx = 0.0, sy = 0.0, sz = 0.0;
-            if (active && mu < nao) {
+            d4 accX[NS], accZ[NS];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = lk + 4 * r;
-                    const long g = g0 + row;
-                    if (g < ngrid) {
-                        const size_t o = (size_t)g * nao + mu;
-                        const double X = accX[r];
-                        const double Z = GGA ? accZ[r] : 2.0 * cs[row] * X;
-                        sx += gx[o] * Z;
-                        sy += gy[o] * Z;
-                        sz += gz[o] * Z;
-                        if (GGA) {
-                            const double c1 = cs[16 + row], c2 = cs[32 + row], c3 = cs[48 + row];
-                            const double hxx = hess[o], hxy = hess[plane + o], hxz = hess[2 * plane + o],
-                                         hyy = hess[3 * plane + o], hyz = hess[4 * plane + o], hzz = hess[5 * plane + o];
-                            sx += (c1 * hxx + c2 * hxy + c3 * hxz) * X;
-                            sy += (c1 * hxy + c2 * hyy + c3 * hyz) * X;
-                            sz += (c1 * hxz + c2 * hyz + c3 * hzz) * X;
-                        }
-                    }
-                }
-            }
-            // the four lanes that share a column (lk = 0..3): every lane gets the total, lk = 0 keeps it
-            sx += __shfl_xor(sx, 16, 64); sx += __shfl_xor(sx, 32, 64);
-            sy += __shfl_xor(sy, 16, 64); sy += __shfl_xor(sy, 32, 64);
-            sz += __shfl_xor(sz, 16, 64); sz += __shfl_xor(sz, 32, 64);
-            if (active && lk == 0) {   // column tile j belongs to this wave in every tile of rows: no other writer
-                Gs[3 * mu] += sx;
-                Gs[3 * mu + 1] += sy;
-                Gs[3 * mu + 2] += sz;
-            }
-        }
-    }
-    __syncthreads();
-    double *slab = slabs + (size_t)blockIdx.x * 3 * nao;
-    for (int i = tid; i < 3 * nao; i += 256) slab[i] = -fac * Gs[i];
-}
-
-// The two launches of k_xc_grad for an open-shell state in one: the AO rows of a tile are staged once, beside the Q rows of
-// both spins; X_a, X_b, Z_a, Z_b of a column tile are formed together, and the epilogue reads each plane element once for
-//     d_x phi (Z_a + Z_b) + sum_k d_xk phi (c_ak X_a + c_bk X_b).
-// Three 16-row tiles: the K chunk is capped at XCGS_KC_MAX.  Same slab per workgroup, same k_xc_grad_reduce.
-// Dynamic LDS: As[16 * ldk], (GGA) Qa[16 * ldk], Qb[16 * ldk], Gs[3 * NP], cs[2 * 4 * 16].
-template <bool GGA>
-__global__ __launch_bounds__(256) void k_xc_grad_spin(long ngrid, int nao, int NP, int kc, int ldk, double fac,
-                                                      const double *__restrict__ ao, const double *__restrict__ gx,
-                                                      const double *__restrict__ gy, const double *__restrict__ gz,
-                                                      const double *__restrict__ hess, const double *__restrict__ coef_a,
-                                                      const double *__restrict__ coef_b, const double *__restrict__ Dpa,
-                                                      const double *__restrict__ Dpb, double *__restrict__ slabs)
-{
-    extern __shared__ double lds[];
-    double *As = lds;
-    double *Qa = As + XCG_ROWS * ldk;
-    double *Qb = Qa + (GGA ? XCG_ROWS * ldk : 0);
-    double *Gs = Qb + (GGA ? XCG_ROWS * ldk : 0);
-    double *cs = Gs + 3 * NP;      // alpha's c0..c3 of the 16 rows, then beta's
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const size_t ng = (size_t)ngrid, plane = ng * nao;
-    const int nct = NP / 16, nround = (nct + 3) / 4, nchunk = (NP + kc - 1) / kc;
-    const long ntile = (ngrid + XCG_ROWS - 1) / XCG_ROWS;
-
-    for (int i = tid; i < 3 * NP; i += 256) Gs[i] = 0.0;
-
-    for (long tl = blockIdx.x; tl < ntile; tl += gridDim.x) {
-        const long g0 = tl * XCG_ROWS;
-        __syncthreads();   // the previous tile's readers of cs and of the staged rows are done
-        if (tid < 128) {
-            const int sp = tid >> 6, k = (tid >> 4) & 3, r = tid & 15;
-            const long g = g0 + r;
-            cs[tid] = (g < ngrid && (GGA || k == 0)) ? (sp ? coef_b : coef_a)[k * ng + g] : 0.0;
-        }
-        __syncthreads();
-        for (int rd = 0; rd < nround; ++rd) {
-            const int j = rd * 4 + wave;
-            const bool active = j < nct;   // wave-uniform
-            d4 xa = (d4){0.0, 0.0, 0.0, 0.0}, xb = xa, za = xa, zb = xa;
+            for (int s = 0; s < NS; ++s) accX[s] = accZ[s] = (d4){0.0, 0.0, 0.0, 0.0};
             for (int c = 0; c < nchunk; ++c) {
                 const int k0 = c * kc, kw = min(kc, NP - k0);
                 if (nchunk > 1 || rd == 0) {   // block-uniform: one staging per tile while the whole row fits
@@ -289,35 +192,43 @@ __global__ __launch_bounds__(256) void k_xc_grad_spin(long ngrid, int nao, int N
                         const int r = idx / kw, k = idx - r * kw;
                         const long g = g0 + r;
                         const int col = k0 + k;
-                        double a = 0.0, qa = 0.0, qb = 0.0;
+                        double a = 0.0, q[NS] = {};
                         if (g < ngrid && col < nao) {
                             const size_t o = (size_t)g * nao + col;
                             a = ao[o];
                             if (GGA) {
                                 const double vx = gx[o], vy = gy[o], vz = gz[o];
-                                qa = 2.0 * cs[r] * a + cs[16 + r] * vx + cs[32 + r] * vy + cs[48 + r] * vz;
-                                qb = 2.0 * cs[64 + r] * a + cs[80 + r] * vx + cs[96 + r] * vy + cs[112 + r] * vz;
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) {
+                                    const double *c4 = cs + 64 * s + r;
+                                    q[s] = 2.0 * c4[0] * a + c4[16] * vx + c4[32] * vy + c4[48] * vz;
+                                }
                             }
                         }
                         As[r * ldk + k] = a;
                         if (GGA) {
-                            Qa[r * ldk + k] = qa;
-                            Qb[r * ldk + k] = qb;
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) Qs[s * qsz + r * ldk + k] = q[s];
                         }
                     }
                     __syncthreads();
                 }
                 if (active) {
-                    const double *arow = As + li * ldk + lk, *qarow = Qa + li * ldk + lk, *qbrow = Qb + li * ldk + lk;
+                    const double *arow = As + li * ldk + lk, *qrow = Qs + li * ldk + lk;
                     const size_t bo = (size_t)(k0 + lk) * NP + 16 * j + li;
-                    const double *ba = Dpa + bo, *bb = Dpb + bo;
+                    const double *bcol[NS];
+                    bcol[0] = Dp_a + bo;
+                    if constexpr (NS == 2) bcol[1] = Dp_b + bo;
                     for (int ks = 0; ks < kw; ks += 4) {
-                        const double va = ba[(size_t)ks * NP], vb = bb[(size_t)ks * NP], a = arow[ks];
-                        xa = mfma_f64(a, va, xa);
-                        xb = mfma_f64(a, vb, xb);
+                        const double a = arow[ks];
+                        double b[NS];
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) b[s] = bcol[s][(size_t)ks * NP];
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) accX[s] = mfma_f64(a, b[s], accX[s]);
                         if (GGA) {
-                            za = mfma_f64(qarow[ks], va, za);
-                            zb = mfma_f64(qbrow[ks], vb, zb);
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) accZ[s] = mfma_f64(qrow[s * qsz + ks], b[s], accZ[s]);
                         }
                     }
                 }
@@ -331,19 +242,29 @@ __global__ __launch_bounds__(256) void k_xc_grad_spin(long ngrid, int nao, int N
                     const long g = g0 + row;
                     if (g < ngrid) {
                         const size_t o = (size_t)g * nao + mu;
-                        const double Xa = xa[r], Xb = xb[r];
-                        const double Z = GGA ? za[r] + zb[r] : 2.0 * (cs[row] * Xa + cs[64 + row] * Xb);
+                        const double *c4 = cs + row;
+                        double Z;
+                        if constexpr (NS == 1) Z = GGA ? accZ[0][r] : 2.0 * c4[0] * accX[0][r];
+                        else Z = GGA ? accZ[0][r] + accZ[1][r] : 2.0 * (c4[0] * accX[0][r] + c4[64] * accX[1][r]);
                         sx += gx[o] * Z;
                         sy += gy[o] * Z;
                         sz += gz[o] * Z;
                         if (GGA) {
-                            const double w1 = cs[16 + row] * Xa + cs[80 + row] * Xb, w2 = cs[32 + row] * Xa + cs[96 + row] * Xb,
-                                         w3 = cs[48 + row] * Xa + cs[112 + row] * Xb;
                             const double hxx = hess[o], hxy = hess[plane + o], hxz = hess[2 * plane + o],
                                          hyy = hess[3 * plane + o], hyz = hess[4 * plane + o], hzz = hess[5 * plane + o];
-                            sx += w1 * hxx + w2 * hxy + w3 * hxz;
-                            sy += w1 * hxy + w2 * hyy + w3 * hyz;
-                            sz += w1 * hxz + w2 * hyz + w3 * hzz;
+                            if constexpr (NS == 1) {   // the closed-shell order of operations: the sum over k first, then X
+                                const double c1 = c4[16], c2 = c4[32], c3 = c4[48], X = accX[0][r];
+                                sx += (c1 * hxx + c2 * hxy + c3 * hxz) * X;
+                                sy += (c1 * hxy + c2 * hyy + c3 * hyz) * X;
+                                sz += (c1 * hxz + c2 * hyz + c3 * hzz) * X;
+                            } else {
+                                const double Xa = accX[0][r], Xb = accX[1][r];
+                                const double w1 = c4[16] * Xa + c4[80] * Xb, w2 = c4[32] * Xa + c4[96] * Xb,
+                                             w3 = c4[48] * Xa + c4[112] * Xb;
+                                sx += w1 * hxx + w2 * hxy + w3 * hxz;
+                                sy += w1 * hxy + w2 * hyy + w3 * hyz;
+                                sz += w1 * hxz + w2 * hyz + w3 * hzz;
+                            }
                         }
                     }
                 }
@@ -388,13 +309,13 @@ hipError_t launch_eval_ao_hess(hipStream_t st, long ngrid, int nao, int nchunk, 
     return hipGetLastError();
 }
 
-XcGradPlan xc_grad_plan(int num_cu, bool gga, long ngrid, int nao)
+XcGradPlan xc_grad_plan(int num_cu, bool gga, int nspin, long ngrid, int nao)
 {
     XcGradPlan p;
     p.NP = ((nao + 15) / 16) * 16;
-    p.kc = std::min(p.NP, XCG_KC_MAX);
+    p.kc = std::min(p.NP, nspin == 2 ? XCGS_KC_MAX : XCG_KC_MAX);
     p.ldk = p.kc | 1;
-    p.lds = sizeof(double) * ((size_t)(gga ? 2 : 1) * XCG_ROWS * p.ldk + 3 * (size_t)p.NP + 64);
+    p.lds = sizeof(double) * ((size_t)(gga ? 1 + nspin : 1) * XCG_ROWS * p.ldk + 3 * (size_t)p.NP + 64 * (size_t)nspin);
     const long ntile = (ngrid + XCG_ROWS - 1) / XCG_ROWS;
     const long per_cu = std::max<long>(1, std::min<long>(8, (160 * 1024) / (long)(p.lds + 512)));
     p.nwg = (int)std::min<long>(ntile, per_cu * num_cu);
@@ -403,9 +324,11 @@ XcGradPlan xc_grad_plan(int num_cu, bool gga, long ngrid, int nao)
 
 namespace {
 
-// k_xc_grad alone: one slab of (nao, 3) per workgroup into `slabs`
+// k_xc_grad<gga, NS> alone: one slab of (nao, 3) per workgroup into `slabs`.  `p`: the plan for NS spins.
+template <int NS>
 hipError_t launch_xc_grad_slabs(hipStream_t st, const XcGradPlan &p, bool gga, double fac, long ngrid, int nao, const double *ao,
-                                const double *ao_grad, const double *hess, const double *coef, const double *Dp, double *slabs)
+                                const double *ao_grad, const double *hess, const double *coef_a, const double *coef_b,
+                                const double *Dp_a, const double *Dp_b, double *slabs)
 {
     if (p.lds > 160 * 1024) return hipErrorInvalidValue;
     const size_t plane = (size_t)ngrid * nao;
@@ -417,11 +340,11 @@ hipError_t launch_xc_grad_slabs(hipStream_t st, const XcGradPlan &p, bool gga, d
             allowed = p.lds;
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)p.nwg), dim3(256), p.lds, st, ngrid, nao, p.NP, p.kc, p.ldk, fac, ao, gx, gy, gz,
-                           hess, coef, Dp, slabs);
+                           hess, coef_a, coef_b, Dp_a, Dp_b, slabs);
         return hipGetLastError();
     };
-    static size_t allowed_gga = 48 * 1024, allowed_lda = 48 * 1024;
-    return gga ? launch(k_xc_grad<true>, allowed_gga) : launch(k_xc_grad<false>, allowed_lda);
+    static size_t allowed_gga = 48 * 1024, allowed_lda = 48 * 1024;   // of this NS
+    return gga ? launch(k_xc_grad<true, NS>, allowed_gga) : launch(k_xc_grad<false, NS>, allowed_lda);
 }
 
 hipError_t launch_xc_grad_reduce(hipStream_t st, int nao, int nslab, const double *slabs, double *out)
@@ -437,43 +360,16 @@ hipError_t launch_xc_grad(hipStream_t st, const XcGradPlan &p, bool gga, double 
                           const double *ao_grad, const double *hess, const double *coef, const double *Dp, double *slabs,
                           double *out)
 {
-    const hipError_t e = launch_xc_grad_slabs(st, p, gga, fac, ngrid, nao, ao, ao_grad, hess, coef, Dp, slabs);
+    const hipError_t e = launch_xc_grad_slabs<1>(st, p, gga, fac, ngrid, nao, ao, ao_grad, hess, coef, nullptr, Dp, nullptr, slabs);
     if (e != hipSuccess) return e;
     return launch_xc_grad_reduce(st, nao, p.nwg, slabs, out);
-}
-
-XcGradPlan xc_grad_spin_fused_plan(int num_cu, bool gga, long ngrid, int nao)
-{
-    XcGradPlan p;
-    p.NP = ((nao + 15) / 16) * 16;
-    p.kc = std::min(p.NP, XCGS_KC_MAX);
-    p.ldk = p.kc | 1;
-    p.lds = sizeof(double) * ((size_t)(gga ? 3 : 1) * XCG_ROWS * p.ldk + 3 * (size_t)p.NP + 128);
-    const long ntile = (ngrid + XCG_ROWS - 1) / XCG_ROWS;
-    const long per_cu = std::max<long>(1, std::min<long>(8, (160 * 1024) / (long)(p.lds + 512)));
-    p.nwg = (int)std::min<long>(ntile, per_cu * num_cu);
-    return p;
 }
 
 hipError_t launch_xc_grad_spin_fused(hipStream_t st, const XcGradPlan &p, bool gga, double fac, long ngrid, int nao, const double *ao,
                                      const double *ao_grad, const double *hess, const double *coef_a, const double *coef_b,
                                      const double *Dp_a, const double *Dp_b, double *slabs, double *out)
 {
-    if (p.lds > 160 * 1024) return hipErrorInvalidValue;
-    const size_t plane = (size_t)ngrid * nao;
-    const double *gx = ao_grad, *gy = ao_grad + plane, *gz = ao_grad + 2 * plane;
-    auto launch = [&](auto kern, size_t &allowed) -> hipError_t {
-        if (p.lds > allowed) {
-            const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
-            if (e != hipSuccess) return e;
-            allowed = p.lds;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)p.nwg), dim3(256), p.lds, st, ngrid, nao, p.NP, p.kc, p.ldk, fac, ao, gx, gy, gz,
-                           hess, coef_a, coef_b, Dp_a, Dp_b, slabs);
-        return hipGetLastError();
-    };
-    static size_t allowed_gga = 48 * 1024, allowed_lda = 48 * 1024;
-    const hipError_t e = gga ? launch(k_xc_grad_spin<true>, allowed_gga) : launch(k_xc_grad_spin<false>, allowed_lda);
+    const hipError_t e = launch_xc_grad_slabs<2>(st, p, gga, fac, ngrid, nao, ao, ao_grad, hess, coef_a, coef_b, Dp_a, Dp_b, slabs);
     if (e != hipSuccess) return e;
     return launch_xc_grad_reduce(st, nao, p.nwg, slabs, out);
 }
@@ -482,9 +378,10 @@ hipError_t launch_xc_grad_spin(hipStream_t st, const XcGradPlan &p, bool gga, do
                                const double *ao_grad, const double *hess, const double *coef_a, const double *coef_b,
                                const double *Dp_a, const double *Dp_b, double *slabs, double *out)
 {
-    hipError_t e = launch_xc_grad_slabs(st, p, gga, fac, ngrid, nao, ao, ao_grad, hess, coef_a, Dp_a, slabs);
+    hipError_t e = launch_xc_grad_slabs<1>(st, p, gga, fac, ngrid, nao, ao, ao_grad, hess, coef_a, nullptr, Dp_a, nullptr, slabs);
     if (e != hipSuccess) return e;
-    e = launch_xc_grad_slabs(st, p, gga, fac, ngrid, nao, ao, ao_grad, hess, coef_b, Dp_b, slabs + (size_t)p.nwg * 3 * nao);
+    e = launch_xc_grad_slabs<1>(st, p, gga, fac, ngrid, nao, ao, ao_grad, hess, coef_b, nullptr, Dp_b, nullptr,
+                                slabs + (size_t)p.nwg * 3 * nao);
     if (e != hipSuccess) return e;
     return launch_xc_grad_reduce(st, nao, 2 * p.nwg, slabs, out);
 }

@@ -97,6 +97,62 @@ def ao_hessian_host(shells, coords):
     return out
 
 
+def _densities(functional, dms, ao, ao_grad):
+    """(library type, reads sigma, ao, ao_grad, the matrices, [(rho, grad rho) of each]) for the host entries below: the
+    planes as C-ordered float64, grad rho None for an LDA-class functional."""
+    t, _, gga = response._kind(functional)
+    if gga and ao_grad is None:
+        raise ValueError("ao_grad is needed for a gradient-corrected functional")
+    ao = np.ascontiguousarray(ao, dtype=np.float64)
+    gr = None if ao_grad is None else np.ascontiguousarray(ao_grad, dtype=np.float64)
+    dms = [np.asarray(d, dtype=np.float64) for d in dms]
+    return t, gga, ao, gr, dms, [response._density(d, ao, gr if gga else None) for d in dms]
+
+
+def _point_closed(functional, rho, g, weights, quirks):
+    """response.point_host at a closed-shell density: sigma from grad rho (zeros for an LDA-class functional, g None)."""
+    if g is None:
+        g, sigma = np.zeros((rho.shape[0], 3)), np.zeros(rho.shape[0])
+    else:
+        sigma = np.einsum("gk,gk->g", g, g)
+    return response.point_host(functional, rho, sigma, g, weights, quirks)
+
+
+def _xc_contract(fac, gga, ao, gr, hs, pairs):
+    """G (nao, 3) = -fac sum_s sum_g [ ao_grad[x] (Q_s D_s) + (sum_k c_sk ao_hess[xk]) (AO D_s) ][g, mu] over the pairs
+    (dm_s, c_s) of a density matrix (its symmetric part counts) and its point coefficients c_s0..c_s3,
+    Q_s = 2 c_s0 AO + sum_k c_sk ao_grad[k]: one pair for the closed shell, one per spin for an open-shell state."""
+    G = np.zeros((ao.shape[1], 3))
+    for dm, c in pairs:
+        ds = 0.5 * (dm + dm.T)
+        X = ao @ ds
+        if not gga:
+            Z = 2.0 * c[0][:, None] * X
+            for x in range(3):
+                G[:, x] -= fac * np.einsum("gm,gm->m", gr[x], Z)
+            continue
+        Q = 2.0 * c[0][:, None] * ao
+        for k in range(3):
+            Q += c[1 + k][:, None] * gr[k]
+        Z = Q @ ds
+        for x in range(3):
+            H = sum(c[1 + k][:, None] * hs[HESS_INDEX[x][k]] for k in range(3))
+            G[:, x] -= fac * (np.einsum("gm,gm->m", gr[x], Z) + np.einsum("gm,gm->m", H, X))
+    return G
+
+
+def _xc_gradient_args(functional, dms, ao, weights, ao_grad, ao_hess):
+    """What xc_gradient_host and xc_gradient_spin_host do first: the refusals, then (_xc_contract's first five arguments,
+    the weights, the matrices, [(rho, grad rho) of each])."""
+    if ao_grad is None:
+        raise ValueError("ao_grad is needed: the derivative of the density by a centre is made of it")
+    t, gga, ao, gr, dms, dens = _densities(functional, dms, ao, ao_grad)
+    if gga and ao_hess is None:
+        raise ValueError("ao_hess is needed for a gradient-corrected functional")
+    hs = np.ascontiguousarray(ao_hess, dtype=np.float64) if gga else None
+    return (2.0 if t == 2 else 1.0, gga, ao, gr, hs), np.ascontiguousarray(weights, dtype=np.float64), dms, dens
+
+
 def xc_gradient_host(functional, dm, ao, weights, ao_grad, ao_hess=None, quirks=True):
     """G (nao, 3) of DFT_ComputeXCGradient from AO planes in numpy: ao (ngrid, nao), ao_grad (3, ngrid, nao), ao_hess
     (6, ngrid, nao) (not needed for an LDA-class functional).  The point coefficients are the sweep's own, in the
@@ -107,39 +163,8 @@ def xc_gradient_host(functional, dm, ao, weights, ao_grad, ao_hess=None, quirks=
 
     with fac = 1 (one-sided) or 2 (B3LYP).  With quirks and vwn5_c / pbe_c in the functional the shipped potentials
     are not the derivatives of the energy; G is then built from the shipped ones."""
-    t, _, gga = response._kind(functional)
-    if ao_grad is None:
-        raise ValueError("ao_grad is needed: the derivative of the density by a centre is made of it")
-    if gga and ao_hess is None:
-        raise ValueError("ao_hess is needed for a gradient-corrected functional")
-    ao = np.ascontiguousarray(ao, dtype=np.float64)
-    gr = np.ascontiguousarray(ao_grad, dtype=np.float64)
-    w = np.ascontiguousarray(weights, dtype=np.float64)
-    dm = np.asarray(dm, dtype=np.float64)
-    ds = 0.5 * (dm + dm.T)
-    rho, g = response._density(dm, ao, gr if gga else None)
-    if gga:
-        sigma = np.einsum("gk,gk->g", g, g)
-    else:
-        g, sigma = np.zeros((ao.shape[0], 3)), np.zeros(ao.shape[0])
-    c = response.point_host(functional, rho, sigma, g, w, quirks)[1:]
-    fac = 2.0 if t == 2 else 1.0
-    X = ao @ ds
-    G = np.zeros((ao.shape[1], 3))
-    if not gga:
-        Z = 2.0 * c[0][:, None] * X
-        for x in range(3):
-            G[:, x] = -fac * np.einsum("gm,gm->m", gr[x], Z)
-        return G
-    hs = np.ascontiguousarray(ao_hess, dtype=np.float64)
-    Q = 2.0 * c[0][:, None] * ao
-    for k in range(3):
-        Q += c[1 + k][:, None] * gr[k]
-    Z = Q @ ds
-    for x in range(3):
-        H = sum(c[1 + k][:, None] * hs[HESS_INDEX[x][k]] for k in range(3))
-        G[:, x] = -fac * (np.einsum("gm,gm->m", gr[x], Z) + np.einsum("gm,gm->m", H, X))
-    return G
+    planes, w, dms, [(rho, g)] = _xc_gradient_args(functional, [dm], ao, weights, ao_grad, ao_hess)
+    return _xc_contract(*planes, [(dms[0], _point_closed(functional, rho, g, w, quirks)[1:])])
 
 
 def xc_gradient_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad, ao_hess=None):
@@ -151,60 +176,21 @@ def xc_gradient_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad, ao_hess=
 
     with fac = 1 (one-sided types) or 2 (B3LYP): xc_gradient_host's formula once per spin.  The spin-resolved bodies are the
     derivatives of the energy: no `quirks`."""
-    t, _, gga = response._kind(functional)
-    if ao_grad is None:
-        raise ValueError("ao_grad is needed: the derivative of the density by a centre is made of it")
-    if gga and ao_hess is None:
-        raise ValueError("ao_hess is needed for a gradient-corrected functional")
-    ao = np.ascontiguousarray(ao, dtype=np.float64)
-    gr = np.ascontiguousarray(ao_grad, dtype=np.float64)
-    w = np.ascontiguousarray(weights, dtype=np.float64)
-    dms = [np.asarray(d, dtype=np.float64) for d in (dm_a, dm_b)]
-    (ra, ga), (rb, gb) = (response._density(d, ao, gr if gga else None) for d in dms)
+    planes, w, dms, [(ra, ga), (rb, gb)] = _xc_gradient_args(functional, [dm_a, dm_b], ao, weights, ao_grad, ao_hess)
     p = response.point_spin_host(functional, ra, rb, ga, gb, w)
-    hs = np.ascontiguousarray(ao_hess, dtype=np.float64) if gga else None
-    fac = 2.0 if t == 2 else 1.0
-    G = np.zeros((ao.shape[1], 3))
-    for dm, c in zip(dms, (p[1:5], p[5:9])):
-        X = ao @ (0.5 * (dm + dm.T))
-        if not gga:
-            Z = 2.0 * c[0][:, None] * X
-            for x in range(3):
-                G[:, x] -= fac * np.einsum("gm,gm->m", gr[x], Z)
-            continue
-        Q = 2.0 * c[0][:, None] * ao
-        for k in range(3):
-            Q += c[1 + k][:, None] * gr[k]
-        Z = Q @ (0.5 * (dm + dm.T))
-        for x in range(3):
-            H = sum(c[1 + k][:, None] * hs[HESS_INDEX[x][k]] for k in range(3))
-            G[:, x] -= fac * (np.einsum("gm,gm->m", gr[x], Z) + np.einsum("gm,gm->m", H, X))
-    return G
+    return _xc_contract(*planes, zip(dms, (p[1:5], p[5:9])))
 
 
 def xc_energy_density_host(functional, dm, ao, ao_grad=None, quirks=True):
     """e_g (ngrid,) of DFT_ComputeXCEnergyDensity from AO planes in numpy: the energy per volume of the sweep's point body at the
     density of dm, without the weight (response.point_host with unit weights)."""
-    _, _, gga = response._kind(functional)
-    if gga and ao_grad is None:
-        raise ValueError("ao_grad is needed for a gradient-corrected functional")
-    ao = np.ascontiguousarray(ao, dtype=np.float64)
-    rho, g = response._density(np.asarray(dm, dtype=np.float64), ao, np.ascontiguousarray(ao_grad, dtype=np.float64) if gga else None)
-    if gga:
-        sigma = np.einsum("gk,gk->g", g, g)
-    else:
-        g, sigma = np.zeros((ao.shape[0], 3)), np.zeros(ao.shape[0])
-    return response.point_host(functional, rho, sigma, g, np.ones(ao.shape[0]), quirks)[0]
+    _, _, ao, _, _, dens = _densities(functional, [dm], ao, ao_grad)
+    return _point_closed(functional, *dens[0], np.ones(ao.shape[0]), quirks)[0]
 
 
 def xc_energy_density_spin_host(functional, dm_a, dm_b, ao, ao_grad=None):
     """e_g (ngrid,) of DFT_ComputeXCEnergyDensitySpin from AO planes in numpy (response.point_spin_host, row 0)."""
-    _, _, gga = response._kind(functional)
-    if gga and ao_grad is None:
-        raise ValueError("ao_grad is needed for a gradient-corrected functional")
-    ao = np.ascontiguousarray(ao, dtype=np.float64)
-    gr = np.ascontiguousarray(ao_grad, dtype=np.float64) if gga else None
-    (ra, ga), (rb, gb) = (response._density(np.asarray(d, dtype=np.float64), ao, gr) for d in (dm_a, dm_b))
+    (ra, ga), (rb, gb) = _densities(functional, [dm_a, dm_b], ao, ao_grad)[5]
     return response.point_spin_host(functional, ra, rb, ga, gb)[0]
 
 
@@ -329,6 +315,69 @@ def _fock(inp, backend, f, dm):
 _QUIRKY = ("vwn5_c", "pbe_c")
 
 
+def _checked(who, inp, backend, functional, two_electron, device_method, wrong_result, grid_response):
+    """The refusals nuclear_gradient and nuclear_gradient_uks share; (the functional, its weight vector).  device_method: what
+    the backend needs for two_electron="device"; wrong_result: why the SCF result is the other assembly's (None: it is not)."""
+    if two_electron not in ("host", "device"):
+        raise ValueError(f"{who}: two_electron must be 'host' or 'device', not {two_electron!r}")
+    if two_electron == "device" and not hasattr(backend, device_method):
+        raise ValueError(f"{who}: two_electron='device' needs a backend with a device two-electron gradient "
+                         "(scf.HipBackend); this backend has none")
+    if wrong_result:
+        raise ValueError(wrong_result)
+    if getattr(inp, "efield", None) is not None:
+        raise ValueError(f"{who}: a run in a uniform electric field (efield) is not supported")
+    if getattr(backend, "world", 1) > 1:
+        raise ValueError(f"{who} runs on one rank: the grid of this backend is sharded over several")
+    if grid_response:
+        _grid_of(inp.grids, inp.symbols, inp.atom_xyz, who)          # refuses a grid that does not say which atom a point moves with
+    f = functionals.resolve(functional if functional is not None else backend.functional)
+    return f, f.weight_vector()
+
+
+def _has_quirky(wv):
+    return any(wv[functionals.COMPONENTS.index(c)] != 0.0 for c in _QUIRKY)
+
+
+def _assemble(inp, backend, f, wv, dm, W, two_electron, mats, host_extra, grid_response):
+    """(g, terms) from the total density dm, W and the finished two-electron term.  mats: the matrices of the XC term --
+    (dm,) for the closed shell (backend.xc_gradient / xc_grid_response, xc_gradient_host / xc_grid_response_host otherwise),
+    (dm_a, dm_b) for an open-shell state (the *_spin ones); host_extra: what the host functions take behind them (quirks)."""
+    spin = len(mats) == 2
+    sfx = "_spin" if spin else ""
+    host_gradient, host_grid = (xc_gradient_spin_host, xc_grid_response_spin_host) if spin else (xc_gradient_host, xc_grid_response_host)
+    sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
+    z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
+    g1 = integrals.grad1e(sh, xyz, z, dm, W)
+    field = integrals.point_coulomb_field(sh, xyz, dm)         # sum D d<1/|r - R_A|>/dR_A: the operator part of V
+    terms = {"one_electron": g1[0] + g1[1] + g1[2] - z[:, None] * field,
+             "two_electron": two_electron,
+             "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
+    if any(w != 0.0 for w in wv):
+        planes = None
+        if hasattr(backend, "xc_gradient" + sfx):
+            G = getattr(backend, "xc_gradient" + sfx)(*mats)
+        else:
+            planes = ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
+            G = host_gradient(f, *mats, ao, inp.grids.weights, gr, hs if f.needs_gradient else None, *host_extra)
+        terms["xc"] = sum_over_atoms(sh, G)
+        if grid_response:
+            if hasattr(backend, "xc_grid_response" + sfx):
+                terms["xc_grid"] = getattr(backend, "xc_grid_response" + sfx)(*mats)
+            else:
+                terms["xc_grid"] = host_grid(f, *mats, sh, inp.grids, inp.symbols, xyz, *host_extra, planes=planes)
+    else:
+        terms["xc"] = np.zeros_like(xyz)
+        if grid_response:
+            terms["xc_grid"] = np.zeros_like(xyz)
+    pc = getattr(inp, "point_charges", None)
+    if pc is not None and len(pc):
+        terms["external"] = integrals.grad1e(sh, pc[:, :3], pc[:, 3], dm, W)[2] + _pair_repulsion_gradient(xyz, z, pc[:, :3], pc[:, 3])
+    else:
+        terms["external"] = np.zeros_like(xyz)
+    return sum(terms.values()), terms
+
+
 def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two_electron="host", grid_response=False):
     """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged closed-shell state `scf_result` (scf.run_scf) and its
     breakdown {"one_electron", "two_electron", "xc", "nuclear", "external"}, each (natm, 3).  By default the derivative at FIXED
@@ -344,63 +393,22 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
     the term "xc_grid": the motion of the quadrature points with their atoms and the derivatives of the Becke weights
     (backend.xc_grid_response on scf.HipBackend, xc_grid_response_host otherwise); g is then the derivative of the energy as the
     grid follows the atoms, and sums to zero over the atoms.  Without it everything is as it was."""
-    if two_electron not in ("host", "device"):
-        raise ValueError(f"nuclear_gradient: two_electron must be 'host' or 'device', not {two_electron!r}")
-    if two_electron == "device" and not hasattr(backend, "grad2e"):
-        raise ValueError("nuclear_gradient: two_electron='device' needs a backend with a device two-electron gradient "
-                         "(scf.HipBackend); this backend has none")
-    if scf_result.get("uks"):
-        raise ValueError("nuclear_gradient: an unrestricted (UKS) result has no analytic gradient here: the assembly is closed-shell "
-                         "(nuclear_gradient_uks assembles the open-shell one)")
-    if getattr(inp, "efield", None) is not None:
-        raise ValueError("nuclear_gradient: a run in a uniform electric field (efield) is not supported")
-    if getattr(backend, "world", 1) > 1:
-        raise ValueError("nuclear_gradient runs on one rank: the grid of this backend is sharded over several")
-    f = functionals.resolve(functional if functional is not None else backend.functional)
+    wrong = ("nuclear_gradient: an unrestricted (UKS) result has no analytic gradient here: the assembly is closed-shell "
+             "(nuclear_gradient_uks assembles the open-shell one)") if scf_result.get("uks") else None
+    f, wv = _checked("nuclear_gradient", inp, backend, functional, two_electron, "grad2e", wrong, grid_response)
     if quirks is None:
         quirks = bool(getattr(backend, "quirks", getattr(backend, "q", True)))
-    wv = f.weight_vector()
-    if quirks and any(wv[functionals.COMPONENTS.index(c)] != 0.0 for c in _QUIRKY):
+    if quirks and _has_quirky(wv):
         raise ValueError("nuclear_gradient: with quirks = 1 the shipped vwn5_c / pbe_c potentials are not the derivatives of their "
                          "energies, so the converged state is not stationary and the analytic gradient is not the energy's; "
                          "run with --quirks 0")
-    if grid_response:
-        _grid_of(inp.grids, inp.symbols, inp.atom_xyz, "nuclear_gradient")          # refuses a grid that does not say which atom a point moves with
     dm = np.asarray(scf_result["dm"], dtype=np.float64)
     dm = np.ascontiguousarray(0.5 * (dm + dm.T))
-    sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
-    z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
     F = _fock(inp, backend, f, dm)
     W = 0.5 * dm @ F @ dm
     W = 0.5 * (W + W.T)
-    g1 = integrals.grad1e(sh, xyz, z, dm, W)
-    field = integrals.point_coulomb_field(sh, xyz, dm)         # sum D d<1/|r - R_A|>/dR_A: the operator part of V
-    terms = {"one_electron": g1[0] + g1[1] + g1[2] - z[:, None] * field,
-             "two_electron": backend.grad2e(dm, f.c_hf) if two_electron == "device" else integrals.grad2e(sh, dm, f.c_hf),
-             "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
-    if any(w != 0.0 for w in wv):
-        planes = None
-        if hasattr(backend, "xc_gradient"):
-            G = backend.xc_gradient(dm)
-        else:
-            planes = ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
-            G = xc_gradient_host(f, dm, ao, inp.grids.weights, gr, hs if f.needs_gradient else None, quirks)
-        terms["xc"] = sum_over_atoms(sh, G)
-        if grid_response:
-            if hasattr(backend, "xc_grid_response"):
-                terms["xc_grid"] = backend.xc_grid_response(dm)
-            else:
-                terms["xc_grid"] = xc_grid_response_host(f, dm, sh, inp.grids, inp.symbols, xyz, quirks, planes=planes)
-    else:
-        terms["xc"] = np.zeros_like(xyz)
-        if grid_response:
-            terms["xc_grid"] = np.zeros_like(xyz)
-    pc = getattr(inp, "point_charges", None)
-    if pc is not None and len(pc):
-        terms["external"] = integrals.grad1e(sh, pc[:, :3], pc[:, 3], dm, W)[2] + _pair_repulsion_gradient(xyz, z, pc[:, :3], pc[:, 3])
-    else:
-        terms["external"] = np.zeros_like(xyz)
-    return sum(terms.values()), terms
+    g2e = backend.grad2e(dm, f.c_hf) if two_electron == "device" else integrals.grad2e(inp.shells, dm, f.c_hf)
+    return _assemble(inp, backend, f, wv, dm, W, g2e, (dm,), (quirks,), grid_response)
 
 
 def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron="host", grid_response=False):
@@ -416,26 +424,14 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
 
     A spin without electrons has D_s = 0 and contributes nothing.  Point charges are served through "external".
     `grid_response` = True adds "xc_grid" as in nuclear_gradient (backend.xc_grid_response_spin / xc_grid_response_spin_host)."""
-    if two_electron not in ("host", "device"):
-        raise ValueError(f"nuclear_gradient_uks: two_electron must be 'host' or 'device', not {two_electron!r}")
-    if two_electron == "device" and not hasattr(backend, "grad2e_spin"):
-        raise ValueError("nuclear_gradient_uks: two_electron='device' needs a backend with a device two-electron gradient "
-                         "(scf.HipBackend); this backend has none")
-    if "dm_a" not in uks_result or "dm_b" not in uks_result:
-        raise ValueError("nuclear_gradient_uks needs a scf.run_uks result (dm_a, dm_b); nuclear_gradient serves the closed shell")
-    if getattr(inp, "efield", None) is not None:
-        raise ValueError("nuclear_gradient_uks: a run in a uniform electric field (efield) is not supported")
-    if getattr(backend, "world", 1) > 1:
-        raise ValueError("nuclear_gradient_uks runs on one rank: the grid of this backend is sharded over several")
+    wrong = None if ("dm_a" in uks_result and "dm_b" in uks_result) else \
+        "nuclear_gradient_uks needs a scf.run_uks result (dm_a, dm_b); nuclear_gradient serves the closed shell"
+    f, wv = _checked("nuclear_gradient_uks", inp, backend, functional, two_electron, "grad2e_spin", wrong, grid_response)
     if getattr(backend, "dm_factor", False):
         raise ValueError("nuclear_gradient_uks takes the density matrices themselves: run without dm_factor")
-    f = functionals.resolve(functional if functional is not None else backend.functional)
-    wv = f.weight_vector()
-    if bool(getattr(backend, "quirks", getattr(backend, "q", False))) and any(wv[functionals.COMPONENTS.index(c)] != 0.0 for c in _QUIRKY):
+    if bool(getattr(backend, "quirks", getattr(backend, "q", False))) and _has_quirky(wv):
         raise ValueError("nuclear_gradient_uks: the spin-resolved potentials are the derivatives of the energy, but with quirks = 1 the "
                          "ground state solved the shipped vwn5_c / pbe_c potentials, which are not; run with --quirks 0")
-    if grid_response:
-        _grid_of(inp.grids, inp.symbols, inp.atom_xyz, "nuclear_gradient_uks")
     from scipy.linalg import eigh
     S = inp.S
     dms = [np.asarray(uks_result[k], dtype=np.float64) for k in ("dm_a", "dm_b")]
@@ -453,34 +449,5 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
         W += d @ F @ d
     W = 0.5 * (W + W.T)
     dm, ms = np.ascontiguousarray(dms[0] + dms[1]), np.ascontiguousarray(dms[0] - dms[1])
-    sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
-    z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
-    g1 = integrals.grad1e(sh, xyz, z, dm, W)
-    field = integrals.point_coulomb_field(sh, xyz, dm)
-    terms = {"one_electron": g1[0] + g1[1] + g1[2] - z[:, None] * field,
-             "two_electron": backend.grad2e_spin(dms[0], dms[1], f.c_hf) if two_electron == "device"
-                             else integrals.grad2e_spin(sh, dm, ms, f.c_hf),
-             "nuclear": _pair_repulsion_gradient(xyz, z, xyz, z)}
-    if any(w != 0.0 for w in wv):
-        planes = None
-        if hasattr(backend, "xc_gradient_spin"):
-            G = backend.xc_gradient_spin(dms[0], dms[1])
-        else:
-            planes = ao, gr, hs = ao_planes_host(sh, inp.grids.coords)
-            G = xc_gradient_spin_host(f, dms[0], dms[1], ao, inp.grids.weights, gr, hs if f.needs_gradient else None)
-        terms["xc"] = sum_over_atoms(sh, G)
-        if grid_response:
-            if hasattr(backend, "xc_grid_response_spin"):
-                terms["xc_grid"] = backend.xc_grid_response_spin(dms[0], dms[1])
-            else:
-                terms["xc_grid"] = xc_grid_response_spin_host(f, dms[0], dms[1], sh, inp.grids, inp.symbols, xyz, planes=planes)
-    else:
-        terms["xc"] = np.zeros_like(xyz)
-        if grid_response:
-            terms["xc_grid"] = np.zeros_like(xyz)
-    pc = getattr(inp, "point_charges", None)
-    if pc is not None and len(pc):
-        terms["external"] = integrals.grad1e(sh, pc[:, :3], pc[:, 3], dm, W)[2] + _pair_repulsion_gradient(xyz, z, pc[:, :3], pc[:, 3])
-    else:
-        terms["external"] = np.zeros_like(xyz)
-    return sum(terms.values()), terms
+    g2e = backend.grad2e_spin(dms[0], dms[1], f.c_hf) if two_electron == "device" else integrals.grad2e_spin(inp.shells, dm, ms, f.c_hf)
+    return _assemble(inp, backend, f, wv, dm, W, g2e, tuple(dms), (), grid_response)

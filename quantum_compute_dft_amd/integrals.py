@@ -163,25 +163,27 @@ def grad1e(shells, centres, charges, dm, w):
     return out
 
 
+def _grad2e_call(name, shells, mats, c_hf, per_shell):
+    """qc_grad2e / qc_grad2e_spin (`name`) on the symmetric matrices `mats`: the owner of every shell (its atom, or with
+    `per_shell` the shell itself), the zeroed output, the call and its refusal."""
+    keep, p = _args(shells)
+    owner = np.arange(shells.nshell, dtype=np.int32) if per_shell else np.ascontiguousarray(shells.atom, dtype=np.int32)
+    natm = int(owner.max()) + 1
+    out = np.zeros((natm, 3))
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    rc = getattr(_load(), "qc_" + name)(shells.nshell, *p, shells.nao, owner.ctypes.data_as(ip), natm,
+                                        *(m.ctypes.data_as(dp) for m in mats), float(c_hf), out.ctypes.data_as(dp))
+    if rc != 0:
+        raise ValueError(f"{name}: unsupported angular momentum (s-f) or a shell without an atom")
+    return out
+
+
 def grad2e(shells, dm, c_hf=0.0, per_shell=False):
     """(natm, 3): d/dR_A of 1/2 sum D_ab D_cd (ab|cd) - c_hf/4 sum D_ac D_bd (ab|cd) for a symmetric dm (qc_grad2e): every
     derivative quartet contracted as it is made, the dense ERI never built, threads as set_threads says.
     `per_shell`: (nshell, 3) instead, the term of every shell's own centre (the same routine with every shell its own
     "atom"); the rows of an atom's shells add up to the atom's row."""
-    keep, p = _args(shells)
-    dm = _sym(dm, "dm")
-    if per_shell:
-        owner = np.arange(shells.nshell, dtype=np.int32)
-    else:
-        owner = np.ascontiguousarray(shells.atom, dtype=np.int32)
-    natm = int(owner.max()) + 1
-    out = np.zeros((natm, 3))
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
-    rc = _load().qc_grad2e(shells.nshell, *p, shells.nao, owner.ctypes.data_as(ip), natm, dm.ctypes.data_as(dp), float(c_hf),
-                           out.ctypes.data_as(dp))
-    if rc != 0:
-        raise ValueError("grad2e: unsupported angular momentum (s-f) or a shell without an atom")
-    return out
+    return _grad2e_call("grad2e", shells, [_sym(dm, "dm")], c_hf, per_shell)
 
 
 def grad2e_spin(shells, dm, ms, c_hf=0.0, per_shell=False):
@@ -189,22 +191,10 @@ def grad2e_spin(shells, dm, ms, c_hf=0.0, per_shell=False):
     an open-shell state with the total density dm = D_a + D_b and the spin density ms = D_a - D_b, both symmetric
     (qc_grad2e_spin): grad2e's pass over the derivative quartets with the extended density quartet.  `per_shell` as in
     grad2e."""
-    keep, p = _args(shells)
     dm, ms = _sym(dm, "dm"), _sym(ms, "ms")
     if ms.shape != dm.shape:
         raise ValueError("grad2e_spin: dm and ms must have the same shape")
-    if per_shell:
-        owner = np.arange(shells.nshell, dtype=np.int32)
-    else:
-        owner = np.ascontiguousarray(shells.atom, dtype=np.int32)
-    natm = int(owner.max()) + 1
-    out = np.zeros((natm, 3))
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
-    rc = _load().qc_grad2e_spin(shells.nshell, *p, shells.nao, owner.ctypes.data_as(ip), natm, dm.ctypes.data_as(dp),
-                                ms.ctypes.data_as(dp), float(c_hf), out.ctypes.data_as(dp))
-    if rc != 0:
-        raise ValueError("grad2e_spin: unsupported angular momentum (s-f) or a shell without an atom")
-    return out
+    return _grad2e_call("grad2e_spin", shells, [dm, ms], c_hf, per_shell)
 
 
 def energy_nuc(symbols, atom_xyz):

@@ -742,15 +742,23 @@ class HipBackend:
         the three gradient planes is copied together, the entry wants them back to back) and are evaluated per slice
         otherwise (an LDA-class run keeps no gradient planes, --ao direct keeps none).  slice_rows: rows per slice (default:
         what keeps the Hessian planes within XC_GRADIENT_HESS_BYTES)."""
-        d_dm = self._dev(dm)
-        return self._xc_gradient_slices(slice_rows, lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient(m, self.nao, d_dm, ao, w, out, gr, hs))
+        return self._xc_gradient_slices(slice_rows, self._xc_gradient_calls(dm)[0])
 
     def xc_gradient_spin(self, dm_a, dm_b, slice_rows=None):
         """G (nao, 3) as a numpy array for an open-shell state: dExc[dm_a, dm_b] / d(centre of basis function mu) at fixed
         points and weights (DFT_ComputeXCGradientSpin), summed over slices of the grid exactly as xc_gradient does."""
-        self._uks_check()
-        d_a, d_b = self._dev(dm_a), self._dev(dm_b)
-        return self._xc_gradient_slices(slice_rows, lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient_spin(m, self.nao, d_a, d_b, ao, w, out, gr, hs))
+        return self._xc_gradient_slices(slice_rows, self._xc_gradient_calls(dm_a, dm_b)[0])
+
+    def _xc_gradient_calls(self, *dms):
+        """(entry, edens): the library calls of a grid slice for one matrix (the closed shell) or two (an open-shell state):
+        entry(m, ao, w, d_out, gr, hs) the XC gradient, edens(m, ao, gr, d_e) the energy density, on the uploaded matrices."""
+        if len(dms) == 2:
+            self._uks_check()
+        d, s = [self._dev(x) for x in dms], self.solver
+        grad, dens = (s.compute_xc_gradient_spin, s.compute_xc_energy_density_spin) if len(dms) == 2 else \
+                     (s.compute_xc_gradient, s.compute_xc_energy_density)
+        return (lambda m, ao, w, out, gr, hs: grad(m, self.nao, *d, ao, w, out, gr, hs),
+                lambda m, ao, gr, e: dens(m, self.nao, *d, ao, e, gr))
 
     def _xc_gradient_slices(self, slice_rows, entry, block=None, after=None):
         """The slicing xc_gradient and xc_gradient_spin share: entry(m, ao, w, d_out, gr, hs) is the library call of a slice.
@@ -810,18 +818,11 @@ class HipBackend:
         G^(A) = xc_gradient's G on the rows of the grid atom A owns (the existing slicing per atom block: a block is cut
         further when its Hessian planes exceed XC_GRADIENT_HESS_BYTES), e_g from DFT_ComputeXCEnergyDensity on the planes
         of each slice, the second sum from DFT_BeckeWeightGradient."""
-        d_dm = self._dev(dm)
-        return self._xc_grid_response(slice_rows,
-                                      lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient(m, self.nao, d_dm, ao, w, out, gr, hs),
-                                      lambda m, ao, gr, e: self.solver.compute_xc_energy_density(m, self.nao, d_dm, ao, e, gr))
+        return self._xc_grid_response(slice_rows, *self._xc_gradient_calls(dm))
 
     def xc_grid_response_spin(self, dm_a, dm_b, slice_rows=None):
         """xc_grid_response for an open-shell state: DFT_ComputeXCGradientSpin and DFT_ComputeXCEnergyDensitySpin per block."""
-        self._uks_check()
-        d_a, d_b = self._dev(dm_a), self._dev(dm_b)
-        return self._xc_grid_response(slice_rows,
-                                      lambda m, ao, w, out, gr, hs: self.solver.compute_xc_gradient_spin(m, self.nao, d_a, d_b, ao, w, out, gr, hs),
-                                      lambda m, ao, gr, e: self.solver.compute_xc_energy_density_spin(m, self.nao, d_a, d_b, ao, e, gr))
+        return self._xc_grid_response(slice_rows, *self._xc_gradient_calls(dm_a, dm_b))
 
     def _xc_grid_response(self, slice_rows, entry, edens):
         from . import basis, grid_gen
@@ -864,28 +865,29 @@ class HipBackend:
         return out + d_out.cpu().numpy()
 
     # ---- two-electron part of the nuclear gradient on the device (integrals.DeviceGrad2e): one rank ----------------
-    def grad2e(self, dm, c_hf):
-        """(natm, 3) as a numpy array: what integrals.grad2e(shells, dm, c_hf) computes on the host, from DFT_Grad2e.  The
-        handle is opened by the first call and lives until close()."""
+    def _grad2e_engine(self):
+        """integrals.DeviceGrad2e on this backend's shells: opened by the first call, alive until close()."""
         if self.world > 1:
             raise ValueError("the device two-electron gradient runs on one rank: this backend is one of several")
         if self._grad2e is None:
             from .integrals import DeviceGrad2e
             self._grad2e = DeviceGrad2e(self.shells, self._lib_path)
+        return self._grad2e
+
+    def grad2e(self, dm, c_hf):
+        """(natm, 3) as a numpy array: what integrals.grad2e(shells, dm, c_hf) computes on the host, from DFT_Grad2e.  The
+        handle is opened by the first call and lives until close()."""
+        g = self._grad2e_engine()
         with self.torch.cuda.device(self.dev):
-            return self._grad2e.grad(dm, c_hf)
+            return g.grad(dm, c_hf)
 
     def grad2e_spin(self, dm_a, dm_b, c_hf):
         """(natm, 3) as a numpy array: what integrals.grad2e_spin(shells, dm_a + dm_b, dm_a - dm_b, c_hf) computes on the
         host, from DFT_Grad2eSpin on grad2e's handle: one pass over the derivative integrals for both spins."""
-        if self.world > 1:
-            raise ValueError("the device two-electron gradient runs on one rank: this backend is one of several")
-        if self._grad2e is None:
-            from .integrals import DeviceGrad2e
-            self._grad2e = DeviceGrad2e(self.shells, self._lib_path)
+        g = self._grad2e_engine()
         dm_a, dm_b = np.asarray(dm_a, dtype=np.float64), np.asarray(dm_b, dtype=np.float64)
         with self.torch.cuda.device(self.dev):
-            return self._grad2e.grad_spin(dm_a + dm_b, dm_a - dm_b, c_hf)
+            return g.grad_spin(dm_a + dm_b, dm_a - dm_b, c_hf)
 
     def close(self):
         """Releases the handles this backend opened on demand (the buffers go with the object)."""

@@ -4,10 +4,11 @@ open-shell energy.
 
 * Device against host at 2e-8 of max|G| (the ERR_REL of tests/test_gpu_xc_gradient.py) on that file's shapes -- (2085, 24),
   (2085, 114), (1100, 130), (37, 50), (37, 530): the last is wider than the K chunk a workgroup stages at once -- and the
-  fully polarised (2085, 50) with three alpha and no beta electrons.  LDA, GGA, B3LYP, PBE0, BLYP, all at quirks 0;
-  `path` 1 and 2.
-* k_xc_grad_spin (the default) against k_xc_grad once per spin (option xcg_spin_fused = 0) at 1e-13 of max|G|, every shape
-  and functional above.
+  fully polarised (2085, 50) with three alpha and no beta electrons; and (37, 330), padded to 336: the smallest width at
+  which the plan of two spins in one kernel chunks K (320 + 16) while the plan of one spin does not.  LDA, GGA, B3LYP,
+  PBE0, BLYP, all at quirks 0; `path` 1 and 2.
+* k_xc_grad on both spins in one launch (the default) against k_xc_grad once per spin (option xcg_spin_fused = 0) at 1e-13
+  of max|G|, every shape and functional above.
 * The closed-shell limit dm_a = dm_b = dm/2 against DFT_ComputeXCGradient at quirks 0.
 * The same call twice is bitwise equal; two grid slices add up to the whole to 1e-13 of max|G|.
 * DFT_ComputeXC, DFT_ComputeXCSpin and the table of DFT_FxcPrepareSpinPol are bit for bit what they were before the call.
@@ -27,7 +28,8 @@ from quantum_compute_dft_amd import gradients  # noqa: E402
 ERR_REL = 2e-8
 FUNCTIONALS = ["LDA", "GGA", "B3LYP", "PBE0", "BLYP"]
 # (ngrid, nao, nalpha, nbeta)
-SHAPES = [(2085, 24, 5, 4), (2085, 114, 21, 19), (1100, 130, 12, 9), (37, 50, 6, 5), (37, 530, 40, 38), (2085, 50, 3, 0)]
+SHAPES = [(2085, 24, 5, 4), (2085, 114, 21, 19), (1100, 130, 12, 9), (37, 50, 6, 5), (37, 530, 40, 38), (2085, 50, 3, 0),
+          (37, 330, 20, 18)]
 
 
 @pytest.fixture(scope="module")
@@ -98,7 +100,7 @@ def test_one_kernel_for_both_spins_matches_one_launch_per_spin(dev, shape, funct
     s.set_option("xcg_spin_fused", 0)
     G2 = p.gradient(s, hess=functional != "LDA")
     err = float(np.abs(G - G2).max() / np.abs(G2).max())
-    print(f"gpu k_xc_grad_spin against two launches of k_xc_grad {functional} {shape}: {err:.2e}")
+    print(f"gpu k_xc_grad on both spins against two launches of k_xc_grad {functional} {shape}: {err:.2e}")
     assert err <= 1e-13
     _check(f"DFT_ComputeXCGradientSpin xcg_spin_fused=0 {functional} {shape}", G2, p.host_gradient(functional))
     assert np.array_equal(G2, p.gradient(s, hess=functional != "LDA"))          # the plain form is reproducible too

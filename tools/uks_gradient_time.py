@@ -4,7 +4,7 @@ events around each call (as tools/gradient_time.py measures).
 * DFT_Grad2eSpin against DFT_Grad2e at Benzene/def2-SVP (c_hf 0.2): the same pass over the derivative integrals with a
   wider gather, so parity is the expectation.  Lines for profiles/grad2e_spin_time.txt.
 * DFT_ComputeXCGradientSpin at the Benzene/def2-SVP shape (143 556 x 114, real shells and grid) and at 60 000 x 494
-  (Anthracene/def2-TZVP shells, the first 60 000 points of its grid), three ways alternating: k_xc_grad_spin (the default,
+  (Anthracene/def2-TZVP shells, the first 60 000 points of its grid), three ways alternating: one k_xc_grad launch (the default,
   one kernel for both spins), k_xc_grad once per spin (option xcg_spin_fused = 0), and the closed-shell
   DFT_ComputeXCGradient of the total density for scale.  The line "fused / two launches" also gives the run-to-run spread
   of the two launches in this very measurement, (max - min) / median: the yardstick for "faster".  Lines for
@@ -99,9 +99,9 @@ def main():
                 s.compute_xc_gradient_spin(ng, n, d_a, d_b, d_ao, d_w, d_g, d_gr, hs)
 
             head = f"{mol}/{bname} {ng} x {n} {functional:5s}"
-            m = report(head, {"spin, k_xc_grad_spin": lambda: spin(1), "spin, k_xc_grad per spin": lambda: spin(0),
+            m = report(head, {"spin, one k_xc_grad launch": lambda: spin(1), "spin, k_xc_grad per spin": lambda: spin(0),
                               "DFT_ComputeXCGradient": lambda: s.compute_xc_gradient(ng, n, d_dm, d_ao, d_w, d_g, d_gr, hs)})
-            one, two, closed = m["spin, k_xc_grad_spin"], m["spin, k_xc_grad per spin"], m["DFT_ComputeXCGradient"]
+            one, two, closed = m["spin, one k_xc_grad launch"], m["spin, k_xc_grad per spin"], m["DFT_ComputeXCGradient"]
             print(f"{head} fused / two launches (medians): {one[0] / two[0]:.3f}   spread of the two launches (max - min) / median: {two[1]:.3f}   "
                   f"fused / closed shell: {one[0] / closed[0]:.3f}")
             del s
