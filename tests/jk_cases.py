@@ -160,10 +160,11 @@ def expected_kernels(c):
 LEDGER_KERNELS = ("k_gemm_tn", "k_jk_stream", "k_j_sym", "k_j_sym8")
 
 
-def parse_instantiation(demangled):
-    """(kernel name, template arguments) of a demangled kernel name of the resource report, None for other kernels."""
+def parse_instantiation(demangled, kernels=LEDGER_KERNELS):
+    """(kernel name, template arguments) of a demangled kernel name of the resource report, None for kernels outside
+    `kernels` (tests/sweep_cases.py hands over its own families)."""
     m = re.match(r"void qcdft::(\w+)<([^>]*)>\(", demangled)
-    if not m or m.group(1) not in LEDGER_KERNELS:
+    if not m or m.group(1) not in kernels:
         return None
     conv = lambda s: True if s == "true" else False if s == "false" else int(s)
     return m.group(1), tuple(conv(a.strip()) for a in m.group(2).split(","))

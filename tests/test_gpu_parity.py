@@ -105,8 +105,10 @@ def test_alternative_kernel_paths_match_oracle(dev, xc_type, path):
 @pytest.mark.parametrize("xc_type", [0, 1, 2])
 def test_eight_wave_kernels_match_oracle(dev, xc_type):
     """The 4 MFMA + 4 loader wave kernels of nao <= 128 (csrc/xc_ws_kernels.hpp; tiny = 0 so that bases of at most
-    32 functions reach them too): every tile count NT = 1..8, ragged grids, both walking orders."""
-    for ngrid, nao in ((7, 3), (1025, 17), (3001, 36), (1531, 65), (2500, 114), (1300, 128), (999, 90)):
+    32 functions reach them too): every tile count NT = 1..8, ragged grids, both walking orders.  (Which template
+    instantiations exist and which shapes reach each of them -- parity of nao, fringe widths, alignment -- is held by the
+    ledger of tests/sweep_cases.py and run by tests/test_gpu_sweep_dispatch.py.)"""
+    for ngrid, nao in ((7, 3), (1025, 17), (3001, 36), (1531, 65), (2500, 114), (1300, 128), (999, 90), (1029, 55), (1029, 103)):
         dm, ao, gr, w = synth_inputs(ngrid, nao, seed=900 + ngrid + nao)
         exc_ref, v_ref = oracle.compute_xc(xc_type, dm, ao, w, gr)
         for order in (0, 3):
