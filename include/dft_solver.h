@@ -335,6 +335,46 @@ int DFT_ComputeXCSpin(XCSolver *solver, long long ngrid, int nao, unsigned long 
                       unsigned long long d_weights_ptr, unsigned long long d_vxc_a_ptr, unsigned long long d_vxc_b_ptr,
                       double *exc);
 
+/* Meta-GGA functionals (closed shell).  Two further components read the kinetic-energy density
+ *     tau(g) = 1/2 sum_k sum_mu,nu D[mu, nu] (d_k phi_mu)(g) (d_k phi_nu)(g):
+ * TPSS exchange and TPSS correlation (csrc/xc_meta_functionals.hpp: energies per volume of the spin variables, first
+ * derivatives by forward mode, written down as recalled -- the numerical rules are stated there). */
+enum XCMetaComponent { XC_TPSS_X = 0, XC_TPSS_C, XC_NMETA };
+
+/* A solver for eps = sum_k weights[k] eps_k + sum_k meta_weights[k] eps_meta_k (type SOLVER_MIX with meta weights; it
+ * always takes the four-plane form: ao_grad is required).  NULL unless ncomp == XC_NCOMP, nmeta == XC_NMETA, every
+ * weight is finite and at least one is non-zero.  With a non-zero meta weight the solver serves DFT_ComputeTau and
+ * DFT_ComputeXCMeta only: every other XC entry refuses it (-1 / NaN and a sentence in DFT_GetLastError), so that tau
+ * cannot be dropped silently.  Added without a change of DFT_GetVersion (it stays 5): look the symbols up. */
+XCSolver *DFT_CreateSolverMeta(const double *weights, int ncomp, const double *meta_weights, int nmeta);
+
+/* The meta weights of a solver (zeros for one made by DFT_CreateSolver / DFT_CreateSolverMix).  0, or -1 for a null
+ * argument or nmeta != XC_NMETA. */
+int DFT_GetMeta(XCSolver *solver, double *meta_weights_out, int nmeta);
+
+/* d_tau (ngrid) receives tau of d_dm (nao, nao; its symmetric part) from the three gradient planes d_ao_grad
+ * (3, ngrid, nao): "tau" (k_tau, csrc/xc_meta.hip) on the matrix pipe, no atomics, bitwise reproducible.  Asynchronous
+ * on the solver's stream.  Any solver.  0, or -1 with DFT_GetLastError. */
+int DFT_ComputeTau(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr, unsigned long long d_ao_grad_ptr,
+                   unsigned long long d_tau_ptr);
+
+/* Exc and Vxc of a meta solver.  d_vxc (nao, nao) receives V in the mix solver's one-sided convention plus the whole
+ * (symmetric) tau term: (V + V^T)/2 is dExc/dD, tr(sym(V) X) = d/dt Exc(D + t X) for symmetric X.  The potentials are
+ * first derivatives of the spin-resolved ENERGY bodies at zero polarisation: "quirks" = 1 with a vwn5_c or pbe_c weight
+ * is refused (DFT_ComputeXCSpin's reason); TPSS itself carries neither.  A point below the density cut-off contributes
+ * exact zeros.
+ * Order of work on the solver's stream: the sweep's density kernels on dm, "tau", "xc_points_meta", the sweep's
+ * contraction and reduce of c0..c3, then T = sum_k (d_k AO)^T diag(ct) (d_k AO) added to V -- three runs of the sweep's
+ * contraction with the plane of d_k AO in the AO slot (option "meta_fused" = 0, the default: the faster form as measured,
+ * profiles/meta_time.txt) or one kernel over the three planes ("vxc_tau", "meta_fused" = 1, tested against the plain form).  With both meta weights zero the tau steps are left
+ * out.  Never the one-kernel plan for small bases, never a recorded graph, never the occupied-orbital density step.
+ * Synchronous: returns after Exc has been copied to *exc.  Its planes are its own: prepared DFT_Fxc* tables and later
+ * DFT_ComputeXC* calls are not disturbed.  Returns 0, or -1 with DFT_GetLastError: a solver not made by
+ * DFT_CreateSolverMeta, a null pointer (ao_grad included), bad sizes, the "quirks" case above. */
+int DFT_ComputeXCMeta(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr, unsigned long long d_ao_ptr,
+                      unsigned long long d_weights_ptr, unsigned long long d_ao_grad_ptr, unsigned long long d_vxc_ptr,
+                      double *exc);
+
 /* Linear response of DFT_ComputeXCSpin, in two halves like DFT_FxcPrepare / DFT_FxcApply: V1_s (nao, nao), s = alpha,
  * beta, is, element for element, d/dt of what DFT_ComputeXCSpin(dm0_a + t dm1_a, dm0_b + t dm1_b) writes into vxc_s at
  * t = 0, in that call's conventions (one-sided for SOLVER_GGA and SOLVER_MIX, M + M^T with the halved table for

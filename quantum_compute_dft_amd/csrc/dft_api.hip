@@ -35,6 +35,7 @@
 #include "xc_spin_launch.hpp"
 #include "xc_grad_launch.hpp"
 #include "becke_launch.hpp"
+#include "xc_meta_launch.hpp"
 
 using namespace qcdft;
 
@@ -104,6 +105,10 @@ struct XCSolver {
     int type = 0;
     bool needs_grad = false;     // the functional reads grad rho: four planes, ao_grad required (every type but LDA and LDA-class mixes)
     xc::MixWeights mix = {};     // SOLVER_MIX: the eight coefficients, fixed at creation (recorded graphs hold them)
+    // DFT_CreateSolverMeta: the two meta-GGA coefficients.  meta_active (one is non-zero): the functional reads tau, which only
+    // DFT_ComputeXCMeta forms -- every other XC entry refuses the solver (enter)
+    bool is_meta = false, meta_active = false;
+    double meta[2] = {0.0, 0.0};
     hipStream_t stream = nullptr;
     bool device_ok = false;
     int device = 0; // the device that was current at DFT_CreateSolver: every entry point runs there
@@ -188,6 +193,17 @@ struct XCSolver {
     // DFT_BeckeWeightGradient: [atoms (natm, 3) | a_CD (natm, natm) | 1 / R_CD (natm, natm)] on the device and the host copy they
     // were made from (uploaded again only when the atoms change), and the slabs of the kernel
     DevBuf becke_tab, becke_slabs;
+    // DFT_ComputeTau / DFT_ComputeXCMeta: planes of their own (rho, grad, sigma, c0..c3, the Exc partials), tau and the tau
+    // coefficient (four planes: ct and, for the plain form, three of zeros), the padded matrix k_tau reads, the slabs of
+    // k_vxc_tau, the matrix one plain contraction leaves, and the scalar of its Exc.  No recorded sweep and no prepared
+    // response table holds or reads any of them.
+    Planes meta_ws;
+    DevBuf meta_tau, meta_ct, meta_dp, meta_slabs, meta_vtmp, meta_exc;
+    // The tau term of the potential.  0 (default): the sweep's contraction once per plane with the plane in the AO slot; 1:
+    // k_vxc_tau, one pass over the three gradient planes.  The dedicated kernel does not beat the plain form (605.8 against 294.8 us
+    // at 143 556 x 114, 2015.7 against 1855.1 us at 60 000 x 494: profiles/meta_time.txt), so it is the option, held to the plain
+    // form by the tests
+    int meta_fused = 0;
     std::vector<double> becke_tab_host;
     std::string last_error;
     std::vector<Timing> timings;
@@ -262,10 +278,15 @@ int xc_type_index(const XCSolver *s)
 }
 
 // What every XC entry does first.  `timed`: timings of the same call that stay in front of the entry's own.
-bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed = 0)
+bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed = 0, bool meta_entry = false)
 {
     s->last_error.clear();
     s->n_timed = timed;
+    if (s->meta_active && !meta_entry) {
+        set_error(s, "the solver's functional is a meta-GGA (non-zero tpss_x / tpss_c weight): it reads the kinetic-energy density, "
+                     "which only DFT_ComputeXCMeta forms; this entry would drop it");
+        return false;
+    }
     if (!s->device_ok) {
         set_error(s, "no usable HIP device");
         return false;
@@ -745,6 +766,83 @@ bool xc_sweep_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const d
         return false;
     *exc_host = out;
     if (std::isnan(out)) { set_error(s, "Exc is NaN after the spin sweep completed (non-finite inputs)"); return false; }
+    return true;
+}
+
+// tau alone (DFT_ComputeTau): the padded symmetric matrix into its own buffer, then k_tau.
+bool compute_tau(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao_grad, double *tau)
+{
+    const TauPlan tp = tau_plan(s->num_cu, ngrid, nao);
+    if (!reserve(s, s->meta_dp, sizeof(double) * (size_t)tp.NP * tp.NP, "hipMalloc(meta Dp)", false)) return false;
+    ScopedTimer t(s, "tau");
+    hipLaunchKernelGGL(k_sym_dm, dim3(tp.NP / 16, tp.NP / 16), dim3(16, 16), 0, s->stream, nao, tp.NP, dm, s->meta_dp.d());
+    return hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, s->meta_dp.d(), tau), "tau launch");
+}
+
+// The meta-GGA sweep (DFT_ComputeXCMeta): the closed-shell sweep's density kernels, k_tau, one pointwise kernel
+// (xc_meta.hip), the closed-shell contraction and reduce of c0..c3 (which finishes Exc from the pointwise kernel's
+// partials), and the tau term added to V.  Never the one-kernel plan for small bases, never recorded.  Shares Dsym, the
+// slabs and M with the other entries (stream order), and nothing else.
+bool xc_sweep_meta(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *w, const double *ao_grad,
+                   double *vxc, double *exc_host)
+{
+    if (!s->is_meta) {
+        s->last_error.clear();
+        set_error(s, "DFT_ComputeXCMeta needs a solver made by DFT_CreateSolverMeta (this one carries no meta-GGA weights)");
+        return false;
+    }
+    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
+    if (!dm || !ao || !w || !vxc || !exc_host) {
+        set_error(s, "DFT_ComputeXCMeta needs the density matrix, the AO values, the grid weights, the output matrix and exc");
+        return false;
+    }
+    if (!spin_quirks_ok(s, "DFT_ComputeXCMeta")) return false;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const long nxb = meta_points_blocks(ngrid);
+    const size_t ng = (size_t)ngrid, nn = (size_t)nao * nao;
+    Planes &p = s->meta_ws;
+    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, p, false, ngrid, WS_ALL, nxb) ||
+        !reserve(s, s->meta_tau, sizeof(double) * ng, "hipMalloc(tau)", false) ||
+        !reserve(s, s->meta_ct, sizeof(double) * 4 * ng, "hipMalloc(tau coefficient)", false) ||
+        !reserve(s, s->meta_exc, 2 * sizeof(double), "hipMalloc(meta exc)", false))
+        return false;
+    launch_density(s, P, ngrid, nao, dm, ao, s->dsym.d(), p.rho.d(), p.grad.d(), p.sigma.d());
+    double *tau = s->meta_tau.d(), *ct = s->meta_ct.d();
+    if (s->meta_active) {
+        if (!compute_tau(s, ngrid, nao, dm, ao_grad, tau)) return false;
+    } else if (!hip_ok(s, hipMemsetAsync(tau, 0, sizeof(double) * ng, s->stream), "clear tau")) {
+        return false;
+    }
+    {
+        ScopedTimer t(s, "xc_points_meta");
+        if (!hip_ok(s, launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, p.rho.d(), p.grad.d(), tau, w, p.coef.d(), ct, p.partial.d()),
+                    "meta pointwise launch"))
+            return false;
+    }
+    double *exc = s->meta_exc.d();
+    const ExcFinish fin{nxb, p.partial.d(), exc, false};   // no host-mapped word, no publishing: Exc is copied below
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, p.coef.d(), s->slabs.d(), vxc, &fin)) return false;
+    if (s->meta_active && s->meta_fused) {
+        const VxcTauPlan vp = vxc_tau_plan(s->num_cu, ngrid, nao);
+        if (!reserve(s, s->meta_slabs, sizeof(double) * (size_t)vp.nslab * nn, "hipMalloc(tau slabs)", false)) return false;
+        ScopedTimer t(s, "vxc_tau");
+        if (!hip_ok(s, launch_vxc_tau(s->stream, vp, ngrid, nao, ao_grad, ct, s->meta_slabs.d(), vxc), "tau potential launch")) return false;
+    } else if (s->meta_active) {
+        // the plain form: Q = c0 (plane in the AO slot) with c0 = ct and c1..c3 = 0, contracted with the same plane
+        if (!reserve(s, s->meta_vtmp, sizeof(double) * nn, "hipMalloc(tau potential)", false) ||
+            !hip_ok(s, hipMemsetAsync(ct + ng, 0, sizeof(double) * 3 * ng, s->stream), "clear coefficients"))
+            return false;
+        for (int k = 0; k < 3; ++k) {
+            if (!vxc_stage(s, P, false, ngrid, nao, ao_grad + (size_t)k * ng * nao, ct, s->slabs.d(), s->meta_vtmp.d(), nullptr)) return false;
+            if (!hip_ok(s, launch_meta_add(s->stream, (long)nn, s->meta_vtmp.d(), vxc), "tau potential add")) return false;
+        }
+    }
+    double out = std::numeric_limits<double>::quiet_NaN();
+    if (!hip_ok(s, hipMemcpyAsync(&out, exc, sizeof(double), hipMemcpyDeviceToHost, s->stream), "copy Exc") ||
+        !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
+        return false;
+    *exc_host = out;
+    if (std::isnan(out)) { set_error(s, "Exc is NaN after the meta-GGA sweep completed (non-finite inputs)"); return false; }
     return true;
 }
 
@@ -1611,6 +1709,37 @@ XCSolver *DFT_CreateSolverMix(const double *weights, int ncomp)
     return create_solver(SOLVER_MIX, weights);
 }
 
+XCSolver *DFT_CreateSolverMeta(const double *weights, int ncomp, const double *meta_weights, int nmeta)
+{
+    if (!weights || ncomp != XC_NCOMP || !meta_weights || nmeta != XC_NMETA) return nullptr;
+    bool any = false;
+    for (int k = 0; k < XC_NCOMP; ++k) {
+        if (!std::isfinite(weights[k])) return nullptr;
+        any = any || weights[k] != 0.0;
+    }
+    for (int k = 0; k < XC_NMETA; ++k) {
+        if (!std::isfinite(meta_weights[k])) return nullptr;
+        any = any || meta_weights[k] != 0.0;
+    }
+    if (!any) return nullptr;
+    XCSolver *s = create_solver(SOLVER_MIX, weights);
+    if (!s) return nullptr;
+    s->is_meta = true;
+    s->needs_grad = true;   // tau is made of the gradient planes: always the four-plane form
+    for (int k = 0; k < XC_NMETA; ++k) {
+        s->meta[k] = meta_weights[k];
+        s->meta_active = s->meta_active || meta_weights[k] != 0.0;
+    }
+    return s;
+}
+
+int DFT_GetMeta(XCSolver *s, double *meta_weights_out, int nmeta)
+{
+    if (!s || !meta_weights_out || nmeta != XC_NMETA) return -1;
+    for (int k = 0; k < XC_NMETA; ++k) meta_weights_out[k] = s->meta[k];
+    return 0;
+}
+
 int DFT_GetMix(XCSolver *s, double *weights_out, int ncomp)
 {
     if (!s || !weights_out || ncomp != XC_NCOMP) return -1;
@@ -1959,6 +2088,27 @@ int DFT_ComputeXCSpin(XCSolver *s, long long ngrid, int nao, unsigned long long 
                          (const double *)d_ao_grad, (const double *)d_w, (double *)d_vxc_a, (double *)d_vxc_b, exc) ? 0 : -1;
 }
 
+int DFT_ComputeTau(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao_grad, unsigned long long d_tau)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return -1; }
+    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%lld nao=%d", ngrid, nao); return -1; }
+    if (!d_dm || !d_ao_grad || !d_tau) { set_error(s, "DFT_ComputeTau needs the density matrix, ao_grad and the output"); return -1; }
+    return compute_tau(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao_grad, (double *)d_tau) ? 0 : -1;
+}
+
+int DFT_ComputeXCMeta(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao, unsigned long long d_w,
+                      unsigned long long d_ao_grad, unsigned long long d_vxc, double *exc)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_sweep_meta(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_w,
+                         (const double *)d_ao_grad, (double *)d_vxc, exc) ? 0 : -1;
+}
+
 void DFT_ComputeCoulomb(XCSolver *s, int nao, unsigned long long d_eri, unsigned long long d_dm,
                         unsigned long long d_J)
 {
@@ -2171,6 +2321,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "ao_pt")) { s->ao_pt = value == 16.0 ? 16 : value == 8.0 ? 8 : 0; return 0; }
     if (!strcmp(key, "ksplit")) { s->ksplit = value > 0 ? (int)value : 0; return 0; }
     if (!strcmp(key, "xcg_spin_fused")) { s->xcg_spin_fused = value != 0.0; return 0; }
+    if (!strcmp(key, "meta_fused")) { s->meta_fused = value != 0.0; return 0; }
     return -1;
 }
 
@@ -2197,6 +2348,7 @@ double DFT_GetOption(XCSolver *s, const char *key)
     if (!strcmp(key, "dm_factor")) return s->dm_factor;
     if (!strcmp(key, "used_dm_factor")) return s->used_dm_factor;                              // the last synchronous call swept with the factor of dm
     if (!strcmp(key, "xcg_spin_fused")) return s->xcg_spin_fused;
+    if (!strcmp(key, "meta_fused")) return s->meta_fused;
     if (!strcmp(key, "dm_factor_rank")) return s->dm_factor_rank;                              // the rank its attempt found (0: rejected / not attempted)
     return unknown;
 }

@@ -3,6 +3,7 @@
 // tests hold it against finite differences of the oracle.  type: 0 LDA, 1 GGA, 2 B3LYP, 3 mix (eight weights).
 #include "xc_functionals.hpp"
 #include "xc_spin_functionals.hpp"
+#include "xc_meta_functionals.hpp"
 
 using namespace qcdft;
 
@@ -192,6 +193,50 @@ int qc_xc_point_spin(int type, const double *mix8, long long n, const double *ra
             out[(5 + k) * n + g] = p.b[k];
         }
         for (int k = 0; k < 5; ++k) out[(9 + k) * n + g] = p.d[k];
+    }
+    return 0;
+}
+
+// One closed-shell point of the meta-GGA sweep, xc::meta_point as k_xc_points_meta runs it: the eight weights, the two
+// meta weights, grad3 three per point (interleaved).  out (10, n): e (no weight); c0..c3; ct; e_rho, e_sigma, e_tau (bare).
+int qc_meta_point(const double *mix8, const double *meta2, long long n, const double *rho, const double *grad3, const double *tau,
+                  const double *w, double *out)
+{
+    if (!mix8 || !meta2 || n < 0 || !rho || !grad3 || !tau || !w || !out) return -1;
+    const xc::MixWeights m = weights(mix8);
+    const xc::MetaWeights mm = {{meta2[0], meta2[1]}};
+    for (long long g = 0; g < n; ++g) {
+        const xc::MetaPoint p = xc::meta_point(m, mm, rho[g], grad3[3 * g], grad3[3 * g + 1], grad3[3 * g + 2], tau[g], w[g]);
+        out[g] = p.e;
+        for (int k = 0; k < 4; ++k) out[(1 + k) * n + g] = p.c[k];
+        out[5 * n + g] = p.ct;
+        for (int k = 0; k < 3; ++k) out[(6 + k) * n + g] = p.d[k];
+    }
+    return 0;
+}
+
+// The energy per volume of the ten weights at any (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb, tau_a, tau_b) into out (n),
+// and (grad non-null) its seven first derivatives into grad (7, n) by xc::Dual.  A variable of an absent channel (density
+// below the cut-off; sigma_ab belongs to both) is not differentiated: its derivative is exactly 0, as in spin_potential_point.
+int qc_meta_energy_spin(const double *mix8, const double *meta2, long long n, const double *ra, const double *rb, const double *saa,
+                        const double *sab, const double *sbb, const double *ta, const double *tb, double *out, double *grad)
+{
+    if (!mix8 || !meta2 || n < 0 || !ra || !rb || !saa || !sab || !sbb || !ta || !tb || !out) return -1;
+    const xc::MixWeights m = weights(mix8);
+    const xc::MetaWeights mm = {{meta2[0], meta2[1]}};
+    for (long long g = 0; g < n; ++g) {
+        const double x[7] = {ra[g], rb[g], saa[g], sab[g], sbb[g], ta[g], tb[g]};
+        out[g] = xc::meta_mix_energy<false>(m, mm, x[0], x[1], x[2], x[3], x[4], x[5], x[6]);
+        if (!grad) continue;
+        const bool pa = x[0] >= xc::kRhoCut, pb = x[1] >= xc::kRhoCut;
+        const bool present[7] = {pa, pb, pa, pa && pb, pb, pa, pb};
+        for (int i = 0; i < 7; ++i) {
+            grad[i * n + g] = 0.0;
+            if (!present[i]) continue;
+            xc::Dual v[7];
+            for (int k = 0; k < 7; ++k) v[k] = xc::Dual(x[k], k == i ? 1.0 : 0.0);
+            grad[i * n + g] = xc::meta_mix_energy<false>(m, mm, v[0], v[1], v[2], v[3], v[4], v[5], v[6]).d;
+        }
     }
     return 0;
 }

@@ -198,7 +198,8 @@ QCDFT_XC_FN T spin_pbe_x(T ra, T rb, T saa, T sbb)
 }
 
 // `ec`: pw92_eps_spin(rho, z), so that a mix which holds PW92 as well evaluates it once.
-template <class T>
+// CUT = false (the meta-GGA bodies of xc_meta_functionals.hpp): sigma enters as it is, H is smooth at sigma = 0.
+template <bool CUT = true, class T>
 QCDFT_XC_FN T spin_pbe_c_with(T ec, T rho, T z, T sig)
 {
     constexpr double beta = 0.066725, gamma = 0.03109069086965489503;
@@ -207,7 +208,7 @@ QCDFT_XC_FN T spin_pbe_c_with(T ec, T rho, T z, T sig)
     const T kF = cbrt(3.0 * kPi * kPi * rho);
     const T den16 = 16.0 * kF * rho * rho;
     T t2 = 0.0;
-    if (den16 > 1e-50) t2 = (((sig > kSigmaCut) ? sig : sigma_at_cut(sig)) * kPi) / (den16 * phi2);
+    if (den16 > 1e-50) t2 = (((!CUT || sig > kSigmaCut) ? sig : sigma_at_cut(sig)) * kPi) / (den16 * phi2);
     if (t2 > 1.0e20) t2 = 1.0e20;
     const T x = -ec / (gamma * phi3);
     const T em1 = expm1(x);
@@ -218,13 +219,13 @@ QCDFT_XC_FN T spin_pbe_c_with(T ec, T rho, T z, T sig)
     return rho * (ec + H);
 }
 
-template <class T>
+template <bool CUT = true, class T>
 QCDFT_XC_FN T spin_pbe_c(T ra, T rb, T saa, T sab, T sbb)
 {
     const T rho = ra + rb;
     if (rho < kRhoCut) return 0.0;
     const T z = (ra - rb) / rho;
-    return spin_pbe_c_with(pw92_eps_spin(rho, z), rho, z, saa + 2.0 * sab + sbb);
+    return spin_pbe_c_with<CUT>(pw92_eps_spin(rho, z), rho, z, saa + 2.0 * sab + sbb);
 }
 
 // rho_s * eps of b88_x for one spin (its energy statements, by value): -beta x^2 rho_s^(4/3) / (1 + 6 beta x asinh x).

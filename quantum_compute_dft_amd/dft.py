@@ -115,8 +115,8 @@ def build_parser():
     p.add_argument("--ao", default="resident", choices=["resident", "direct"],
                    help="resident: AO values and gradients of the whole grid stay in HBM (the reference's layout, dft.py:155,172); "
                         "direct: they are re-evaluated chunk by chunk inside every XC call (DFT_ComputeXCDirect), memory ~100 MB")
-    p.add_argument("--xc-occ", type=int, default=1, choices=[0, 1],
-                   help="1 (default): the XC sweep's density step through the occupied orbitals (DFT_ComputeXCOcc, 4 nao nocc flops "
+    p.add_argument("--xc-occ", type=int, default=None, choices=[0, 1],
+                   help="1 (default; a meta-GGA: 0, it has no occupied-orbital form): the XC sweep's density step through the occupied orbitals (DFT_ComputeXCOcc, 4 nao nocc flops "
                         "per grid point); 0: the reference's call with the full density matrix (DFT_ComputeXC, dft.py:206)")
     p.add_argument("--dm-factor", action="store_true",
                    help="with --xc-occ 0: the reference's call, with the library factorising the density matrix on the device "
@@ -191,6 +191,14 @@ def main(argv=None):
     if args.charge_forces_out and not args.point_charges:
         p.error("--charge-forces-out needs --point-charges")
     fn = functionals.resolve(args.functional)
+    if fn.needs_tau:
+        for flag, on in (("--spin", args.spin is not None), ("--polarizability", args.polarizability), ("--excitations", args.excitations),
+                         ("--gradient", args.gradient), ("--optimize", args.optimize)):
+            if on:
+                p.error(f"{flag}: {args.functional} is a meta-GGA and this feature is not built for meta-GGA functionals "
+                        "(only the closed-shell ground state is)")
+    if args.xc_occ is None:
+        args.xc_occ = None if fn.needs_tau else 1
     if args.polarizability and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident"):
         p.error("--polarizability runs on one rank with --ao resident")
     if args.excitations < 0 or (args.tda and not args.excitations):
@@ -292,7 +300,7 @@ def main(argv=None):
         backend = scf.HipBackend(inp, args.functional, args.lib, quirks=bool(args.quirks), rank=rank, world=world, device=device,
                                  device_resident=False if uks else None if args.device_resident < 0 else bool(args.device_resident),
                                  fused_tail=False if uks else None if args.fused_tail < 0 else bool(args.fused_tail),
-                                 eigensolver="exact" if uks else args.eigensolver, ao_mode=args.ao, xc_occ=bool(args.xc_occ), dm_factor=args.dm_factor)
+                                 eigensolver="exact" if uks else args.eigensolver, ao_mode=args.ao, xc_occ=None if args.xc_occ is None else bool(args.xc_occ), dm_factor=args.dm_factor)
     except Exception as e:  # dft.py:149-153
         print(e)
         sys.exit(1)
@@ -401,11 +409,11 @@ def main(argv=None):
                                  point_charges=charges, charge=args.charge, spin=args.spin or 0, atom_xyz=xyz)
             if uks:
                 be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, device_resident=False,
-                                      fused_tail=False, eigensolver="exact", ao_mode=args.ao, xc_occ=bool(args.xc_occ))
+                                      fused_tail=False, eigensolver="exact", ao_mode=args.ao, xc_occ=None if args.xc_occ is None else bool(args.xc_occ))
                 res_k = scf.run_uks(inp_k, be_k, args.functional, log=None)
             else:
                 be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, eigensolver=args.eigensolver,
-                                      ao_mode=args.ao, xc_occ=bool(args.xc_occ))
+                                      ao_mode=args.ao, xc_occ=None if args.xc_occ is None else bool(args.xc_occ))
                 res_k = scf.run_scf(inp_k, be_k, args.functional, log=None)
             if not res_k["converged"]:
                 raise RuntimeError("--optimize: the SCF did not converge at a geometry of the optimisation")

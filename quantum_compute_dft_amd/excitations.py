@@ -46,6 +46,7 @@ class ResponseOperators:
 
     def __init__(self, inp, scf_result, backend, functional=None, triplet=False):
         f = functionals.resolve(functional if functional is not None else backend.functional)
+        functionals.refuse_meta(f, "excitations (TDDFT / TDA)")
         quirks = bool(getattr(backend, "quirks", True))
         self.triplet = bool(triplet)
         if self.triplet and quirks and (f.weight_vector()[_VWN5_C] != 0.0 or f.weight_vector()[_PBE_C] != 0.0):

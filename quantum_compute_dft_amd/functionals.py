@@ -1,4 +1,5 @@
-"""Exchange-correlation functionals as weighted sums of the engine's eight pointwise components.
+"""Exchange-correlation functionals as weighted sums of the engine's eight pointwise components and its two meta-GGA
+components (tpss_x, tpss_c: functions of the kinetic-energy density tau as well).
 
 `resolve(spec)` turns a table name ("PBE0", case-insensitive) or an expression
 ("0.75*pbe_x + pbe_c + 0.25*hf") into a `Functional`.  Three names keep the reference's built-in
@@ -8,7 +9,8 @@ include/dft_solver.h.
 
 The named recipes are the literature's definitions as far as they could be written down from memory; the
 COMPOSITION is tested (against the oracle's own pieces), the recipes are not cross-checked against another
-code.  "B3LYP" carries VWN-RPA (the reference's choice), "B3LYP5" carries VWN5.
+code.  "TPSS" / "TPSSH" are as recalled too: their exchange is pinned by the exact hydrogen-atom energy, their correlation by
+its one-electron and slowly-varying limits (tests/test_meta_cpu.py).  "B3LYP" carries VWN-RPA (the reference's choice), "B3LYP5" carries VWN5.
 """
 import math
 import re
@@ -19,6 +21,8 @@ COMPONENTS = ("slater_x", "vwn5_c", "vwn_rpa_c", "pw92_c", "pbe_x", "pbe_c", "b8
 # spellings accepted in expressions and in the table below (the oracle's short names among them)
 _ALIASES = {"slater": "slater_x", "vwn5": "vwn5_c", "vwn_rpa": "vwn_rpa_c", "pw92": "pw92_c", "b88": "b88_x", "lyp": "lyp_c"}
 _GRADIENT = COMPONENTS[4:]
+# ABI order: enum XCMetaComponent of include/dft_solver.h; a functional that carries one needs tau (DFT_CreateSolverMeta)
+META_COMPONENTS = ("tpss_x", "tpss_c")
 _QUIRKY = ("vwn5_c", "pbe_c")          # the two components option "quirks" changes
 
 
@@ -29,7 +33,12 @@ class Functional(namedtuple("Functional", "name weights c_hf builtin_type")):
 
     @property
     def needs_gradient(self):
-        return any(k in _GRADIENT for k in self.weights)
+        return self.needs_tau or any(k in _GRADIENT for k in self.weights)
+
+    @property
+    def needs_tau(self):
+        """A meta-GGA: the functional reads the kinetic-energy density."""
+        return any(k in META_COMPONENTS for k in self.weights)
 
     @property
     def uses_quirks(self):
@@ -42,6 +51,10 @@ class Functional(namedtuple("Functional", "name weights c_hf builtin_type")):
     def weight_vector(self):
         """The eight coefficients in ABI order."""
         return [float(self.weights.get(k, 0.0)) for k in COMPONENTS]
+
+    def meta_weight_vector(self):
+        """The coefficients of the meta-GGA components in ABI order."""
+        return [float(self.weights.get(k, 0.0)) for k in META_COMPONENTS]
 
 
 def _f(name, c_hf=0.0, builtin=None, **w):
@@ -62,6 +75,11 @@ TABLE = {f.name: f for f in (
     _f("B1LYP", 0.25, slater=0.75, b88=0.75, lyp=1),
     _f("BHANDHLYP", 0.5, slater=0.5, b88=0.5, lyp=1),
     _f("B3LYP5", 0.2, vwn5=0.19, **_B3),
+)}
+# The meta-GGA names, a table of their own beside the twelve above: resolve() knows both
+META_TABLE = {f.name: f for f in (
+    _f("TPSS", tpss_x=1, tpss_c=1),
+    _f("TPSSH", 0.1, tpss_x=0.9, tpss_c=1),
 )}
 
 _TERM = re.compile(r"^(?:([^*]+)\*)?([A-Za-z_][A-Za-z0-9_]*)$")
@@ -89,9 +107,9 @@ def _parse(spec):
             raise ValueError(f"non-finite coefficient in term {t!r} of functional expression {spec!r}")
         name = m.group(2).lower()
         name = _ALIASES.get(name, name)
-        if name != "hf" and name not in COMPONENTS:
+        if name != "hf" and name not in COMPONENTS and name not in META_COMPONENTS:
             raise ValueError(f"unknown component {m.group(2)!r} in functional expression {spec!r} "
-                             f"(known: {', '.join(COMPONENTS)}, hf)")
+                             f"(known: {', '.join(COMPONENTS + META_COMPONENTS)}, hf)")
         if name in seen:
             raise ValueError(f"component {name!r} appears twice in functional expression {spec!r}")
         seen.add(name)
@@ -104,6 +122,14 @@ def _parse(spec):
     return Functional(spec.strip(), weights, c_hf, None)
 
 
+def refuse_meta(spec, what):
+    """ValueError when `spec` is a meta-GGA: `what` (a sentence's subject) is built for LDA / GGA / hybrid functionals only."""
+    f = resolve(spec)
+    if f.needs_tau:
+        raise ValueError(f"{what}: {f.name!r} is a meta-GGA (it reads the kinetic-energy density tau) and this feature is not built "
+                         "for meta-GGA functionals -- only the closed-shell ground state is")
+
+
 def resolve(spec):
     """Functional of a table name or an expression; ValueError for anything else."""
     if isinstance(spec, Functional):
@@ -113,7 +139,9 @@ def resolve(spec):
     key = spec.strip().upper()
     if key in TABLE:
         return TABLE[key]
+    if key in META_TABLE:
+        return META_TABLE[key]
     try:
         return _parse(spec)
     except ValueError as e:
-        raise ValueError(f"Unsupported functional type: {key!r} ({e}; table: {', '.join(TABLE)})") from None
+        raise ValueError(f"Unsupported functional type: {key!r} ({e}; table: {', '.join(list(TABLE) + list(META_TABLE))})") from None

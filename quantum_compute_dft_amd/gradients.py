@@ -233,6 +233,7 @@ def xc_grid_response_host(functional, dm, shells, grids, symbols, atom_xyz, quir
     the energy per volume (response.point_host with unit weights) and the last sum grid_gen.becke_weight_gradient_host.
     planes: (ao, ao_grad, ao_hess) at grids.coords when the caller has them (evaluated here otherwise)."""
     f = functionals.resolve(functional)
+    functionals.refuse_meta(f, "xc_grid_response_host")
     ao, gr, hs = planes if planes is not None else ao_planes_host(shells, grids.coords)
     w = np.asarray(grids.weights, dtype=np.float64)
     gga = f.needs_gradient
@@ -245,6 +246,7 @@ def xc_grid_response_host(functional, dm, shells, grids, symbols, atom_xyz, quir
 def xc_grid_response_spin_host(functional, dm_a, dm_b, shells, grids, symbols, atom_xyz, planes=None):
     """xc_grid_response_host for an open-shell state: xc_gradient_spin_host per atom block and response.point_spin_host's e."""
     f = functionals.resolve(functional)
+    functionals.refuse_meta(f, "xc_grid_response_spin_host")
     ao, gr, hs = planes if planes is not None else ao_planes_host(shells, grids.coords)
     w = np.asarray(grids.weights, dtype=np.float64)
     gga = f.needs_gradient
@@ -332,6 +334,7 @@ def _checked(who, inp, backend, functional, two_electron, device_method, wrong_r
     if grid_response:
         _grid_of(inp.grids, inp.symbols, inp.atom_xyz, who)          # refuses a grid that does not say which atom a point moves with
     f = functionals.resolve(functional if functional is not None else backend.functional)
+    functionals.refuse_meta(f, who)
     return f, f.weight_vector()
 
 

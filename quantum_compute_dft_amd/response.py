@@ -386,6 +386,7 @@ def uks_orbitals(inp, uks_result, backend, functional=None):
     matrices of the converged densities (backend.uks_parts), then backend.uks_response_prepare.  Returns (f, spins) with
     f the resolved functional and spins a list of two dicts {Co (nao, n_s), Cv (nao, nv_s), gap (n_s, nv_s)}."""
     f = functionals.resolve(functional if functional is not None else backend.functional)
+    functionals.refuse_meta(f, "open-shell response")
     wv = f.weight_vector()
     if bool(getattr(backend, "quirks", False)) and (wv[_VWN5_C] != 0.0 or wv[_PBE_C] != 0.0):
         raise ValueError("open-shell response: the spin-resolved kernel is the second derivative of the energy, but with quirks = 1 the "
@@ -504,6 +505,7 @@ def polarizability(inp, scf_result, backend, functional=None, tol=1e-8, max_iter
     if scf_result.get("uks"):
         return _polarizability_uks(inp, scf_result, backend, functional, tol, max_iter, log)
     f = functionals.resolve(functional if functional is not None else backend.functional)
+    functionals.refuse_meta(f, "polarizability (CPKS)")
     c_hf, want_k = f.c_hf, f.c_hf != 0.0
     S, nocc = inp.S, inp.nocc
     dm0 = np.ascontiguousarray(scf_result["dm"], dtype=np.float64)

@@ -360,7 +360,7 @@ class HipBackend:
     rows of J (and, through the (i,k) view, its partial K); the all-reduce assembles them."""
 
     def __init__(self, inp, functional, lib_path=None, quirks=True, rank=0, world=1, device=None, group=None,
-                 device_resident=None, device_from=200, eigensolver="auto", ao_mode="resident", ao_chunk=0, xc_occ=True,
+                 device_resident=None, device_from=200, eigensolver="auto", ao_mode="resident", ao_chunk=0, xc_occ=None,
                  fused_tail=None, dm_factor=False):
         import torch
         from .build import library_path
@@ -374,6 +374,21 @@ class HipBackend:
         self.solver = DFTSolverWrapper(lib_path or library_path(), functional)   # any name or expression of functionals.resolve()
         self.solver.set_option("quirks", 1 if quirks else 0)
         self.quirks = bool(quirks)
+        # A meta-GGA (functionals.Functional.needs_tau) sweeps through DFT_ComputeXCMeta: synchronous, the density matrix itself,
+        # resident planes, one rank -- the host loop.  What cannot serve it is refused here, by name, not switched off silently.
+        self.meta = bool(self.solver.functional.needs_tau)
+        if self.meta:
+            for bad, why in ((world > 1, "more than one rank (the grid is not sharded for DFT_ComputeXCMeta)"),
+                             (ao_mode == "direct", "--ao direct (tau is formed from resident gradient planes)"),
+                             (bool(dm_factor), "dm_factor (the sweep takes the density matrix itself)"),
+                             (xc_occ is not None and bool(xc_occ), "xc_occ (there is no occupied-orbital form of tau)"),
+                             (bool(fused_tail), "the fused tail (it pre-queues the asynchronous sweep entries, which have no meta form)"),
+                             (bool(device_resident), "the device-resident loop (it queues the asynchronous sweep entries, which have no meta form)")):
+                if bad:
+                    raise ValueError(f"{self.functional} is a meta-GGA: it runs on the host loop with resident AO planes, not with {why}")
+            xc_occ, fused_tail, device_resident = False, False, False
+        elif xc_occ is None:
+            xc_occ = True
         self._lib_path, self._grad2e = lib_path, None       # the device two-electron gradient: opened by the first grad2e()
         t0 = time.time()
         self.rank, self.world = rank, world
@@ -562,7 +577,9 @@ class HipBackend:
         if self.ao_mode == "direct":
             self.solver.compute_xc_direct(self.shells, self.ngrid, self.d_coords, self.d_w, self.d_dm, self.d_v, self._d_exc, self.ao_chunk)
             return float(self._d_exc.item())                                             # device sync, like the ABI call
-        if self.xc_occ:
+        if self.meta:
+            exc = self.solver.compute_xc_meta(self.ngrid, self.nao, self.d_dm, self.d_ao, self.d_w, self.d_v, self.d_gr)
+        elif self.xc_occ:
             exc = self.solver.compute_xc_occ(self.ngrid, self.nao, self.nocc, self.d_cocc, self.d_ao, self.d_w, self.d_v, self.d_gr, self.d_dm)
         else:
             exc = self.solver.compute_xc(self.ngrid, self.nao, self.d_dm, self.d_ao, self.d_w, self.d_v, self.d_gr)
@@ -580,6 +597,7 @@ class HipBackend:
 
     # ---- open-shell (scf.run_uks): one rank, resident AO planes, the host loop -----------------------------------------
     def _uks_check(self):
+        functionals.refuse_meta(self.solver.functional, "open-shell DFT (UKS)")
         if self.world > 1:
             raise ValueError("open-shell DFT (UKS) runs on one rank: the grid of this backend is sharded over several")
         if self.ao_mode != "resident":
@@ -673,6 +691,7 @@ class HipBackend:
 
     # ---- linear response (response.polarizability): one rank, resident AO planes ------------------------------
     def _response_check(self):
+        functionals.refuse_meta(self.solver.functional, "linear response (fxc / CPKS / excitations)")
         if self.world > 1:
             raise ValueError("linear response (fxc / CPKS) runs on one rank: the grid of this backend is sharded over several")
         if self.ao_mode != "resident":
@@ -764,6 +783,7 @@ class HipBackend:
         """The slicing xc_gradient and xc_gradient_spin share: entry(m, ao, w, d_out, gr, hs) is the library call of a slice.
         block = (lo, hi): the rows of the grid to sweep (default: all of it); after(lo, hi, ao, gr), when given, runs behind
         the entry of every slice on the same planes (the grid response takes the energy density there)."""
+        functionals.refuse_meta(self.solver.functional, "the XC part of the nuclear gradient")
         if self.world > 1:
             raise ValueError("the XC gradient runs on one rank: the grid of this backend is sharded over several")
         if self.dm_factor:
@@ -826,6 +846,7 @@ class HipBackend:
 
     def _xc_grid_response(self, slice_rows, entry, edens):
         from . import basis, grid_gen
+        functionals.refuse_meta(self.solver.functional, "the grid response of the nuclear gradient")
         if self.world > 1:
             raise ValueError("the grid response runs on one rank: the grid of this backend is sharded over several")
         if self.dm_factor:
@@ -1335,6 +1356,7 @@ def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, 
     the old ones, convergence |dE| < conv_e and |dD_a| + |dD_b| (Frobenius) < conv_dm.  With nalpha = nbeta the loop is
     run_scf's host loop term by term.  Returns run_scf's fields with dm the total density, and dm_a, dm_b, mo_energy_a,
     mo_energy_b, mo_coeff_a, mo_coeff_b, s_squared (spin_square), nalpha, nbeta, uks = True."""
+    functionals.refuse_meta(functional, "open-shell DFT (run_uks)")
     from .hostinfo import blas_threads
     Hcore, S = inp.Hcore, inp.S
     na = int(getattr(inp, "nalpha", None) if getattr(inp, "nalpha", None) is not None else inp.nocc)

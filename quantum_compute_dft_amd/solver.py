@@ -70,6 +70,8 @@ class DFTSolverWrapper:
         self.c_hf = self.functional.c_hf                       # exact-exchange fraction the SCF loop applies
         self.needs_gradient = self.functional.needs_gradient   # ao_grad is required
         self.weights = self.functional.weight_vector()         # the eight coefficients, functionals.COMPONENTS order
+        self.needs_tau = self.functional.needs_tau             # a meta-GGA: compute_xc_meta is its sweep
+        self.meta_weights = self.functional.meta_weight_vector()
         L = self.lib
         # --- the four reference symbols, declared exactly as dft.py:27-50 does
         L.DFT_CreateSolver.argtypes = [ctypes.c_int]
@@ -162,12 +164,30 @@ class DFTSolverWrapper:
         L.DFT_BeckeWeightGradient.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, dp, dp, _u64, _u64, _u64, _u64, _u64]
         L.DFT_BeckeWeightGradient.restype = ctypes.c_int
 
-        if self.functional.builtin_type is not None:
+        if self.needs_tau:
+            # added without a change of DFT_GetVersion: the symbols are looked up, a library without them cannot serve a meta-GGA
+            if not hasattr(L, "DFT_CreateSolverMeta"):
+                raise RuntimeError(f"{lib_path} has no DFT_CreateSolverMeta: it cannot run the meta-GGA {self.functional_type}")
+            self._declare_meta()
+            self.solver = L.DFT_CreateSolverMeta((ctypes.c_double * len(self.weights))(*self.weights), len(self.weights),
+                                                 (ctypes.c_double * len(self.meta_weights))(*self.meta_weights), len(self.meta_weights))
+        elif self.functional.builtin_type is not None:
             self.solver = L.DFT_CreateSolver(self.functional.builtin_type)
         else:
             self.solver = L.DFT_CreateSolverMix((ctypes.c_double * len(self.weights))(*self.weights), len(self.weights))
         if not self.solver:
             raise RuntimeError("Failed to create C++ DFT Solver instance.")
+
+    def _declare_meta(self):
+        L, dp = self.lib, ctypes.POINTER(ctypes.c_double)
+        L.DFT_CreateSolverMeta.argtypes = [dp, ctypes.c_int, dp, ctypes.c_int]
+        L.DFT_CreateSolverMeta.restype = ctypes.c_void_p
+        L.DFT_GetMeta.argtypes = [ctypes.c_void_p, dp, ctypes.c_int]
+        L.DFT_GetMeta.restype = ctypes.c_int
+        L.DFT_ComputeTau.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64]
+        L.DFT_ComputeTau.restype = ctypes.c_int
+        L.DFT_ComputeXCMeta.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, dp]
+        L.DFT_ComputeXCMeta.restype = ctypes.c_int
 
     def __del__(self):
         if hasattr(self, "lib") and hasattr(self, "solver") and self.solver:
@@ -338,6 +358,33 @@ class DFTSolverWrapper:
                                    ctypes.byref(exc))
         self._check()
         return exc.value
+
+    def compute_tau(self, ngrid, nao, d_dm, d_ao_grad, d_tau):
+        """tau (ngrid) of d_dm from the three gradient planes d_ao_grad (3, ngrid, nao) into d_tau (DFT_ComputeTau); any
+        solver; asynchronous on the solver's stream."""
+        self._declare_meta()
+        rc = self.lib.DFT_ComputeTau(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_tau)))
+        self._check()
+        return rc
+
+    def compute_xc_meta(self, ngrid, nao, d_dm, d_ao, d_weights, d_vxc, d_ao_grad=None):
+        """Exc of a meta-GGA solver (DFT_ComputeXCMeta); d_vxc receives V in the mix solver's one-sided convention plus the
+        whole tau term: (V + V^T)/2 is dExc/dD.  With option quirks = 1 a functional with vwn5_c or pbe_c is refused, as by
+        compute_xc_spin.  Synchronous."""
+        self._declare_meta()
+        exc = ctypes.c_double(float("nan"))
+        self.lib.DFT_ComputeXCMeta(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)), _u64(_ptr(d_weights)),
+                                   _u64(_ptr(d_ao_grad)), _u64(_ptr(d_vxc)), ctypes.byref(exc))
+        self._check()
+        return exc.value
+
+    def meta(self):
+        """The solver's meta weights as the library reports them (DFT_GetMeta)."""
+        self._declare_meta()
+        out = (ctypes.c_double * len(functionals.META_COMPONENTS))()
+        if self.lib.DFT_GetMeta(self.solver, out, len(out)) != 0:
+            raise RuntimeError("DFT_GetMeta failed")
+        return list(out)
 
     def fxc_prepare_spinpol(self, ngrid, nao, d_dm0_a, d_dm0_b, d_ao, d_weights, d_ao_grad=None):
         """First half of the open-shell response of Vxc (DFT_FxcPrepareSpinPol): the densities of the two spins and the
