@@ -48,6 +48,16 @@ class Shell:
     def key(self):
         return (self.l, self.centre, self.exps, self.coefs)
 
+    def moved(self, axis, step):
+        """A copy whose centre is displaced by `step` along `axis` and kept as mpf at DPS digits, NOT rounded to double:
+        the finite-difference references (tests/golden/make_grad_reference.py) step by far less than a double resolves."""
+        out = Shell(self.l, self.centre, self.exps, self.coefs)
+        with mp.workdps(DPS):
+            c = [mpf(x) for x in self.centre]
+            c[axis] = c[axis] + mpf(step)
+            out.centre = tuple(c)
+        return out
+
     @property
     def nfun(self):
         return 2 * self.l + 1

@@ -1,6 +1,14 @@
-"""Shared pieces of the two-electron-gradient tests (test_grad2e_cpu.py, test_gpu_grad2e.py): the CH/def2-TZVP fragment
-that meets every angular class s-f on bra and ket, the same molecule with its atoms in another order (and the density
-permuted with them), the host engine's results -- computed once per case and shared, never modified -- and the yardstick.
+"""Shared pieces of the two-electron-gradient tests (test_grad2e_cpu.py, test_gpu_grad2e.py, test_gpu_grad2e_spin.py,
+test_gpu_grad2e_reference.py): the CH/def2-TZVP fragment that meets every angular class s-f on bra and ket, the same
+molecule with its atoms in another order (and the density permuted with them), two molecules with enough shells for the
+kernel's ket-slice loop to run several times per workgroup, the host engine's results -- computed once per case and
+shared, never modified -- and the yardstick.
+
+What CH/def2-TZVP does NOT reach: its d and f shells all sit on the carbon, so every quartet with three or four shells
+of l >= 2 is a one-centre quartet (X_AB = X_CD = 0, P = Q, Boys argument exactly 0, every recurrence term that multiplies
+a centre difference vanishes), and (ff|ff) from the one f shell has a derivative that is zero by parity.  The four-centre
+classes are held against the 100-digit reference of tests/golden/grad_ref_g*.npz (test_grad_reference_cpu.py on the host,
+test_gpu_grad2e_reference.py on the device).
 
 The yardstick is the host engine's own rounding floor: `bar` = the largest per-atom difference, relative to max|g|,
 between integrals.grad2e on a molecule and on the same molecule with the atoms listed in the other order (another order
@@ -19,6 +27,14 @@ CH = (["C", "H"], [[0.10, -0.20, 0.05], [1.25, 0.90, 1.60]], "def2-tzvp")       
 H2O_STO = (*basis.parse_xyz(_H2O), "sto-3g")
 H2O_SVP = (*basis.parse_xyz(_H2O), "def2-svp")
 H_ATOM = (["H"], [[0.3, -0.1, 0.2]], "sto-3g")
+# More than 16 shells: the device kernel cuts the ket-pair list into nslice = ceil(32768 / nshell^2) < nket slices, so a
+# workgroup's loop over its ket pairs runs several times (slice_counts).  Generic orientations, no atom on an axis.
+C2H4_SVP = (["C", "C", "H", "H", "H", "H"],                                        # 24 shells, 48 functions, d on two centres
+            [[0.6786, 0.7885, 0.5927], [-0.3786, -1.2885, -0.3927], [-0.2744, 1.8787, 2.0496], [2.5207, 1.4453, -0.0355],
+             [-2.2207, -1.9453, 0.2355], [0.5744, -2.3787, -1.8496]], "def2-svp")
+C2_TZVP = (["C", "C"], [[0.10, -0.20, 0.05], [1.204, 1.18, 1.522]], "def2-tzvp")   # 22 shells, 62 functions, 2.3 bohr, f on both
+SLICE_CASES = {"C2H4/def2-SVP": C2H4_SVP, "C2/def2-TZVP": C2_TZVP}
+SLICE_TARGET = 32768                                 # csrc/grad2e.hip, DFT_Grad2eOpen: the (bra pair, slice) count aimed at
 
 
 def molecule(case, order=None):
@@ -101,6 +117,35 @@ def _ch_case(c_hf, swapped, blocked):
     for a in (D, rows, atoms):
         a.setflags(write=False)
     return dict(shells=sh, D=D, per_shell=rows, per_atom=atoms, bar=bar)
+
+
+def slice_counts(nshell):
+    """(nslice, nket, ket pairs per workgroup at least, at most) of DFT_Grad2eOpen for a molecule of `nshell` shells."""
+    nket = nshell * (nshell + 1) // 2
+    nslice = max(1, min(nket, -(-SLICE_TARGET // (nshell * nshell))))
+    return nslice, nket, nket // nslice, -(-nket // nslice)
+
+
+def slice_case(name, c_hf, blocked=False):
+    """A molecule of SLICE_CASES with the random D and M (seeds 7, 23; optionally block-diagonal per atom), atoms as written:
+    dict(shells, D, M, per_shell, per_atom, spin_per_shell, spin_per_atom, bar), host results, computed once.  `bar` is
+    reorder_bar of this very case."""
+    return _slice_case(name, float(c_hf), bool(blocked))
+
+
+@functools.lru_cache(maxsize=None)
+def _slice_case(name, c_hf, blocked):
+    case = SLICE_CASES[name]
+    sh = molecule(case)[2]
+    D, M = random_density(sh.nao), random_density(sh.nao, seed=23)
+    if blocked:
+        D, M = np.ascontiguousarray(block_diagonal(sh, D)), np.ascontiguousarray(block_diagonal(sh, M))
+    rows, atoms = host_pair(sh, D, c_hf)
+    srows, satoms = integrals.grad2e_spin(sh, D, M, c_hf, per_shell=True), integrals.grad2e_spin(sh, D, M, c_hf)
+    bar = reorder_bar(case, D, c_hf, atoms)
+    for a in (D, M, rows, atoms, srows, satoms):
+        a.setflags(write=False)
+    return dict(shells=sh, D=D, M=M, per_shell=rows, per_atom=atoms, spin_per_shell=srows, spin_per_atom=satoms, bar=bar)
 
 
 def record(label, bar, err):

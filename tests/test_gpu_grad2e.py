@@ -32,8 +32,12 @@ def ch_engines():
 @pytest.mark.parametrize("swapped", [False, True])
 @pytest.mark.parametrize("c_hf", [0.0, 0.25])
 def test_every_class(ch_engines, c_hf, swapped):
-    """CH/def2-TZVP: s-f on bra and ket, L up to 13 ((ff|ff) from the one f shell); with the atoms swapped the (l_a < l_b)
-    classes and the ket pairs C >= D come in the other index order."""
+    """CH/def2-TZVP: s-f on bra and ket; with the atoms swapped the (l_a < l_b) classes and the ket pairs C >= D come in
+    the other index order.  The d and f shells all sit on the carbon, so every quartet with three or four shells of
+    l >= 2 is a ONE-centre quartet here (no centre difference, Boys argument exactly 0), and (ff|ff) from the one f shell
+    has a derivative that is zero by parity: the ff bra's largest LDS configuration is launched, its values are not
+    tested.  The four-centre classes, (dd|dd) and (ff|ff) at L = 13 among them, are held against the 100-digit reference
+    in tests/test_gpu_grad2e_reference.py."""
     c = gh.ch_case(c_hf, swapped)
     eng = ch_engines[swapped]
     rows = eng.per_shell(_dev(c["D"]), c_hf).cpu().numpy()

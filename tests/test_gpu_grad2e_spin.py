@@ -37,7 +37,9 @@ def ch_engines():
 @pytest.mark.parametrize("swapped", [False, True])
 @pytest.mark.parametrize("c_hf", [0.0, 0.25])
 def test_every_class(ch_engines, c_hf, swapped):
-    """CH/def2-TZVP: s-f on bra and ket, both orders of the atoms."""
+    """CH/def2-TZVP: s-f on bra and ket, both orders of the atoms.  Its quartets with three or four shells of l >= 2 are
+    one-centre quartets and (ff|ff) is zero by parity (see test_gpu_grad2e.test_every_class); the four-centre classes of
+    the spin entry are in tests/test_gpu_grad2e_reference.py."""
     c = gh.ch_case(c_hf, swapped)
     M = spin_density(c)
     eng = ch_engines[swapped]

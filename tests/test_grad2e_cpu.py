@@ -52,6 +52,27 @@ def test_the_yardstick_is_tight():
         assert np.abs(sw["per_atom"][::-1] - gh.ch_case(c_hf)["per_atom"]).max() <= bar * np.abs(sw["per_atom"]).max() * (1 + 1e-12)
 
 
+@pytest.mark.parametrize("name", list(gh.SLICE_CASES))
+def test_the_multi_slice_molecules(name):
+    """The two molecules of tests/test_gpu_grad2e_reference.py whose workgroups loop over several ket pairs: the shell
+    counts that make it so, tied to the constant in DFT_Grad2eOpen; and the host engine the device is compared with there,
+    held by translational invariance: d (f) shells on two centres, so an error in a term of the raised bra's recurrence
+    that multiplies X_AB -- invisible where all shells of l >= 2 share a centre -- leaves a net force (measured 7e-14 of the largest row; the
+    finite-difference projection of test_gradient_integrals_cpu on C2/def2-TZVP would take twice that file's slowest
+    case and was left out)."""
+    import os
+    src = open(os.path.join(os.path.dirname(integrals.__file__), "csrc", "grad2e.hip")).read()
+    assert f"std::min(c->nket, ({gh.SLICE_TARGET} + nshell * nshell - 1) / (nshell * nshell))" in src
+    sh = gh.molecule(gh.SLICE_CASES[name])[2]
+    nslice, nket, least, most = gh.slice_counts(sh.nshell)
+    assert (sh.nshell, sh.nao, nslice, nket, least, most) == {"C2H4/def2-SVP": (24, 48, 57, 300, 5, 6), "C2/def2-TZVP": (22, 62, 68, 253, 3, 4)}[name]
+    assert gh.slice_counts(15) == (120, 120, 1, 1) and gh.slice_counts(16) == (128, 136, 1, 2)      # every other test: one pair
+    rows = integrals.grad2e(sh, gh.random_density(sh.nao), 0.25, per_shell=True)
+    net = np.abs(rows.sum(axis=0)).max() / np.abs(rows).max()
+    print(f"cpu grad2e {name} c_hf 0.25: |sum over shells| / max|row| {net:.2e}")
+    assert net <= 1e-10                              # the bound of every invariance test of the gradient terms
+
+
 def test_device_engine_without_a_device_says_so():
     import torch
     if torch.cuda.is_available():
