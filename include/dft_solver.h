@@ -335,7 +335,7 @@ int DFT_ComputeXCSpin(XCSolver *solver, long long ngrid, int nao, unsigned long 
                       unsigned long long d_weights_ptr, unsigned long long d_vxc_a_ptr, unsigned long long d_vxc_b_ptr,
                       double *exc);
 
-/* Meta-GGA functionals (closed shell).  Two further components read the kinetic-energy density
+/* Meta-GGA functionals.  Two further components read the kinetic-energy density
  *     tau(g) = 1/2 sum_k sum_mu,nu D[mu, nu] (d_k phi_mu)(g) (d_k phi_nu)(g):
  * TPSS exchange and TPSS correlation (csrc/xc_meta_functionals.hpp: energies per volume of the spin variables, first
  * derivatives by forward mode, written down as recalled -- the numerical rules are stated there). */
@@ -343,8 +343,8 @@ enum XCMetaComponent { XC_TPSS_X = 0, XC_TPSS_C, XC_NMETA };
 
 /* A solver for eps = sum_k weights[k] eps_k + sum_k meta_weights[k] eps_meta_k (type SOLVER_MIX with meta weights; it
  * always takes the four-plane form: ao_grad is required).  NULL unless ncomp == XC_NCOMP, nmeta == XC_NMETA, every
- * weight is finite and at least one is non-zero.  With a non-zero meta weight the solver serves DFT_ComputeTau and
- * DFT_ComputeXCMeta only: every other XC entry refuses it (-1 / NaN and a sentence in DFT_GetLastError), so that tau
+ * weight is finite and at least one is non-zero.  With a non-zero meta weight the solver serves DFT_ComputeTau,
+ * DFT_ComputeXCMeta and their open-shell counterparts DFT_ComputeTauSpin / DFT_ComputeXCMetaSpin only: every other XC entry refuses it (-1 / NaN and a sentence in DFT_GetLastError), so that tau
  * cannot be dropped silently.  Added without a change of DFT_GetVersion (it stays 5): look the symbols up. */
 XCSolver *DFT_CreateSolverMeta(const double *weights, int ncomp, const double *meta_weights, int nmeta);
 
@@ -374,6 +374,32 @@ int DFT_ComputeTau(XCSolver *solver, long long ngrid, int nao, unsigned long lon
 int DFT_ComputeXCMeta(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr, unsigned long long d_ao_ptr,
                       unsigned long long d_weights_ptr, unsigned long long d_ao_grad_ptr, unsigned long long d_vxc_ptr,
                       double *exc);
+
+/* Meta-GGA functionals, open shell.  d_tau_a, d_tau_b (ngrid each) receive tau of d_dm_a, d_dm_b (their symmetric parts)
+ * from the three gradient planes.  Option "tau_spin_fused" = 1 (the default: the faster form as measured,
+ * profiles/meta_spin_time.txt): "tau_spin" (k_tau_spin, csrc/xc_meta_spin.hip), one staging of the gradient rows for both
+ * spins; 0: k_tau once per spin ("tau x2"), what the tests hold the two-spin kernel to.  Either way no atomics, bitwise reproducible, and per spin the operations of
+ * DFT_ComputeTau.  Asynchronous on the solver's stream.  Any solver.  0, or -1 with DFT_GetLastError (bad sizes, a null
+ * pointer).  Added without a change of DFT_GetVersion: look the symbols up. */
+int DFT_ComputeTauSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr, unsigned long long d_dm_b_ptr,
+                       unsigned long long d_ao_grad_ptr, unsigned long long d_tau_a_ptr, unsigned long long d_tau_b_ptr);
+
+/* Exc and the two spin potentials of a meta solver at the spin density matrices d_dm_a, d_dm_b.  d_vxc_s (nao, nao)
+ * receives V_s in the mix solver's one-sided convention (DFT_ComputeXCSpin's, scale 1) plus the whole (symmetric) tau term
+ * of spin s: (V_s + V_s^T)/2 is dExc/dD_s.  At dm_a = dm_b = dm/2 both are DFT_ComputeXCMeta's V.  A spin channel whose
+ * density is below the cut-off at a point is absent there (exact zeros in its coefficients, the zeta = +-1 rules of
+ * csrc/xc_meta_functionals.hpp for the other): a spin without electrons gets V_s = 0 exactly.
+ * Order of work on the solver's stream: the sweep's density kernels per spin, tau per spin (DFT_ComputeTauSpin's two
+ * forms), "xc_points_meta_spin" (xc::meta_spin_point: seven first derivatives by forward mode), the sweep's contraction
+ * and reduce of c0..c3 per spin, then the tau term per spin in the form "meta_fused" chooses.  With both meta weights
+ * zero tau is cleared instead of computed and the tau terms are left out.  Never the one-kernel plan for small bases,
+ * never a recorded graph.  Synchronous.  Its planes are its own: prepared DFT_Fxc* tables and later DFT_ComputeXC,
+ * DFT_ComputeXCSpin and DFT_ComputeXCMeta calls are not disturbed.  Returns 0, or -1 with DFT_GetLastError and no kernel
+ * launched: a solver not made by DFT_CreateSolverMeta, a null pointer (ao_grad included), bad sizes, "quirks" = 1 with a
+ * vwn5_c or pbe_c weight. */
+int DFT_ComputeXCMetaSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr, unsigned long long d_dm_b_ptr,
+                          unsigned long long d_ao_ptr, unsigned long long d_weights_ptr, unsigned long long d_ao_grad_ptr,
+                          unsigned long long d_vxc_a_ptr, unsigned long long d_vxc_b_ptr, double *exc);
 
 /* Linear response of DFT_ComputeXCSpin, in two halves like DFT_FxcPrepare / DFT_FxcApply: V1_s (nao, nao), s = alpha,
  * beta, is, element for element, d/dt of what DFT_ComputeXCSpin(dm0_a + t dm1_a, dm0_b + t dm1_b) writes into vxc_s at

@@ -36,6 +36,7 @@
 #include "xc_grad_launch.hpp"
 #include "becke_launch.hpp"
 #include "xc_meta_launch.hpp"
+#include "xc_meta_spin_launch.hpp"
 
 using namespace qcdft;
 
@@ -204,6 +205,17 @@ struct XCSolver {
     // at 143 556 x 114, 2015.7 against 1855.1 us at 60 000 x 494: profiles/meta_time.txt), so it is the option, held to the plain
     // form by the tests
     int meta_fused = 0;
+    // DFT_ComputeTauSpin / DFT_ComputeXCMetaSpin: a set of their own again -- the planes of each spin (the Exc partials with
+    // [0]), tau of each spin (2 ngrid), the tau coefficients (two sets of four planes: ct_s and, for the plain form, three of
+    // zeros), the two padded matrices k_tau / k_tau_spin read, the slabs of k_vxc_tau, the matrix one plain contraction
+    // leaves, and the scalar of its Exc.  No recorded sweep, no prepared response table and no other entry holds or reads
+    // any of them.
+    Planes mspin[2];
+    DevBuf mspin_tau, mspin_ct, mspin_dp, mspin_slabs, mspin_vtmp, mspin_exc;
+    // The tau stage of an open-shell call.  1 (default): k_tau_spin, one staging of the gradient rows for both spins
+    // (xc_meta_spin.hip; 0.80 x / 0.61 x of the two launches at 143 556 x 114 / 60 000 x 494: profiles/meta_spin_time.txt); 0:
+    // k_tau once per spin, what the tests hold the two-spin kernel to
+    int tau_spin_fused = 1;
     std::vector<double> becke_tab_host;
     std::string last_error;
     std::vector<Timing> timings;
@@ -284,7 +296,7 @@ bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed
     s->n_timed = timed;
     if (s->meta_active && !meta_entry) {
         set_error(s, "the solver's functional is a meta-GGA (non-zero tpss_x / tpss_c weight): it reads the kinetic-energy density, "
-                     "which only DFT_ComputeXCMeta forms; this entry would drop it");
+                     "which only DFT_ComputeXCMeta and DFT_ComputeXCMetaSpin form; this entry would drop it");
         return false;
     }
     if (!s->device_ok) {
@@ -843,6 +855,103 @@ bool xc_sweep_meta(XCSolver *s, long ngrid, int nao, const double *dm, const dou
         return false;
     *exc_host = out;
     if (std::isnan(out)) { set_error(s, "Exc is NaN after the meta-GGA sweep completed (non-finite inputs)"); return false; }
+    return true;
+}
+
+// tau of both spins (DFT_ComputeTauSpin): the two padded symmetric matrices into a buffer of their own, then k_tau_spin
+// (option "tau_spin_fused" = 1) or k_tau once per spin.
+bool compute_tau_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao_grad, double *tau_a,
+                      double *tau_b)
+{
+    const TauPlan tp = s->tau_spin_fused ? tau_spin_plan(s->num_cu, ngrid, nao) : tau_plan(s->num_cu, ngrid, nao);
+    const size_t np2 = (size_t)tp.NP * tp.NP;
+    if (!reserve(s, s->mspin_dp, sizeof(double) * 2 * np2, "hipMalloc(meta Dp of both spins)", false)) return false;
+    double *Dpa = s->mspin_dp.d(), *Dpb = Dpa + np2;
+    ScopedTimer t(s, s->tau_spin_fused ? "tau_spin" : "tau x2");
+    hipLaunchKernelGGL(k_sym_dm, dim3(tp.NP / 16, tp.NP / 16), dim3(16, 16), 0, s->stream, nao, tp.NP, dm_a, Dpa);
+    hipLaunchKernelGGL(k_sym_dm, dim3(tp.NP / 16, tp.NP / 16), dim3(16, 16), 0, s->stream, nao, tp.NP, dm_b, Dpb);
+    if (s->tau_spin_fused) return hip_ok(s, launch_tau_spin(s->stream, tp, ngrid, nao, ao_grad, Dpa, Dpb, tau_a, tau_b), "two-spin tau launch");
+    return hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, Dpa, tau_a), "tau launch (alpha)") &&
+           hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, Dpb, tau_b), "tau launch (beta)");
+}
+
+// The spin-resolved meta-GGA sweep (DFT_ComputeXCMetaSpin): the closed-shell sweep's density kernels per spin, tau per spin,
+// one pointwise kernel (xc_meta_spin.hip), the closed-shell contraction and reduce of c0..c3 once per spin (the second
+// finishes Exc from the pointwise kernel's partials, as in xc_sweep_spin), and the tau term of each spin added to its V in
+// either form of "meta_fused".  Never the one-kernel plan for small bases, never recorded, synchronous.  Shares Dsym, the
+// slabs and M with the other entries (stream order), and nothing else.  The refusals come before anything touches the
+// device, so that they can be told apart from "no usable HIP device".
+bool xc_sweep_meta_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao, const double *w,
+                        const double *ao_grad, double *vxc_a, double *vxc_b, double *exc_host)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->is_meta) {
+        set_error(s, "DFT_ComputeXCMetaSpin needs a solver made by DFT_CreateSolverMeta (this one carries no meta-GGA weights)");
+        return false;
+    }
+    if (!dm_a || !dm_b || !ao || !w || !ao_grad || !vxc_a || !vxc_b || !exc_host) {
+        set_error(s, "DFT_ComputeXCMetaSpin needs both density matrices, the AO values, the grid weights, ao_grad (tau is made of the "
+                     "gradient planes), both output matrices and exc: a pointer is null");
+        return false;
+    }
+    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
+    if (!spin_quirks_ok(s, "DFT_ComputeXCMetaSpin")) return false;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const long nxb = meta_points_blocks(ngrid);
+    const size_t ng = (size_t)ngrid, nn = (size_t)nao * nao;
+    Planes &a = s->mspin[0], &b = s->mspin[1];
+    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, a, false, ngrid, WS_ALL, nxb) ||
+        !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD) ||
+        !reserve(s, s->mspin_tau, sizeof(double) * 2 * ng, "hipMalloc(tau of both spins)", false) ||
+        !reserve(s, s->mspin_ct, sizeof(double) * 8 * ng, "hipMalloc(tau coefficients of both spins)", false) ||
+        !reserve(s, s->mspin_exc, 2 * sizeof(double), "hipMalloc(spin meta exc)", false))
+        return false;
+    // the density kernels on each spin's matrix (launch_density_spin's two launches, into the planes of this entry)
+    launch_density(s, P, ngrid, nao, dm_a, ao, s->dsym.d(), a.rho.d(), a.grad.d(), a.sigma.d());
+    launch_density(s, P, ngrid, nao, dm_b, ao, s->dsym.d(), b.rho.d(), b.grad.d(), a.sigma.d());
+    double *tau = s->mspin_tau.d(), *ct = s->mspin_ct.d();
+    if (s->meta_active) {
+        if (!compute_tau_spin(s, ngrid, nao, dm_a, dm_b, ao_grad, tau, tau + ng)) return false;
+    } else if (!hip_ok(s, hipMemsetAsync(tau, 0, sizeof(double) * 2 * ng, s->stream), "clear tau")) {
+        return false;
+    }
+    {
+        ScopedTimer t(s, "xc_points_meta_spin");
+        if (!hip_ok(s, launch_xc_points_meta_spin(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), b.rho.d(), a.grad.d(), b.grad.d(), tau, tau + ng,
+                                                  w, a.coef.d(), b.coef.d(), ct, ct + 4 * ng, a.partial.d()), "spin meta pointwise launch"))
+            return false;
+    }
+    double *exc = s->mspin_exc.d();
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, a.coef.d(), s->slabs.d(), vxc_a, nullptr)) return false;
+    const ExcFinish fin{nxb, a.partial.d(), exc, false};   // no host-mapped word, no publishing: Exc is copied below
+    if (!vxc_stage(s, P, false, ngrid, nao, ao, b.coef.d(), s->slabs.d(), vxc_b, &fin)) return false;
+    if (s->meta_active && s->meta_fused) {
+        const VxcTauPlan vp = vxc_tau_plan(s->num_cu, ngrid, nao);
+        if (!reserve(s, s->mspin_slabs, sizeof(double) * (size_t)vp.nslab * nn, "hipMalloc(tau slabs)", false)) return false;
+        ScopedTimer t(s, "vxc_tau x2");
+        if (!hip_ok(s, launch_vxc_tau(s->stream, vp, ngrid, nao, ao_grad, ct, s->mspin_slabs.d(), vxc_a), "tau potential launch (alpha)") ||
+            !hip_ok(s, launch_vxc_tau(s->stream, vp, ngrid, nao, ao_grad, ct + 4 * ng, s->mspin_slabs.d(), vxc_b), "tau potential launch (beta)"))
+            return false;
+    } else if (s->meta_active) {
+        // the plain form, per spin: Q = c0 (plane in the AO slot) with c0 = ct_s and c1..c3 = 0, contracted with the same plane
+        if (!reserve(s, s->mspin_vtmp, sizeof(double) * nn, "hipMalloc(tau potential)", false) ||
+            !hip_ok(s, hipMemsetAsync(ct + ng, 0, sizeof(double) * 3 * ng, s->stream), "clear coefficients") ||
+            !hip_ok(s, hipMemsetAsync(ct + 5 * ng, 0, sizeof(double) * 3 * ng, s->stream), "clear coefficients"))
+            return false;
+        for (int sp = 0; sp < 2; ++sp)
+            for (int k = 0; k < 3; ++k) {
+                if (!vxc_stage(s, P, false, ngrid, nao, ao_grad + (size_t)k * ng * nao, ct + (size_t)sp * 4 * ng, s->slabs.d(), s->mspin_vtmp.d(), nullptr))
+                    return false;
+                if (!hip_ok(s, launch_meta_add(s->stream, (long)nn, s->mspin_vtmp.d(), sp ? vxc_b : vxc_a), "tau potential add")) return false;
+            }
+    }
+    double out = std::numeric_limits<double>::quiet_NaN();
+    if (!hip_ok(s, hipMemcpyAsync(&out, exc, sizeof(double), hipMemcpyDeviceToHost, s->stream), "copy Exc") ||
+        !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
+        return false;
+    *exc_host = out;
+    if (std::isnan(out)) { set_error(s, "Exc is NaN after the spin-resolved meta-GGA sweep completed (non-finite inputs)"); return false; }
     return true;
 }
 
@@ -2109,6 +2218,33 @@ int DFT_ComputeXCMeta(XCSolver *s, long long ngrid, int nao, unsigned long long 
                          (const double *)d_ao_grad, (double *)d_vxc, exc) ? 0 : -1;
 }
 
+int DFT_ComputeTauSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                       unsigned long long d_ao_grad, unsigned long long d_tau_a, unsigned long long d_tau_b)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%lld nao=%d", ngrid, nao); return -1; }
+    if (!d_dm_a || !d_dm_b || !d_ao_grad || !d_tau_a || !d_tau_b) {
+        set_error(s, "DFT_ComputeTauSpin needs both density matrices, ao_grad and both outputs: a pointer is null");
+        return -1;
+    }
+    if (!s->device_ok) { set_error(s, "no usable HIP device"); return -1; }
+    return compute_tau_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao_grad,
+                            (double *)d_tau_a, (double *)d_tau_b) ? 0 : -1;
+}
+
+int DFT_ComputeXCMetaSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                          unsigned long long d_ao, unsigned long long d_w, unsigned long long d_ao_grad,
+                          unsigned long long d_vxc_a, unsigned long long d_vxc_b, double *exc)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_sweep_meta_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
+                              (const double *)d_w, (const double *)d_ao_grad, (double *)d_vxc_a, (double *)d_vxc_b, exc) ? 0 : -1;
+}
+
 void DFT_ComputeCoulomb(XCSolver *s, int nao, unsigned long long d_eri, unsigned long long d_dm,
                         unsigned long long d_J)
 {
@@ -2322,6 +2458,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "ksplit")) { s->ksplit = value > 0 ? (int)value : 0; return 0; }
     if (!strcmp(key, "xcg_spin_fused")) { s->xcg_spin_fused = value != 0.0; return 0; }
     if (!strcmp(key, "meta_fused")) { s->meta_fused = value != 0.0; return 0; }
+    if (!strcmp(key, "tau_spin_fused")) { s->tau_spin_fused = value != 0.0; return 0; }
     return -1;
 }
 
@@ -2349,6 +2486,7 @@ double DFT_GetOption(XCSolver *s, const char *key)
     if (!strcmp(key, "used_dm_factor")) return s->used_dm_factor;                              // the last synchronous call swept with the factor of dm
     if (!strcmp(key, "xcg_spin_fused")) return s->xcg_spin_fused;
     if (!strcmp(key, "meta_fused")) return s->meta_fused;
+    if (!strcmp(key, "tau_spin_fused")) return s->tau_spin_fused;
     if (!strcmp(key, "dm_factor_rank")) return s->dm_factor_rank;                              // the rank its attempt found (0: rejected / not attempted)
     return unknown;
 }

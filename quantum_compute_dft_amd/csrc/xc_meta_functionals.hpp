@@ -194,5 +194,73 @@ QCDFT_XC_FN MetaPoint meta_point(const MixWeights &m, const MetaWeights &mm, dou
     return o;
 }
 
+// One point of the spin-resolved meta-GGA sweep (DFT_ComputeXCMetaSpin), the counterpart of spin_potential_point through
+// meta_mix_energy: the energy per volume e and, per spin s (s' the other one),
+//     c0_s  = w e_rho_s
+//     c_s,k = 2 w (2 e_sigma_ss grad rho_s + e_sigma_ab grad rho_s')_k
+//     ct_s  = w e_tau_s / 2
+// one-sided, scale 1 (a meta solver is a mix solver: no B3LYP halving); at rho_a = rho_b, grad rho_a = grad rho_b,
+// tau_a = tau_b these are meta_point's.  Seven xc::Dual evaluations, one after the other, so that one evaluation's registers
+// are live at a time; the two tau directions see the meta components alone.  d[] keeps the derivatives bare, in the order
+// (ra, rb, saa, sab, sbb, ta, tb), for the tests.
+//
+// A channel whose density is below kRhoCut is absent, as in spin_potential_point and qc_meta_energy_spin: its rho, sigma_ss,
+// sigma_ab and tau count as exactly 0, its coefficients are exactly 0 and it is not differentiated; the other channel gets
+// the zeta = +-1 rules of the bodies above.  Both absent: zeros.
+struct MetaSpinPoint {
+    double e;
+    double a[4], b[4];
+    double cta, ctb;
+    double d[7];
+};
+
+QCDFT_XC_FN MetaSpinPoint meta_spin_point(const MixWeights &m, const MetaWeights &mm, double ra, double rb, double gax, double gay,
+                                          double gaz, double gbx, double gby, double gbz, double ta, double tb, double w)
+{
+    MetaSpinPoint o = {};
+    const bool pa = ra >= kRhoCut, pb = rb >= kRhoCut;
+    if (!pa && !pb) return o;
+    if (!pa) { ra = 0.0; ta = 0.0; }
+    if (!pb) { rb = 0.0; tb = 0.0; }
+    double saa = 0.0, sab = 0.0, sbb = 0.0;
+    if (pa) saa = gax * gax + gay * gay + gaz * gaz;
+    if (pb) sbb = gbx * gbx + gby * gby + gbz * gbz;
+    if (pa && pb) sab = gax * gbx + gay * gby + gaz * gbz;
+    const bool meta = mm.c[0] != 0.0 || mm.c[1] != 0.0;
+    if (pa) {
+        const Dual e = meta_mix_energy<false>(m, mm, Dual(ra, 1.0), Dual(rb), Dual(saa), Dual(sab), Dual(sbb), Dual(ta), Dual(tb));
+        o.e = e.v;
+        o.d[0] = e.d;
+    }
+    if (pb) {
+        const Dual e = meta_mix_energy<false>(m, mm, Dual(ra), Dual(rb, 1.0), Dual(saa), Dual(sab), Dual(sbb), Dual(ta), Dual(tb));
+        if (!pa) o.e = e.v;
+        o.d[1] = e.d;
+    }
+    if (pa) o.d[2] = meta_mix_energy<false>(m, mm, Dual(ra), Dual(rb), Dual(saa, 1.0), Dual(sab), Dual(sbb), Dual(ta), Dual(tb)).d;
+    if (pa && pb) o.d[3] = meta_mix_energy<false>(m, mm, Dual(ra), Dual(rb), Dual(saa), Dual(sab, 1.0), Dual(sbb), Dual(ta), Dual(tb)).d;
+    if (pb) o.d[4] = meta_mix_energy<false>(m, mm, Dual(ra), Dual(rb), Dual(saa), Dual(sab), Dual(sbb, 1.0), Dual(ta), Dual(tb)).d;
+    if (meta && pa) o.d[5] = meta_mix_energy<true>(m, mm, Dual(ra), Dual(rb), Dual(saa), Dual(sab), Dual(sbb), Dual(ta, 1.0), Dual(tb)).d;
+    if (meta && pb) o.d[6] = meta_mix_energy<true>(m, mm, Dual(ra), Dual(rb), Dual(saa), Dual(sab), Dual(sbb), Dual(ta), Dual(tb, 1.0)).d;
+    const double f = 2.0 * w;
+    if (pa) {
+        const double u = 2.0 * o.d[2], v = pb ? o.d[3] : 0.0;
+        o.a[0] = w * o.d[0];
+        o.a[1] = f * (u * gax + (pb ? v * gbx : 0.0));
+        o.a[2] = f * (u * gay + (pb ? v * gby : 0.0));
+        o.a[3] = f * (u * gaz + (pb ? v * gbz : 0.0));
+        o.cta = 0.5 * w * o.d[5];
+    }
+    if (pb) {
+        const double u = 2.0 * o.d[4], v = pa ? o.d[3] : 0.0;
+        o.b[0] = w * o.d[1];
+        o.b[1] = f * (u * gbx + (pa ? v * gax : 0.0));
+        o.b[2] = f * (u * gby + (pa ? v * gay : 0.0));
+        o.b[3] = f * (u * gbz + (pa ? v * gaz : 0.0));
+        o.ctb = 0.5 * w * o.d[6];
+    }
+    return o;
+}
+
 } // namespace xc
 } // namespace qcdft

@@ -215,6 +215,30 @@ int qc_meta_point(const double *mix8, const double *meta2, long long n, const do
     return 0;
 }
 
+// One point of the spin-resolved meta-GGA sweep, xc::meta_spin_point as k_xc_points_meta_spin runs it.  ga3 / gb3: three per
+// point, interleaved.  out (18, n): e (no weight); c0..c3 of alpha; c0..c3 of beta; ct of alpha, of beta; the bare
+// derivatives of e by rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb, tau_a, tau_b (zero for an absent channel).
+int qc_meta_point_spin(const double *mix8, const double *meta2, long long n, const double *ra, const double *rb, const double *ga3,
+                       const double *gb3, const double *ta, const double *tb, const double *w, double *out)
+{
+    if (!mix8 || !meta2 || n < 0 || !ra || !rb || !ga3 || !gb3 || !ta || !tb || !w || !out) return -1;
+    const xc::MixWeights m = weights(mix8);
+    const xc::MetaWeights mm = {{meta2[0], meta2[1]}};
+    for (long long g = 0; g < n; ++g) {
+        const xc::MetaSpinPoint p = xc::meta_spin_point(m, mm, ra[g], rb[g], ga3[3 * g], ga3[3 * g + 1], ga3[3 * g + 2], gb3[3 * g],
+                                                        gb3[3 * g + 1], gb3[3 * g + 2], ta[g], tb[g], w[g]);
+        out[g] = p.e;
+        for (int k = 0; k < 4; ++k) {
+            out[(1 + k) * n + g] = p.a[k];
+            out[(5 + k) * n + g] = p.b[k];
+        }
+        out[9 * n + g] = p.cta;
+        out[10 * n + g] = p.ctb;
+        for (int k = 0; k < 7; ++k) out[(11 + k) * n + g] = p.d[k];
+    }
+    return 0;
+}
+
 // The energy per volume of the ten weights at any (rho_a, rho_b, sigma_aa, sigma_ab, sigma_bb, tau_a, tau_b) into out (n),
 // and (grad non-null) its seven first derivatives into grad (7, n) by xc::Dual.  A variable of an absent channel (density
 // below the cut-off; sigma_ab belongs to both) is not differentiated: its derivative is exactly 0, as in spin_potential_point.

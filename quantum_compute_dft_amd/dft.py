@@ -159,6 +159,10 @@ def build_parser():
                    help="with --spin: allow --dipole, --polarizability (unrestricted CPKS) and --excitations (spin-conserving U-TDDFT / "
                         "U-TDA, rows U1 ...) from the unrestricted reference (the open-shell response of Vxc on the device: "
                         "DFT_FxcPrepareSpinPol / DFT_FxcApplySpinPol); --triplets stays refused")
+    p.add_argument("--open-shell-meta", action="store_true",
+                   help="with --spin and a meta-GGA (TPSS, TPSSh, expressions with tpss_x / tpss_c): run the unrestricted loop on the "
+                        "spin-resolved meta-GGA sweep (DFT_ComputeXCMetaSpin: tau and the tau term of the potential per spin); without "
+                        "the flag --spin refuses a meta-GGA.  Response, excitations and gradients of such a state are not built")
     p.add_argument("--open-shell-gradient", action="store_true",
                    help="with --spin: let --gradient and --optimize run on the unrestricted state (gradients.nuclear_gradient_uks: the XC "
                         "term per spin by DFT_ComputeXCGradientSpin, the two-electron term with the spin density, DFT_Grad2eSpin under "
@@ -191,12 +195,21 @@ def main(argv=None):
     if args.charge_forces_out and not args.point_charges:
         p.error("--charge-forces-out needs --point-charges")
     fn = functionals.resolve(args.functional)
+    if args.open_shell_meta and args.spin is None:
+        p.error("--open-shell-meta goes with --spin N (the closed shell of a meta-GGA needs no flag)")
+    if args.open_shell_meta and not fn.needs_tau:
+        p.error(f"--open-shell-meta is for a meta-GGA: {args.functional} carries no tpss_x / tpss_c weight; --spin N alone runs it")
     if fn.needs_tau:
-        for flag, on in (("--spin", args.spin is not None), ("--polarizability", args.polarizability), ("--excitations", args.excitations),
-                         ("--gradient", args.gradient), ("--optimize", args.optimize)):
+        if args.spin is not None and not args.open_shell_meta:
+            p.error(f"--spin: {args.functional} is a meta-GGA and the unrestricted loop is not built for meta-GGA functionals unless "
+                    "--open-shell-meta asks for the spin-resolved meta-GGA sweep (DFT_ComputeXCMetaSpin)")
+        for flag, on in (("--polarizability", args.polarizability), ("--excitations", args.excitations),
+                         ("--gradient", args.gradient), ("--optimize", args.optimize),
+                         ("--open-shell-response", args.open_shell_response), ("--open-shell-gradient", args.open_shell_gradient),
+                         ("--grid-response", args.grid_response)):
             if on:
                 p.error(f"{flag}: {args.functional} is a meta-GGA and this feature is not built for meta-GGA functionals "
-                        "(only the closed-shell ground state is)")
+                        "(only the ground state is: closed shell, and open shell with --spin N --open-shell-meta)")
     if args.xc_occ is None:
         args.xc_occ = None if fn.needs_tau else 1
     if args.polarizability and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident"):
@@ -305,7 +318,7 @@ def main(argv=None):
         print(e)
         sys.exit(1)
     print(f"GPU Init Time: {backend.init_time:.4f}s" + (f"  ({world} ranks: grid block + Cholesky-vector slice per GPU)" if world > 1 else ""))
-    res = scf.run_uks(inp, backend, args.functional) if uks else scf.run_scf(inp, backend, args.functional)
+    res = scf.run_uks(inp, backend, args.functional, meta=args.open_shell_meta) if uks else scf.run_scf(inp, backend, args.functional)
     eig_stats = dict(backend.occ_solver.stats) if backend.occ_solver is not None else None   # of THIS run (the second one below adds to the counters)
     other = None
     if args.both_quirks and fn.uses_quirks:   # only VWN5 and PBE-c have two forms (B3LYP's four components are derivative-correct: one answer)

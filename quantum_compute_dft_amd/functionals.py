@@ -122,12 +122,18 @@ def _parse(spec):
     return Functional(spec.strip(), weights, c_hf, None)
 
 
-def refuse_meta(spec, what):
-    """ValueError when `spec` is a meta-GGA: `what` (a sentence's subject) is built for LDA / GGA / hybrid functionals only."""
+# What the open-shell refusals add: the open-shell ground state of a meta-GGA is built, but opt-in
+OPEN_SHELL_META_HINT = ("the open-shell ground state is too, but only on request: scf.run_uks(..., meta=True) / the driver's "
+                        "--open-shell-meta, which go through HipBackend.uks_meta_parts (DFT_ComputeXCMetaSpin)")
+
+
+def refuse_meta(spec, what, hint=None):
+    """ValueError when `spec` is a meta-GGA: `what` (a sentence's subject) is built for LDA / GGA / hybrid functionals only.
+    `hint`: a sentence added for the callers that have an opt-in way round."""
     f = resolve(spec)
     if f.needs_tau:
         raise ValueError(f"{what}: {f.name!r} is a meta-GGA (it reads the kinetic-energy density tau) and this feature is not built "
-                         "for meta-GGA functionals -- only the closed-shell ground state is")
+                         "for meta-GGA functionals -- only the closed-shell ground state is" + (f"; {hint}" if hint else ""))
 
 
 def resolve(spec):

@@ -1,4 +1,4 @@
-"""Host counterparts of the meta-GGA sweep (DFT_ComputeTau / DFT_ComputeXCMeta): the bodies of csrc/xc_meta_functionals.hpp
+"""Host counterparts of the meta-GGA sweeps (DFT_ComputeTau / DFT_ComputeXCMeta and their open-shell forms): the bodies of csrc/xc_meta_functionals.hpp
 through lib/libqcfxc.so (g++), the contractions in numpy.  The CPU tests hold these against a 60-digit reference, exact
 constraints and finite differences; the GPU tests hold the device against these.
 
@@ -24,6 +24,8 @@ def _load():
         L.qc_meta_point.argtypes = [dp, dp, ctypes.c_longlong, dp, dp, dp, dp, dp]
         L.qc_meta_energy_spin.restype = ctypes.c_int
         L.qc_meta_energy_spin.argtypes = [dp, dp, ctypes.c_longlong] + [dp] * 9
+        L.qc_meta_point_spin.restype = ctypes.c_int
+        L.qc_meta_point_spin.argtypes = [dp, dp, ctypes.c_longlong] + [dp] * 8
         _lib = L
     return _lib
 
@@ -105,3 +107,41 @@ def xc_meta_host(functional, dm, ao, weights, ao_grad):
     v = q.T @ ao
     v += sum((p["ct"][:, None] * ao_grad[k]).T @ ao_grad[k] for k in range(3))
     return exc, v
+
+
+# ---- open shell (DFT_ComputeTauSpin / DFT_ComputeXCMetaSpin) -------------------------------------------------------------------
+def point_meta_spin_host(functional, ra, rb, grad_a, grad_b, ta, tb, weights):
+    """One point per entry at any polarisation, xc::meta_spin_point as the device's pointwise kernel runs it.  ra, rb, ta, tb,
+    weights (n,), grad_a, grad_b (n, 3).  Returns a dict: e (energy per volume, no weight), coef_a / coef_b (4, n) = c0..c3 of
+    each spin (c0_s = w e_rho_s, c_s,k = 2 w (2 e_sigma_ss grad rho_s + e_sigma_ab grad rho_s')_k), ct_a / ct_b = w e_tau_s / 2,
+    and de (7, n), the bare derivatives by (ra, rb, saa, sab, sbb, ta, tb).  A spin channel below the density cut-off is
+    absent: exact zeros in everything of its own."""
+    w8, w2 = _weights(functional)
+    ra = _c(np.atleast_1d(ra))
+    n = ra.size
+    rb, ta, tb, weights = (_c(x, (n,)) for x in (rb, ta, tb, weights))
+    grad_a, grad_b = _c(grad_a, (n, 3)), _c(grad_b, (n, 3))
+    out = np.zeros((18, n))
+    if _load().qc_meta_point_spin(_p(w8), _p(w2), n, _p(ra), _p(rb), _p(grad_a), _p(grad_b), _p(ta), _p(tb), _p(weights), _p(out)) != 0:
+        raise ValueError("point_meta_spin_host: bad arguments")
+    return {"e": out[0], "coef_a": out[1:5], "coef_b": out[5:9], "ct_a": out[9], "ct_b": out[10], "de": out[11:18]}
+
+
+def density_spin_host(dm_a, dm_b, ao, ao_grad):
+    """(rho_a, grad_a, tau_a, rho_b, grad_b, tau_b): density_host of each spin's matrix."""
+    return density_host(dm_a, ao, ao_grad) + density_host(dm_b, ao, ao_grad)
+
+
+def xc_meta_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad):
+    """(Exc, V_a, V_b) of DFT_ComputeXCMetaSpin in numpy: V_s = AO^T diag(c0_s) AO + sum_k (c_s,k AO)^T (d_k AO) (one-sided) +
+    sum_k (d_k AO)^T diag(ct_s) (d_k AO); (V_s + V_s^T)/2 is dExc/dD_s."""
+    ra, ga, ta, rb, gb, tb = density_spin_host(dm_a, dm_b, ao, ao_grad)
+    p = point_meta_spin_host(functional, ra, rb, ga, gb, ta, tb, weights)
+    exc = float(np.sum(weights * p["e"]))
+    out = []
+    for c, ct in ((p["coef_a"], p["ct_a"]), (p["coef_b"], p["ct_b"])):
+        q = c[0][:, None] * ao + sum(c[1 + k][:, None] * ao_grad[k] for k in range(3))
+        v = q.T @ ao
+        v += sum((ct[:, None] * ao_grad[k]).T @ ao_grad[k] for k in range(3))
+        out.append(v)
+    return exc, out[0], out[1]

@@ -596,8 +596,13 @@ class HipBackend:
 
 
     # ---- open-shell (scf.run_uks): one rank, resident AO planes, the host loop -----------------------------------------
-    def _uks_check(self):
-        functionals.refuse_meta(self.solver.functional, "open-shell DFT (UKS)")
+    def _uks_check(self, meta=False, hint=None):
+        if meta:
+            if not self.meta:
+                raise ValueError(f"uks_meta_parts is the open-shell sweep of a meta-GGA (DFT_ComputeXCMetaSpin): {self.functional} is not "
+                                 "one (it carries no tpss_x / tpss_c weight); its open-shell sweep is uks_parts")
+        else:
+            functionals.refuse_meta(self.solver.functional, "open-shell DFT (UKS)", hint)
         if self.world > 1:
             raise ValueError("open-shell DFT (UKS) runs on one rank: the grid of this backend is sharded over several")
         if self.ao_mode != "resident":
@@ -613,7 +618,17 @@ class HipBackend:
         cocc_s^T, as numpy arrays: J of the total density and K of each spin through the closed-shell entries (Cholesky
         vectors: one DFT_ComputeJKFactorized call for J with the total dm alone, one per spin for K with that spin's dm and
         orbitals), Exc and the two potentials from DFT_ComputeXCSpin.  A spin without electrons has K = 0."""
-        self._uks_check()
+        self._uks_check(hint=functionals.OPEN_SHELL_META_HINT)
+        return self._uks_parts(dm_a, dm_b, cocc_a, cocc_b, want_k, self.solver.compute_xc_spin)
+
+    def uks_meta_parts(self, dm_a, dm_b, cocc_a, cocc_b, want_k):
+        """uks_parts for a meta-GGA (run_uks(meta=True)): the same return tuple, J and K taken exactly as there, Exc and the
+        two potentials (tau terms included) from DFT_ComputeXCMetaSpin.  Refuses what uks_parts refuses but the meta-GGA, and
+        a functional that is not one."""
+        self._uks_check(meta=True)
+        return self._uks_parts(dm_a, dm_b, cocc_a, cocc_b, want_k, self.solver.compute_xc_meta_spin)
+
+    def _uks_parts(self, dm_a, dm_b, cocc_a, cocc_b, want_k, sweep):
         t, n = self.torch, self.nao
         d_s = [self._dev(dm_a), self._dev(dm_b)]
         d_c = [self._dev(cocc_a), self._dev(cocc_b)]
@@ -633,7 +648,7 @@ class HipBackend:
             for k in range(2):
                 if want_k and d_c[k].shape[1]:
                     self.solver.compute_exchange(n, self.d_eri, d_s[k], o[1 + k])
-        exc = self.solver.compute_xc_spin(self.ngrid, n, d_s[0], d_s[1], self.d_ao, self.d_w, o[3], o[4], self.d_gr)
+        exc = sweep(self.ngrid, n, d_s[0], d_s[1], self.d_ao, self.d_w, o[3], o[4], self.d_gr)
         t.cuda.synchronize()
         h = o.cpu().numpy()
         return h[0], (h[1] if want_k else None), (h[2] if want_k else None), exc, h[3], h[4]
@@ -1341,7 +1356,7 @@ def spin_square(S, cocc_a, cocc_b):
     return sz * (sz + 1.0) + nb - float(np.sum((cocc_a.T @ S @ cocc_b) ** 2))
 
 
-def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, log=print):
+def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, log=print, meta=False):
     """Unrestricted Kohn-Sham loop on the host, for inp.nalpha / inp.nbeta electrons of the two spins (inputs.build(...,
     charge, spin)).  `backend.uks_parts(dm_a, dm_b, cocc_a, cocc_b, want_k)` supplies (J[D_a + D_b], K[D_a], K[D_b], Exc,
     V_a, V_b) with the potentials in the library's convention (HipBackend on the device; the tests have a numpy one).
@@ -1355,8 +1370,21 @@ def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, 
     both errors, their Gram matrix is the sum), eigh(F_s, S) per spin, energies from the NEW densities with J / K / Exc of
     the old ones, convergence |dE| < conv_e and |dD_a| + |dD_b| (Frobenius) < conv_dm.  With nalpha = nbeta the loop is
     run_scf's host loop term by term.  Returns run_scf's fields with dm the total density, and dm_a, dm_b, mo_energy_a,
-    mo_energy_b, mo_coeff_a, mo_coeff_b, s_squared (spin_square), nalpha, nbeta, uks = True."""
-    functionals.refuse_meta(functional, "open-shell DFT (run_uks)")
+    mo_energy_b, mo_coeff_a, mo_coeff_b, s_squared (spin_square), nalpha, nbeta, uks = True.
+
+    meta=True (the driver's --open-shell-meta): the functional is a meta-GGA and the parts come from
+    `backend.uks_meta_parts`, same arguments and same tuple (HipBackend: DFT_ComputeXCMetaSpin); the loop itself is the
+    same.  Without it a meta-GGA is refused, as before the open-shell meta-GGA sweep existed."""
+    if meta:
+        if not functionals.resolve(functional).needs_tau:
+            raise ValueError(f"run_uks(meta=True) is for a meta-GGA: {functional} carries no tpss_x / tpss_c weight; run it with meta=False")
+        if not callable(getattr(backend, "uks_meta_parts", None)):
+            raise ValueError(f"run_uks(meta=True): the backend ({type(backend).__name__}) has no uks_meta_parts, the open-shell meta-GGA "
+                             "sweep (HipBackend has one; the tests have a numpy one)")
+        parts = backend.uks_meta_parts
+    else:
+        functionals.refuse_meta(functional, "open-shell DFT (run_uks)", functionals.OPEN_SHELL_META_HINT)
+        parts = backend.uks_parts
     from .hostinfo import blas_threads
     Hcore, S = inp.Hcore, inp.S
     na = int(getattr(inp, "nalpha", None) if getattr(inp, "nalpha", None) is not None else inp.nocc)
@@ -1373,7 +1401,7 @@ def run_uks(inp, backend, functional, max_cycle=200, conv_e=1e-8, conv_dm=1e-6, 
         c_hf, want_k = led.c_hf, led.want_k
         for _ in range(max_cycle):
             t_it = led.start()
-            J, Ka, Kb, E_xc, Va, Vb = backend.uks_parts(dm[0], dm[1], cocc[0], cocc[1], want_k)
+            J, Ka, Kb, E_xc, Va, Vb = parts(dm[0], dm[1], cocc[0], cocc[1], want_k)
             led.xc_times.append(time.time() - t_it); led.jk_times.append(0.0)        # one bracket: the parts are not timed apart here
             F = [Hcore + J + 0.5 * (V + V.T) - (c_hf * K if K is not None else 0.0) for V, K in ((Va, Ka), (Vb, Kb))]
             Fx = diis.update(S2, _blockdiag(dm[0], dm[1]), _blockdiag(F[0], F[1]))

@@ -189,6 +189,16 @@ class DFTSolverWrapper:
         L.DFT_ComputeXCMeta.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, _u64, _u64, _u64, _u64, _u64, dp]
         L.DFT_ComputeXCMeta.restype = ctypes.c_int
 
+    def _declare_meta_spin(self):
+        L, dp = self.lib, ctypes.POINTER(ctypes.c_double)
+        # added without a change of DFT_GetVersion: a library without them cannot serve an open-shell meta-GGA
+        if not hasattr(L, "DFT_ComputeXCMetaSpin") or not hasattr(L, "DFT_ComputeTauSpin"):
+            raise RuntimeError("the library has no DFT_ComputeTauSpin / DFT_ComputeXCMetaSpin: it cannot run an open-shell meta-GGA")
+        L.DFT_ComputeTauSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + [_u64] * 5
+        L.DFT_ComputeTauSpin.restype = ctypes.c_int
+        L.DFT_ComputeXCMetaSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + [_u64] * 7 + [dp]
+        L.DFT_ComputeXCMetaSpin.restype = ctypes.c_int
+
     def __del__(self):
         if hasattr(self, "lib") and hasattr(self, "solver") and self.solver:
             self.lib.DFT_DestroySolver(self.solver)
@@ -375,6 +385,27 @@ class DFTSolverWrapper:
         exc = ctypes.c_double(float("nan"))
         self.lib.DFT_ComputeXCMeta(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)), _u64(_ptr(d_weights)),
                                    _u64(_ptr(d_ao_grad)), _u64(_ptr(d_vxc)), ctypes.byref(exc))
+        self._check()
+        return exc.value
+
+    def compute_tau_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao_grad, d_tau_a, d_tau_b):
+        """tau of each spin's matrix into d_tau_a / d_tau_b (DFT_ComputeTauSpin): one two-spin kernel with option
+        tau_spin_fused = 1, compute_tau's kernel once per spin with 0; any solver; asynchronous on the solver's stream."""
+        self._declare_meta_spin()
+        rc = self.lib.DFT_ComputeTauSpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)), _u64(_ptr(d_ao_grad)),
+                                         _u64(_ptr(d_tau_a)), _u64(_ptr(d_tau_b)))
+        self._check()
+        return rc
+
+    def compute_xc_meta_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_weights, d_vxc_a, d_vxc_b, d_ao_grad=None):
+        """Exc of a meta-GGA solver at the spin density matrices d_dm_a / d_dm_b (DFT_ComputeXCMetaSpin); d_vxc_s receives V_s in
+        the mix solver's one-sided convention plus the whole tau term of spin s: (V_s + V_s^T)/2 is dExc/dD_s.  Refusals as
+        compute_xc_meta's (RuntimeError).  Synchronous."""
+        self._declare_meta_spin()
+        exc = ctypes.c_double(float("nan"))
+        self.lib.DFT_ComputeXCMetaSpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)), _u64(_ptr(d_ao)),
+                                       _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_vxc_a)), _u64(_ptr(d_vxc_b)),
+                                       ctypes.byref(exc))
         self._check()
         return exc.value
 
