@@ -6,14 +6,24 @@
  * planes [1:4]): contracted real-spherical Gaussian AO values and their
  * Cartesian gradients on a set of points.
  *
- * PARITY UNPINNED: the arithmetic lives in third-party PySCF/libcint (version
- * not pinned by the reference, README.md:31-36; not installed here) and the
- * reference holds no test vector at this boundary.  This file restates the
- * published conventions: phi = R(r) * S_lm, R = sum_p c_p
- * exp(-a_p r^2) with normalised coefficients supplied by the caller, S_lm real
- * solid harmonics ordered p: x,y,z; d: xy,yz,z2,xz,x2-y2; f: m=-3..3.
- * It is checked offline by tests/test_ao_oracle.py (finite differences,
- * quadrature normalisation, orthogonality of the 2l+1 components).
+ * This file restates the published conventions: phi = R(r)
+ * * S_lm, R = sum_p c_p exp(-a_p r^2) with normalised coefficients supplied by
+ * the caller, S_lm real solid harmonics ordered p: x,y,z; d: xy,yz,z2,xz,x2-y2;
+ * f: m=-3..3.
+ *
+ * WHAT IS HELD: the mathematics.  Values and gradients (and the Hessians of
+ * gradients.ao_hessian_host, the kernels k_eval_ao / k_eval_ao_hess) agree
+ * element by element with oracle/ao_reference.py -- mpmath, 100 digits, fitted
+ * harmonics, normalisation from its own self-overlaps, Cartesian-monomial
+ * derivatives: none of the constants typed below -- to a few units of 2^-53
+ * times the magnitude of the sums (tests/ao_reference_cases.py,
+ * tests/test_ao_reference_cpu.py, tests/test_gpu_ao_reference.py;
+ * profiles/ao_reference_parity.txt).  tests/test_ao_oracle.py adds finite
+ * differences, quadrature normalisation and orthogonality.
+ * WHAT IS NOT: the convention against PySCF itself.  The arithmetic lives in
+ * third-party PySCF/libcint (version not pinned by the reference,
+ * README.md:31-36; not installed here) and the reference holds no test vector
+ * at this boundary; component order and normalisation are the published ones.
  */
 #include <math.h>
 #include <stddef.h>

@@ -1,4 +1,6 @@
-"""Offline pins for the AO oracle (parity with PySCF itself is unpinned: PySCF is
+"""Offline pins for the AO oracle: quadrature norms, orthogonality, finite differences, ordering.  The mathematics of its
+values and gradients is held element by element to the 100-digit reference (oracle/ao_reference.py,
+tests/test_ao_reference_cpu.py); the convention against PySCF itself is still only the published one (PySCF is
 third-party, not installed, and the reference holds no vector at this boundary)."""
 import numpy as np
 import pytest
