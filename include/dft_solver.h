@@ -487,6 +487,34 @@ int DFT_ComputeXCGradientSpin(XCSolver *solver, long long ngrid, int nao, unsign
                               unsigned long long d_ao_grad_ptr, unsigned long long d_ao_hess_ptr,
                               unsigned long long d_out_ptr);
 
+/* XC part of the nuclear gradient of a meta-GGA (csrc/xc_grad_meta.hip), a solver made by DFT_CreateSolverMeta.
+ * DFT_ComputeXCGradientMeta: d_out (nao, 3) receives G of the Exc DFT_ComputeXCMeta returns, under DFT_ComputeXCGradient's
+ * column replacement (dm and the weights fixed; tau changes through its gradient planes).  With ct = w e_tau / 2 as
+ * "xc_points_meta" writes it and Y_k = (d_k AO) Ds,
+ *     G[mu, x] = G_gga[mu, x; c0..c3] - 2 sum_g ct sum_k hess_xk[g, mu] Y_k[g, mu]:
+ * the six Hessian planes, no third derivatives.  Order of work on the solver's stream: the sweep's density kernels with
+ * the sweep's choices into planes of this entry, the padded symmetric matrix, "tau" on it, "xc_points_meta", then the
+ * contraction in the form option "xcg_meta_fused" chooses -- 1 (the default: the faster form as measured,
+ * profiles/xc_gradient_meta_time.txt): k_xc_grad_meta<true>, one pass over the ten planes with five products per load of
+ * the matrix; 0: k_xc_grad on c0..c3 and k_xc_grad_meta<false> (the tau term) into two slab sets
+ * and one fixed-order sum over both, the plain form the fused kernel is tested against.  With both meta weights zero the
+ * tau stage and the tau term are left out and the result is DFT_ComputeXCGradient's of the same mix.  No atomics: a call
+ * is bitwise reproducible.  Asynchronous, never the one-kernel plan, never a recorded graph; its planes, tau, coefficients,
+ * padded matrix and slabs are its own, so later DFT_ComputeXCMeta / DFT_ComputeXCGradient / DFT_ComputeXC results and
+ * prepared DFT_Fxc* tables are bit for bit what they were.
+ * DFT_ComputeXCEnergyDensityMeta: d_e_out (ngrid) receives the energy per volume of the meta point WITHOUT the weight
+ * (density stage and "tau" as above, then "xc_edens_meta"): sum_g w_g e_g is DFT_ComputeXCMeta's Exc.
+ * Both return 0, or -1 with DFT_GetLastError, before any launch: a solver without meta weights, a null pointer (ao_grad
+ * and ao_hess included), bad sizes, "quirks" = 1 with vwn5_c / pbe_c, and a basis whose tiles do not fit 160 KB of LDS
+ * (nao above 1216 in the fused form, above 1328 in the plain one, whose k_xc_grad tiles are the wider). */
+int DFT_ComputeXCGradientMeta(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr,
+                              unsigned long long d_ao_ptr, unsigned long long d_weights_ptr,
+                              unsigned long long d_ao_grad_ptr, unsigned long long d_ao_hess_ptr,
+                              unsigned long long d_out_ptr);
+int DFT_ComputeXCEnergyDensityMeta(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr,
+                                   unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
+                                   unsigned long long d_e_out_ptr);
+
 /* Grid response of the nuclear gradient (csrc/becke.hip): what the derivative at fixed points and weights leaves out.
  * With Exc = sum_g w0_g cell_g e_g -- w0 the atomic radial x angular weight, cell_g = P_own(r_g) / sum_C P_C(r_g) the
  * Becke cell function of the point's own atom (three smoothing iterations, radius adjustment a_CD clipped to +-1/2),
@@ -696,8 +724,10 @@ void DFT_ScfTailClose(void *handle);
  * the host waits for -- same contract, no launch; taken only where a probe at DFT_CreateSolver found the runtime
  * performs the operation, else the kernel stays; -1 = auto, default: the kernel, which measured 1-2 us faster per call.
  * A recorded graph always ends with the kernel), "xcg_spin_fused" (DFT_ComputeXCGradientSpin: 1, default = both spins in
- * one k_xc_grad launch; 0 = k_xc_grad once per spin, the plain form the tests hold it to).  Returns 0 if the key is
- * known. */
+ * one k_xc_grad launch; 0 = k_xc_grad once per spin, the plain form the tests hold it to), "xcg_meta_fused"
+ * (DFT_ComputeXCGradientMeta: 1, default = k_xc_grad_meta<true>, one pass, the faster form as measured; 0 = k_xc_grad and
+ * the tau-term kernel, the plain form the tests hold it to).
+ * Returns 0 if the key is known. */
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
 
 /* Read-back of "publish", "vxc_fringe", "fuse_finish", "strict_sync", "spin_wait", "graph", "tiny", "sweep_order", "path",

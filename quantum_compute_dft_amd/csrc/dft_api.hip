@@ -37,6 +37,7 @@
 #include "becke_launch.hpp"
 #include "xc_meta_launch.hpp"
 #include "xc_meta_spin_launch.hpp"
+#include "xc_grad_meta_launch.hpp"
 
 using namespace qcdft;
 
@@ -216,6 +217,15 @@ struct XCSolver {
     // (xc_meta_spin.hip; 0.80 x / 0.61 x of the two launches at 143 556 x 114 / 60 000 x 494: profiles/meta_spin_time.txt); 0:
     // k_tau once per spin, what the tests hold the two-spin kernel to
     int tau_spin_fused = 1;
+    // DFT_ComputeXCGradientMeta / DFT_ComputeXCEnergyDensityMeta: a set of their own again -- the planes, tau, ct, the padded
+    // matrix k_tau and the contraction read, and the slabs (two sets with "xcg_meta_fused" = 0).  No recorded sweep, no prepared
+    // response table and no other entry holds or reads any of them.
+    Planes xcgm;
+    DevBuf xcgm_tau, xcgm_ct, xcgm_dp, xcgm_slabs;
+    // The contraction of DFT_ComputeXCGradientMeta.  1 (default): k_xc_grad_meta<true>, everything in one pass over the ten planes
+    // (0.90 x / 0.80 x of the plain form at 143 556 x 114 / 60 000 x 494, TPSS: profiles/xc_gradient_meta_time.txt); 0: k_xc_grad on
+    // c0..c3 and k_xc_grad_meta<false> (the tau term) into two slab sets and one sum, what the tests hold the fused kernel to
+    int xcg_meta_fused = 1;
     std::vector<double> becke_tab_host;
     std::string last_error;
     std::vector<Timing> timings;
@@ -1674,6 +1684,122 @@ bool xc_energy_density(XCSolver *s, int nspin, long ngrid, int nao, const double
                                           gga ? b.grad.d() : nullptr, e_out), "spin energy density launch");
 }
 
+// What DFT_ComputeXCGradientMeta and DFT_ComputeXCEnergyDensityMeta refuse first, before anything touches the device (so that
+// the refusals can be told apart from "no usable HIP device"): `needs` names the pointers, ptrs_ok says that none is null.
+bool xcg_meta_check(XCSolver *s, const char *who, long ngrid, int nao, bool ptrs_ok, const char *needs)
+{
+    s->last_error.clear();
+    s->n_timed = 0;
+    if (!s->is_meta) {
+        set_error(s, "%s needs a solver made by DFT_CreateSolverMeta (this one carries no meta-GGA weights)", who);
+        return false;
+    }
+    if (!ptrs_ok) {
+        set_error(s, "%s needs %s: a pointer is null", who, needs);
+        return false;
+    }
+    if (ngrid <= 0 || nao <= 0) {
+        set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao);
+        return false;
+    }
+    return spin_quirks_ok(s, who);
+}
+
+bool reserve_xcg_meta(XCSolver *s, const SweepPlan &P, long ngrid, long nxb, bool coef)
+{
+    const size_t ng = sizeof(double) * (size_t)ngrid;
+    return reserve_planes(s, s->xcgm, false, ngrid, coef ? WS_ALL : (WS_GRAD | WS_SIGMA), nxb) &&
+           reserve(s, s->xcgm_dp, sizeof(double) * (size_t)P.NP * P.NP, "hipMalloc(meta gradient Dsym)", false) &&
+           reserve(s, s->xcgm_tau, ng, "hipMalloc(meta gradient tau)", false) &&
+           (!coef || reserve(s, s->xcgm_ct, ng, "hipMalloc(meta gradient tau coefficient)", false));
+}
+
+// The density stage the two entries share: the sweep's density kernels with the sweep's choices into the planes of these
+// entries, the padded symmetric matrix (the wave-specialised density kernel symmetrises dm itself, so k_sym_dm runs here on
+// that plan; the other plans leave it behind), and k_tau on that matrix -- compute_tau's launch without its second
+// symmetrisation.  With both meta weights zero tau is not formed: the planes of zeros the pointwise kernels read.
+bool xcg_meta_density(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm, const double *ao, const double *ao_grad)
+{
+    const Planes &p = s->xcgm;
+    double *Dp = s->xcgm_dp.d(), *tau = s->xcgm_tau.d();
+    launch_density(s, P, ngrid, nao, dm, ao, Dp, p.rho.d(), p.grad.d(), p.sigma.d());
+    if (P.fast) {
+        ScopedTimer t(s, "sym_dm");
+        hipLaunchKernelGGL(k_sym_dm, dim3(P.NP / 16, P.NP / 16), dim3(16, 16), 0, s->stream, nao, P.NP, dm, Dp);
+    }
+    if (!hip_ok(s, hipGetLastError(), "meta gradient: density launch")) return false;
+    if (!s->meta_active) return hip_ok(s, hipMemsetAsync(tau, 0, sizeof(double) * (size_t)ngrid, s->stream), "clear tau");
+    const TauPlan tp = tau_plan(s->num_cu, ngrid, nao);   // tp.NP = P.NP
+    ScopedTimer t(s, "tau");
+    return hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, Dp, tau), "tau launch");
+}
+
+// XC part of the nuclear gradient of a meta-GGA (DFT_ComputeXCGradientMeta): the density stage above, k_xc_points_meta, and
+// the contraction of c0..c3, ct with the ten planes -- k_xc_grad_meta<true> (option "xcg_meta_fused" = 1) or k_xc_grad on
+// c0..c3 and k_xc_grad_meta<false> into two slab sets with one sum (0, the plain form).  With both meta weights zero the
+// tau stage and the tau term are left out: k_xc_grad alone, as DFT_ComputeXCGradient runs it.  Never the one-kernel plan,
+// never recorded; asynchronous on the solver's stream.
+bool xc_gradient_meta(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *w, const double *ao_grad,
+                      const double *ao_hess, double *out)
+{
+    const char *who = "DFT_ComputeXCGradientMeta";
+    if (!xcg_meta_check(s, who, ngrid, nao, dm && ao && w && ao_grad && ao_hess && out,
+                        "dm, the AO values, the grid weights, ao_grad (tau is made of the gradient planes), ao_hess and the output"))
+        return false;
+    const bool tau_term = s->meta_active, fused = tau_term && s->xcg_meta_fused != 0;
+    const XcGradPlan G = xc_grad_plan(s->num_cu, true, 1, ngrid, nao);            // k_xc_grad<true, 1>: the plain form, zero meta weights
+    const XcGradPlan T = xc_grad_meta_plan(s->num_cu, fused, ngrid, nao);         // k_xc_grad_meta<fused>
+    const size_t lds = fused ? T.lds : tau_term ? std::max(G.lds, T.lds) : G.lds;
+    if (lds > 160 * 1024) {
+        set_error(s, "%s: nao=%d needs %zu bytes of LDS per workgroup, above the 160 KB a workgroup has", who, nao, lds);
+        return false;
+    }
+    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    const long nxb = meta_points_blocks(ngrid);
+    const int nslab = fused ? T.nwg : tau_term ? G.nwg + T.nwg : G.nwg;
+    if (!reserve_xcg_meta(s, P, ngrid, nxb, true) ||
+        !reserve(s, s->xcgm_slabs, sizeof(double) * (size_t)nslab * 3 * nao, "hipMalloc(meta gradient slabs)", false))
+        return false;
+    if (!xcg_meta_density(s, P, ngrid, nao, dm, ao, ao_grad)) return false;
+    const Planes &p = s->xcgm;
+    const double *Dp = s->xcgm_dp.d();
+    double *ct = s->xcgm_ct.d(), *slabs = s->xcgm_slabs.d();
+    {
+        ScopedTimer t(s, "xc_points_meta");
+        if (!hip_ok(s, launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, p.rho.d(), p.grad.d(), s->xcgm_tau.d(), w, p.coef.d(), ct,
+                                             p.partial.d()), "meta pointwise launch"))
+            return false;
+    }
+    if (!tau_term) {
+        ScopedTimer t(s, "xc_grad");
+        return hip_ok(s, launch_xc_grad(s->stream, G, true, 1.0, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), Dp, slabs, out), "XC gradient launch");
+    }
+    if (fused) {
+        ScopedTimer t(s, "xc_grad_meta");
+        return hip_ok(s, launch_xc_grad_meta_fused(s->stream, T, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), ct, Dp, slabs, out),
+                      "meta XC gradient launch (fused)");
+    }
+    ScopedTimer t(s, "xc_grad + xc_grad_tau");
+    return hip_ok(s, launch_xc_grad_meta_plain(s->stream, G, T, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), ct, Dp, slabs, out),
+                  "meta XC gradient launch");
+}
+
+// The energy per volume of a meta-GGA at the density and tau of dm (DFT_ComputeXCEnergyDensityMeta): the density stage above,
+// then the body of k_xc_points_meta at unit weight (k_xc_edens_meta).  Asynchronous on the solver's stream.
+bool xc_energy_density_meta(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *ao_grad, double *e_out)
+{
+    if (!xcg_meta_check(s, "DFT_ComputeXCEnergyDensityMeta", ngrid, nao, dm && ao && ao_grad && e_out,
+                        "dm, the AO values, ao_grad (tau is made of the gradient planes) and the output"))
+        return false;
+    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
+    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
+    if (!reserve_xcg_meta(s, P, ngrid, 0, false) || !xcg_meta_density(s, P, ngrid, nao, dm, ao, ao_grad)) return false;
+    ScopedTimer t(s, "xc_edens_meta");
+    return hip_ok(s, launch_xc_edens_meta(s->stream, s->mix.c, s->meta, ngrid, s->xcgm.rho.d(), s->xcgm.grad.d(), s->xcgm_tau.d(), e_out),
+                  "meta energy density launch");
+}
+
 // sum_g f_g D_B cell_g (DFT_BeckeWeightGradient, becke.hip).  The tables a_CD = clamp((rad_D / rad_C - rad_C / rad_D) / 4,
 // +-1/2) with rad = sqrt(radius) + 1e-200 (grid_gen.becke_weights, operation for operation) and 1 / R_CD are made here and
 // kept on the device until the atoms change; only then does the call wait for the stream.
@@ -2384,6 +2510,25 @@ int DFT_ComputeXCEnergyDensitySpin(XCSolver *s, long long ngrid, int nao, unsign
                              (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
 }
 
+int DFT_ComputeXCGradientMeta(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
+                              unsigned long long d_weights, unsigned long long d_ao_grad, unsigned long long d_ao_hess,
+                              unsigned long long d_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_gradient_meta(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_weights,
+                            (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+}
+
+int DFT_ComputeXCEnergyDensityMeta(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
+                                   unsigned long long d_ao_grad, unsigned long long d_e_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    return xc_energy_density_meta(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_ao_grad,
+                                  (double *)d_e_out) ? 0 : -1;
+}
+
 int DFT_BeckeWeightGradient(XCSolver *s, long long ngrid, int natm, const double *atom_xyz, const double *atom_radius,
                             unsigned long long d_coords, unsigned long long d_owner, unsigned long long d_f,
                             unsigned long long d_cell_out, unsigned long long d_out)
@@ -2458,6 +2603,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "ksplit")) { s->ksplit = value > 0 ? (int)value : 0; return 0; }
     if (!strcmp(key, "xcg_spin_fused")) { s->xcg_spin_fused = value != 0.0; return 0; }
     if (!strcmp(key, "meta_fused")) { s->meta_fused = value != 0.0; return 0; }
+    if (!strcmp(key, "xcg_meta_fused")) { s->xcg_meta_fused = value != 0.0; return 0; }
     if (!strcmp(key, "tau_spin_fused")) { s->tau_spin_fused = value != 0.0; return 0; }
     return -1;
 }
@@ -2486,6 +2632,7 @@ double DFT_GetOption(XCSolver *s, const char *key)
     if (!strcmp(key, "used_dm_factor")) return s->used_dm_factor;                              // the last synchronous call swept with the factor of dm
     if (!strcmp(key, "xcg_spin_fused")) return s->xcg_spin_fused;
     if (!strcmp(key, "meta_fused")) return s->meta_fused;
+    if (!strcmp(key, "xcg_meta_fused")) return s->xcg_meta_fused;
     if (!strcmp(key, "tau_spin_fused")) return s->tau_spin_fused;
     if (!strcmp(key, "dm_factor_rank")) return s->dm_factor_rank;                              // the rank its attempt found (0: rejected / not attempted)
     return unknown;

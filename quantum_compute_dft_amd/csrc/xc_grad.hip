@@ -356,6 +356,17 @@ hipError_t launch_xc_grad_reduce(hipStream_t st, int nao, int nslab, const doubl
 
 } // namespace
 
+hipError_t launch_xc_grad_gga_slabs(hipStream_t st, const XcGradPlan &p, double fac, long ngrid, int nao, const double *ao,
+                                    const double *ao_grad, const double *hess, const double *coef, const double *Dp, double *slabs)
+{
+    return launch_xc_grad_slabs<1>(st, p, true, fac, ngrid, nao, ao, ao_grad, hess, coef, nullptr, Dp, nullptr, slabs);
+}
+
+hipError_t launch_xc_grad_sum(hipStream_t st, int nao, int nslab, const double *slabs, double *out)
+{
+    return launch_xc_grad_reduce(st, nao, nslab, slabs, out);
+}
+
 hipError_t launch_xc_grad(hipStream_t st, const XcGradPlan &p, bool gga, double fac, long ngrid, int nao, const double *ao,
                           const double *ao_grad, const double *hess, const double *coef, const double *Dp, double *slabs,
                           double *out)

@@ -45,4 +45,10 @@ hipError_t launch_xc_grad_spin_fused(hipStream_t st, const XcGradPlan &p, bool g
                                      const double *ao_grad, const double *hess, const double *coef_a, const double *coef_b,
                                      const double *Dp_a, const double *Dp_b, double *slabs, double *out);
 
+// The two halves of launch_xc_grad on their own, for a caller that sums slab sets of several kernels (xc_grad_meta.hip):
+// k_xc_grad<true, 1> into p.nwg slabs of (nao, 3) without the sum, and the fixed-order sum of `nslab` slabs into out.
+hipError_t launch_xc_grad_gga_slabs(hipStream_t st, const XcGradPlan &p, double fac, long ngrid, int nao, const double *ao,
+                                    const double *ao_grad, const double *hess, const double *coef, const double *Dp, double *slabs);
+hipError_t launch_xc_grad_sum(hipStream_t st, int nao, int nslab, const double *slabs, double *out);
+
 } // namespace qcdft

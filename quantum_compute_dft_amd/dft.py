@@ -163,6 +163,11 @@ def build_parser():
                    help="with --spin and a meta-GGA (TPSS, TPSSh, expressions with tpss_x / tpss_c): run the unrestricted loop on the "
                         "spin-resolved meta-GGA sweep (DFT_ComputeXCMetaSpin: tau and the tau term of the potential per spin); without "
                         "the flag --spin refuses a meta-GGA.  Response, excitations and gradients of such a state are not built")
+    p.add_argument("--meta-gradient", action="store_true",
+                   help="with --gradient / --optimize and a meta-GGA (TPSS, TPSSh, expressions with tpss_x / tpss_c): the closed-shell "
+                        "nuclear gradient with the tau term of the XC force (gradients.nuclear_gradient(meta=True), "
+                        "DFT_ComputeXCGradientMeta), in every step of --optimize too; --grid-response and --grad2e are honoured.  "
+                        "Without the flag --gradient / --optimize refuse a meta-GGA.  Closed shell only: not with --spin")
     p.add_argument("--open-shell-gradient", action="store_true",
                    help="with --spin: let --gradient and --optimize run on the unrestricted state (gradients.nuclear_gradient_uks: the XC "
                         "term per spin by DFT_ComputeXCGradientSpin, the two-electron term with the spin density, DFT_Grad2eSpin under "
@@ -199,6 +204,15 @@ def main(argv=None):
         p.error("--open-shell-meta goes with --spin N (the closed shell of a meta-GGA needs no flag)")
     if args.open_shell_meta and not fn.needs_tau:
         p.error(f"--open-shell-meta is for a meta-GGA: {args.functional} carries no tpss_x / tpss_c weight; --spin N alone runs it")
+    if args.meta_gradient:
+        if not fn.needs_tau:
+            p.error(f"--meta-gradient is for a meta-GGA: {args.functional} carries no tpss_x / tpss_c weight; --gradient / --optimize "
+                    "alone run it")
+        if args.spin is not None:
+            p.error("--meta-gradient is the closed-shell gradient of a meta-GGA: the gradient of an unrestricted (--spin) meta-GGA "
+                    "state is not built")
+        if not (args.gradient or args.optimize):
+            p.error("--meta-gradient goes with --gradient or --optimize")
     if fn.needs_tau:
         if args.spin is not None and not args.open_shell_meta:
             p.error(f"--spin: {args.functional} is a meta-GGA and the unrestricted loop is not built for meta-GGA functionals unless "
@@ -207,9 +221,12 @@ def main(argv=None):
                          ("--gradient", args.gradient), ("--optimize", args.optimize),
                          ("--open-shell-response", args.open_shell_response), ("--open-shell-gradient", args.open_shell_gradient),
                          ("--grid-response", args.grid_response)):
-            if on:
+            by_request = flag in ("--gradient", "--optimize", "--grid-response")
+            if on and not (by_request and args.meta_gradient):
                 p.error(f"{flag}: {args.functional} is a meta-GGA and this feature is not built for meta-GGA functionals "
-                        "(only the ground state is: closed shell, and open shell with --spin N --open-shell-meta)")
+                        "(only the ground state is: closed shell, and open shell with --spin N --open-shell-meta)" +
+                        ("; the closed-shell nuclear gradient is too, but only on request: add --meta-gradient "
+                         "(DFT_ComputeXCGradientMeta)" if by_request else ""))
     if args.xc_occ is None:
         args.xc_occ = None if fn.needs_tau else 1
     if args.polarizability and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.ao != "resident"):
@@ -414,6 +431,8 @@ def main(argv=None):
         from . import gradients, optimize
         nuclear_gradient = gradients.nuclear_gradient_uks if uks else gradients.nuclear_gradient
         grad_kw = dict(two_electron=args.grad2e, grid_response=True) if args.grid_response else dict(two_electron=args.grad2e)
+        if args.meta_gradient:
+            grad_kw["meta"] = True
         grad, grad_terms = nuclear_gradient(inp, res, backend, args.functional, **grad_kw)
         print_gradient(inp.symbols, grad, args.grid_response)
     if args.optimize and res["converged"]:

@@ -126,6 +126,10 @@ def _parse(spec):
 OPEN_SHELL_META_HINT = ("the open-shell ground state is too, but only on request: scf.run_uks(..., meta=True) / the driver's "
                         "--open-shell-meta, which go through HipBackend.uks_meta_parts (DFT_ComputeXCMetaSpin)")
 
+# What the closed-shell gradient refusals add: the nuclear gradient of a meta-GGA is built, but opt-in
+META_GRADIENT_HINT = ("the closed-shell nuclear gradient is too, but only on request: gradients.nuclear_gradient(..., meta=True) / the "
+                      "driver's --meta-gradient, which go through HipBackend.xc_gradient_meta (DFT_ComputeXCGradientMeta)")
+
 
 def refuse_meta(spec, what, hint=None):
     """ValueError when `spec` is a meta-GGA: `what` (a sentence's subject) is built for LDA / GGA / hybrid functionals only.

@@ -11,7 +11,8 @@ with W = 2 C_occ diag(eps_occ) C_occ^T = D F D / 2.  `nuclear_gradient` assemble
 DFT_EvalAOHess / DFT_ComputeXCGradient (csrc/xc_grad.hip; solver.eval_ao_hess / compute_xc_gradient,
 scf.HipBackend.xc_gradient) below.  `nuclear_gradient_uks` is the same assembly for a run_uks state: W = sum_s D_s F_s D_s, the
 two-electron term with the spin density beside the total one (integrals.grad2e_spin / DFT_Grad2eSpin), the XC term once
-per spin (xc_gradient_spin_host / DFT_ComputeXCGradientSpin).
+per spin (xc_gradient_spin_host / DFT_ComputeXCGradientSpin).  `nuclear_gradient(meta=True)` is the closed-shell assembly for a
+meta-GGA: the same terms, the XC part with the tau term (xc_gradient_meta_host / DFT_ComputeXCGradientMeta, csrc/xc_grad_meta.hip).
 
     G[mu, x] = d/dt Exc  when, in column mu only,  ao[:, mu] -> ao[:, mu] - t ao_grad[x][:, mu]  and
                ao_grad[k][:, mu] -> ao_grad[k][:, mu] - t ao_hess[xk][:, mu]          (dm and the weights fixed)
@@ -194,6 +195,49 @@ def xc_energy_density_spin_host(functional, dm_a, dm_b, ao, ao_grad=None):
     return response.point_spin_host(functional, ra, rb, ga, gb)[0]
 
 
+def _meta_planes(who, *planes):
+    """The planes of a meta host entry as C-ordered float64; none may be missing (tau is made of the gradient planes, its
+    derivative by a centre of the Hessian planes)."""
+    if any(x is None for x in planes):
+        raise ValueError(f"{who}: ao_grad{' and ao_hess are' if len(planes) == 3 else ' is'} needed for a meta-GGA")
+    return [np.ascontiguousarray(x, dtype=np.float64) for x in planes]
+
+
+def xc_gradient_meta_host(functional, dm, ao, weights, ao_grad, ao_hess, tau_term=True):
+    """G (nao, 3) of DFT_ComputeXCGradientMeta from AO planes in numpy: the derivative of metagga.xc_meta_host's Exc under the
+    column replacement above.  tau = 1/2 sum_k (d_k AO) Ds (d_k AO) moves through its gradient planes alone, so with the meta
+    point's coefficients (metagga.point_meta_host: c0..c3 one-sided, ct = w e_tau / 2) and Y_k = ao_grad[k] Ds
+
+        G[mu, x] = G_gga[mu, x; c0..c3] - 2 sum_g ct sum_k ao_hess[xk][g, mu] Y_k[g, mu],
+
+    G_gga xc_gradient_host's formula at fac = 1.  The six Hessian planes, no third derivatives.  A functional without a
+    meta weight has ct = 0 and gets xc_gradient_host's G of the same mix at quirks 0.  tau_term=False leaves the second sum
+    out (for the tests: what a force without the tau term misses)."""
+    from . import metagga
+    ao, gr, hs = _meta_planes("xc_gradient_meta_host", ao, ao_grad, ao_hess)
+    dm = np.asarray(dm, dtype=np.float64)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    rho, g, tau = metagga.density_host(dm, ao, gr)
+    p = metagga.point_meta_host(functional, rho, g, tau, w)
+    G = _xc_contract(1.0, True, ao, gr, hs, [(dm, p["coef"])])
+    ct = p["ct"]
+    if tau_term and np.any(ct != 0.0):
+        ds = 0.5 * (dm + dm.T)
+        Y = [gr[k] @ ds for k in range(3)]
+        for x in range(3):
+            G[:, x] -= 2.0 * np.einsum("g,gm->m", ct, sum(hs[HESS_INDEX[x][k]] * Y[k] for k in range(3)))
+    return G
+
+
+def xc_energy_density_meta_host(functional, dm, ao, ao_grad):
+    """e_g (ngrid,) of DFT_ComputeXCEnergyDensityMeta from AO planes in numpy: the energy per volume of the meta point at the
+    density and tau of dm, without the weight (metagga.point_meta_host with unit weights)."""
+    from . import metagga
+    ao, gr = _meta_planes("xc_energy_density_meta_host", ao, ao_grad)
+    rho, g, tau = metagga.density_host(np.asarray(dm, dtype=np.float64), ao, gr)
+    return metagga.point_meta_host(functional, rho, g, tau, np.ones(ao.shape[0]))["e"]
+
+
 def _grid_of(grids, symbols, atom_xyz, who):
     """(owner, atomic weights, charges) of a grid that says which atom each point moves with, checked against the atoms."""
     own, w0 = getattr(grids, "atom_index", None), getattr(grids, "atomic_weights", None)
@@ -256,6 +300,18 @@ def xc_grid_response_spin_host(functional, dm_a, dm_b, shells, grids, symbols, a
         lambda r: xc_energy_density_spin_host(f, dm_a, dm_b, ao[r], gr[:, r] if gga else None), "xc_grid_response_spin_host")
 
 
+def xc_grid_response_meta_host(functional, dm, shells, grids, symbols, atom_xyz, planes=None):
+    """xc_grid_response_host for a meta-GGA: xc_gradient_meta_host per atom block and xc_energy_density_meta_host's e.  The
+    formula is the same: it holds for any e built from AO values and derivatives at the point."""
+    f = functionals.resolve(functional)
+    ao, gr, hs = planes if planes is not None else ao_planes_host(shells, grids.coords)
+    w = np.asarray(grids.weights, dtype=np.float64)
+    return _xc_grid_response_host(
+        grids, symbols, atom_xyz,
+        lambda r: xc_gradient_meta_host(f, dm, ao[r], w[r], gr[:, r], hs[:, r]),
+        lambda r: xc_energy_density_meta_host(f, dm, ao[r], gr[:, r]), "xc_grid_response_meta_host")
+
+
 def sum_over_atoms(shells, G):
     """(natm, 3): G (nao, 3) summed over the functions each atom owns (the shell-to-atom map of the shell table)."""
     G = np.asarray(G, dtype=np.float64)
@@ -302,11 +358,15 @@ def _fock(inp, backend, f, dm):
     """The Fock matrix of dm from the backend's parts: ground_state_parts (scf.HipBackend, response.HostResponse) or the
     set_dm / jk / xc interface of the host SCF backends."""
     want_k = f.c_hf != 0.0
-    if hasattr(backend, "ground_state_parts"):
+    if f.needs_tau and hasattr(backend, "ground_state_parts_meta"):
+        parts = backend.ground_state_parts_meta
+    else:
+        parts = getattr(backend, "ground_state_parts", None)
+    if parts is not None:
         from scipy.linalg import eigh
         e0, C0 = eigh(inp.S @ dm @ inp.S, inp.S)
         cocc = np.ascontiguousarray(C0[:, ::-1][:, :inp.nocc] * np.sqrt(np.maximum(e0[::-1][:inp.nocc], 0.0)))
-        J, K, V = backend.ground_state_parts(dm, cocc, want_k)
+        J, K, V = parts(dm, cocc, want_k)
     else:
         backend.set_dm(dm)
         J, K = backend.jk(want_k)
@@ -317,9 +377,11 @@ def _fock(inp, backend, f, dm):
 _QUIRKY = ("vwn5_c", "pbe_c")
 
 
-def _checked(who, inp, backend, functional, two_electron, device_method, wrong_result, grid_response):
+def _checked(who, inp, backend, functional, two_electron, device_method, wrong_result, grid_response, meta=False, hint=None):
     """The refusals nuclear_gradient and nuclear_gradient_uks share; (the functional, its weight vector).  device_method: what
-    the backend needs for two_electron="device"; wrong_result: why the SCF result is the other assembly's (None: it is not)."""
+    the backend needs for two_electron="device"; wrong_result: why the SCF result is the other assembly's (None: it is not).
+    meta: the caller asked for the meta-GGA assembly -- a meta-GGA is then what is wanted (the weight vector carries the two
+    meta weights behind the eight) and anything else is refused; hint: what the meta-GGA refusal adds."""
     if two_electron not in ("host", "device"):
         raise ValueError(f"{who}: two_electron must be 'host' or 'device', not {two_electron!r}")
     if two_electron == "device" and not hasattr(backend, device_method):
@@ -334,7 +396,12 @@ def _checked(who, inp, backend, functional, two_electron, device_method, wrong_r
     if grid_response:
         _grid_of(inp.grids, inp.symbols, inp.atom_xyz, who)          # refuses a grid that does not say which atom a point moves with
     f = functionals.resolve(functional if functional is not None else backend.functional)
-    functionals.refuse_meta(f, who)
+    if meta:
+        if not f.needs_tau:
+            raise ValueError(f"{who}(meta=True) is the gradient of a meta-GGA (DFT_ComputeXCGradientMeta): {f.name} is not one (it "
+                             "carries no tpss_x / tpss_c weight); its gradient is meta=False's")
+        return f, f.weight_vector() + f.meta_weight_vector()
+    functionals.refuse_meta(f, who, hint)
     return f, f.weight_vector()
 
 
@@ -342,13 +409,16 @@ def _has_quirky(wv):
     return any(wv[functionals.COMPONENTS.index(c)] != 0.0 for c in _QUIRKY)
 
 
-def _assemble(inp, backend, f, wv, dm, W, two_electron, mats, host_extra, grid_response):
+def _assemble(inp, backend, f, wv, dm, W, two_electron, mats, host_extra, grid_response, meta=False):
     """(g, terms) from the total density dm, W and the finished two-electron term.  mats: the matrices of the XC term --
     (dm,) for the closed shell (backend.xc_gradient / xc_grid_response, xc_gradient_host / xc_grid_response_host otherwise),
-    (dm_a, dm_b) for an open-shell state (the *_spin ones); host_extra: what the host functions take behind them (quirks)."""
+    (dm_a, dm_b) for an open-shell state (the *_spin ones); host_extra: what the host functions take behind them (quirks).
+    meta: the closed shell of a meta-GGA (the *_meta ones; wv then carries the meta weights too, so that TPSS, whose eight are
+    all zero, keeps its XC term)."""
     spin = len(mats) == 2
-    sfx = "_spin" if spin else ""
-    host_gradient, host_grid = (xc_gradient_spin_host, xc_grid_response_spin_host) if spin else (xc_gradient_host, xc_grid_response_host)
+    sfx = "_spin" if spin else "_meta" if meta else ""
+    host_gradient, host_grid = (xc_gradient_spin_host, xc_grid_response_spin_host) if spin else \
+                               (xc_gradient_meta_host, xc_grid_response_meta_host) if meta else (xc_gradient_host, xc_grid_response_host)
     sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
     z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
     g1 = integrals.grad1e(sh, xyz, z, dm, W)
@@ -381,7 +451,7 @@ def _assemble(inp, backend, f, wv, dm, W, two_electron, mats, host_extra, grid_r
     return sum(terms.values()), terms
 
 
-def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two_electron="host", grid_response=False):
+def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two_electron="host", grid_response=False, meta=False):
     """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged closed-shell state `scf_result` (scf.run_scf) and its
     breakdown {"one_electron", "two_electron", "xc", "nuclear", "external"}, each (natm, 3).  By default the derivative at FIXED
     quadrature points and weights: the Becke-weight derivatives and the motion of the points with their atoms are not
@@ -395,10 +465,16 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
     made and contracted on the device, csrc/grad2e.hip); every other term is the same either way.  `grid_response` = True adds
     the term "xc_grid": the motion of the quadrature points with their atoms and the derivatives of the Becke weights
     (backend.xc_grid_response on scf.HipBackend, xc_grid_response_host otherwise); g is then the derivative of the energy as the
-    grid follows the atoms, and sums to zero over the atoms.  Without it everything is as it was."""
+    grid follows the atoms, and sums to zero over the atoms.  Without it everything is as it was.
+    `meta` = True (the driver's --meta-gradient): the functional is a meta-GGA and the XC terms carry the tau term --
+    backend.xc_gradient_meta / xc_grid_response_meta (scf.HipBackend: DFT_ComputeXCGradientMeta) where the backend has them,
+    xc_gradient_meta_host / xc_grid_response_meta_host on planes evaluated here otherwise; the Fock matrix of W comes from
+    backend.ground_state_parts_meta where there is one.  The other terms do not depend on the functional.  A functional
+    that is no meta-GGA is refused; without the keyword a meta-GGA is refused, as before this assembly existed."""
     wrong = ("nuclear_gradient: an unrestricted (UKS) result has no analytic gradient here: the assembly is closed-shell "
              "(nuclear_gradient_uks assembles the open-shell one)") if scf_result.get("uks") else None
-    f, wv = _checked("nuclear_gradient", inp, backend, functional, two_electron, "grad2e", wrong, grid_response)
+    f, wv = _checked("nuclear_gradient", inp, backend, functional, two_electron, "grad2e", wrong, grid_response, meta,
+                     functionals.META_GRADIENT_HINT)
     if quirks is None:
         quirks = bool(getattr(backend, "quirks", getattr(backend, "q", True)))
     if quirks and _has_quirky(wv):
@@ -411,7 +487,7 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
     W = 0.5 * dm @ F @ dm
     W = 0.5 * (W + W.T)
     g2e = backend.grad2e(dm, f.c_hf) if two_electron == "device" else integrals.grad2e(inp.shells, dm, f.c_hf)
-    return _assemble(inp, backend, f, wv, dm, W, g2e, (dm,), (quirks,), grid_response)
+    return _assemble(inp, backend, f, wv, dm, W, g2e, (dm,), () if meta else (quirks,), grid_response, meta)
 
 
 def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron="host", grid_response=False):

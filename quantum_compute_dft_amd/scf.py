@@ -794,11 +794,13 @@ class HipBackend:
         return (lambda m, ao, w, out, gr, hs: grad(m, self.nao, *d, ao, w, out, gr, hs),
                 lambda m, ao, gr, e: dens(m, self.nao, *d, ao, e, gr))
 
-    def _xc_gradient_slices(self, slice_rows, entry, block=None, after=None):
-        """The slicing xc_gradient and xc_gradient_spin share: entry(m, ao, w, d_out, gr, hs) is the library call of a slice.
-        block = (lo, hi): the rows of the grid to sweep (default: all of it); after(lo, hi, ao, gr), when given, runs behind
-        the entry of every slice on the same planes (the grid response takes the energy density there)."""
-        functionals.refuse_meta(self.solver.functional, "the XC part of the nuclear gradient")
+    def _xc_gradient_slices(self, slice_rows, entry, block=None, after=None, refuse_meta=True):
+        """The slicing xc_gradient, xc_gradient_spin and xc_gradient_meta share: entry(m, ao, w, d_out, gr, hs) is the library
+        call of a slice.  block = (lo, hi): the rows of the grid to sweep (default: all of it); after(lo, hi, ao, gr), when
+        given, runs behind the entry of every slice on the same planes (the grid response takes the energy density there).
+        refuse_meta=False: the caller is the meta-GGA form (a meta solver always takes the Hessian planes)."""
+        if refuse_meta:
+            functionals.refuse_meta(self.solver.functional, "the XC part of the nuclear gradient", functionals.META_GRADIENT_HINT)
         if self.world > 1:
             raise ValueError("the XC gradient runs on one rank: the grid of this backend is sharded over several")
         if self.dm_factor:
@@ -859,9 +861,10 @@ class HipBackend:
         """xc_grid_response for an open-shell state: DFT_ComputeXCGradientSpin and DFT_ComputeXCEnergyDensitySpin per block."""
         return self._xc_grid_response(slice_rows, *self._xc_gradient_calls(dm_a, dm_b))
 
-    def _xc_grid_response(self, slice_rows, entry, edens):
+    def _xc_grid_response(self, slice_rows, entry, edens, refuse_meta=True):
         from . import basis, grid_gen
-        functionals.refuse_meta(self.solver.functional, "the grid response of the nuclear gradient")
+        if refuse_meta:
+            functionals.refuse_meta(self.solver.functional, "the grid response of the nuclear gradient", functionals.META_GRADIENT_HINT)
         if self.world > 1:
             raise ValueError("the grid response runs on one rank: the grid of this backend is sharded over several")
         if self.dm_factor:
@@ -889,7 +892,7 @@ class HipBackend:
 
         for lo, hi in zip(los, his):
             if hi > lo:
-                G = self._xc_gradient_slices(slice_rows, entry, block=(int(lo), int(hi)), after=after)
+                G = self._xc_gradient_slices(slice_rows, entry, block=(int(lo), int(hi)), after=after, refuse_meta=refuse_meta)
                 out[int(own[lo])] -= G.sum(axis=0)
         d_f = d_e[:self.ngrid] * t.as_tensor(w0, dtype=t.float64, device=self.dev)
         d_own = t.as_tensor(own.astype(np.int32), dtype=t.int32, device=self.dev)
@@ -899,6 +902,37 @@ class HipBackend:
         self.solver.becke_weight_gradient(self.ngrid, xyz, radii, self.d_coords, d_own, d_f, d_out)
         t.cuda.synchronize()
         return out + d_out.cpu().numpy()
+
+    # ---- nuclear gradient of a meta-GGA (gradients.nuclear_gradient(meta=True)): one rank, closed shell ----------------
+    def _meta_gradient_check(self, who):
+        if not self.meta:
+            raise ValueError(f"{who} is the gradient of a meta-GGA (DFT_ComputeXCGradientMeta): {self.functional} is not one (it "
+                             f"carries no tpss_x / tpss_c weight); its gradient is {who[:-5]}")
+
+    def _xc_gradient_meta_calls(self, dm):
+        """_xc_gradient_calls for a meta-GGA: DFT_ComputeXCGradientMeta and DFT_ComputeXCEnergyDensityMeta on the uploaded dm."""
+        d, s = self._dev(dm), self.solver
+        return (lambda m, ao, w, out, gr, hs: s.compute_xc_gradient_meta(m, self.nao, d, ao, w, out, gr, hs),
+                lambda m, ao, gr, e: s.compute_xc_energy_density_meta(m, self.nao, d, ao, e, gr))
+
+    def xc_gradient_meta(self, dm, slice_rows=None):
+        """xc_gradient for a meta-GGA: G (nao, 3) with the tau term (DFT_ComputeXCGradientMeta), summed over slices of the grid
+        exactly as xc_gradient does.  Refuses what xc_gradient refuses but the meta-GGA, and a functional that is not one."""
+        self._meta_gradient_check("xc_gradient_meta")
+        return self._xc_gradient_slices(slice_rows, self._xc_gradient_meta_calls(dm)[0], refuse_meta=False)
+
+    def xc_grid_response_meta(self, dm, slice_rows=None):
+        """xc_grid_response for a meta-GGA: DFT_ComputeXCGradientMeta and DFT_ComputeXCEnergyDensityMeta per block."""
+        self._meta_gradient_check("xc_grid_response_meta")
+        return self._xc_grid_response(slice_rows, *self._xc_gradient_meta_calls(dm), refuse_meta=False)
+
+    def ground_state_parts_meta(self, dm, cocc, want_k):
+        """ground_state_parts for a meta-GGA (the Fock matrix of W in the gradient): set_state and fock_parts, which sweep through
+        DFT_ComputeXCMeta.  ground_state_parts itself serves the response and keeps refusing a meta-GGA."""
+        self._meta_gradient_check("ground_state_parts_meta")
+        self.set_state(dm, cocc)
+        J, K, _, V, _, _ = self.fock_parts(want_k)
+        return J, K, V
 
     # ---- two-electron part of the nuclear gradient on the device (integrals.DeviceGrad2e): one rank ----------------
     def _grad2e_engine(self):

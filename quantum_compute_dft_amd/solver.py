@@ -487,6 +487,37 @@ class DFTSolverWrapper:
         self._check()
         return rc
 
+    def _declare_meta_gradient(self):
+        L = self.lib
+        # added without a change of DFT_GetVersion: a library without them cannot serve the gradient of a meta-GGA
+        if not hasattr(L, "DFT_ComputeXCGradientMeta") or not hasattr(L, "DFT_ComputeXCEnergyDensityMeta"):
+            raise RuntimeError("the library has no DFT_ComputeXCGradientMeta / DFT_ComputeXCEnergyDensityMeta: it cannot run the "
+                               "nuclear gradient of a meta-GGA")
+        L.DFT_ComputeXCGradientMeta.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + [_u64] * 6
+        L.DFT_ComputeXCGradientMeta.restype = ctypes.c_int
+        L.DFT_ComputeXCEnergyDensityMeta.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + [_u64] * 4
+        L.DFT_ComputeXCEnergyDensityMeta.restype = ctypes.c_int
+
+    def compute_xc_gradient_meta(self, ngrid, nao, d_dm, d_ao, d_weights, d_out, d_ao_grad=None, d_ao_hess=None):
+        """G (nao, 3) into d_out (DFT_ComputeXCGradientMeta): the derivative of compute_xc_meta's Exc by the centre of every
+        basis function at fixed points and weights, the tau term included (gradients.xc_gradient_meta_host is its host
+        counterpart); a solver with meta weights, d_ao_grad and d_ao_hess always.  Option xcg_meta_fused chooses the one-pass
+        kernel (1) or the plain form (0).  Asynchronous on the solver's stream."""
+        self._declare_meta_gradient()
+        rc = self.lib.DFT_ComputeXCGradientMeta(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
+                                                _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
+        self._check()
+        return rc
+
+    def compute_xc_energy_density_meta(self, ngrid, nao, d_dm, d_ao, d_e_out, d_ao_grad=None):
+        """e_g of a meta-GGA at the density and tau of d_dm into d_e_out (ngrid) without the weight
+        (DFT_ComputeXCEnergyDensityMeta): sum_g w_g e_g is compute_xc_meta's Exc.  Asynchronous on the solver's stream."""
+        self._declare_meta_gradient()
+        rc = self.lib.DFT_ComputeXCEnergyDensityMeta(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
+                                                     _u64(_ptr(d_ao_grad)), _u64(_ptr(d_e_out)))
+        self._check()
+        return rc
+
     def becke_weight_gradient(self, ngrid, atom_xyz, atom_radius, d_coords, d_owner, d_f, d_out, d_cell_out=None):
         """sum_g f_g D_B cell_g into d_out (natm, 3) (DFT_BeckeWeightGradient; grid_gen.becke_weight_gradient_host is its
         host counterpart): atom_xyz (natm, 3) and atom_radius (natm; grid_gen.bragg_radii_bohr) are host arrays, d_coords

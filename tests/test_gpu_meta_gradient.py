@@ -1,0 +1,390 @@
+"""DFT_ComputeXCGradientMeta / DFT_ComputeXCEnergyDensityMeta (csrc/xc_grad_meta.hip) against their host counterparts
+(gradients.xc_gradient_meta_host / xc_energy_density_meta_host), which tests/test_meta_gradient_cpu.py holds against finite
+differences of metagga.xc_meta_host's Exc.
+
+* Device against host: 2e-8 of max|G| (tests/test_gpu_xc_gradient.py's ERR_REL), for TPSS, TPSSh and a mix with one meta
+  component, in both forms of option xcg_meta_fused.  Shapes (tests/xc_gradient_reference.py's planes): (2085, 24),
+  (2085, 114) seven whole column tiles and two columns, a ragged last tile of rows, more tiles than one round of
+  workgroups; (1100, 130) past 128, nine column tiles: three rounds of the four waves; (37, 50) fewer than three tiles of
+  rows; (333, 50) with one orbital (z = 1 to rounding).  K chunks at 37 rows, the caps read from the header: the five-tile
+  cap of k_xc_grad_meta<true>, one column above it, three chunks with a ragged last one, and the same for the three-tile cap
+  of k_xc_grad_meta<false>.  path 1 and 2 (the validation density kernels, which leave the padded matrix themselves).
+* Fused against plain 1e-13 of max|G|; each form twice bitwise; two ragged grid slices against the whole 1e-12.
+* dm - 0.3 I (indefinite: points below the cut-off, z clamped, tau <= 0): finite, and the host's to the same 2e-8.
+* Zero meta weights against DFT_ComputeXCGradient of the same mix: 4e-14 of max|G| (the same kernel on coefficients of two
+  pointwise bodies that agree to rounding).
+* DFT_ComputeXCEnergyDensityMeta against the host 1e-12 of max|e|; sum w e against DFT_ComputeXCMeta's Exc 1e-12.
+* DFT_ComputeXCMeta, DFT_ComputeXCGradient and DFT_ComputeXC bitwise what they were before a call of the new entries.
+* The refusals, each with its sentence.
+* nuclear_gradient(meta=True) on HipBackend, TPSS, H2O/def2-SVP, against the host assembly from the same dm: 2e-8 of max|g|.
+* The driver: --optimize --meta-gradient --grid-response --grad2e device relaxes H2O/STO-3G TPSS, every step through the flag.
+
+With QCDFT_WRITE_PROFILES set the figures are recorded as "gpu ..." lines of meta_gradient_parity.txt in that directory.
+"""
+import ctypes
+import functools
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+import meta_gradient_reference as mg  # noqa: E402
+import quantum_compute_dft_amd as q  # noqa: E402
+from quantum_compute_dft_amd import functionals, gradients, inputs, metagga, scf  # noqa: E402
+
+ERR_REL = 2e-8
+_HEADER = open(os.path.join(os.path.dirname(q.__file__), "csrc", "xc_grad_meta_launch.hpp")).read()
+CAP5 = int(re.search(r"constexpr int XCGM_KC_MAX = (\d+);", _HEADER).group(1))
+CAP3 = int(re.search(r"constexpr int XCGT_KC_MAX = (\d+);", _HEADER).group(1))
+SHAPES = [(2085, 24), (2085, 114), (1100, 130), (37, 50), (333, 50, 1)]
+# at the cap: one chunk; one column above: two, the second a single tile; three chunks, the last ragged (2 cap + 40 -> 48 padded)
+CHUNK_SHAPES = [(37, n) for cap in (CAP5, CAP3) for n in (cap, cap + 1, 2 * cap + 40)]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return torch.device("cuda:0")
+
+
+def _solver(functional, quirks=0, **opts):
+    s = q.DFTSolverWrapper(q.build_library(), functional)
+    s.set_option("quirks", quirks)
+    for k, v in opts.items():
+        s.set_option(k, v)
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def _host_inputs(shape, shift=0.0):
+    """(dm, ao, ao_grad, w, ao_hess) of a shape; a third entry: dm of that many orbitals; shift: dm - shift I."""
+    dm, ao, gr, w, hs = mg.inputs(shape[0], shape[1])
+    if len(shape) == 3:
+        c = 0.7 * np.random.default_rng(5).standard_normal((shape[1], shape[2]))
+        dm = 2.0 * c @ c.T
+    if shift:
+        dm = dm - shift * np.eye(shape[1])
+    dm.setflags(write=False)
+    return dm, ao, gr, w, hs
+
+
+@functools.lru_cache(maxsize=None)
+def _host_gradient(functional, shape, shift=0.0):
+    dm, ao, gr, w, hs = _host_inputs(shape, shift)
+    G = gradients.xc_gradient_meta_host(functional, dm, ao, w, gr, hs)
+    G.setflags(write=False)
+    return G
+
+
+class Planes:
+    """The inputs of one shape on the device (copies: the cached host arrays are shared between tests)."""
+
+    def __init__(self, dev, shape, shift=0.0):
+        self.host = _host_inputs(shape, shift)
+        self.ngrid, self.nao, self.dev = shape[0], shape[1], dev
+        self.d_dm, self.d_ao, self.d_gr, self.d_w, self.d_hs = (torch.as_tensor(np.array(a), device=dev) for a in self.host)
+
+    def gradient(self, s, lo=0, hi=None, entry="compute_xc_gradient_meta"):
+        hi = self.ngrid if hi is None else hi
+        d_out = torch.full((self.nao, 3), 7.0, dtype=torch.float64, device=self.dev)
+        gr, hs = self.d_gr[:, lo:hi].contiguous(), self.d_hs[:, lo:hi].contiguous()
+        assert getattr(s, entry)(hi - lo, self.nao, self.d_dm, self.d_ao[lo:hi], self.d_w[lo:hi], d_out, gr, hs) == 0
+        torch.cuda.synchronize()
+        return d_out.cpu().numpy()
+
+    def edens(self, s):
+        d_e = torch.full((self.ngrid,), 7.0, dtype=torch.float64, device=self.dev)
+        assert s.compute_xc_energy_density_meta(self.ngrid, self.nao, self.d_dm, self.d_ao, d_e, self.d_gr) == 0
+        torch.cuda.synchronize()
+        return d_e.cpu().numpy()
+
+    def meta(self, s):
+        v = torch.full((self.nao, self.nao), 7.0, dtype=torch.float64, device=self.dev)
+        exc = s.compute_xc_meta(self.ngrid, self.nao, self.d_dm, self.d_ao, self.d_w, v, self.d_gr)
+        torch.cuda.synchronize()
+        return exc, v.cpu().numpy()
+
+    def closed(self, s):
+        v = torch.full((self.nao, self.nao), 7.0, dtype=torch.float64, device=self.dev)
+        exc = s.compute_xc(self.ngrid, self.nao, self.d_dm, self.d_ao, self.d_w, v, self.d_gr)
+        torch.cuda.synchronize()
+        return exc, v.cpu().numpy()
+
+
+def _check(label, G, ref, bound=ERR_REL):
+    scale = float(np.abs(ref).max())
+    err = float(np.abs(G - ref).max())
+    print(f"gpu {label}: max {scale:.3e}  err {err / scale:.2e}")
+    mg.record("gpu", label, None, err / scale)
+    assert np.all(np.isfinite(G)) and scale > 0.0, label
+    assert err <= bound * scale, (label, err / scale)
+
+
+# ---- 0. what the code before this feature cannot do ---------------------------------------------------------------------
+def test_the_entries_exist():
+    lib = q.load_library(q.build_library())
+    for name in ("DFT_ComputeXCGradientMeta", "DFT_ComputeXCEnergyDensityMeta"):
+        assert hasattr(lib, name), name
+    lib.DFT_GetVersion.restype = ctypes.c_int
+    assert lib.DFT_GetVersion() == 5
+    s = _solver("TPSS")
+    assert s.get_option("xcg_meta_fused") in (0.0, 1.0)
+
+
+# ---- a. device against host ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("functional", mg.FUNCTIONALS)
+@pytest.mark.parametrize("shape", SHAPES + CHUNK_SHAPES, ids=str)
+def test_gradient_matches_the_host(dev, shape, functional, fused):
+    p = Planes(dev, shape)
+    G = p.gradient(_solver(functional, xcg_meta_fused=fused))
+    _check(f"DFT_ComputeXCGradientMeta {functional} {shape} fused={fused}", G, _host_gradient(functional, shape))
+
+
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("path", [1, 2])
+@pytest.mark.parametrize("functional", mg.FUNCTIONALS)
+def test_validation_paths(dev, functional, path, fused):
+    shape = (2085, 24)
+    p = Planes(dev, shape)
+    G = p.gradient(_solver(functional, xcg_meta_fused=fused, path=path))
+    _check(f"DFT_ComputeXCGradientMeta {functional} {shape} fused={fused} path={path}", G, _host_gradient(functional, shape))
+
+
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("shift", [0.3, 2.0])
+@pytest.mark.parametrize("functional", mg.FUNCTIONALS)
+def test_an_indefinite_matrix_is_served(dev, functional, shift, fused):
+    """dm - 0.3 I: negative densities (below the cut-off: exact zeros) and z > 1 (clamped).  These planes have no point with
+    tau <= 0 at that shift; dm - 2 I has about a hundred, beside a quarter of the grid below the cut-off."""
+    shape = (2085, 24)
+    dm, ao, gr, w, hs = _host_inputs(shape, shift)
+    rho, g, tau = metagga.density_host(dm, ao, gr)
+    live = rho > 1e-12
+    assert (~live).any() and live.sum() > 1000                                       # the inputs are what the case is about
+    assert (np.einsum("gk,gk->g", g, g)[live & (tau > 0)] > (8.0 * rho * tau)[live & (tau > 0)]).any()
+    assert (tau[live] <= 0.0).any() == (shift == 2.0)
+    p = Planes(dev, shape, shift)
+    G = p.gradient(_solver(functional, xcg_meta_fused=fused))
+    _check(f"DFT_ComputeXCGradientMeta {functional} {shape} dm - {shift} I fused={fused}", G, _host_gradient(functional, shape, shift))
+
+
+# ---- b. the two forms, reproducibility, slices --------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(2085, 114), (1100, 130), (37, 2 * CAP5 + 40)], ids=str)
+def test_fused_against_plain_bitwise_repeats_and_slices(dev, shape):
+    p = Planes(dev, shape)
+    G = {}
+    for fused in (0, 1):
+        s = _solver("TPSSh", xcg_meta_fused=fused)
+        G[fused] = p.gradient(s)
+        assert np.array_equal(G[fused], p.gradient(s)), fused
+        cut = min(16 * 41 + 3, shape[0] - 5)      # not a multiple of the row tile: both slices end ragged
+        two = p.gradient(s, 0, cut) + p.gradient(s, cut, shape[0])
+        err = float(np.abs(two - G[fused]).max() / np.abs(G[fused]).max())
+        print(f"gpu two slices against the whole grid {shape} fused={fused}: {err:.2e}")
+        mg.record("gpu", f"two slices against the whole grid TPSSh {shape} fused={fused}", None, err)
+        assert err <= 1e-12
+    err = float(np.abs(G[1] - G[0]).max() / np.abs(G[0]).max())
+    print(f"gpu fused against plain {shape}: {err:.2e}")
+    mg.record("gpu", f"fused against plain TPSSh {shape}", None, err)
+    assert err <= 1e-13
+
+
+# ---- c. zero meta weights -----------------------------------------------------------------------------------------------
+def _zero_meta_solver(mix):
+    """(wrapper, raw handle): a DFT_CreateSolverMeta solver with the mix's eight weights and zero meta weights."""
+    f = functionals.resolve(mix)
+    z = _solver(mix)
+    lib = z.lib
+    lib.DFT_CreateSolverMeta.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+    lib.DFT_CreateSolverMeta.restype = ctypes.c_void_p
+    w8 = f.weight_vector()
+    h = lib.DFT_CreateSolverMeta((ctypes.c_double * 8)(*w8), 8, (ctypes.c_double * 2)(0.0, 0.0), 2)
+    assert h
+    lib.DFT_DestroySolver(ctypes.c_void_p(z.solver))
+    z.solver = h
+    z.set_option("quirks", 0)
+    return z
+
+
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("mix", ["PBE0", "BLYP"])
+@pytest.mark.parametrize("shape", [(2085, 24), (2085, 114), (1100, 130)], ids=str)
+def test_zero_meta_weights_give_the_mix(dev, shape, mix, fused):
+    p = Planes(dev, shape)
+    z = _zero_meta_solver(mix)
+    z.set_option("xcg_meta_fused", fused)
+    G = p.gradient(z)
+    G0 = p.gradient(_solver(mix), entry="compute_xc_gradient")
+    _check(f"zero meta weights {mix} {shape} fused={fused} against DFT_ComputeXCGradient", G, G0, 4e-14)
+    # ... and the sweep and the GGA gradient of that very solver are bit for bit what they were before the meta entries ran
+    e0, v0 = p.closed(z)
+    g0 = p.gradient(z, entry="compute_xc_gradient")
+    p.gradient(z); p.edens(z)
+    e1, v1 = p.closed(z)
+    assert e0 == e1 and np.array_equal(v0, v1)
+    assert np.array_equal(g0, p.gradient(z, entry="compute_xc_gradient"))
+
+
+# ---- d. the energy density ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("functional", mg.FUNCTIONALS)
+@pytest.mark.parametrize("shape", [(2085, 24), (2085, 114), (1100, 130), (333, 50, 1)], ids=str)
+def test_energy_density(dev, shape, functional):
+    p = Planes(dev, shape)
+    s = _solver(functional)
+    dm, ao, gr, w, _ = p.host
+    e = p.edens(s)
+    _check(f"DFT_ComputeXCEnergyDensityMeta {functional} {shape}", e, gradients.xc_energy_density_meta_host(functional, dm, ao, gr), 1e-12)
+    exc = p.meta(s)[0]
+    err = abs(float(np.sum(w * e)) - exc) / abs(exc)
+    print(f"gpu sum w e against DFT_ComputeXCMeta's Exc {functional} {shape}: {err:.2e}")
+    mg.record("gpu", f"sum w e against DFT_ComputeXCMeta's Exc {functional} {shape}", None, err, "Exc")
+    assert err <= 1e-12
+
+
+# ---- e. nothing else is disturbed ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [0, 1])
+@pytest.mark.parametrize("shape", [(2085, 24), (2085, 114), (1100, 130)], ids=str)
+def test_the_other_entries_are_left_as_they_were(dev, shape, fused):
+    p = Planes(dev, shape)
+    m, g = _solver("TPSS", xcg_meta_fused=fused), _solver("GGA")
+    e0, v0 = p.meta(m)
+    c0, g0 = p.closed(g), p.gradient(g, entry="compute_xc_gradient")
+    G = p.gradient(m)
+    e = p.edens(m)
+    assert np.all(np.isfinite(G)) and np.all(np.isfinite(e))
+    e1, v1 = p.meta(m)
+    c1, g1 = p.closed(g), p.gradient(g, entry="compute_xc_gradient")
+    assert e0 == e1 and np.array_equal(v0, v1)
+    assert c0[0] == c1[0] and np.array_equal(c0[1], c1[1]) and np.array_equal(g0, g1)
+    assert np.array_equal(G, p.gradient(m))        # ... and the sweep in between left the gradient entry's own buffers alone
+
+
+# ---- f. refusals --------------------------------------------------------------------------------------------------------
+def test_refusals(dev):
+    p = Planes(dev, (37, 50))
+    n, ng = p.nao, p.ngrid
+    out, e = torch.zeros((n, 3), dtype=torch.float64, device=dev), torch.zeros(ng, dtype=torch.float64, device=dev)
+    s = _solver("TPSS")
+    grad = lambda s, ng=ng, n=n, dm=p.d_dm, ao=p.d_ao, w=p.d_w, gr=p.d_gr, hs=p.d_hs, out=out: s.compute_xc_gradient_meta(ng, n, dm, ao, w, out, gr, hs)
+    dens = lambda s, ng=ng, n=n, dm=p.d_dm, ao=p.d_ao, gr=p.d_gr, e=e: s.compute_xc_energy_density_meta(ng, n, dm, ao, e, gr)
+    for entry, name in ((grad, "DFT_ComputeXCGradientMeta"), (dens, "DFT_ComputeXCEnergyDensityMeta")):
+        with pytest.raises(RuntimeError, match=f"{name} needs a solver made by DFT_CreateSolverMeta"):
+            entry(_solver("GGA"))
+        for kw in ({"dm": None}, {"ao": None}, {"gr": None}):
+            with pytest.raises(RuntimeError, match=f"{name} needs .*a pointer is null"):
+                entry(s, **kw)
+        for kw in ({"ng": 0}, {"n": 0}, {"ng": -3}):
+            with pytest.raises(RuntimeError, match="bad sizes"):
+                entry(s, **kw)
+        for functional in ("tpss_x + pbe_c", "tpss_x + tpss_c + 0.1*vwn5_c"):
+            with pytest.raises(RuntimeError, match="quirks = 1.*not the derivatives of their energies"):
+                entry(_solver(functional, quirks=1))
+        assert entry(_solver("tpss_x + pbe_c", quirks=0)) == 0
+        assert entry(_solver("TPSS", quirks=1)) == 0          # TPSS itself runs at either setting
+    for kw in ({"hs": None}, {"w": None}, {"out": None}):
+        with pytest.raises(RuntimeError, match="DFT_ComputeXCGradientMeta needs .*a pointer is null"):
+            grad(s, **kw)
+    with pytest.raises(RuntimeError, match="DFT_ComputeXCEnergyDensityMeta needs .*a pointer is null"):
+        dens(s, e=None)
+    for fused in (0, 1):                                        # refused before any launch: the planes are never read
+        s.set_option("xcg_meta_fused", fused)
+        with pytest.raises(RuntimeError, match="bytes of LDS per workgroup"):
+            grad(s, n=1700)
+    assert grad(s) == 0                                         # ... and the solver stays usable
+    torch.cuda.synchronize()
+    assert s.last_error() == ""
+
+
+# ---- g. end to end ------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def water():
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    dense = inputs.build("H2O", "def2-svp", 1, verbose=False)
+    be = scf.HipBackend(dense, "TPSS", quirks=False)
+    res = scf.run_scf(dense, be, "TPSS", log=None, conv_e=1e-10)
+    assert res["converged"]
+    return dense, be, res
+
+
+@functools.lru_cache(maxsize=None)
+def _host_assembly(dm_bytes, grid_response):
+    from meta_reference import MetaHostBackend
+    dense = inputs.build("H2O", "def2-svp", 1, verbose=False)
+    dm = np.frombuffer(dm_bytes).reshape(dense.shells.nao, -1)
+    return gradients.nuclear_gradient(dense, {"dm": dm}, MetaHostBackend(dense, "TPSS"), "TPSS", quirks=False, grid_response=grid_response, meta=True)
+
+
+@pytest.mark.parametrize("case", ["dense", "grid_response", "grad2e_device"])
+def test_nuclear_gradient_on_the_device(water, case):
+    dense, be, res = water
+    grid = case == "grid_response"
+    g, terms = gradients.nuclear_gradient(dense, res, be, grid_response=grid, two_electron="device" if case == "grad2e_device" else "host", meta=True)
+    ref, ref_terms = _host_assembly(np.ascontiguousarray(res["dm"]).tobytes(), grid)
+    scale = float(np.abs(ref).max())
+    for k in ref_terms:
+        print(f"gpu nuclear_gradient(meta=True) H2O/def2-SVP TPSS {case} {k}: {np.abs(terms[k] - ref_terms[k]).max() / scale:.2e}")
+    assert float(np.abs(terms["xc"]).max()) > 1e-3               # TPSS's eight weights are zero: the meta weights count
+    _check(f"nuclear_gradient(meta=True) H2O/def2-SVP TPSS {case}", g, ref)
+    net = float(np.abs(g.sum(axis=0)).max())
+    print(f"gpu nuclear_gradient(meta=True) H2O/def2-SVP TPSS {case}: net force {net:.2e}")
+    assert (net <= 1e-10) if grid else (net < 1e-3)
+
+
+def test_nuclear_gradient_on_cholesky_vectors():
+    """Cholesky vectors to 1e-10, so that their share of W stays below the bound."""
+    inp = inputs.build("H2O", "def2-svp", 1, verbose=False, eri_mode="cholesky", chol_tol=1e-10)
+    be = scf.HipBackend(inp, "TPSS", quirks=False)
+    res = scf.run_scf(inp, be, "TPSS", log=None, conv_e=1e-10)
+    assert res["converged"]
+    g, _ = gradients.nuclear_gradient(inp, res, be, meta=True)
+    ref, _ = _host_assembly(np.ascontiguousarray(res["dm"]).tobytes(), False)
+    _check("nuclear_gradient(meta=True) H2O/def2-SVP TPSS cholesky", g, ref)
+
+
+def test_backend_methods_and_refusals(water):
+    dense, be, res = water
+    dm = np.ascontiguousarray(res["dm"])
+    G = be.xc_gradient_meta(dm)
+    assert np.array_equal(G, be.xc_gradient_meta(dm)) and G.shape == (dense.shells.nao, 3)
+    G3 = be.xc_gradient_meta(dm, slice_rows=3000)
+    assert np.abs(G3 - G).max() <= 1e-12 * np.abs(G).max()
+    for f in (lambda: be.xc_gradient(dm), lambda: be.xc_grid_response(dm), lambda: be.ground_state_parts(dm, dm[:, :5], False),
+              lambda: gradients.nuclear_gradient(dense, res, be)):
+        with pytest.raises(ValueError, match="meta-GGA.*not built"):
+            f()
+    with pytest.raises(ValueError, match="meta=True.*--meta-gradient"):
+        gradients.nuclear_gradient(dense, res, be)
+    pbe = scf.HipBackend(dense, "PBE0", quirks=False)
+    for name in ("xc_gradient_meta", "xc_grid_response_meta"):
+        with pytest.raises(ValueError, match="is not one"):
+            getattr(pbe, name)(dm)
+    with pytest.raises(ValueError, match="is not one"):
+        gradients.nuclear_gradient(dense, res, pbe, meta=True)
+
+
+def test_driver_relaxes_water_with_the_flag(tmp_path):
+    """--optimize --meta-gradient --grid-response --grad2e device, TPSS H2O/STO-3G at grid level 1: every step honours the flags,
+    the record has the fields of the closed-shell run."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "run.json"
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    cmd = [sys.executable, "-m", "quantum_compute_dft_amd.dft", "TPSS", "H2O", "--basis", "sto-3g", "--grid-level", "1", "--optimize",
+           "--meta-gradient", "--grid-response", "--grad2e", "device", "--json", str(out)]
+    r = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    rec = json.loads(out.read_text().splitlines()[-1])
+    assert rec["grid_response"] is True and rec["grad2e_engine"] == "device" and not rec.get("uks")
+    assert set(rec["gradient_terms"]) == {"one_electron", "two_electron", "xc", "nuclear", "external", "xc_grid"}
+    assert np.abs(np.asarray(rec["gradient_terms"]["xc"])).max() > 1e-3
+    assert rec["opt_converged"] and 1 <= rec["opt_steps"] <= 30
+    assert rec["opt_energies"][-1] < rec["opt_energies"][0] - 1e-5
+    assert np.abs(rec["net_force"]).max() < 1e-9
+    assert "the derivative includes the grid" in r.stdout and (tmp_path / "H2O_opt.xyz").exists()
