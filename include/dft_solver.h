@@ -329,7 +329,16 @@ int DFT_FxcApplyKind(XCSolver *solver, long long ngrid, int nao, unsigned long l
  * occupied-orbital density step.  Synchronous: returns after Exc has been copied to *exc.  Prepared DFT_Fxc* tables and
  * later DFT_ComputeXC* calls are not disturbed.  Returns 0, or -1 with DFT_GetLastError (nothing aborts): a null
  * pointer, bad sizes, a null ao_grad on a gradient solver, the "quirks" case above.  Added without a change of
- * DFT_GetVersion (it stays 5): look the symbol up. */
+ * DFT_GetVersion (it stays 5): look the symbol up.
+ *
+ * DFT_ComputeXCSpin, DFT_ComputeXCMeta and DFT_ComputeXCMetaSpin are one synchronous sweep over the spins of the call
+ * (xc_sweep_sync, csrc/dft_api.hip).  Where a call has more than one fault, all three refuse in this order: the solver's
+ * kind (a meta entry on a solver without meta weights; DFT_ComputeXCSpin on one with a non-zero meta weight), a null
+ * pointer ("... needs ..."; ao_grad counts here for DFT_ComputeXCMetaSpin only), no usable device, bad sizes, a null
+ * ao_grad on a gradient solver ("ao_grad pointer is null"), then the "quirks" case.  Nothing has touched the device by
+ * then.  The three entries, DFT_ComputeTau / DFT_ComputeTauSpin and the open-shell response pair (DFT_FxcPrepareSpinPol /
+ * DFT_FxcApplySpinPol) work in one set of buffers of the solver, in stream order, each call writing whole what it reads:
+ * no result of one depends on what another left there, and no recorded graph or prepared table holds any of them. */
 int DFT_ComputeXCSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr,
                       unsigned long long d_dm_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
                       unsigned long long d_weights_ptr, unsigned long long d_vxc_a_ptr, unsigned long long d_vxc_b_ptr,
@@ -368,8 +377,8 @@ int DFT_ComputeTau(XCSolver *solver, long long ngrid, int nao, unsigned long lon
  * contraction with the plane of d_k AO in the AO slot (option "meta_fused" = 0, the default: the faster form as measured,
  * profiles/meta_time.txt) or one kernel over the three planes ("vxc_tau", "meta_fused" = 1, tested against the plain form).  With both meta weights zero the tau steps are left
  * out.  Never the one-kernel plan for small bases, never a recorded graph, never the occupied-orbital density step.
- * Synchronous: returns after Exc has been copied to *exc.  Its planes are its own: prepared DFT_Fxc* tables and later
- * DFT_ComputeXC* calls are not disturbed.  Returns 0, or -1 with DFT_GetLastError: a solver not made by
+ * Synchronous: returns after Exc has been copied to *exc.  Prepared DFT_Fxc* tables and later DFT_ComputeXC* calls are
+ * not disturbed (the buffers: see DFT_ComputeXCSpin).  Returns 0, or -1 with DFT_GetLastError: a solver not made by
  * DFT_CreateSolverMeta, a null pointer (ao_grad included), bad sizes, the "quirks" case above. */
 int DFT_ComputeXCMeta(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr, unsigned long long d_ao_ptr,
                       unsigned long long d_weights_ptr, unsigned long long d_ao_grad_ptr, unsigned long long d_vxc_ptr,
@@ -393,8 +402,8 @@ int DFT_ComputeTauSpin(XCSolver *solver, long long ngrid, int nao, unsigned long
  * forms), "xc_points_meta_spin" (xc::meta_spin_point: seven first derivatives by forward mode), the sweep's contraction
  * and reduce of c0..c3 per spin, then the tau term per spin in the form "meta_fused" chooses.  With both meta weights
  * zero tau is cleared instead of computed and the tau terms are left out.  Never the one-kernel plan for small bases,
- * never a recorded graph.  Synchronous.  Its planes are its own: prepared DFT_Fxc* tables and later DFT_ComputeXC,
- * DFT_ComputeXCSpin and DFT_ComputeXCMeta calls are not disturbed.  Returns 0, or -1 with DFT_GetLastError and no kernel
+ * never a recorded graph.  Synchronous.  Prepared DFT_Fxc* tables and later DFT_ComputeXC, DFT_ComputeXCSpin and
+ * DFT_ComputeXCMeta calls are not disturbed (the buffers: see DFT_ComputeXCSpin).  Returns 0, or -1 with DFT_GetLastError and no kernel
  * launched: a solver not made by DFT_CreateSolverMeta, a null pointer (ao_grad included), bad sizes, "quirks" = 1 with a
  * vwn5_c or pbe_c weight. */
 int DFT_ComputeXCMetaSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr, unsigned long long d_dm_b_ptr,

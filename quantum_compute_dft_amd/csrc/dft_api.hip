@@ -174,13 +174,17 @@ struct XCSolver {
     // prepares at different dm0 and applies of every kind interleave freely.
     FxcSlot fxc[3];
     // DFT_FxcPrepareSpinPol: the second-derivative table of the energy at (rho0_a, rho0_b) and the two ground-state gradients,
-    // a slot of its own again; DFT_FxcApplySpinPol works in the spin planes below, which every user overwrites whole
+    // a slot of its own again; DFT_FxcApplySpinPol works in the planes of the synchronous entries below
     FxcSlot fxc_pol;
-    // DFT_ComputeXCSpin: densities, gradients and coefficient planes of the two spins (sigma and the Exc partials with
-    // spin[0] alone) and the scalar of its Exc -- buffers of its own, so that no recorded sweep and no prepared response
-    // table holds or reads any of them
-    Planes spin[2];
-    DevBuf spin_exc;
+    // The synchronous entries past xc_sweep -- DFT_ComputeXCSpin, DFT_ComputeXCMeta, DFT_ComputeXCMetaSpin, DFT_ComputeTau,
+    // DFT_ComputeTauSpin -- and the open-shell response pair (DFT_FxcPrepareSpinPol / DFT_FxcApplySpinPol) work in one set,
+    // in stream order: the planes of each spin (a closed-shell call uses [0]; sigma, which nobody reads, and the Exc partials
+    // with [0] alone), tau of each spin (2 ngrid), the tau coefficients (four planes per spin: ct_s and, for the plain form,
+    // three of zeros), the padded matrix of each spin that k_tau reads (2 NP^2), the slabs of k_vxc_tau, the matrix one plain
+    // contraction leaves, and the scalar of Exc.  An entry reserves what it uses at the size of its call, and every call
+    // writes whole what it reads.  No recorded sweep and no prepared response table holds or reads any of them.
+    Planes sync_ws[2];
+    DevBuf sync_tau, sync_ct, sync_dp, sync_slabs, sync_vtmp, sync_exc;
     // DFT_ComputeXCGradient / DFT_ComputeXCGradientSpin and DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin: one set
     // of their own -- the planes of each spin (a closed-shell call uses [0]), the padded matrix of each spin that k_xc_grad reads
     // (the closed-shell entry's too: it no longer takes the shared Dsym) and the slabs (two sets with "xcg_spin_fused" = 0).  No
@@ -195,24 +199,11 @@ struct XCSolver {
     // DFT_BeckeWeightGradient: [atoms (natm, 3) | a_CD (natm, natm) | 1 / R_CD (natm, natm)] on the device and the host copy they
     // were made from (uploaded again only when the atoms change), and the slabs of the kernel
     DevBuf becke_tab, becke_slabs;
-    // DFT_ComputeTau / DFT_ComputeXCMeta: planes of their own (rho, grad, sigma, c0..c3, the Exc partials), tau and the tau
-    // coefficient (four planes: ct and, for the plain form, three of zeros), the padded matrix k_tau reads, the slabs of
-    // k_vxc_tau, the matrix one plain contraction leaves, and the scalar of its Exc.  No recorded sweep and no prepared
-    // response table holds or reads any of them.
-    Planes meta_ws;
-    DevBuf meta_tau, meta_ct, meta_dp, meta_slabs, meta_vtmp, meta_exc;
     // The tau term of the potential.  0 (default): the sweep's contraction once per plane with the plane in the AO slot; 1:
     // k_vxc_tau, one pass over the three gradient planes.  The dedicated kernel does not beat the plain form (605.8 against 294.8 us
     // at 143 556 x 114, 2015.7 against 1855.1 us at 60 000 x 494: profiles/meta_time.txt), so it is the option, held to the plain
     // form by the tests
     int meta_fused = 0;
-    // DFT_ComputeTauSpin / DFT_ComputeXCMetaSpin: a set of their own again -- the planes of each spin (the Exc partials with
-    // [0]), tau of each spin (2 ngrid), the tau coefficients (two sets of four planes: ct_s and, for the plain form, three of
-    // zeros), the two padded matrices k_tau / k_tau_spin read, the slabs of k_vxc_tau, the matrix one plain contraction
-    // leaves, and the scalar of its Exc.  No recorded sweep, no prepared response table and no other entry holds or reads
-    // any of them.
-    Planes mspin[2];
-    DevBuf mspin_tau, mspin_ct, mspin_dp, mspin_slabs, mspin_vtmp, mspin_exc;
     // The tau stage of an open-shell call.  1 (default): k_tau_spin, one staging of the gradient rows for both spins
     // (xc_meta_spin.hip; 0.80 x / 0.61 x of the two launches at 143 556 x 114 / 60 000 x 494: profiles/meta_spin_time.txt); 0:
     // k_tau once per spin, what the tests hold the two-spin kernel to
@@ -299,16 +290,26 @@ int xc_type_index(const XCSolver *s)
     return s->type == SOLVER_LDA ? 0 : s->type == SOLVER_GGA ? 1 : s->type == SOLVER_B3LYP ? 2 : 3;
 }
 
-// What every XC entry does first.  `timed`: timings of the same call that stay in front of the entry's own.
-bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed = 0, bool meta_entry = false)
+// What every XC entry does first, in two halves: the solver's kind, then the device, the sizes and ao_grad.  `timed`: timings of
+// the same call that stay in front of the entry's own.  `meta_who`: the name of an entry that forms tau (null: any other).
+bool enter_kind(XCSolver *s, size_t timed = 0, const char *meta_who = nullptr)
 {
     s->last_error.clear();
     s->n_timed = timed;
-    if (s->meta_active && !meta_entry) {
+    if (meta_who && !s->is_meta) {
+        set_error(s, "%s needs a solver made by DFT_CreateSolverMeta (this one carries no meta-GGA weights)", meta_who);
+        return false;
+    }
+    if (s->meta_active && !meta_who) {
         set_error(s, "the solver's functional is a meta-GGA (non-zero tpss_x / tpss_c weight): it reads the kinetic-energy density, "
                      "which only DFT_ComputeXCMeta and DFT_ComputeXCMetaSpin form; this entry would drop it");
         return false;
     }
+    return true;
+}
+
+bool enter_sizes(XCSolver *s, long ngrid, int nao, const double *ao_grad)
+{
     if (!s->device_ok) {
         set_error(s, "no usable HIP device");
         return false;
@@ -322,6 +323,11 @@ bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed
         return false;
     }
     return true;
+}
+
+bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed = 0)
+{
+    return enter_kind(s, timed) && enter_sizes(s, ngrid, nao, ao_grad);
 }
 
 // Every entry point runs on the solver's device (its workspace and stream live there): a caller that
@@ -740,220 +746,135 @@ bool spin_quirks_ok(XCSolver *s, const char *who)
     return true;
 }
 
-// The density kernels on the matrix of spin alpha, then of spin beta (linear in the matrix), into the spin planes; `ga`,
-// `gb`: where the two gradients go.  sigma is what the kernels write beside the gradient; nobody reads it.
+// The density kernels on the matrix of spin alpha, then of spin beta (linear in the matrix), into the planes of the
+// synchronous entries; `ga`, `gb`: where the two gradients go.  sigma is what the kernels write beside the gradient; nobody
+// reads it.
 void launch_density_spin(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
                          double *ga, double *gb)
 {
-    double *sigma = s->spin[0].sigma.d(), *Dp = s->dsym.d();
-    launch_density(s, P, ngrid, nao, dm_a, ao, Dp, s->spin[0].rho.d(), ga, sigma);
-    launch_density(s, P, ngrid, nao, dm_b, ao, Dp, s->spin[1].rho.d(), gb, sigma);
+    double *sigma = s->sync_ws[0].sigma.d(), *Dp = s->dsym.d();
+    launch_density(s, P, ngrid, nao, dm_a, ao, Dp, s->sync_ws[0].rho.d(), ga, sigma);
+    launch_density(s, P, ngrid, nao, dm_b, ao, Dp, s->sync_ws[1].rho.d(), gb, sigma);
 }
 
-// The spin-resolved sweep (DFT_ComputeXCSpin): the closed-shell sweep's density kernels on dm_a and on dm_b, one
-// pointwise kernel (xc_spin.hip), the closed-shell contraction and reduce once per spin; the second reduce finishes Exc
-// from the pointwise kernel's partials, as xc_sweep's does.  Never the one-kernel plan for small bases (it keeps no
-// density), never recorded.  Shares Dsym, the slabs and M with the other entries (stream order), and nothing else: the
-// response tables and the workspace a recorded sweep holds are not written.
-bool xc_sweep_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
-                   const double *ao_grad, const double *w, double *vxc_a, double *vxc_b, double *exc_host)
+// The launches of a tau stage on `nspin` matrices that are already padded and symmetrised (Dp, NP^2 apart).  `both`: the plan is
+// tau_spin_plan's and k_tau_spin takes the two matrices at once (anything but two is refused here); otherwise the plan is
+// tau_plan's and k_tau runs once per spin.
+bool launch_tau_stage(XCSolver *s, const TauPlan &tp, bool both, int nspin, long ngrid, int nao, const double *ao_grad, const double *Dp,
+                      double *const tau[2])
 {
-    if (!enter(s, ngrid, nao, ao_grad)) return false;
-    if (!dm_a || !dm_b || !ao || !w || !vxc_a || !vxc_b || !exc_host) {
-        set_error(s, "DFT_ComputeXCSpin needs both density matrices, the AO values, the grid weights, both output matrices and exc");
-        return false;
-    }
-    if (!spin_quirks_ok(s, "DFT_ComputeXCSpin")) return false;
-    const bool gga = s->needs_grad;
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const long nxb = spin_points_blocks(ngrid);
-    Planes &a = s->spin[0], &b = s->spin[1];
-    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, a, false, ngrid, WS_ALL, nxb) ||
-        !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD) || !reserve(s, s->spin_exc, 2 * sizeof(double), "hipMalloc(spin exc)", false))
-        return false;
-    launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, a.grad.d(), b.grad.d());
-    {
-        ScopedTimer t(s, "xc_points_spin");
-        if (!hip_ok(s, launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
-                                             gga ? b.grad.d() : nullptr, w, a.coef.d(), b.coef.d(), a.partial.d()), "spin pointwise launch"))
-            return false;
-    }
-    double *exc = s->spin_exc.d();
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, a.coef.d(), s->slabs.d(), vxc_a, nullptr)) return false;
-    const ExcFinish fin{nxb, a.partial.d(), exc, false};   // no host-mapped word, no publishing: Exc is copied below
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, b.coef.d(), s->slabs.d(), vxc_b, &fin)) return false;
-    double out = std::numeric_limits<double>::quiet_NaN();
-    if (!hip_ok(s, hipMemcpyAsync(&out, exc, sizeof(double), hipMemcpyDeviceToHost, s->stream), "copy Exc") ||
-        !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
-        return false;
-    *exc_host = out;
-    if (std::isnan(out)) { set_error(s, "Exc is NaN after the spin sweep completed (non-finite inputs)"); return false; }
-    return true;
-}
-
-// tau alone (DFT_ComputeTau): the padded symmetric matrix into its own buffer, then k_tau.
-bool compute_tau(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao_grad, double *tau)
-{
-    const TauPlan tp = tau_plan(s->num_cu, ngrid, nao);
-    if (!reserve(s, s->meta_dp, sizeof(double) * (size_t)tp.NP * tp.NP, "hipMalloc(meta Dp)", false)) return false;
-    ScopedTimer t(s, "tau");
-    hipLaunchKernelGGL(k_sym_dm, dim3(tp.NP / 16, tp.NP / 16), dim3(16, 16), 0, s->stream, nao, tp.NP, dm, s->meta_dp.d());
-    return hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, s->meta_dp.d(), tau), "tau launch");
-}
-
-// The meta-GGA sweep (DFT_ComputeXCMeta): the closed-shell sweep's density kernels, k_tau, one pointwise kernel
-// (xc_meta.hip), the closed-shell contraction and reduce of c0..c3 (which finishes Exc from the pointwise kernel's
-// partials), and the tau term added to V.  Never the one-kernel plan for small bases, never recorded.  Shares Dsym, the
-// slabs and M with the other entries (stream order), and nothing else.
-bool xc_sweep_meta(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *w, const double *ao_grad,
-                   double *vxc, double *exc_host)
-{
-    if (!s->is_meta) {
-        s->last_error.clear();
-        set_error(s, "DFT_ComputeXCMeta needs a solver made by DFT_CreateSolverMeta (this one carries no meta-GGA weights)");
-        return false;
-    }
-    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
-    if (!dm || !ao || !w || !vxc || !exc_host) {
-        set_error(s, "DFT_ComputeXCMeta needs the density matrix, the AO values, the grid weights, the output matrix and exc");
-        return false;
-    }
-    if (!spin_quirks_ok(s, "DFT_ComputeXCMeta")) return false;
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const long nxb = meta_points_blocks(ngrid);
-    const size_t ng = (size_t)ngrid, nn = (size_t)nao * nao;
-    Planes &p = s->meta_ws;
-    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, p, false, ngrid, WS_ALL, nxb) ||
-        !reserve(s, s->meta_tau, sizeof(double) * ng, "hipMalloc(tau)", false) ||
-        !reserve(s, s->meta_ct, sizeof(double) * 4 * ng, "hipMalloc(tau coefficient)", false) ||
-        !reserve(s, s->meta_exc, 2 * sizeof(double), "hipMalloc(meta exc)", false))
-        return false;
-    launch_density(s, P, ngrid, nao, dm, ao, s->dsym.d(), p.rho.d(), p.grad.d(), p.sigma.d());
-    double *tau = s->meta_tau.d(), *ct = s->meta_ct.d();
-    if (s->meta_active) {
-        if (!compute_tau(s, ngrid, nao, dm, ao_grad, tau)) return false;
-    } else if (!hip_ok(s, hipMemsetAsync(tau, 0, sizeof(double) * ng, s->stream), "clear tau")) {
-        return false;
-    }
-    {
-        ScopedTimer t(s, "xc_points_meta");
-        if (!hip_ok(s, launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, p.rho.d(), p.grad.d(), tau, w, p.coef.d(), ct, p.partial.d()),
-                    "meta pointwise launch"))
-            return false;
-    }
-    double *exc = s->meta_exc.d();
-    const ExcFinish fin{nxb, p.partial.d(), exc, false};   // no host-mapped word, no publishing: Exc is copied below
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, p.coef.d(), s->slabs.d(), vxc, &fin)) return false;
-    if (s->meta_active && s->meta_fused) {
-        const VxcTauPlan vp = vxc_tau_plan(s->num_cu, ngrid, nao);
-        if (!reserve(s, s->meta_slabs, sizeof(double) * (size_t)vp.nslab * nn, "hipMalloc(tau slabs)", false)) return false;
-        ScopedTimer t(s, "vxc_tau");
-        if (!hip_ok(s, launch_vxc_tau(s->stream, vp, ngrid, nao, ao_grad, ct, s->meta_slabs.d(), vxc), "tau potential launch")) return false;
-    } else if (s->meta_active) {
-        // the plain form: Q = c0 (plane in the AO slot) with c0 = ct and c1..c3 = 0, contracted with the same plane
-        if (!reserve(s, s->meta_vtmp, sizeof(double) * nn, "hipMalloc(tau potential)", false) ||
-            !hip_ok(s, hipMemsetAsync(ct + ng, 0, sizeof(double) * 3 * ng, s->stream), "clear coefficients"))
-            return false;
-        for (int k = 0; k < 3; ++k) {
-            if (!vxc_stage(s, P, false, ngrid, nao, ao_grad + (size_t)k * ng * nao, ct, s->slabs.d(), s->meta_vtmp.d(), nullptr)) return false;
-            if (!hip_ok(s, launch_meta_add(s->stream, (long)nn, s->meta_vtmp.d(), vxc), "tau potential add")) return false;
-        }
-    }
-    double out = std::numeric_limits<double>::quiet_NaN();
-    if (!hip_ok(s, hipMemcpyAsync(&out, exc, sizeof(double), hipMemcpyDeviceToHost, s->stream), "copy Exc") ||
-        !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
-        return false;
-    *exc_host = out;
-    if (std::isnan(out)) { set_error(s, "Exc is NaN after the meta-GGA sweep completed (non-finite inputs)"); return false; }
-    return true;
-}
-
-// tau of both spins (DFT_ComputeTauSpin): the two padded symmetric matrices into a buffer of their own, then k_tau_spin
-// (option "tau_spin_fused" = 1) or k_tau once per spin.
-bool compute_tau_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao_grad, double *tau_a,
-                      double *tau_b)
-{
-    const TauPlan tp = s->tau_spin_fused ? tau_spin_plan(s->num_cu, ngrid, nao) : tau_plan(s->num_cu, ngrid, nao);
+    static const char *const what[2][2] = {{"tau launch", "tau launch"}, {"tau launch (alpha)", "tau launch (beta)"}};
     const size_t np2 = (size_t)tp.NP * tp.NP;
-    if (!reserve(s, s->mspin_dp, sizeof(double) * 2 * np2, "hipMalloc(meta Dp of both spins)", false)) return false;
-    double *Dpa = s->mspin_dp.d(), *Dpb = Dpa + np2;
-    ScopedTimer t(s, s->tau_spin_fused ? "tau_spin" : "tau x2");
-    hipLaunchKernelGGL(k_sym_dm, dim3(tp.NP / 16, tp.NP / 16), dim3(16, 16), 0, s->stream, nao, tp.NP, dm_a, Dpa);
-    hipLaunchKernelGGL(k_sym_dm, dim3(tp.NP / 16, tp.NP / 16), dim3(16, 16), 0, s->stream, nao, tp.NP, dm_b, Dpb);
-    if (s->tau_spin_fused) return hip_ok(s, launch_tau_spin(s->stream, tp, ngrid, nao, ao_grad, Dpa, Dpb, tau_a, tau_b), "two-spin tau launch");
-    return hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, Dpa, tau_a), "tau launch (alpha)") &&
-           hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, Dpb, tau_b), "tau launch (beta)");
+    if (nspin < 1 || nspin > 2 || (both && nspin != 2)) {
+        set_error(s, "tau stage: %s on %d matrices", both ? "the two-spin kernel" : "the one-spin kernel", nspin);
+        return false;
+    }
+    if (both) return hip_ok(s, launch_tau_spin(s->stream, tp, ngrid, nao, ao_grad, Dp, Dp + np2, tau[0], tau[1]), "two-spin tau launch");
+    for (int sp = 0; sp < nspin; ++sp)
+        if (!hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, Dp + sp * np2, tau[sp]), what[nspin - 1][sp])) return false;
+    return true;
 }
 
-// The spin-resolved meta-GGA sweep (DFT_ComputeXCMetaSpin): the closed-shell sweep's density kernels per spin, tau per spin,
-// one pointwise kernel (xc_meta_spin.hip), the closed-shell contraction and reduce of c0..c3 once per spin (the second
-// finishes Exc from the pointwise kernel's partials, as in xc_sweep_spin), and the tau term of each spin added to its V in
-// either form of "meta_fused".  Never the one-kernel plan for small bases, never recorded, synchronous.  Shares Dsym, the
-// slabs and M with the other entries (stream order), and nothing else.  The refusals come before anything touches the
-// device, so that they can be told apart from "no usable HIP device".
-bool xc_sweep_meta_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao, const double *w,
-                        const double *ao_grad, double *vxc_a, double *vxc_b, double *exc_host)
+// tau of one spin or of both (DFT_ComputeTau, DFT_ComputeTauSpin and the meta-GGA sweeps): the padded symmetric matrix of each
+// spin into the entries' buffer, then k_tau_spin (two spins with option "tau_spin_fused" = 1) or k_tau once per spin.
+bool compute_tau(XCSolver *s, int nspin, long ngrid, int nao, const double *const dm[2], const double *ao_grad, double *const tau[2])
 {
-    s->last_error.clear();
-    s->n_timed = 0;
-    if (!s->is_meta) {
-        set_error(s, "DFT_ComputeXCMetaSpin needs a solver made by DFT_CreateSolverMeta (this one carries no meta-GGA weights)");
+    const bool both = nspin == 2 && s->tau_spin_fused;
+    const TauPlan tp = both ? tau_spin_plan(s->num_cu, ngrid, nao) : tau_plan(s->num_cu, ngrid, nao);
+    const size_t np2 = (size_t)tp.NP * tp.NP;
+    if (!reserve(s, s->sync_dp, sizeof(double) * nspin * np2, nspin == 2 ? "hipMalloc(meta Dp of both spins)" : "hipMalloc(meta Dp)", false)) return false;
+    double *Dp = s->sync_dp.d();
+    ScopedTimer t(s, nspin == 1 ? "tau" : both ? "tau_spin" : "tau x2");
+    for (int sp = 0; sp < nspin; ++sp)
+        hipLaunchKernelGGL(k_sym_dm, dim3(tp.NP / 16, tp.NP / 16), dim3(16, 16), 0, s->stream, nao, tp.NP, dm[sp], Dp + sp * np2);
+    return launch_tau_stage(s, tp, both, nspin, ngrid, nao, ao_grad, Dp, tau);
+}
+
+// What tells DFT_ComputeXCSpin, DFT_ComputeXCMeta and DFT_ComputeXCMetaSpin apart: the entry's name, its sentence for a null
+// pointer, the sweep's name in the NaN message, what a failed allocation of the Exc scalar and a failed pointwise launch are
+// called, the number of spins, whether it forms tau, and whether ao_grad is among the pointers of `needs` (otherwise
+// enter_sizes names it, for a gradient-corrected functional).
+struct SyncEntry {
+    const char *who, *needs, *what, *alloc_exc, *launch_points;
+    int nspin;
+    bool meta, grad_in_needs;
+};
+
+// The synchronous sweep of the three entries above, each stage once over sp < nspin: the closed-shell sweep's density kernels on
+// each spin's matrix, tau (meta entries; zeros when both meta weights are), one pointwise kernel (xc_spin.hip, xc_meta.hip
+// or xc_meta_spin.hip), the closed-shell contraction and reduce of each spin's coefficient planes -- the last reduce finishes
+// Exc from the pointwise kernel's partials, as xc_sweep's does -- and the tau term of each spin added to its V in either form
+// of "meta_fused".  Never the one-kernel plan for small bases (it keeps no density), never recorded.  Shares Dsym, the slabs
+// and M with the other entries (stream order) and works in the planes of the synchronous entries otherwise: the response
+// tables and the workspace a recorded sweep holds are not written.  Refusals, in this order for every entry: the solver's
+// kind, a null pointer, then the device, the sizes and ao_grad (enter_sizes), then quirks = 1 -- all before anything touches
+// the device, so that the first two can be told apart from "no usable HIP device".
+bool xc_sweep_sync(XCSolver *s, const SyncEntry &E, long ngrid, int nao, const double *const dm[2], const double *ao, const double *ao_grad,
+                   const double *w, double *const vxc[2], double *exc_host)
+{
+    const int nspin = E.nspin;
+    if (!enter_kind(s, 0, E.meta ? E.who : nullptr)) return false;
+    bool ptrs = ao && w && exc_host && (ao_grad || !E.grad_in_needs);
+    for (int sp = 0; sp < nspin; ++sp) ptrs = ptrs && dm[sp] && vxc[sp];
+    if (!ptrs) {
+        set_error(s, "%s", E.needs);
         return false;
     }
-    if (!dm_a || !dm_b || !ao || !w || !ao_grad || !vxc_a || !vxc_b || !exc_host) {
-        set_error(s, "DFT_ComputeXCMetaSpin needs both density matrices, the AO values, the grid weights, ao_grad (tau is made of the "
-                     "gradient planes), both output matrices and exc: a pointer is null");
-        return false;
-    }
-    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
-    if (!spin_quirks_ok(s, "DFT_ComputeXCMetaSpin")) return false;
+    if (!enter_sizes(s, ngrid, nao, ao_grad) || !spin_quirks_ok(s, E.who)) return false;
+    const bool gga = s->needs_grad, tau_term = E.meta && s->meta_active;
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const long nxb = meta_points_blocks(ngrid);
+    const long nxb = E.meta ? meta_points_blocks(ngrid) : spin_points_blocks(ngrid);
     const size_t ng = (size_t)ngrid, nn = (size_t)nao * nao;
-    Planes &a = s->mspin[0], &b = s->mspin[1];
-    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, a, false, ngrid, WS_ALL, nxb) ||
-        !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD) ||
-        !reserve(s, s->mspin_tau, sizeof(double) * 2 * ng, "hipMalloc(tau of both spins)", false) ||
-        !reserve(s, s->mspin_ct, sizeof(double) * 8 * ng, "hipMalloc(tau coefficients of both spins)", false) ||
-        !reserve(s, s->mspin_exc, 2 * sizeof(double), "hipMalloc(spin meta exc)", false))
+    Planes *p = s->sync_ws;
+    if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, p[0], false, ngrid, WS_ALL, nxb) ||
+        (nspin == 2 && !reserve_planes(s, p[1], false, ngrid, WS_COEF | WS_GRAD)) ||
+        (E.meta && (!reserve(s, s->sync_tau, sizeof(double) * nspin * ng, nspin == 2 ? "hipMalloc(tau of both spins)" : "hipMalloc(tau)", false) ||
+                    !reserve(s, s->sync_ct, sizeof(double) * 4 * nspin * ng,
+                             nspin == 2 ? "hipMalloc(tau coefficients of both spins)" : "hipMalloc(tau coefficient)", false))) ||
+        !reserve(s, s->sync_exc, 2 * sizeof(double), E.alloc_exc, false))
         return false;
-    // the density kernels on each spin's matrix (launch_density_spin's two launches, into the planes of this entry)
-    launch_density(s, P, ngrid, nao, dm_a, ao, s->dsym.d(), a.rho.d(), a.grad.d(), a.sigma.d());
-    launch_density(s, P, ngrid, nao, dm_b, ao, s->dsym.d(), b.rho.d(), b.grad.d(), a.sigma.d());
-    double *tau = s->mspin_tau.d(), *ct = s->mspin_ct.d();
-    if (s->meta_active) {
-        if (!compute_tau_spin(s, ngrid, nao, dm_a, dm_b, ao_grad, tau, tau + ng)) return false;
-    } else if (!hip_ok(s, hipMemsetAsync(tau, 0, sizeof(double) * 2 * ng, s->stream), "clear tau")) {
+    for (int sp = 0; sp < nspin; ++sp)
+        launch_density(s, P, ngrid, nao, dm[sp], ao, s->dsym.d(), p[sp].rho.d(), p[sp].grad.d(), p[0].sigma.d());
+    double *ct = s->sync_ct.d();
+    double *const tau[2] = {s->sync_tau.d(), E.meta ? s->sync_tau.d() + ng : nullptr};
+    if (tau_term) {
+        if (!compute_tau(s, nspin, ngrid, nao, dm, ao_grad, tau)) return false;
+    } else if (E.meta && !hip_ok(s, hipMemsetAsync(tau[0], 0, sizeof(double) * nspin * ng, s->stream), "clear tau")) {
         return false;
     }
-    {
-        ScopedTimer t(s, "xc_points_meta_spin");
-        if (!hip_ok(s, launch_xc_points_meta_spin(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), b.rho.d(), a.grad.d(), b.grad.d(), tau, tau + ng,
-                                                  w, a.coef.d(), b.coef.d(), ct, ct + 4 * ng, a.partial.d()), "spin meta pointwise launch"))
-            return false;
+    {   // the one stage that differs in more than its loop count: three kernels
+        ScopedTimer t(s, !E.meta ? "xc_points_spin" : nspin == 2 ? "xc_points_meta_spin" : "xc_points_meta");
+        const hipError_t e =
+            !E.meta ? launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, p[0].rho.d(), p[1].rho.d(), gga ? p[0].grad.d() : nullptr,
+                                            gga ? p[1].grad.d() : nullptr, w, p[0].coef.d(), p[1].coef.d(), p[0].partial.d())
+            : nspin == 2 ? launch_xc_points_meta_spin(s->stream, s->mix.c, s->meta, ngrid, p[0].rho.d(), p[1].rho.d(), p[0].grad.d(), p[1].grad.d(),
+                                                      tau[0], tau[1], w, p[0].coef.d(), p[1].coef.d(), ct, ct + 4 * ng, p[0].partial.d())
+                         : launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, p[0].rho.d(), p[0].grad.d(), tau[0], w, p[0].coef.d(), ct,
+                                                 p[0].partial.d());
+        if (!hip_ok(s, e, E.launch_points)) return false;
     }
-    double *exc = s->mspin_exc.d();
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, a.coef.d(), s->slabs.d(), vxc_a, nullptr)) return false;
-    const ExcFinish fin{nxb, a.partial.d(), exc, false};   // no host-mapped word, no publishing: Exc is copied below
-    if (!vxc_stage(s, P, false, ngrid, nao, ao, b.coef.d(), s->slabs.d(), vxc_b, &fin)) return false;
-    if (s->meta_active && s->meta_fused) {
+    double *exc = s->sync_exc.d();
+    const ExcFinish fin{nxb, p[0].partial.d(), exc, false};   // no host-mapped word, no publishing: Exc is copied below
+    for (int sp = 0; sp < nspin; ++sp)
+        if (!vxc_stage(s, P, false, ngrid, nao, ao, p[sp].coef.d(), s->slabs.d(), vxc[sp], sp == nspin - 1 ? &fin : nullptr)) return false;
+    if (tau_term && s->meta_fused) {
         const VxcTauPlan vp = vxc_tau_plan(s->num_cu, ngrid, nao);
-        if (!reserve(s, s->mspin_slabs, sizeof(double) * (size_t)vp.nslab * nn, "hipMalloc(tau slabs)", false)) return false;
-        ScopedTimer t(s, "vxc_tau x2");
-        if (!hip_ok(s, launch_vxc_tau(s->stream, vp, ngrid, nao, ao_grad, ct, s->mspin_slabs.d(), vxc_a), "tau potential launch (alpha)") ||
-            !hip_ok(s, launch_vxc_tau(s->stream, vp, ngrid, nao, ao_grad, ct + 4 * ng, s->mspin_slabs.d(), vxc_b), "tau potential launch (beta)"))
-            return false;
-    } else if (s->meta_active) {
+        if (!reserve(s, s->sync_slabs, sizeof(double) * (size_t)vp.nslab * nn, "hipMalloc(tau slabs)", false)) return false;
+        static const char *const what[2][2] = {{"tau potential launch", ""}, {"tau potential launch (alpha)", "tau potential launch (beta)"}};
+        ScopedTimer t(s, nspin == 2 ? "vxc_tau x2" : "vxc_tau");
+        for (int sp = 0; sp < nspin; ++sp)
+            if (!hip_ok(s, launch_vxc_tau(s->stream, vp, ngrid, nao, ao_grad, ct + (size_t)sp * 4 * ng, s->sync_slabs.d(), vxc[sp]), what[nspin - 1][sp]))
+                return false;
+    } else if (tau_term) {
         // the plain form, per spin: Q = c0 (plane in the AO slot) with c0 = ct_s and c1..c3 = 0, contracted with the same plane
-        if (!reserve(s, s->mspin_vtmp, sizeof(double) * nn, "hipMalloc(tau potential)", false) ||
-            !hip_ok(s, hipMemsetAsync(ct + ng, 0, sizeof(double) * 3 * ng, s->stream), "clear coefficients") ||
-            !hip_ok(s, hipMemsetAsync(ct + 5 * ng, 0, sizeof(double) * 3 * ng, s->stream), "clear coefficients"))
-            return false;
-        for (int sp = 0; sp < 2; ++sp)
+        if (!reserve(s, s->sync_vtmp, sizeof(double) * nn, "hipMalloc(tau potential)", false)) return false;
+        for (int sp = 0; sp < nspin; ++sp)
+            if (!hip_ok(s, hipMemsetAsync(ct + (size_t)(4 * sp + 1) * ng, 0, sizeof(double) * 3 * ng, s->stream), "clear coefficients")) return false;
+        for (int sp = 0; sp < nspin; ++sp)
             for (int k = 0; k < 3; ++k) {
-                if (!vxc_stage(s, P, false, ngrid, nao, ao_grad + (size_t)k * ng * nao, ct + (size_t)sp * 4 * ng, s->slabs.d(), s->mspin_vtmp.d(), nullptr))
+                if (!vxc_stage(s, P, false, ngrid, nao, ao_grad + (size_t)k * ng * nao, ct + (size_t)sp * 4 * ng, s->slabs.d(), s->sync_vtmp.d(), nullptr))
                     return false;
-                if (!hip_ok(s, launch_meta_add(s->stream, (long)nn, s->mspin_vtmp.d(), sp ? vxc_b : vxc_a), "tau potential add")) return false;
+                if (!hip_ok(s, launch_meta_add(s->stream, (long)nn, s->sync_vtmp.d(), vxc[sp]), "tau potential add")) return false;
             }
     }
     double out = std::numeric_limits<double>::quiet_NaN();
@@ -961,7 +882,7 @@ bool xc_sweep_meta_spin(XCSolver *s, long ngrid, int nao, const double *dm_a, co
         !hip_ok(s, hipStreamSynchronize(s->stream), "synchronise"))
         return false;
     *exc_host = out;
-    if (std::isnan(out)) { set_error(s, "Exc is NaN after the spin-resolved meta-GGA sweep completed (non-finite inputs)"); return false; }
+    if (std::isnan(out)) { set_error(s, "Exc is NaN after the %s completed (non-finite inputs)", E.what); return false; }
     return true;
 }
 
@@ -1044,8 +965,8 @@ bool fxc_apply(XCSolver *s, long ngrid, int nao, const double *dm1, const double
 }
 
 // Open-shell response of Vxc, first half (DFT_FxcPrepareSpinPol): the density kernels on dm0_a, then on dm0_b, as
-// xc_sweep_spin runs them, and the second-derivative table of the energy at that point (xc_response_pol.hip).  The
-// table and the two gradients stay in a slot of their own; the densities pass through the spin sweep's scratch.
+// DFT_ComputeXCSpin runs them, and the second-derivative table of the energy at that point (xc_response_pol.hip).  The
+// table and the two gradients stay in a slot of their own; the densities pass through the synchronous entries' planes.
 bool fxc_prepare_spinpol(XCSolver *s, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
                          const double *ao_grad, const double *w)
 {
@@ -1060,7 +981,7 @@ bool fxc_prepare_spinpol(XCSolver *s, long ngrid, int nao, const double *dm_a, c
     const bool gga = s->needs_grad;
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
     const size_t ng = (size_t)ngrid;
-    if (!reserve_dsym(s, P) || !reserve_planes(s, s->spin[0], false, ngrid, WS_SIGMA) || !reserve_planes(s, s->spin[1], false, ngrid, 0) ||
+    if (!reserve_dsym(s, P) || !reserve_planes(s, s->sync_ws[0], false, ngrid, WS_SIGMA) || !reserve_planes(s, s->sync_ws[1], false, ngrid, 0) ||
         !reserve(s, f.table, sizeof(double) * ng * fxc_pol_planes(gga), "hipMalloc(fxc pol table)", false))
         return false;
     for (int k = 0; k < 2; ++k)
@@ -1069,7 +990,7 @@ bool fxc_prepare_spinpol(XCSolver *s, long ngrid, int nao, const double *dm_a, c
     launch_density_spin(s, P, ngrid, nao, dm_a, dm_b, ao, g_a, g_b);
     {
         ScopedTimer t(s, "fxc_table_pol");
-        if (!hip_ok(s, launch_fxc_table_pol(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, s->spin[0].rho.d(), s->spin[1].rho.d(),
+        if (!hip_ok(s, launch_fxc_table_pol(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, s->sync_ws[0].rho.d(), s->sync_ws[1].rho.d(),
                                             gga ? g_a : nullptr, gga ? g_b : nullptr, w, f.table.d()), "open-shell response table launch"))
             return false;
     }
@@ -1090,7 +1011,7 @@ bool fxc_apply_spinpol(XCSolver *s, long ngrid, int nao, const double *dm1_a, co
         return false;
     }
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    Planes &a = s->spin[0], &b = s->spin[1];
+    Planes &a = s->sync_ws[0], &b = s->sync_ws[1];
     if (!reserve_dsym(s, P) || !reserve_slabs(s, P, nao) || !reserve_planes(s, a, false, ngrid, WS_ALL) ||
         !reserve_planes(s, b, false, ngrid, WS_COEF | WS_GRAD))
         return false;
@@ -1716,7 +1637,7 @@ bool reserve_xcg_meta(XCSolver *s, const SweepPlan &P, long ngrid, long nxb, boo
 
 // The density stage the two entries share: the sweep's density kernels with the sweep's choices into the planes of these
 // entries, the padded symmetric matrix (the wave-specialised density kernel symmetrises dm itself, so k_sym_dm runs here on
-// that plan; the other plans leave it behind), and k_tau on that matrix -- compute_tau's launch without its second
+// that plan; the other plans leave it behind), and k_tau on that matrix -- compute_tau's launch half, without its second
 // symmetrisation.  With both meta weights zero tau is not formed: the planes of zeros the pointwise kernels read.
 bool xcg_meta_density(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm, const double *ao, const double *ao_grad)
 {
@@ -1730,8 +1651,9 @@ bool xcg_meta_density(XCSolver *s, const SweepPlan &P, long ngrid, int nao, cons
     if (!hip_ok(s, hipGetLastError(), "meta gradient: density launch")) return false;
     if (!s->meta_active) return hip_ok(s, hipMemsetAsync(tau, 0, sizeof(double) * (size_t)ngrid, s->stream), "clear tau");
     const TauPlan tp = tau_plan(s->num_cu, ngrid, nao);   // tp.NP = P.NP
+    double *const t1[2] = {tau, nullptr};
     ScopedTimer t(s, "tau");
-    return hip_ok(s, launch_tau(s->stream, tp, ngrid, nao, ao_grad, Dp, tau), "tau launch");
+    return launch_tau_stage(s, tp, false, 1, ngrid, nao, ao_grad, Dp, t1);
 }
 
 // XC part of the nuclear gradient of a meta-GGA (DFT_ComputeXCGradientMeta): the density stage above, k_xc_points_meta, and
@@ -1754,7 +1676,7 @@ bool xc_gradient_meta(XCSolver *s, long ngrid, int nao, const double *dm, const 
         set_error(s, "%s: nao=%d needs %zu bytes of LDS per workgroup, above the 160 KB a workgroup has", who, nao, lds);
         return false;
     }
-    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
+    if (!enter_sizes(s, ngrid, nao, ao_grad)) return false;
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
     const long nxb = meta_points_blocks(ngrid);
     const int nslab = fused ? T.nwg : tau_term ? G.nwg + T.nwg : G.nwg;
@@ -1792,7 +1714,7 @@ bool xc_energy_density_meta(XCSolver *s, long ngrid, int nao, const double *dm, 
     if (!xcg_meta_check(s, "DFT_ComputeXCEnergyDensityMeta", ngrid, nao, dm && ao && ao_grad && e_out,
                         "dm, the AO values, ao_grad (tau is made of the gradient planes) and the output"))
         return false;
-    if (!enter(s, ngrid, nao, ao_grad, 0, true)) return false;
+    if (!enter_sizes(s, ngrid, nao, ao_grad)) return false;
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
     if (!reserve_xcg_meta(s, P, ngrid, 0, false) || !xcg_meta_density(s, P, ngrid, nao, dm, ao, ao_grad)) return false;
     ScopedTimer t(s, "xc_edens_meta");
@@ -2319,8 +2241,12 @@ int DFT_ComputeXCSpin(XCSolver *s, long long ngrid, int nao, unsigned long long 
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_sweep_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
-                         (const double *)d_ao_grad, (const double *)d_w, (double *)d_vxc_a, (double *)d_vxc_b, exc) ? 0 : -1;
+    static const SyncEntry E{"DFT_ComputeXCSpin",
+                             "DFT_ComputeXCSpin needs both density matrices, the AO values, the grid weights, both output matrices and exc",
+                             "spin sweep", "hipMalloc(spin exc)", "spin pointwise launch", 2, false, false};
+    const double *const dm[2] = {(const double *)d_dm_a, (const double *)d_dm_b};
+    double *const vxc[2] = {(double *)d_vxc_a, (double *)d_vxc_b};
+    return xc_sweep_sync(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (const double *)d_w, vxc, exc) ? 0 : -1;
 }
 
 int DFT_ComputeTau(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao_grad, unsigned long long d_tau)
@@ -2332,7 +2258,9 @@ int DFT_ComputeTau(XCSolver *s, long long ngrid, int nao, unsigned long long d_d
     if (!s->device_ok) { set_error(s, "no usable HIP device"); return -1; }
     if (ngrid <= 0 || nao <= 0) { set_error(s, "bad sizes ngrid=%lld nao=%d", ngrid, nao); return -1; }
     if (!d_dm || !d_ao_grad || !d_tau) { set_error(s, "DFT_ComputeTau needs the density matrix, ao_grad and the output"); return -1; }
-    return compute_tau(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao_grad, (double *)d_tau) ? 0 : -1;
+    const double *const dm[2] = {(const double *)d_dm, nullptr};
+    double *const tau[2] = {(double *)d_tau, nullptr};
+    return compute_tau(s, 1, (long)ngrid, nao, dm, (const double *)d_ao_grad, tau) ? 0 : -1;
 }
 
 int DFT_ComputeXCMeta(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao, unsigned long long d_w,
@@ -2340,8 +2268,12 @@ int DFT_ComputeXCMeta(XCSolver *s, long long ngrid, int nao, unsigned long long 
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_sweep_meta(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_w,
-                         (const double *)d_ao_grad, (double *)d_vxc, exc) ? 0 : -1;
+    static const SyncEntry E{"DFT_ComputeXCMeta",
+                             "DFT_ComputeXCMeta needs the density matrix, the AO values, the grid weights, the output matrix and exc",
+                             "meta-GGA sweep", "hipMalloc(meta exc)", "meta pointwise launch", 1, true, false};
+    const double *const dm[2] = {(const double *)d_dm, nullptr};
+    double *const vxc[2] = {(double *)d_vxc, nullptr};
+    return xc_sweep_sync(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (const double *)d_w, vxc, exc) ? 0 : -1;
 }
 
 int DFT_ComputeTauSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
@@ -2357,8 +2289,9 @@ int DFT_ComputeTauSpin(XCSolver *s, long long ngrid, int nao, unsigned long long
         return -1;
     }
     if (!s->device_ok) { set_error(s, "no usable HIP device"); return -1; }
-    return compute_tau_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao_grad,
-                            (double *)d_tau_a, (double *)d_tau_b) ? 0 : -1;
+    const double *const dm[2] = {(const double *)d_dm_a, (const double *)d_dm_b};
+    double *const tau[2] = {(double *)d_tau_a, (double *)d_tau_b};
+    return compute_tau(s, 2, (long)ngrid, nao, dm, (const double *)d_ao_grad, tau) ? 0 : -1;
 }
 
 int DFT_ComputeXCMetaSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
@@ -2367,8 +2300,13 @@ int DFT_ComputeXCMetaSpin(XCSolver *s, long long ngrid, int nao, unsigned long l
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_sweep_meta_spin(s, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
-                              (const double *)d_w, (const double *)d_ao_grad, (double *)d_vxc_a, (double *)d_vxc_b, exc) ? 0 : -1;
+    static const SyncEntry E{"DFT_ComputeXCMetaSpin",
+                             "DFT_ComputeXCMetaSpin needs both density matrices, the AO values, the grid weights, ao_grad (tau is made of the "
+                             "gradient planes), both output matrices and exc: a pointer is null",
+                             "spin-resolved meta-GGA sweep", "hipMalloc(spin meta exc)", "spin meta pointwise launch", 2, true, true};
+    const double *const dm[2] = {(const double *)d_dm_a, (const double *)d_dm_b};
+    double *const vxc[2] = {(double *)d_vxc_a, (double *)d_vxc_b};
+    return xc_sweep_sync(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (const double *)d_w, vxc, exc) ? 0 : -1;
 }
 
 void DFT_ComputeCoulomb(XCSolver *s, int nao, unsigned long long d_eri, unsigned long long d_dm,

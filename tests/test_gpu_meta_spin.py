@@ -280,6 +280,41 @@ def test_other_entries_are_not_disturbed(dev, shape):
     assert same(p.meta_spin(m), a)
 
 
+def test_the_shared_workspace_carries_nothing_between_users(dev):
+    """DFT_ComputeXCMeta, DFT_ComputeXCMetaSpin (meta_fused 0 and 1), DFT_ComputeTau and DFT_ComputeTauSpin on one TPSS solver,
+    DFT_ComputeXCSpin, DFT_FxcPrepareSpinPol + DFT_FxcApplySpinPol and the two tau entries on one GGA solver: the entries of a
+    solver work in one set of buffers, whose planes move as the sizes shrink and grow from call to call.  Each result is
+    bitwise what the same call gives on a fresh solver that has run nothing else."""
+    def calls(p, d_dm):
+        def response(s):
+            va, vb = p._out(2)
+            assert s.fxc_prepare_spinpol(p.ngrid, p.nao, p.d_a, p.d_b, p.d_ao, p.d_w, p.d_gr) == 0
+            assert s.fxc_apply_spinpol(p.ngrid, p.nao, p.d_b, p.d_a, p.d_ao, va, vb, p.d_gr) == 0
+            torch.cuda.synchronize()
+            return 0.0, va.cpu().numpy(), vb.cpu().numpy()
+        tau = lambda s: (0.0, p.tau(s, d_dm))
+        tau_spin = lambda s: (0.0,) + p.tau_spin(s)
+        return [("TPSS", "meta", {}, lambda s: p.meta(s, d_dm)), ("TPSS", "meta spin", dict(meta_fused=0), p.meta_spin),
+                ("TPSS", "meta spin fused", dict(meta_fused=1), p.meta_spin), ("GGA", "spin", {}, p.spin), ("GGA", "response", {}, response),
+                ("TPSS", "tau", {}, tau), ("GGA", "tau", {}, tau), ("TPSS", "tau spin", dict(tau_spin_fused=1), tau_spin),
+                ("GGA", "tau spin plain", dict(tau_spin_fused=0), tau_spin)]
+
+    used = {"TPSS": _solver("TPSS"), "GGA": _solver("GGA")}
+    order = (ms.SHAPES[0], ms.SHAPES[1], ms.SHAPES[0], ms.TAU_SHAPES[1])
+    assert [(s[0], s[1]) for s in order] == [(2085, 24), (2085, 114), (2085, 24), (400, 385)]
+    for shape in order:
+        p = Planes(dev, shape)
+        d_dm = torch.as_tensor(p.dm_a + p.dm_b, device=dev)
+        for functional, label, opts, run in calls(p, d_dm):
+            if shape == ms.TAU_SHAPES[1] and "tau" not in label:
+                continue                                             # the two-chunk shape: tau alone
+            opts = dict(dict(meta_fused=0, tau_spin_fused=1), **opts)    # the options are the solver's: the same on both
+            fresh = _solver(functional, **opts)
+            for k, v in opts.items():
+                used[functional].set_option(k, v)
+            assert same(run(used[functional]), run(fresh)), (shape, functional, label)
+
+
 def test_refusals(dev):
     shape = ms.SHAPES[0]
     p = Planes(dev, shape)
