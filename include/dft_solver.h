@@ -338,7 +338,22 @@ int DFT_FxcApplyKind(XCSolver *solver, long long ngrid, int nao, unsigned long l
  * ao_grad on a gradient solver ("ao_grad pointer is null"), then the "quirks" case.  Nothing has touched the device by
  * then.  The three entries, DFT_ComputeTau / DFT_ComputeTauSpin and the open-shell response pair (DFT_FxcPrepareSpinPol /
  * DFT_FxcApplySpinPol) work in one set of buffers of the solver, in stream order, each call writing whole what it reads:
- * no result of one depends on what another left there, and no recorded graph or prepared table holds any of them. */
+ * no result of one depends on what another left there, and no recorded graph or prepared table holds any of them.
+ *
+ * The six gradient-side entries further down -- DFT_ComputeXCGradient / DFT_ComputeXCGradientSpin / DFT_ComputeXCGradientMeta and
+ * DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin / DFT_ComputeXCEnergyDensityMeta -- are likewise one gradient path
+ * and one energy-density path over (spins, meta) with one density stage (xc_gradient, xc_energy_density, xcg_density,
+ * csrc/dft_api.hip).  Where a call has more than one fault, all six refuse in this order: the solver's kind (a meta entry on a
+ * solver without meta weights; any other on one with a non-zero meta weight), a null pointer ("... needs ..."; ao_grad and
+ * ao_hess count here for the meta pair only), bad sizes, a null ao_grad on a gradient solver ("ao_grad pointer is null"), for
+ * the gradients a null ao_hess on a gradient solver ("ao_hess pointer is null") and a null ao_grad on any other ("... needs
+ * ao_grad"), the "quirks" case (every entry but the two closed-shell non-meta ones), for the gradients an LDS request above
+ * 160 KB, and last no usable device: a caller without a device still learns every fault of its arguments.  Nothing has touched
+ * the device by then.  Two spins with tau -- the gradient of an open-shell meta-GGA -- have no kernel and no entry; the shared
+ * path refuses the pair in one place (xcg_enter).  The six work in one set of buffers of the solver of their own -- the planes
+ * and the padded matrix of each spin, tau and its coefficient plane, the slabs of the contraction -- in stream order: an entry
+ * reserves what it uses at the size of its call, every call writes whole what it reads, so no result of one depends on what
+ * another left there (each is bitwise what a fresh solver gives), and no recorded graph and no prepared table holds any of them. */
 int DFT_ComputeXCSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr,
                       unsigned long long d_dm_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
                       unsigned long long d_weights_ptr, unsigned long long d_vxc_a_ptr, unsigned long long d_vxc_b_ptr,
@@ -458,7 +473,7 @@ int DFT_FxcSpinPolTable(XCSolver *solver, unsigned long long d_out_ptr, long lon
  * vwn5_c or pbe_c in the functional the shipped potentials are not the derivatives of the energy, and G is built from
  * the shipped ones.  Linear in the grid points: a caller may sum G over slices of the grid.
  * On the solver's stream, no host wait: the density kernels and the pointwise kernel of the sweep with the sweep's
- * choices ("path", nao, plane size), into buffers of this entry, then "xc_grad": per tile of 16 grid rows X = AO D and
+ * choices ("path", nao, plane size), into the gradient entries' set of buffers (see DFT_ComputeXCSpin), then "xc_grad": per tile of 16 grid rows X = AO D and
  * Z = Q D (Q = 2 c0 AO + sum_k c_k ao_grad[k]) on the fp64 matrix pipe, contracted with ao_grad and ao_hess into one
  * (nao, 3) slab per workgroup, and a fixed-order slab sum, so a call is bitwise reproducible.  Never the one-kernel
  * plan, never a recorded graph; prepared DFT_Fxc* tables and later DFT_ComputeXC results are left bit for bit as they
@@ -480,7 +495,7 @@ int DFT_ComputeXCGradient(XCSolver *solver, long long ngrid, int nao, unsigned l
  *   G[mu, x] = -fac sum_s sum_g [ d_x phi_mu Z_s + (sum_k c_sk d_xk phi_mu) X_s ][g, mu],  X_s = AO D_s,  Z_s = Q_s D_s,
  * Q_s = 2 c_s0 AO + sum_k c_sk ao_grad[k], fac = 1 (one-sided types) or 2 (B3LYP): the closed-shell formula once per spin.
  * On the solver's stream, no host wait: the density kernels on dm_a and on dm_b and the spin-resolved pointwise kernel
- * exactly as DFT_ComputeXCSpin runs them, into buffers of this entry, then "xc_grad_spin": k_xc_grad on both spins stages the AO
+ * exactly as DFT_ComputeXCSpin runs them, into the gradient entries' set of buffers, then "xc_grad_spin": k_xc_grad on both spins stages the AO
  * rows of a tile once beside the Q rows of both spins, forms X_a, X_b, Z_a, Z_b of a column tile together and reads each
  * gradient and Hessian plane element once, for d_x phi (Z_a + Z_b) + sum_k d_xk phi (c_ak X_a + c_bk X_b), into one
  * (nao, 3) slab per workgroup; a fixed-order slab sum finishes, so a call is bitwise reproducible.  Option
@@ -502,20 +517,22 @@ int DFT_ComputeXCGradientSpin(XCSolver *solver, long long ngrid, int nao, unsign
  * "xc_points_meta" writes it and Y_k = (d_k AO) Ds,
  *     G[mu, x] = G_gga[mu, x; c0..c3] - 2 sum_g ct sum_k hess_xk[g, mu] Y_k[g, mu]:
  * the six Hessian planes, no third derivatives.  Order of work on the solver's stream: the sweep's density kernels with
- * the sweep's choices into planes of this entry, the padded symmetric matrix, "tau" on it, "xc_points_meta", then the
+ * the sweep's choices into the planes of that set, the padded symmetric matrix, "tau" on it, "xc_points_meta", then the
  * contraction in the form option "xcg_meta_fused" chooses -- 1 (the default: the faster form as measured,
  * profiles/xc_gradient_meta_time.txt): k_xc_grad_meta<true>, one pass over the ten planes with five products per load of
  * the matrix; 0: k_xc_grad on c0..c3 and k_xc_grad_meta<false> (the tau term) into two slab sets
  * and one fixed-order sum over both, the plain form the fused kernel is tested against.  With both meta weights zero the
  * tau stage and the tau term are left out and the result is DFT_ComputeXCGradient's of the same mix.  No atomics: a call
  * is bitwise reproducible.  Asynchronous, never the one-kernel plan, never a recorded graph; its planes, tau, coefficients,
- * padded matrix and slabs are its own, so later DFT_ComputeXCMeta / DFT_ComputeXCGradient / DFT_ComputeXC results and
- * prepared DFT_Fxc* tables are bit for bit what they were.
+ * padded matrix and slabs are the gradient entries' one set (see DFT_ComputeXCSpin), which no sweep and no prepared table
+ * holds, so later DFT_ComputeXCMeta / DFT_ComputeXCGradient / DFT_ComputeXC results and prepared DFT_Fxc* tables are bit for
+ * bit what they were.
  * DFT_ComputeXCEnergyDensityMeta: d_e_out (ngrid) receives the energy per volume of the meta point WITHOUT the weight
  * (density stage and "tau" as above, then "xc_edens_meta"): sum_g w_g e_g is DFT_ComputeXCMeta's Exc.
  * Both return 0, or -1 with DFT_GetLastError, before any launch: a solver without meta weights, a null pointer (ao_grad
  * and ao_hess included), bad sizes, "quirks" = 1 with vwn5_c / pbe_c, and a basis whose tiles do not fit 160 KB of LDS
- * (nao above 1216 in the fused form, above 1328 in the plain one, whose k_xc_grad tiles are the wider). */
+ * (nao above 1216 in the fused form, above 1328 in the plain one, whose k_xc_grad tiles are the wider); several faults in one
+ * call: the order stated at DFT_ComputeXCSpin. */
 int DFT_ComputeXCGradientMeta(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr,
                               unsigned long long d_ao_ptr, unsigned long long d_weights_ptr,
                               unsigned long long d_ao_grad_ptr, unsigned long long d_ao_hess_ptr,
@@ -530,7 +547,7 @@ int DFT_ComputeXCEnergyDensityMeta(XCSolver *solver, long long ngrid, int nao, u
  * e_g the energy per volume -- the entries below give e_g and sum_g f_g D_B cell_g for the caller's f_g = w0_g e_g.
  * DFT_ComputeXCEnergyDensity: d_e_out (ngrid) receives e_g of the density of dm, WITHOUT the weight: sum_g w_g e_g is the
  * Exc DFT_ComputeXC returns.  The density kernels of the sweep with the sweep's choices ("path", nao, plane size) into
- * planes of this entry, then "xc_edens": the body the sweep's pointwise kernel runs for the solver's type with unit
+ * the planes of the gradient entries' set, then "xc_edens": the body the sweep's pointwise kernel runs for the solver's type with unit
  * weight, so the density cut-off, "quirks" and the mix weights are the sweep's.
  * DFT_ComputeXCEnergyDensitySpin: the same of DFT_ComputeXCSpin(dm_a, dm_b): the density kernels on dm_a and on dm_b and
  * the spin-resolved body; it refuses what DFT_ComputeXCSpin refuses ("quirks" = 1 with vwn5_c / pbe_c).

@@ -185,13 +185,14 @@ struct XCSolver {
     // writes whole what it reads.  No recorded sweep and no prepared response table holds or reads any of them.
     Planes sync_ws[2];
     DevBuf sync_tau, sync_ct, sync_dp, sync_slabs, sync_vtmp, sync_exc;
-    // DFT_ComputeXCGradient / DFT_ComputeXCGradientSpin and DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin: one set
-    // of their own -- the planes of each spin (a closed-shell call uses [0]), the padded matrix of each spin that k_xc_grad reads
-    // (the closed-shell entry's too: it no longer takes the shared Dsym) and the slabs (two sets with "xcg_spin_fused" = 0).  No
-    // recorded sweep and no prepared response table holds or reads any of them; the four entries share them in stream order, and
-    // every call overwrites whole what it reads.  The energy-density entries, which read no matrix back, symmetrise into Dsym.
+    // The six gradient-side entries -- DFT_ComputeXCGradient / Spin / Meta and DFT_ComputeXCEnergyDensity / Spin / Meta -- work in
+    // one set of their own, in stream order: the planes of each spin (a closed-shell call uses [0]; sigma and the Exc partials,
+    // which nobody reads, with [0] alone), the padded matrix of each spin (NP^2 apart) that k_xc_grad and k_tau read -- every
+    // entry symmetrises into it, none into the shared Dsym -- tau and its coefficient plane (meta entries), and the slabs of the
+    // contraction (as many as the call's form writes).  An entry reserves what it uses at the size of its call, and every call
+    // writes whole what it reads.  No recorded sweep and no prepared response table holds or reads any of them.
     Planes xcg[2];
-    DevBuf xcg_dp[2], xcg_slabs;
+    DevBuf xcg_dp, xcg_tau, xcg_ct, xcg_slabs;
     // DFT_ComputeXCGradientSpin.  1 (default): k_xc_grad on both spins' (coef, D) pairs in one launch (0.64 x / 0.82 x of the two
     // launches at 143 556 x 114 / 60 000 x 494, GGA: profiles/xc_gradient_spin_time.txt); 0: k_xc_grad once per spin into two slab
     // sets, what the tests hold the two-spin instantiation to
@@ -208,11 +209,6 @@ struct XCSolver {
     // (xc_meta_spin.hip; 0.80 x / 0.61 x of the two launches at 143 556 x 114 / 60 000 x 494: profiles/meta_spin_time.txt); 0:
     // k_tau once per spin, what the tests hold the two-spin kernel to
     int tau_spin_fused = 1;
-    // DFT_ComputeXCGradientMeta / DFT_ComputeXCEnergyDensityMeta: a set of their own again -- the planes, tau, ct, the padded
-    // matrix k_tau and the contraction read, and the slabs (two sets with "xcg_meta_fused" = 0).  No recorded sweep, no prepared
-    // response table and no other entry holds or reads any of them.
-    Planes xcgm;
-    DevBuf xcgm_tau, xcgm_ct, xcgm_dp, xcgm_slabs;
     // The contraction of DFT_ComputeXCGradientMeta.  1 (default): k_xc_grad_meta<true>, everything in one pass over the ten planes
     // (0.90 x / 0.80 x of the plain form at 143 556 x 114 / 60 000 x 494, TPSS: profiles/xc_gradient_meta_time.txt); 0: k_xc_grad on
     // c0..c3 and k_xc_grad_meta<false> (the tau term) into two slab sets and one sum, what the tests hold the fused kernel to
@@ -292,6 +288,8 @@ int xc_type_index(const XCSolver *s)
 
 // What every XC entry does first, in two halves: the solver's kind, then the device, the sizes and ao_grad.  `timed`: timings of
 // the same call that stay in front of the entry's own.  `meta_who`: the name of an entry that forms tau (null: any other).
+// enter_sizes is itself two steps, which the gradient-side entries (xcg_enter) take apart: they name every fault of the
+// arguments before the device.
 bool enter_kind(XCSolver *s, size_t timed = 0, const char *meta_who = nullptr)
 {
     s->last_error.clear();
@@ -308,12 +306,14 @@ bool enter_kind(XCSolver *s, size_t timed = 0, const char *meta_who = nullptr)
     return true;
 }
 
-bool enter_sizes(XCSolver *s, long ngrid, int nao, const double *ao_grad)
+bool device_ready(XCSolver *s)
 {
-    if (!s->device_ok) {
-        set_error(s, "no usable HIP device");
-        return false;
-    }
+    if (!s->device_ok) set_error(s, "no usable HIP device");
+    return s->device_ok;
+}
+
+bool sizes_ok(XCSolver *s, long ngrid, int nao, const double *ao_grad)
+{
     if (ngrid <= 0 || nao <= 0) {
         set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao);
         return false;
@@ -323,6 +323,11 @@ bool enter_sizes(XCSolver *s, long ngrid, int nao, const double *ao_grad)
         return false;
     }
     return true;
+}
+
+bool enter_sizes(XCSolver *s, long ngrid, int nao, const double *ao_grad)
+{
+    return device_ready(s) && sizes_ok(s, ngrid, nao, ao_grad);
 }
 
 bool enter(XCSolver *s, long ngrid, int nao, const double *ao_grad, size_t timed = 0)
@@ -1505,221 +1510,158 @@ __global__ void k_accumulate_chunk(long n2, int add, const double *__restrict__ 
     if (i == 0) *e = add ? *e + *ec : *ec;
 }
 
-// XC part of the nuclear gradient, closed shell (DFT_ComputeXCGradient: nspin = 1, dm_b unused) and open shell
-// (DFT_ComputeXCGradientSpin: nspin = 2).  The sweep's own density kernels on each matrix and its pointwise kernel -- the
-// spin-resolved one exactly as DFT_ComputeXCSpin runs it for two spins -- into planes of these entries (XCSolver::xcg), then
-// k_xc_grad (xc_grad.hip) on the (coefficient planes, padded matrix) pair of every spin and the fixed-order slab sum: both
-// spins' pairs in one launch, or, with option "xcg_spin_fused" = 0, one launch per spin into two slab sets.  Never the
-// one-kernel plan for small bases (it keeps no coefficients), never recorded; asynchronous on the solver's stream.  The
-// padded matrices are these entries' too: both are read after both are written.
-bool xc_gradient(XCSolver *s, int nspin, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao, const double *w,
+// What tells the six gradient-side entries apart: the entry's name, its sentence for a null pointer, what a failed allocation
+// of the padded matrices and of the slabs and a failed density or pointwise launch are called, the timer label of that
+// pointwise kernel (the closed-shell gradient's is launch_xc_points' own), the number of spins and whether the entry forms
+// tau.  A meta entry counts ao_grad and ao_hess among the pointers of `needs`; the others name them in sentences of their own.
+struct XcgEntry {
+    const char *who, *needs, *alloc_dp, *alloc_slabs, *density_launch, *launch, *timer;
+    int nspin;
+    bool meta;
+};
+
+// What the six refuse first, in this order for every entry: the solver's kind, two spins with tau (no kernel takes them:
+// no entry asks), a null pointer, the sizes and a null ao_grad on a gradient-corrected solver (sizes_ok), for a gradient a
+// null ao_hess on such a solver and a null ao_grad on any other, then quirks = 1 where the potentials are derivatives of the
+// energy.  The callers go on with the LDS request (a gradient) and, last, the device: every fault of the arguments can be
+// told apart from "no usable HIP device", and nothing has touched the device by then.
+bool xcg_enter(XCSolver *s, const XcgEntry &E, bool gradient, long ngrid, int nao, const double *const dm[2], const double *ao,
+               const double *w, const double *ao_grad, const double *ao_hess, const double *out)
+{
+    if (!enter_kind(s, 0, E.meta ? E.who : nullptr)) return false;
+    if (E.meta && E.nspin == 2) {
+        set_error(s, "%s: the open-shell meta-GGA gradient is not built (no kernel takes two spins and tau)", E.who);
+        return false;
+    }
+    bool ptrs = ao && out && (w || !gradient) && (!E.meta || (ao_grad && (ao_hess || !gradient)));
+    for (int sp = 0; sp < E.nspin; ++sp) ptrs = ptrs && dm[sp];
+    if (!ptrs) {
+        set_error(s, "%s", E.needs);
+        return false;
+    }
+    if (!sizes_ok(s, ngrid, nao, ao_grad)) return false;
+    if (gradient && s->needs_grad && !ao_hess) { set_error(s, "ao_hess pointer is null for a gradient-corrected functional"); return false; }
+    if (gradient && !ao_grad) { set_error(s, "%s needs ao_grad: the derivative of the density by a centre is made of it", E.who); return false; }
+    return (E.nspin == 1 && !E.meta) || spin_quirks_ok(s, E.who);
+}
+
+// The set's buffers at the size of this call: `parts` of each spin's planes (sigma and `nxb` Exc partials with [0] alone), the
+// padded matrix of each spin, and for a meta entry tau and, beside coefficient planes, ct.
+bool reserve_xcg(XCSolver *s, const XcgEntry &E, const SweepPlan &P, long ngrid, unsigned parts, long nxb)
+{
+    const size_t ng = sizeof(double) * (size_t)ngrid * E.nspin;
+    return reserve_planes(s, s->xcg[0], false, ngrid, parts, nxb) &&
+           (E.nspin == 1 || reserve_planes(s, s->xcg[1], false, ngrid, parts & ~WS_SIGMA)) &&
+           reserve(s, s->xcg_dp, sizeof(double) * E.nspin * P.NP * P.NP, E.alloc_dp, false) &&
+           (!E.meta || (reserve(s, s->xcg_tau, ng, "hipMalloc(meta gradient tau)", false) &&
+                        (!(parts & WS_COEF) || reserve(s, s->xcg_ct, ng, "hipMalloc(meta gradient tau coefficient)", false))));
+}
+
+// The density stage the six share: the sweep's density kernels with the sweep's choices on each spin's matrix into that
+// spin's planes; the padded symmetric matrix of each spin where something reads it back (`keep_dp`: k_xc_grad and k_tau do.
+// The wave-specialised density kernel symmetrises dm itself, so k_sym_dm runs here on that plan; the other plans leave the
+// matrix behind); and for a meta entry k_tau on that matrix -- compute_tau's launch half, without its second
+// symmetrisation -- or, with both meta weights zero, the plane of zeros the pointwise kernels read.
+bool xcg_density(XCSolver *s, const XcgEntry &E, const SweepPlan &P, bool keep_dp, long ngrid, int nao, const double *const dm[2],
+                 const double *ao, const double *ao_grad)
+{
+    const size_t np2 = (size_t)P.NP * P.NP, ng = (size_t)ngrid;
+    double *Dp = s->xcg_dp.d();
+    for (int sp = 0; sp < E.nspin; ++sp)
+        launch_density(s, P, ngrid, nao, dm[sp], ao, Dp + sp * np2, s->xcg[sp].rho.d(), s->xcg[sp].grad.d(), s->xcg[0].sigma.d());
+    if (P.fast && keep_dp) {
+        ScopedTimer t(s, "sym_dm");
+        for (int sp = 0; sp < E.nspin; ++sp)
+            hipLaunchKernelGGL(k_sym_dm, dim3(P.NP / 16, P.NP / 16), dim3(16, 16), 0, s->stream, nao, P.NP, dm[sp], Dp + sp * np2);
+    }
+    if (!hip_ok(s, hipGetLastError(), E.density_launch)) return false;
+    if (!E.meta) return true;
+    double *const tau[2] = {s->xcg_tau.d(), s->xcg_tau.d() + ng};
+    if (!s->meta_active) return hip_ok(s, hipMemsetAsync(tau[0], 0, sizeof(double) * E.nspin * ng, s->stream), "clear tau");
+    const TauPlan tp = tau_plan(s->num_cu, ngrid, nao);   // tp.NP = P.NP
+    ScopedTimer t(s, "tau");
+    return launch_tau_stage(s, tp, false, E.nspin, ngrid, nao, ao_grad, Dp, tau);
+}
+
+// XC part of the nuclear gradient: DFT_ComputeXCGradient, DFT_ComputeXCGradientSpin and DFT_ComputeXCGradientMeta, each
+// stage once over sp < nspin.  The density stage above, the pointwise kernel of the entry's sweep exactly as that sweep runs
+// it (launch_xc_points, xc_spin.hip, xc_meta.hip), then the contraction of every spin's (coefficient planes, padded matrix)
+// pair with the ten planes and a fixed-order slab sum: k_xc_grad; for two spins both pairs in one launch or, with option
+// "xcg_spin_fused" = 0, one launch per spin into two slab sets; for a meta-GGA k_xc_grad_meta<true> with c0..c3 and ct in one
+// pass or, with "xcg_meta_fused" = 0, k_xc_grad and k_xc_grad_meta<false> into two slab sets.  With both meta weights zero
+// the tau stage and the tau term are left out: k_xc_grad alone, as DFT_ComputeXCGradient runs it.  Never the one-kernel plan
+// for small bases (it keeps no coefficients), never recorded; asynchronous on the solver's stream.
+bool xc_gradient(XCSolver *s, const XcgEntry &E, long ngrid, int nao, const double *const dm[2], const double *ao, const double *w,
                  const double *ao_grad, const double *ao_hess, double *out)
 {
-    const bool spin = nspin == 2;
-    const char *who = spin ? "DFT_ComputeXCGradientSpin" : "DFT_ComputeXCGradient";
-    if (!enter(s, ngrid, nao, ao_grad)) return false;
-    if (!dm_a || (spin && !dm_b) || !ao || !w || !out) {
-        set_error(s, "%s needs %s, the AO values, the grid weights and the output", who, spin ? "both density matrices" : "dm");
+    if (!xcg_enter(s, E, true, ngrid, nao, dm, ao, w, ao_grad, ao_hess, out)) return false;
+    const bool spin = E.nspin == 2, gga = s->needs_grad, tau_term = E.meta && s->meta_active;
+    const bool fused = spin ? s->xcg_spin_fused != 0 : tau_term && s->xcg_meta_fused != 0;
+    const XcGradPlan G = xc_grad_plan(s->num_cu, gga, spin && fused ? 2 : 1, ngrid, nao);                      // k_xc_grad
+    const XcGradPlan T = tau_term ? xc_grad_meta_plan(s->num_cu, fused, ngrid, nao) : XcGradPlan{};          // k_xc_grad_meta<fused>
+    const size_t lds = !tau_term ? G.lds : fused ? T.lds : std::max(G.lds, T.lds);
+    if (lds > 160 * 1024) {
+        set_error(s, "%s: nao=%d needs %zu bytes of LDS per workgroup%s", E.who, nao, lds, E.meta ? ", above the 160 KB a workgroup has" : "");
         return false;
     }
-    const bool gga = s->needs_grad;
-    if (gga && !ao_hess) { set_error(s, "ao_hess pointer is null for a gradient-corrected functional"); return false; }
-    if (!ao_grad) { set_error(s, "%s needs ao_grad: the derivative of the density by a centre is made of it", who); return false; }
-    if (spin && !spin_quirks_ok(s, who)) return false;
-    const bool fused = spin && s->xcg_spin_fused != 0;
-    const XcGradPlan G = xc_grad_plan(s->num_cu, gga, fused ? 2 : 1, ngrid, nao);
-    if (G.lds > 160 * 1024) { set_error(s, "%s: nao=%d needs %zu bytes of LDS per workgroup", who, nao, G.lds); return false; }
+    if (!device_ready(s)) return false;
     // an LDA-class solver's density kernels read ao_grad's first plane pointer only as a dummy: plan as the sweep does
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
-    const long nxb = spin ? spin_points_blocks(ngrid) : (ngrid + 255) / 256;
-    const Planes &a = s->xcg[0], &b = s->xcg[1];   // sigma and the Exc partials with [0] alone
-    const size_t dpb = sizeof(double) * P.NP * P.NP, slab = sizeof(double) * (size_t)G.nwg * 3 * nao;
-    if (!reserve_planes(s, s->xcg[0], false, ngrid, WS_ALL, nxb) || (spin && !reserve_planes(s, s->xcg[1], false, ngrid, WS_COEF | WS_GRAD)) ||
-        !reserve(s, s->xcg_dp[0], dpb, spin ? "hipMalloc(Dsym alpha)" : "hipMalloc(Dsym)", false) ||
-        (spin && !reserve(s, s->xcg_dp[1], dpb, "hipMalloc(Dsym beta)", false)) ||
-        !reserve(s, s->xcg_slabs, (spin && !fused ? 2 : 1) * slab, spin ? "hipMalloc(spin gradient slabs)" : "hipMalloc(gradient slabs)", false))
+    const long nxb = E.meta ? meta_points_blocks(ngrid) : spin ? spin_points_blocks(ngrid) : (ngrid + 255) / 256;
+    const int nslab = !tau_term ? (spin && !fused ? 2 : 1) * G.nwg : fused ? T.nwg : G.nwg + T.nwg;
+    if (!reserve_xcg(s, E, P, ngrid, WS_ALL, nxb) ||
+        !reserve(s, s->xcg_slabs, sizeof(double) * (size_t)nslab * 3 * nao, E.alloc_slabs, false) ||
+        !xcg_density(s, E, P, true, ngrid, nao, dm, ao, ao_grad))
         return false;
-    const double *dm[2] = {dm_a, dm_b};
-    double *Dp[2] = {s->xcg_dp[0].d(), s->xcg_dp[1].d()};
-    for (int sp = 0; sp < nspin; ++sp)
-        launch_density(s, P, ngrid, nao, dm[sp], ao, Dp[sp], s->xcg[sp].rho.d(), s->xcg[sp].grad.d(), a.sigma.d());
-    if (P.fast) {   // the wave-specialised density kernel symmetrises dm itself: k_xc_grad reads the padded matrices
-        ScopedTimer t(s, "sym_dm");
-        dim3 bl(16, 16), g(P.NP / 16, P.NP / 16);
-        for (int sp = 0; sp < nspin; ++sp) hipLaunchKernelGGL(k_sym_dm, g, bl, 0, s->stream, nao, P.NP, dm[sp], Dp[sp]);
-    }
-    if (!spin) {
+    const Planes &a = s->xcg[0], &b = s->xcg[1];   // sigma and the Exc partials with [0] alone
+    const double *Da = s->xcg_dp.d(), *Db = Da + (size_t)P.NP * P.NP;
+    double *ct = s->xcg_ct.d(), *slabs = s->xcg_slabs.d();
+    if (!spin && !E.meta) {   // the pointwise kernel: the first of the two stages that differ in more than their loop count
         launch_xc_points(s, ngrid, nxb, w, a);
-        if (!hip_ok(s, hipGetLastError(), "XC gradient density launch")) return false;
+        if (!hip_ok(s, hipGetLastError(), E.launch)) return false;
     } else {
-        ScopedTimer t(s, "xc_points_spin");
-        if (!hip_ok(s, launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
-                                             gga ? b.grad.d() : nullptr, w, a.coef.d(), b.coef.d(), a.partial.d()), "spin pointwise launch"))
-            return false;
+        ScopedTimer t(s, E.timer);
+        const hipError_t e =
+            E.meta ? launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), a.grad.d(), s->xcg_tau.d(), w, a.coef.d(), ct, a.partial.d())
+                   : launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
+                                           gga ? b.grad.d() : nullptr, w, a.coef.d(), b.coef.d(), a.partial.d());
+        if (!hip_ok(s, e, E.launch)) return false;
     }
-    ScopedTimer t(s, spin ? "xc_grad_spin" : "xc_grad");
-    // one-sided types hand over c0 = w vrho, c_k = 4 w vsigma grad_k rho; B3LYP half of each (its M + M^T)
+    // ... and the contraction.  One-sided types hand over c0 = w vrho, c_k = 4 w vsigma grad_k rho; B3LYP half of each (its M + M^T)
     const double fac = s->type == SOLVER_B3LYP ? 2.0 : 1.0;
-    double *slabs = s->xcg_slabs.d();
-    if (!spin)
-        return hip_ok(s, launch_xc_grad(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), Dp[0], slabs, out),
-                      "XC gradient launch");
-    if (fused)
-        return hip_ok(s, launch_xc_grad_spin_fused(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp[0], Dp[1],
-                                                   slabs, out), "XC spin gradient launch (fused)");
-    return hip_ok(s, launch_xc_grad_spin(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Dp[0], Dp[1], slabs, out),
-                  "XC spin gradient launch");
+    struct Form { const char *timer, *what; };
+    const Form form = tau_term ? (fused ? Form{"xc_grad_meta", "meta XC gradient launch (fused)"} : Form{"xc_grad + xc_grad_tau", "meta XC gradient launch"})
+                      : spin   ? Form{"xc_grad_spin", fused ? "XC spin gradient launch (fused)" : "XC spin gradient launch"}
+                               : Form{"xc_grad", "XC gradient launch"};
+    ScopedTimer t(s, form.timer);
+    const hipError_t e =
+        tau_term ? (fused ? launch_xc_grad_meta_fused(s->stream, T, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), ct, Da, slabs, out)
+                          : launch_xc_grad_meta_plain(s->stream, G, T, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), ct, Da, slabs, out))
+        : spin   ? (fused ? launch_xc_grad_spin_fused(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Da, Db, slabs, out)
+                          : launch_xc_grad_spin(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Da, Db, slabs, out))
+                 : launch_xc_grad(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), Da, slabs, out);
+    return hip_ok(s, e, form.what);
 }
 
-// The energy per volume of the functional at the density of dm (DFT_ComputeXCEnergyDensity: nspin = 1, dm_b unused) or of
-// an open-shell state (DFT_ComputeXCEnergyDensitySpin: nspin = 2, with DFT_ComputeXCSpin's refusal): the density kernels of
-// the sweep with the sweep's choices, then the body of the sweep's pointwise kernel with unit weight (k_xc_edens, or the
-// spin-resolved body), into the planes of the gradient entries.  Never the one-kernel plan, never recorded; asynchronous on
-// the solver's stream.
-bool xc_energy_density(XCSolver *s, int nspin, long ngrid, int nao, const double *dm_a, const double *dm_b, const double *ao,
-                       const double *ao_grad, double *e_out)
+// The energy per volume of the functional at the density of the call -- DFT_ComputeXCEnergyDensity, its open-shell
+// counterpart (DFT_ComputeXCSpin's refusal) and the meta-GGA's, at the density and tau of dm: the density stage above, then
+// the body of the entry's pointwise kernel with unit weight (k_xc_edens, the spin-resolved body, k_xc_edens_meta).  Nothing
+// here reads the padded matrix but k_tau.  Never the one-kernel plan, never recorded; asynchronous on the solver's stream.
+bool xc_energy_density(XCSolver *s, const XcgEntry &E, long ngrid, int nao, const double *const dm[2], const double *ao, const double *ao_grad,
+                       double *e_out)
 {
-    const bool spin = nspin == 2;
-    const char *who = spin ? "DFT_ComputeXCEnergyDensitySpin" : "DFT_ComputeXCEnergyDensity";
-    if (!enter(s, ngrid, nao, ao_grad)) return false;
-    if (!dm_a || (spin && !dm_b) || !ao || !e_out) {
-        set_error(s, "%s needs %s, the AO values and the output", who, spin ? "both density matrices" : "dm");
-        return false;
-    }
-    if (spin && !spin_quirks_ok(s, who)) return false;
+    if (!xcg_enter(s, E, false, ngrid, nao, dm, ao, nullptr, ao_grad, nullptr, e_out) || !device_ready(s)) return false;
     const bool gga = s->needs_grad;
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
+    if (!reserve_xcg(s, E, P, ngrid, WS_GRAD | WS_SIGMA, 0) || !xcg_density(s, E, P, E.meta, ngrid, nao, dm, ao, ao_grad)) return false;
     const Planes &a = s->xcg[0], &b = s->xcg[1];
-    if (!reserve_dsym(s, P) || !reserve_planes(s, s->xcg[0], false, ngrid, WS_GRAD | WS_SIGMA) ||
-        (spin && !reserve_planes(s, s->xcg[1], false, ngrid, WS_GRAD)))
-        return false;
-    const double *dm[2] = {dm_a, dm_b};
-    for (int sp = 0; sp < nspin; ++sp)
-        launch_density(s, P, ngrid, nao, dm[sp], ao, s->dsym.d(), s->xcg[sp].rho.d(), s->xcg[sp].grad.d(), a.sigma.d());
-    if (!hip_ok(s, hipGetLastError(), spin ? "spin energy density: density launch" : "energy density: density launch")) return false;
-    ScopedTimer t(s, spin ? "xc_edens_spin" : "xc_edens");
-    if (!spin)
-        return hip_ok(s, launch_xc_edens(s->stream, xc_type_index(s), gga, s->mix.c, s->quirks, ngrid, a.rho.d(), a.sigma.d(), a.grad.d(), e_out),
-                      "energy density launch");
-    return hip_ok(s, launch_xc_edens_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
-                                          gga ? b.grad.d() : nullptr, e_out), "spin energy density launch");
-}
-
-// What DFT_ComputeXCGradientMeta and DFT_ComputeXCEnergyDensityMeta refuse first, before anything touches the device (so that
-// the refusals can be told apart from "no usable HIP device"): `needs` names the pointers, ptrs_ok says that none is null.
-bool xcg_meta_check(XCSolver *s, const char *who, long ngrid, int nao, bool ptrs_ok, const char *needs)
-{
-    s->last_error.clear();
-    s->n_timed = 0;
-    if (!s->is_meta) {
-        set_error(s, "%s needs a solver made by DFT_CreateSolverMeta (this one carries no meta-GGA weights)", who);
-        return false;
-    }
-    if (!ptrs_ok) {
-        set_error(s, "%s needs %s: a pointer is null", who, needs);
-        return false;
-    }
-    if (ngrid <= 0 || nao <= 0) {
-        set_error(s, "bad sizes ngrid=%ld nao=%d", ngrid, nao);
-        return false;
-    }
-    return spin_quirks_ok(s, who);
-}
-
-bool reserve_xcg_meta(XCSolver *s, const SweepPlan &P, long ngrid, long nxb, bool coef)
-{
-    const size_t ng = sizeof(double) * (size_t)ngrid;
-    return reserve_planes(s, s->xcgm, false, ngrid, coef ? WS_ALL : (WS_GRAD | WS_SIGMA), nxb) &&
-           reserve(s, s->xcgm_dp, sizeof(double) * (size_t)P.NP * P.NP, "hipMalloc(meta gradient Dsym)", false) &&
-           reserve(s, s->xcgm_tau, ng, "hipMalloc(meta gradient tau)", false) &&
-           (!coef || reserve(s, s->xcgm_ct, ng, "hipMalloc(meta gradient tau coefficient)", false));
-}
-
-// The density stage the two entries share: the sweep's density kernels with the sweep's choices into the planes of these
-// entries, the padded symmetric matrix (the wave-specialised density kernel symmetrises dm itself, so k_sym_dm runs here on
-// that plan; the other plans leave it behind), and k_tau on that matrix -- compute_tau's launch half, without its second
-// symmetrisation.  With both meta weights zero tau is not formed: the planes of zeros the pointwise kernels read.
-bool xcg_meta_density(XCSolver *s, const SweepPlan &P, long ngrid, int nao, const double *dm, const double *ao, const double *ao_grad)
-{
-    const Planes &p = s->xcgm;
-    double *Dp = s->xcgm_dp.d(), *tau = s->xcgm_tau.d();
-    launch_density(s, P, ngrid, nao, dm, ao, Dp, p.rho.d(), p.grad.d(), p.sigma.d());
-    if (P.fast) {
-        ScopedTimer t(s, "sym_dm");
-        hipLaunchKernelGGL(k_sym_dm, dim3(P.NP / 16, P.NP / 16), dim3(16, 16), 0, s->stream, nao, P.NP, dm, Dp);
-    }
-    if (!hip_ok(s, hipGetLastError(), "meta gradient: density launch")) return false;
-    if (!s->meta_active) return hip_ok(s, hipMemsetAsync(tau, 0, sizeof(double) * (size_t)ngrid, s->stream), "clear tau");
-    const TauPlan tp = tau_plan(s->num_cu, ngrid, nao);   // tp.NP = P.NP
-    double *const t1[2] = {tau, nullptr};
-    ScopedTimer t(s, "tau");
-    return launch_tau_stage(s, tp, false, 1, ngrid, nao, ao_grad, Dp, t1);
-}
-
-// XC part of the nuclear gradient of a meta-GGA (DFT_ComputeXCGradientMeta): the density stage above, k_xc_points_meta, and
-// the contraction of c0..c3, ct with the ten planes -- k_xc_grad_meta<true> (option "xcg_meta_fused" = 1) or k_xc_grad on
-// c0..c3 and k_xc_grad_meta<false> into two slab sets with one sum (0, the plain form).  With both meta weights zero the
-// tau stage and the tau term are left out: k_xc_grad alone, as DFT_ComputeXCGradient runs it.  Never the one-kernel plan,
-// never recorded; asynchronous on the solver's stream.
-bool xc_gradient_meta(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *w, const double *ao_grad,
-                      const double *ao_hess, double *out)
-{
-    const char *who = "DFT_ComputeXCGradientMeta";
-    if (!xcg_meta_check(s, who, ngrid, nao, dm && ao && w && ao_grad && ao_hess && out,
-                        "dm, the AO values, the grid weights, ao_grad (tau is made of the gradient planes), ao_hess and the output"))
-        return false;
-    const bool tau_term = s->meta_active, fused = tau_term && s->xcg_meta_fused != 0;
-    const XcGradPlan G = xc_grad_plan(s->num_cu, true, 1, ngrid, nao);            // k_xc_grad<true, 1>: the plain form, zero meta weights
-    const XcGradPlan T = xc_grad_meta_plan(s->num_cu, fused, ngrid, nao);         // k_xc_grad_meta<fused>
-    const size_t lds = fused ? T.lds : tau_term ? std::max(G.lds, T.lds) : G.lds;
-    if (lds > 160 * 1024) {
-        set_error(s, "%s: nao=%d needs %zu bytes of LDS per workgroup, above the 160 KB a workgroup has", who, nao, lds);
-        return false;
-    }
-    if (!enter_sizes(s, ngrid, nao, ao_grad)) return false;
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    const long nxb = meta_points_blocks(ngrid);
-    const int nslab = fused ? T.nwg : tau_term ? G.nwg + T.nwg : G.nwg;
-    if (!reserve_xcg_meta(s, P, ngrid, nxb, true) ||
-        !reserve(s, s->xcgm_slabs, sizeof(double) * (size_t)nslab * 3 * nao, "hipMalloc(meta gradient slabs)", false))
-        return false;
-    if (!xcg_meta_density(s, P, ngrid, nao, dm, ao, ao_grad)) return false;
-    const Planes &p = s->xcgm;
-    const double *Dp = s->xcgm_dp.d();
-    double *ct = s->xcgm_ct.d(), *slabs = s->xcgm_slabs.d();
-    {
-        ScopedTimer t(s, "xc_points_meta");
-        if (!hip_ok(s, launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, p.rho.d(), p.grad.d(), s->xcgm_tau.d(), w, p.coef.d(), ct,
-                                             p.partial.d()), "meta pointwise launch"))
-            return false;
-    }
-    if (!tau_term) {
-        ScopedTimer t(s, "xc_grad");
-        return hip_ok(s, launch_xc_grad(s->stream, G, true, 1.0, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), Dp, slabs, out), "XC gradient launch");
-    }
-    if (fused) {
-        ScopedTimer t(s, "xc_grad_meta");
-        return hip_ok(s, launch_xc_grad_meta_fused(s->stream, T, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), ct, Dp, slabs, out),
-                      "meta XC gradient launch (fused)");
-    }
-    ScopedTimer t(s, "xc_grad + xc_grad_tau");
-    return hip_ok(s, launch_xc_grad_meta_plain(s->stream, G, T, ngrid, nao, ao, ao_grad, ao_hess, p.coef.d(), ct, Dp, slabs, out),
-                  "meta XC gradient launch");
-}
-
-// The energy per volume of a meta-GGA at the density and tau of dm (DFT_ComputeXCEnergyDensityMeta): the density stage above,
-// then the body of k_xc_points_meta at unit weight (k_xc_edens_meta).  Asynchronous on the solver's stream.
-bool xc_energy_density_meta(XCSolver *s, long ngrid, int nao, const double *dm, const double *ao, const double *ao_grad, double *e_out)
-{
-    if (!xcg_meta_check(s, "DFT_ComputeXCEnergyDensityMeta", ngrid, nao, dm && ao && ao_grad && e_out,
-                        "dm, the AO values, ao_grad (tau is made of the gradient planes) and the output"))
-        return false;
-    if (!enter_sizes(s, ngrid, nao, ao_grad)) return false;
-    const SweepPlan P = plan_sweep(s, ngrid, nao, ao, ao_grad, false);
-    if (!reserve_xcg_meta(s, P, ngrid, 0, false) || !xcg_meta_density(s, P, ngrid, nao, dm, ao, ao_grad)) return false;
-    ScopedTimer t(s, "xc_edens_meta");
-    return hip_ok(s, launch_xc_edens_meta(s->stream, s->mix.c, s->meta, ngrid, s->xcgm.rho.d(), s->xcgm.grad.d(), s->xcgm_tau.d(), e_out),
-                  "meta energy density launch");
+    ScopedTimer t(s, E.timer);
+    const hipError_t e =
+        E.meta         ? launch_xc_edens_meta(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), a.grad.d(), s->xcg_tau.d(), e_out)
+        : E.nspin == 2 ? launch_xc_edens_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
+                                              gga ? b.grad.d() : nullptr, e_out)
+                       : launch_xc_edens(s->stream, xc_type_index(s), gga, s->mix.c, s->quirks, ngrid, a.rho.d(), a.sigma.d(), a.grad.d(), e_out);
+    return hip_ok(s, e, E.launch);
 }
 
 // sum_g f_g D_B cell_g (DFT_BeckeWeightGradient, becke.hip).  The tables a_CD = clamp((rad_D / rad_C - rad_C / rad_D) / 4,
@@ -2416,8 +2358,12 @@ int DFT_ComputeXCGradient(XCSolver *s, long long ngrid, int nao, unsigned long l
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_gradient(s, 1, (long)ngrid, nao, (const double *)d_dm, nullptr, (const double *)d_ao, (const double *)d_weights,
-                       (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+    static const XcgEntry E{"DFT_ComputeXCGradient", "DFT_ComputeXCGradient needs dm, the AO values, the grid weights and the output",
+                            "hipMalloc(Dsym)", "hipMalloc(gradient slabs)", "XC gradient density launch", "XC gradient pointwise launch",
+                            "xc_points", 1, false};
+    const double *const dm[2] = {(const double *)d_dm, nullptr};
+    return xc_gradient(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_weights, (const double *)d_ao_grad,
+                       (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
 }
 
 int DFT_ComputeXCGradientSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
@@ -2426,26 +2372,13 @@ int DFT_ComputeXCGradientSpin(XCSolver *s, long long ngrid, int nao, unsigned lo
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_gradient(s, 2, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
-                       (const double *)d_weights, (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
-}
-
-int DFT_ComputeXCEnergyDensity(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
-                               unsigned long long d_ao_grad, unsigned long long d_e_out)
-{
-    if (!s) return -1;
-    DeviceGuard dg(s);
-    return xc_energy_density(s, 1, (long)ngrid, nao, (const double *)d_dm, nullptr, (const double *)d_ao, (const double *)d_ao_grad,
-                             (double *)d_e_out) ? 0 : -1;
-}
-
-int DFT_ComputeXCEnergyDensitySpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
-                                   unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_e_out)
-{
-    if (!s) return -1;
-    DeviceGuard dg(s);
-    return xc_energy_density(s, 2, (long)ngrid, nao, (const double *)d_dm_a, (const double *)d_dm_b, (const double *)d_ao,
-                             (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
+    static const XcgEntry E{"DFT_ComputeXCGradientSpin",
+                            "DFT_ComputeXCGradientSpin needs both density matrices, the AO values, the grid weights and the output",
+                            "hipMalloc(Dsym of both spins)", "hipMalloc(spin gradient slabs)", "spin gradient: density launch",
+                            "spin pointwise launch", "xc_points_spin", 2, false};
+    const double *const dm[2] = {(const double *)d_dm_a, (const double *)d_dm_b};
+    return xc_gradient(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_weights, (const double *)d_ao_grad,
+                       (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
 }
 
 int DFT_ComputeXCGradientMeta(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
@@ -2454,8 +2387,38 @@ int DFT_ComputeXCGradientMeta(XCSolver *s, long long ngrid, int nao, unsigned lo
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_gradient_meta(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_weights,
-                            (const double *)d_ao_grad, (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+    static const XcgEntry E{"DFT_ComputeXCGradientMeta",
+                            "DFT_ComputeXCGradientMeta needs dm, the AO values, the grid weights, ao_grad (tau is made of the gradient planes), "
+                            "ao_hess and the output: a pointer is null",
+                            "hipMalloc(meta gradient Dsym)", "hipMalloc(meta gradient slabs)", "meta gradient: density launch",
+                            "meta pointwise launch", "xc_points_meta", 1, true};
+    const double *const dm[2] = {(const double *)d_dm, nullptr};
+    return xc_gradient(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_weights, (const double *)d_ao_grad,
+                       (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+}
+
+int DFT_ComputeXCEnergyDensity(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
+                               unsigned long long d_ao_grad, unsigned long long d_e_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    static const XcgEntry E{"DFT_ComputeXCEnergyDensity", "DFT_ComputeXCEnergyDensity needs dm, the AO values and the output",
+                            "hipMalloc(Dsym)", nullptr, "energy density: density launch", "energy density launch", "xc_edens", 1, false};
+    const double *const dm[2] = {(const double *)d_dm, nullptr};
+    return xc_energy_density(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
+}
+
+int DFT_ComputeXCEnergyDensitySpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                                   unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_e_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    static const XcgEntry E{"DFT_ComputeXCEnergyDensitySpin",
+                            "DFT_ComputeXCEnergyDensitySpin needs both density matrices, the AO values and the output",
+                            "hipMalloc(Dsym of both spins)", nullptr, "spin energy density: density launch", "spin energy density launch",
+                            "xc_edens_spin", 2, false};
+    const double *const dm[2] = {(const double *)d_dm_a, (const double *)d_dm_b};
+    return xc_energy_density(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
 }
 
 int DFT_ComputeXCEnergyDensityMeta(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
@@ -2463,8 +2426,13 @@ int DFT_ComputeXCEnergyDensityMeta(XCSolver *s, long long ngrid, int nao, unsign
 {
     if (!s) return -1;
     DeviceGuard dg(s);
-    return xc_energy_density_meta(s, (long)ngrid, nao, (const double *)d_dm, (const double *)d_ao, (const double *)d_ao_grad,
-                                  (double *)d_e_out) ? 0 : -1;
+    static const XcgEntry E{"DFT_ComputeXCEnergyDensityMeta",
+                            "DFT_ComputeXCEnergyDensityMeta needs dm, the AO values, ao_grad (tau is made of the gradient planes) and the "
+                            "output: a pointer is null",
+                            "hipMalloc(meta gradient Dsym)", nullptr, "meta gradient: density launch", "meta energy density launch",
+                            "xc_edens_meta", 1, true};
+    const double *const dm[2] = {(const double *)d_dm, nullptr};
+    return xc_energy_density(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
 }
 
 int DFT_BeckeWeightGradient(XCSolver *s, long long ngrid, int natm, const double *atom_xyz, const double *atom_radius,

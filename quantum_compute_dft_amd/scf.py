@@ -715,6 +715,9 @@ class HipBackend:
     def ground_state_parts(self, dm, cocc, want_k):
         """(J, K or None, Vxc_raw) of a density, as numpy arrays: the parts of its Fock matrix."""
         self._response_check()
+        return self._ground_state_parts(dm, cocc, want_k)
+
+    def _ground_state_parts(self, dm, cocc, want_k):
         self.set_state(dm, cocc)
         J, K, _, V, _, _ = self.fock_parts(want_k)
         return J, K, V
@@ -783,23 +786,28 @@ class HipBackend:
         points and weights (DFT_ComputeXCGradientSpin), summed over slices of the grid exactly as xc_gradient does."""
         return self._xc_gradient_slices(slice_rows, self._xc_gradient_calls(dm_a, dm_b)[0])
 
-    def _xc_gradient_calls(self, *dms):
-        """(entry, edens): the library calls of a grid slice for one matrix (the closed shell) or two (an open-shell state):
-        entry(m, ao, w, d_out, gr, hs) the XC gradient, edens(m, ao, gr, d_e) the energy density, on the uploaded matrices."""
+    def _xc_gradient_calls(self, *dms, meta=False):
+        """(entry, edens): the library calls of a grid slice for one matrix (the closed shell; meta: of a meta-GGA, through
+        DFT_ComputeXCGradientMeta / DFT_ComputeXCEnergyDensityMeta) or two (an open-shell state): entry(m, ao, w, d_out, gr, hs)
+        the XC gradient, edens(m, ao, gr, d_e) the energy density, on the uploaded matrices.  The flag travels on the entry
+        (entry.meta): whoever runs it refuses a meta-GGA unless the entry is the meta-GGA's own."""
         if len(dms) == 2:
             self._uks_check()
         d, s = [self._dev(x) for x in dms], self.solver
-        grad, dens = (s.compute_xc_gradient_spin, s.compute_xc_energy_density_spin) if len(dms) == 2 else \
+        grad, dens = (s.compute_xc_gradient_meta, s.compute_xc_energy_density_meta) if meta else \
+                     (s.compute_xc_gradient_spin, s.compute_xc_energy_density_spin) if len(dms) == 2 else \
                      (s.compute_xc_gradient, s.compute_xc_energy_density)
-        return (lambda m, ao, w, out, gr, hs: grad(m, self.nao, *d, ao, w, out, gr, hs),
-                lambda m, ao, gr, e: dens(m, self.nao, *d, ao, e, gr))
+        entry = lambda m, ao, w, out, gr, hs: grad(m, self.nao, *d, ao, w, out, gr, hs)      # noqa: E731
+        entry.meta = meta
+        return entry, lambda m, ao, gr, e: dens(m, self.nao, *d, ao, e, gr)
 
-    def _xc_gradient_slices(self, slice_rows, entry, block=None, after=None, refuse_meta=True):
+    def _xc_gradient_slices(self, slice_rows, entry, block=None, after=None):
         """The slicing xc_gradient, xc_gradient_spin and xc_gradient_meta share: entry(m, ao, w, d_out, gr, hs) is the library
         call of a slice.  block = (lo, hi): the rows of the grid to sweep (default: all of it); after(lo, hi, ao, gr), when
         given, runs behind the entry of every slice on the same planes (the grid response takes the energy density there).
-        refuse_meta=False: the caller is the meta-GGA form (a meta solver always takes the Hessian planes)."""
-        if refuse_meta:
+        A meta-GGA is refused unless the entry says it is the meta-GGA form (entry.meta, _xc_gradient_calls; a meta solver
+        always takes the Hessian planes)."""
+        if not getattr(entry, "meta", False):
             functionals.refuse_meta(self.solver.functional, "the XC part of the nuclear gradient", functionals.META_GRADIENT_HINT)
         if self.world > 1:
             raise ValueError("the XC gradient runs on one rank: the grid of this backend is sharded over several")
@@ -861,9 +869,9 @@ class HipBackend:
         """xc_grid_response for an open-shell state: DFT_ComputeXCGradientSpin and DFT_ComputeXCEnergyDensitySpin per block."""
         return self._xc_grid_response(slice_rows, *self._xc_gradient_calls(dm_a, dm_b))
 
-    def _xc_grid_response(self, slice_rows, entry, edens, refuse_meta=True):
+    def _xc_grid_response(self, slice_rows, entry, edens):
         from . import basis, grid_gen
-        if refuse_meta:
+        if not entry.meta:
             functionals.refuse_meta(self.solver.functional, "the grid response of the nuclear gradient", functionals.META_GRADIENT_HINT)
         if self.world > 1:
             raise ValueError("the grid response runs on one rank: the grid of this backend is sharded over several")
@@ -892,7 +900,7 @@ class HipBackend:
 
         for lo, hi in zip(los, his):
             if hi > lo:
-                G = self._xc_gradient_slices(slice_rows, entry, block=(int(lo), int(hi)), after=after, refuse_meta=refuse_meta)
+                G = self._xc_gradient_slices(slice_rows, entry, block=(int(lo), int(hi)), after=after)
                 out[int(own[lo])] -= G.sum(axis=0)
         d_f = d_e[:self.ngrid] * t.as_tensor(w0, dtype=t.float64, device=self.dev)
         d_own = t.as_tensor(own.astype(np.int32), dtype=t.int32, device=self.dev)
@@ -909,30 +917,22 @@ class HipBackend:
             raise ValueError(f"{who} is the gradient of a meta-GGA (DFT_ComputeXCGradientMeta): {self.functional} is not one (it "
                              f"carries no tpss_x / tpss_c weight); its gradient is {who[:-5]}")
 
-    def _xc_gradient_meta_calls(self, dm):
-        """_xc_gradient_calls for a meta-GGA: DFT_ComputeXCGradientMeta and DFT_ComputeXCEnergyDensityMeta on the uploaded dm."""
-        d, s = self._dev(dm), self.solver
-        return (lambda m, ao, w, out, gr, hs: s.compute_xc_gradient_meta(m, self.nao, d, ao, w, out, gr, hs),
-                lambda m, ao, gr, e: s.compute_xc_energy_density_meta(m, self.nao, d, ao, e, gr))
-
     def xc_gradient_meta(self, dm, slice_rows=None):
         """xc_gradient for a meta-GGA: G (nao, 3) with the tau term (DFT_ComputeXCGradientMeta), summed over slices of the grid
         exactly as xc_gradient does.  Refuses what xc_gradient refuses but the meta-GGA, and a functional that is not one."""
         self._meta_gradient_check("xc_gradient_meta")
-        return self._xc_gradient_slices(slice_rows, self._xc_gradient_meta_calls(dm)[0], refuse_meta=False)
+        return self._xc_gradient_slices(slice_rows, self._xc_gradient_calls(dm, meta=True)[0])
 
     def xc_grid_response_meta(self, dm, slice_rows=None):
         """xc_grid_response for a meta-GGA: DFT_ComputeXCGradientMeta and DFT_ComputeXCEnergyDensityMeta per block."""
         self._meta_gradient_check("xc_grid_response_meta")
-        return self._xc_grid_response(slice_rows, *self._xc_gradient_meta_calls(dm), refuse_meta=False)
+        return self._xc_grid_response(slice_rows, *self._xc_gradient_calls(dm, meta=True))
 
     def ground_state_parts_meta(self, dm, cocc, want_k):
         """ground_state_parts for a meta-GGA (the Fock matrix of W in the gradient): set_state and fock_parts, which sweep through
         DFT_ComputeXCMeta.  ground_state_parts itself serves the response and keeps refusing a meta-GGA."""
         self._meta_gradient_check("ground_state_parts_meta")
-        self.set_state(dm, cocc)
-        J, K, _, V, _, _ = self.fock_parts(want_k)
-        return J, K, V
+        return self._ground_state_parts(dm, cocc, want_k)
 
     # ---- two-electron part of the nuclear gradient on the device (integrals.DeviceGrad2e): one rank ----------------
     def _grad2e_engine(self):

@@ -452,40 +452,40 @@ class DFTSolverWrapper:
         self._check()
         return rc
 
+    def _xc_gradient(self, fn, dms, ngrid, nao, d_ao, d_weights, d_out, d_ao_grad, d_ao_hess):
+        """The three gradient entries: `fn` takes the matrices `dms`, then ao, the weights, ao_grad, ao_hess and the output."""
+        rc = fn(self.solver, int(ngrid), int(nao), *(_u64(_ptr(d)) for d in (*dms, d_ao, d_weights, d_ao_grad, d_ao_hess, d_out)))
+        self._check()
+        return rc
+
+    def _xc_energy_density(self, fn, dms, ngrid, nao, d_ao, d_e_out, d_ao_grad):
+        """The three energy-density entries: `fn` takes the matrices `dms`, then ao, ao_grad and the output."""
+        rc = fn(self.solver, int(ngrid), int(nao), *(_u64(_ptr(d)) for d in (*dms, d_ao, d_ao_grad, d_e_out)))
+        self._check()
+        return rc
+
     def compute_xc_gradient(self, ngrid, nao, d_dm, d_ao, d_weights, d_out, d_ao_grad=None, d_ao_hess=None):
         """G (nao, 3) into d_out (DFT_ComputeXCGradient): the derivative of compute_xc's Exc by the centre of every basis
         function at fixed points and weights; asynchronous on the solver's stream.  d_ao_hess may be None for an
         LDA-class functional."""
-        rc = self.lib.DFT_ComputeXCGradient(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
-                                            _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
-        self._check()
-        return rc
+        return self._xc_gradient(self.lib.DFT_ComputeXCGradient, [d_dm], ngrid, nao, d_ao, d_weights, d_out, d_ao_grad, d_ao_hess)
 
     def compute_xc_gradient_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_weights, d_out, d_ao_grad=None, d_ao_hess=None):
         """G (nao, 3) into d_out (DFT_ComputeXCGradientSpin): the derivative of compute_xc_spin's Exc by the centre of every
         basis function at fixed points and weights; asynchronous on the solver's stream.  d_ao_hess may be None for an
         LDA-class functional.  With option quirks = 1 a functional with vwn5_c or pbe_c is refused, as by compute_xc_spin."""
-        rc = self.lib.DFT_ComputeXCGradientSpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)), _u64(_ptr(d_ao)),
-                                                _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
-        self._check()
-        return rc
+        return self._xc_gradient(self.lib.DFT_ComputeXCGradientSpin, [d_dm_a, d_dm_b], ngrid, nao, d_ao, d_weights, d_out, d_ao_grad, d_ao_hess)
 
     def compute_xc_energy_density(self, ngrid, nao, d_dm, d_ao, d_e_out, d_ao_grad=None):
         """e_g, the energy per volume of the functional at the density of d_dm, into d_e_out (ngrid) without the weight
         (DFT_ComputeXCEnergyDensity): sum_g w_g e_g is compute_xc's Exc.  The body, cut-offs, quirks and mix weights of the
         sweep's pointwise kernel; asynchronous on the solver's stream."""
-        rc = self.lib.DFT_ComputeXCEnergyDensity(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
-                                                 _u64(_ptr(d_ao_grad)), _u64(_ptr(d_e_out)))
-        self._check()
-        return rc
+        return self._xc_energy_density(self.lib.DFT_ComputeXCEnergyDensity, [d_dm], ngrid, nao, d_ao, d_e_out, d_ao_grad)
 
     def compute_xc_energy_density_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_e_out, d_ao_grad=None):
         """e_g of the spin density matrices d_dm_a / d_dm_b into d_e_out (DFT_ComputeXCEnergyDensitySpin): sum_g w_g e_g is
         compute_xc_spin's Exc.  With option quirks = 1 a functional with vwn5_c or pbe_c is refused, as by compute_xc_spin."""
-        rc = self.lib.DFT_ComputeXCEnergyDensitySpin(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm_a)), _u64(_ptr(d_dm_b)),
-                                                     _u64(_ptr(d_ao)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_e_out)))
-        self._check()
-        return rc
+        return self._xc_energy_density(self.lib.DFT_ComputeXCEnergyDensitySpin, [d_dm_a, d_dm_b], ngrid, nao, d_ao, d_e_out, d_ao_grad)
 
     def _declare_meta_gradient(self):
         L = self.lib
@@ -497,26 +497,19 @@ class DFTSolverWrapper:
         L.DFT_ComputeXCGradientMeta.restype = ctypes.c_int
         L.DFT_ComputeXCEnergyDensityMeta.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + [_u64] * 4
         L.DFT_ComputeXCEnergyDensityMeta.restype = ctypes.c_int
+        return L
 
     def compute_xc_gradient_meta(self, ngrid, nao, d_dm, d_ao, d_weights, d_out, d_ao_grad=None, d_ao_hess=None):
         """G (nao, 3) into d_out (DFT_ComputeXCGradientMeta): the derivative of compute_xc_meta's Exc by the centre of every
         basis function at fixed points and weights, the tau term included (gradients.xc_gradient_meta_host is its host
         counterpart); a solver with meta weights, d_ao_grad and d_ao_hess always.  Option xcg_meta_fused chooses the one-pass
         kernel (1) or the plain form (0).  Asynchronous on the solver's stream."""
-        self._declare_meta_gradient()
-        rc = self.lib.DFT_ComputeXCGradientMeta(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
-                                                _u64(_ptr(d_weights)), _u64(_ptr(d_ao_grad)), _u64(_ptr(d_ao_hess)), _u64(_ptr(d_out)))
-        self._check()
-        return rc
+        return self._xc_gradient(self._declare_meta_gradient().DFT_ComputeXCGradientMeta, [d_dm], ngrid, nao, d_ao, d_weights, d_out, d_ao_grad, d_ao_hess)
 
     def compute_xc_energy_density_meta(self, ngrid, nao, d_dm, d_ao, d_e_out, d_ao_grad=None):
         """e_g of a meta-GGA at the density and tau of d_dm into d_e_out (ngrid) without the weight
         (DFT_ComputeXCEnergyDensityMeta): sum_g w_g e_g is compute_xc_meta's Exc.  Asynchronous on the solver's stream."""
-        self._declare_meta_gradient()
-        rc = self.lib.DFT_ComputeXCEnergyDensityMeta(self.solver, int(ngrid), int(nao), _u64(_ptr(d_dm)), _u64(_ptr(d_ao)),
-                                                     _u64(_ptr(d_ao_grad)), _u64(_ptr(d_e_out)))
-        self._check()
-        return rc
+        return self._xc_energy_density(self._declare_meta_gradient().DFT_ComputeXCEnergyDensityMeta, [d_dm], ngrid, nao, d_ao, d_e_out, d_ao_grad)
 
     def becke_weight_gradient(self, ngrid, atom_xyz, atom_radius, d_coords, d_owner, d_f, d_out, d_cell_out=None):
         """sum_g f_g D_B cell_g into d_out (natm, 3) (DFT_BeckeWeightGradient; grid_gen.becke_weight_gradient_host is its

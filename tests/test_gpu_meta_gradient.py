@@ -15,7 +15,10 @@ differences of metagga.xc_meta_host's Exc.
   pointwise bodies that agree to rounding).
 * DFT_ComputeXCEnergyDensityMeta against the host 1e-12 of max|e|; sum w e against DFT_ComputeXCMeta's Exc 1e-12.
 * DFT_ComputeXCMeta, DFT_ComputeXCGradient and DFT_ComputeXC bitwise what they were before a call of the new entries.
-* The refusals, each with its sentence.
+* The six gradient-side entries interleaved on one solver with zero meta weights, through shapes that grow and shrink their
+  shared buffers, in both settings of the two fused options, and a TPSS solver's two around DFT_ComputeXCMetaSpin: each
+  result bitwise a fresh solver's.
+* The refusals, each with its sentence; of two faults in one call, the first in the order include/dft_solver.h states.
 * nuclear_gradient(meta=True) on HipBackend, TPSS, H2O/def2-SVP, against the host assembly from the same dm: 2e-8 of max|g|.
 * The driver: --optimize --meta-gradient --grid-response --grad2e device relaxes H2O/STO-3G TPSS, every step through the flag.
 
@@ -267,6 +270,65 @@ def test_the_other_entries_are_left_as_they_were(dev, shape, fused):
     assert np.array_equal(G, p.gradient(m))        # ... and the sweep in between left the gradient entry's own buffers alone
 
 
+def test_the_shared_gradient_set_carries_nothing_between_users(dev):
+    """The six gradient-side entries work in one set of buffers of the solver.  A DFT_CreateSolverMeta solver with zero meta
+    weights (PBE0 at quirks = 0: the one kind that may call all six) runs them interleaved, in another order on every pass so
+    that each follows several different ones, over shapes that reserve the buffers small, grow them and come back -- (37, 50),
+    (2085, 114) the wave-specialised plan, (1100, 130) chunked K past 128 with a ragged nao, (37, 50) -- in both settings of
+    xcg_spin_fused and xcg_meta_fused; a TPSS solver runs its two entries around a DFT_ComputeXCMetaSpin call in the same way.
+    Each result is bitwise what the same call gives on a fresh solver that has run nothing else."""
+    def calls(p):
+        d_a, d_b = (0.6 * p.d_dm).contiguous(), (0.4 * p.d_dm).contiguous()
+
+        def gradient_spin(s):
+            d_out = torch.full((p.nao, 3), 7.0, dtype=torch.float64, device=dev)
+            assert s.compute_xc_gradient_spin(p.ngrid, p.nao, d_a, d_b, p.d_ao, p.d_w, d_out, p.d_gr, p.d_hs) == 0
+            torch.cuda.synchronize()
+            return d_out.cpu().numpy()
+
+        def edens(s, name, *dms):
+            d_e = torch.full((p.ngrid,), 7.0, dtype=torch.float64, device=dev)
+            assert getattr(s, name)(p.ngrid, p.nao, *dms, p.d_ao, d_e, p.d_gr) == 0
+            torch.cuda.synchronize()
+            return d_e.cpu().numpy()
+
+        def meta_spin(s):
+            va, vb = (torch.full((p.nao, p.nao), 7.0, dtype=torch.float64, device=dev) for _ in range(2))
+            exc = s.compute_xc_meta_spin(p.ngrid, p.nao, d_a, d_b, p.d_ao, p.d_w, va, vb, p.d_gr)
+            torch.cuda.synchronize()
+            return np.array([exc]), va.cpu().numpy(), vb.cpu().numpy()
+
+        six = {"gradient": lambda s: p.gradient(s, entry="compute_xc_gradient"), "gradient_spin": gradient_spin, "gradient_meta": p.gradient,
+               "edens": lambda s: edens(s, "compute_xc_energy_density", p.d_dm),
+               "edens_spin": lambda s: edens(s, "compute_xc_energy_density_spin", d_a, d_b), "edens_meta": p.edens}
+        return six, {"gradient_meta": p.gradient, "meta_spin": meta_spin, "edens_meta": p.edens}
+
+    def same(x, y):
+        x, y = (a if isinstance(a, tuple) else (a,) for a in (x, y))
+        return len(x) == len(y) and all(np.array_equal(a, b) and np.all(np.isfinite(a)) for a, b in zip(x, y))
+
+    used = {"zero": _zero_meta_solver("PBE0"), "TPSS": _solver("TPSS")}
+    fresh = {"zero": lambda: _zero_meta_solver("PBE0"), "TPSS": lambda: _solver("TPSS")}
+    rng = np.random.default_rng(11)
+    followed, last = {}, None
+    for shape in ((37, 50), (2085, 114), (1100, 130), (37, 50)):
+        p = Planes(dev, shape)
+        six, tpss = calls(p)
+        for fused in (1, 0):
+            opts = dict(xcg_spin_fused=fused, xcg_meta_fused=fused)
+            for kind, table in (("zero", six), ("TPSS", tpss)):
+                for name in rng.permutation(sorted(table)):
+                    f = fresh[kind]()
+                    for s in (used[kind], f):
+                        for k, v in opts.items():
+                            s.set_option(k, v)
+                    assert same(table[name](used[kind]), table[name](f)), (shape, fused, kind, name)
+                    if kind == "zero":
+                        followed.setdefault(name, set()).add(last)
+                        last = name
+    assert all(len(v - {None, k}) >= 3 for k, v in followed.items()), followed     # each entry behind at least three others
+
+
 # ---- f. refusals --------------------------------------------------------------------------------------------------------
 def test_refusals(dev):
     p = Planes(dev, (37, 50))
@@ -289,6 +351,17 @@ def test_refusals(dev):
                 entry(_solver(functional, quirks=1))
         assert entry(_solver("tpss_x + pbe_c", quirks=0)) == 0
         assert entry(_solver("TPSS", quirks=1)) == 0          # TPSS itself runs at either setting
+        # Two faults in one call: the first in the order include/dft_solver.h states for the six gradient-side entries, one
+        # case per adjacent pair of those a meta entry can meet (ao_grad and ao_hess are among its pointers; the device ends
+        # the order: tests/test_meta_gradient_cpu.py, where there is none)
+        with pytest.raises(RuntimeError, match=f"{name} needs a solver made by DFT_CreateSolverMeta"):     # the kind, a null pointer
+            entry(_solver("GGA"), dm=None)
+        with pytest.raises(RuntimeError, match=f"{name} needs .*a pointer is null"):                       # a null pointer, the sizes
+            entry(s, gr=None, ng=0)
+        with pytest.raises(RuntimeError, match="bad sizes"):                                               # the sizes, quirks = 1
+            entry(_solver("tpss_x + pbe_c", quirks=1), n=0)
+    with pytest.raises(RuntimeError, match="quirks = 1.*not the derivatives of their energies"):           # quirks = 1, the LDS request
+        grad(_solver("tpss_x + pbe_c", quirks=1), n=1700)
     for kw in ({"hs": None}, {"w": None}, {"out": None}):
         with pytest.raises(RuntimeError, match="DFT_ComputeXCGradientMeta needs .*a pointer is null"):
             grad(s, **kw)

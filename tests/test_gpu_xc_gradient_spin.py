@@ -202,3 +202,22 @@ def test_refusals(dev):
     s.set_option("quirks", 1)
     assert s.compute_xc_gradient_spin(*args, p.d_gr, p.d_hs) == 0
     torch.cuda.synchronize()
+    # Two faults in one call: the first in the order include/dft_solver.h states for the six gradient-side entries, one case
+    # per adjacent pair (the LDS request and the device end it: tests/test_meta_gradient_cpu.py, where there is no device)
+    nodm = (37, 50, None, p.d_b, p.d_ao, p.d_w, d_out)
+    with pytest.raises(RuntimeError, match="meta-GGA.*this entry would drop it"):       # the solver's kind, a null pointer
+        _solver("TPSS").compute_xc_gradient_spin(*nodm, p.d_gr, p.d_hs)
+    with pytest.raises(RuntimeError, match="needs both density matrices"):              # a null pointer, the sizes
+        _solver("GGA").compute_xc_gradient_spin(0, 50, None, p.d_b, p.d_ao, p.d_w, d_out, p.d_gr, p.d_hs)
+    with pytest.raises(RuntimeError, match="bad sizes"):                                # the sizes, ao_grad of a gradient solver
+        _solver("GGA").compute_xc_gradient_spin(0, 50, p.d_a, p.d_b, p.d_ao, p.d_w, d_out, None, p.d_hs)
+    with pytest.raises(RuntimeError, match="ao_grad pointer is null"):                  # ao_grad, ao_hess of a gradient solver
+        _solver("GGA").compute_xc_gradient_spin(*args, None, None)
+    with pytest.raises(RuntimeError, match="ao_hess pointer is null"):                  # ao_hess, quirks = 1
+        _solver("GGA", quirks=1).compute_xc_gradient_spin(*args, p.d_gr, None)
+    with pytest.raises(RuntimeError, match="needs ao_grad"):                            # ao_grad of an LDA solver, quirks = 1
+        _solver("LDA", quirks=1).compute_xc_gradient_spin(*args, None, None)
+    with pytest.raises(RuntimeError, match="first derivatives of the energy"):          # quirks = 1, the LDS request
+        _solver("GGA", quirks=1).compute_xc_gradient_spin(37, 1700, p.d_a, p.d_b, p.d_ao, p.d_w, d_out, p.d_gr, p.d_hs)
+    with pytest.raises(RuntimeError, match="bytes of LDS per workgroup"):               # ... which alone is refused too, before any launch
+        _solver("GGA").compute_xc_gradient_spin(37, 1700, p.d_a, p.d_b, p.d_ao, p.d_w, d_out, p.d_gr, p.d_hs)
