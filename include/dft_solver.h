@@ -340,17 +340,17 @@ int DFT_FxcApplyKind(XCSolver *solver, long long ngrid, int nao, unsigned long l
  * DFT_FxcApplySpinPol) work in one set of buffers of the solver, in stream order, each call writing whole what it reads:
  * no result of one depends on what another left there, and no recorded graph or prepared table holds any of them.
  *
- * The six gradient-side entries further down -- DFT_ComputeXCGradient / DFT_ComputeXCGradientSpin / DFT_ComputeXCGradientMeta and
- * DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin / DFT_ComputeXCEnergyDensityMeta -- are likewise one gradient path
+ * The eight gradient-side entries further down -- DFT_ComputeXCGradient / DFT_ComputeXCGradientSpin / DFT_ComputeXCGradientMeta /
+ * DFT_ComputeXCGradientMetaSpin and DFT_ComputeXCEnergyDensity / DFT_ComputeXCEnergyDensitySpin / DFT_ComputeXCEnergyDensityMeta /
+ * DFT_ComputeXCEnergyDensityMetaSpin -- are likewise one gradient path
  * and one energy-density path over (spins, meta) with one density stage (xc_gradient, xc_energy_density, xcg_density,
- * csrc/dft_api.hip).  Where a call has more than one fault, all six refuse in this order: the solver's kind (a meta entry on a
+ * csrc/dft_api.hip).  Where a call has more than one fault, all eight refuse in this order: the solver's kind (a meta entry on a
  * solver without meta weights; any other on one with a non-zero meta weight), a null pointer ("... needs ..."; ao_grad and
- * ao_hess count here for the meta pair only), bad sizes, a null ao_grad on a gradient solver ("ao_grad pointer is null"), for
+ * ao_hess count here for the meta entries only), bad sizes, a null ao_grad on a gradient solver ("ao_grad pointer is null"), for
  * the gradients a null ao_hess on a gradient solver ("ao_hess pointer is null") and a null ao_grad on any other ("... needs
  * ao_grad"), the "quirks" case (every entry but the two closed-shell non-meta ones), for the gradients an LDS request above
  * 160 KB, and last no usable device: a caller without a device still learns every fault of its arguments.  Nothing has touched
- * the device by then.  Two spins with tau -- the gradient of an open-shell meta-GGA -- have no kernel and no entry; the shared
- * path refuses the pair in one place (xcg_enter).  The six work in one set of buffers of the solver of their own -- the planes
+ * the device by then.  The eight work in one set of buffers of the solver of their own -- the planes
  * and the padded matrix of each spin, tau and its coefficient plane, the slabs of the contraction -- in stream order: an entry
  * reserves what it uses at the size of its call, every call writes whole what it reads, so no result of one depends on what
  * another left there (each is bitwise what a fresh solver gives), and no recorded graph and no prepared table holds any of them. */
@@ -540,6 +540,36 @@ int DFT_ComputeXCGradientMeta(XCSolver *solver, long long ngrid, int nao, unsign
 int DFT_ComputeXCEnergyDensityMeta(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_ptr,
                                    unsigned long long d_ao_ptr, unsigned long long d_ao_grad_ptr,
                                    unsigned long long d_e_out_ptr);
+
+/* The same at two spin densities (csrc/xc_grad_meta_spin.hip): the XC part of the nuclear gradient of an open-shell meta-GGA.
+ * DFT_ComputeXCGradientMetaSpin: d_out (nao, 3) receives G of the Exc DFT_ComputeXCMetaSpin returns, under the same column
+ * replacement.  With the coefficients of the spin point as "xc_points_meta_spin" writes them (one-sided, ct_s = w e_tau_s / 2),
+ * Ds_s the symmetric part of dm_s and Y_sk = (d_k AO) Ds_s,
+ *     G[mu, x] = sum_s { G_gga[mu, x; c_s0..c_s3, Ds_s] - 2 sum_g ct_s sum_k hess_xk[g, mu] Y_sk[g, mu] }.
+ * Order of work on the solver's stream: the sweep's density kernels once per spin, the padded symmetric matrices, the tau
+ * stage of the open-shell sweep on them ("tau_spin", or "tau x2" with option "tau_spin_fused" = 0), "xc_points_meta_spin",
+ * then the contraction in the form option "xcg_meta_spin_fused" chooses -- 1 (the default: the faster form as measured,
+ * profiles/xc_gradient_meta_spin_time.txt): k_xc_grad_meta_spin, both spins in one pass over the ten planes, six staged
+ * tiles and ten products per step on two loads of the matrices; 0: per spin k_xc_grad on c_s0..c_s3 and k_xc_grad_meta<false> (the tau term), four slab sets and one
+ * fixed-order sum over them, the plain form the fused kernel is tested against.  With both meta weights zero the tau stage and
+ * the tau term are left out and the contraction is DFT_ComputeXCGradientSpin's of the same mix, honouring "xcg_spin_fused".
+ * No atomics: a call is bitwise reproducible.  Asynchronous, never the one-kernel plan, never a recorded graph; it works in
+ * the gradient entries' one set (see DFT_ComputeXCSpin), so later sweeps, the other gradient-side entries and prepared
+ * DFT_Fxc* tables are bit for bit what they were.
+ * DFT_ComputeXCEnergyDensityMetaSpin: d_e_out (ngrid) receives the energy per volume of the spin meta point WITHOUT the
+ * weight (density stage and "tau" as above, then "xc_edens_meta_spin"; a channel below the density cut-off is absent as in
+ * the sweep): sum_g w_g e_g is DFT_ComputeXCMetaSpin's Exc.
+ * Both return 0, or -1 with DFT_GetLastError, before any launch: a solver without meta weights, a null pointer (ao_grad
+ * and ao_hess included), bad sizes, "quirks" = 1 with vwn5_c / pbe_c, and a basis whose tiles do not fit 160 KB of LDS
+ * (nao above 1616 in the fused form, above 1328 in the plain one, whose k_xc_grad tiles are the wider); several faults in one
+ * call: the order stated at DFT_ComputeXCSpin. */
+int DFT_ComputeXCGradientMetaSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr,
+                                  unsigned long long d_dm_b_ptr, unsigned long long d_ao_ptr, unsigned long long d_weights_ptr,
+                                  unsigned long long d_ao_grad_ptr, unsigned long long d_ao_hess_ptr,
+                                  unsigned long long d_out_ptr);
+int DFT_ComputeXCEnergyDensityMetaSpin(XCSolver *solver, long long ngrid, int nao, unsigned long long d_dm_a_ptr,
+                                       unsigned long long d_dm_b_ptr, unsigned long long d_ao_ptr,
+                                       unsigned long long d_ao_grad_ptr, unsigned long long d_e_out_ptr);
 
 /* Grid response of the nuclear gradient (csrc/becke.hip): what the derivative at fixed points and weights leaves out.
  * With Exc = sum_g w0_g cell_g e_g -- w0 the atomic radial x angular weight, cell_g = P_own(r_g) / sum_C P_C(r_g) the
@@ -752,7 +782,9 @@ void DFT_ScfTailClose(void *handle);
  * A recorded graph always ends with the kernel), "xcg_spin_fused" (DFT_ComputeXCGradientSpin: 1, default = both spins in
  * one k_xc_grad launch; 0 = k_xc_grad once per spin, the plain form the tests hold it to), "xcg_meta_fused"
  * (DFT_ComputeXCGradientMeta: 1, default = k_xc_grad_meta<true>, one pass, the faster form as measured; 0 = k_xc_grad and
- * the tau-term kernel, the plain form the tests hold it to).
+ * the tau-term kernel, the plain form the tests hold it to), "xcg_meta_spin_fused" (DFT_ComputeXCGradientMetaSpin: 1, default =
+ * k_xc_grad_meta_spin, both spins in one pass, the faster form as measured; 0 = the plain pair once per spin, the form the
+ * tests hold it to).
  * Returns 0 if the key is known. */
 int DFT_SetOption(XCSolver *solver, const char *key, double value);
 

@@ -26,8 +26,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdft.so")
 STAMP_PATH = LIB_PATH + ".srchash"
-SOURCES = ["dft_api.hip", "xc_occ.hip", "eri_cols.hip", "scf_tail.hip", "xc_tiny.hip", "point_coulomb.hip", "dm_factor.hip", "xc_response.hip", "xc_spin.hip", "xc_response_pol.hip", "xc_grad.hip", "grad2e.hip", "becke.hip", "xc_meta.hip", "xc_meta_spin.hip", "xc_grad_meta.hip"]   # one object each, compiled in parallel, linked into libdft.so
-HEADERS = ["xc_functionals.hpp", "xc_spin_functionals.hpp", "xc_meta_functionals.hpp", "xc_meta_launch.hpp", "xc_meta_spin_launch.hpp", "xc_grad_meta_launch.hpp", "xc_kernels.hpp", "xc_ws_kernels.hpp", "xc_big_kernels.hpp",
+SOURCES = ["dft_api.hip", "xc_occ.hip", "eri_cols.hip", "scf_tail.hip", "xc_tiny.hip", "point_coulomb.hip", "dm_factor.hip", "xc_response.hip", "xc_spin.hip", "xc_response_pol.hip", "xc_grad.hip", "grad2e.hip", "becke.hip", "xc_meta.hip", "xc_meta_spin.hip", "xc_grad_meta.hip", "xc_grad_meta_spin.hip"]   # one object each, compiled in parallel, linked into libdft.so
+HEADERS = ["xc_functionals.hpp", "xc_spin_functionals.hpp", "xc_meta_functionals.hpp", "xc_meta_launch.hpp", "xc_meta_spin_launch.hpp", "xc_grad_meta_launch.hpp", "xc_grad_meta_spin_launch.hpp", "xc_kernels.hpp", "xc_ws_kernels.hpp", "xc_big_kernels.hpp",
            "xc_occ_kernels.hpp", "xc_occ_launch.hpp", "xc_tiny_kernels.hpp", "xc_tiny_launch.hpp", "dm_factor_launch.hpp", "xc_response_launch.hpp", "xc_response_pol_launch.hpp", "xc_spin_launch.hpp", "xc_grad_launch.hpp", "becke_launch.hpp", "jk_kernels.hpp", "ao_kernels.hpp", "cd_kernels.hpp", "cd_response_kernels.hpp", "device_util.hpp", "md_device.hpp",
            os.path.join("..", "..", "include", "dft_solver.h")]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950's register file is unified);

@@ -38,6 +38,7 @@
 #include "xc_meta_launch.hpp"
 #include "xc_meta_spin_launch.hpp"
 #include "xc_grad_meta_launch.hpp"
+#include "xc_grad_meta_spin_launch.hpp"
 
 using namespace qcdft;
 
@@ -185,10 +186,12 @@ struct XCSolver {
     // writes whole what it reads.  No recorded sweep and no prepared response table holds or reads any of them.
     Planes sync_ws[2];
     DevBuf sync_tau, sync_ct, sync_dp, sync_slabs, sync_vtmp, sync_exc;
-    // The six gradient-side entries -- DFT_ComputeXCGradient / Spin / Meta and DFT_ComputeXCEnergyDensity / Spin / Meta -- work in
+    // The eight gradient-side entries -- DFT_ComputeXCGradient / Spin / Meta / MetaSpin and DFT_ComputeXCEnergyDensity / Spin / Meta /
+    // MetaSpin -- work in
     // one set of their own, in stream order: the planes of each spin (a closed-shell call uses [0]; sigma and the Exc partials,
     // which nobody reads, with [0] alone), the padded matrix of each spin (NP^2 apart) that k_xc_grad and k_tau read -- every
-    // entry symmetrises into it, none into the shared Dsym -- tau and its coefficient plane (meta entries), and the slabs of the
+    // entry symmetrises into it, none into the shared Dsym -- tau and its coefficient plane (meta entries; beta's ngrid after
+    // alpha's), and the slabs of the
     // contraction (as many as the call's form writes).  An entry reserves what it uses at the size of its call, and every call
     // writes whole what it reads.  No recorded sweep and no prepared response table holds or reads any of them.
     Planes xcg[2];
@@ -213,6 +216,11 @@ struct XCSolver {
     // (0.90 x / 0.80 x of the plain form at 143 556 x 114 / 60 000 x 494, TPSS: profiles/xc_gradient_meta_time.txt); 0: k_xc_grad on
     // c0..c3 and k_xc_grad_meta<false> (the tau term) into two slab sets and one sum, what the tests hold the fused kernel to
     int xcg_meta_fused = 1;
+    // The contraction of DFT_ComputeXCGradientMetaSpin.  1 (default): k_xc_grad_meta_spin, both spins in one pass over the ten planes
+    // (0.65 x / 0.59 x of the plain form at 143 556 x 114 / 60 000 x 494, TPSS: profiles/xc_gradient_meta_spin_time.txt); 0: per spin
+    // k_xc_grad on c0..c3 and k_xc_grad_meta<false> (the tau term) into four slab sets and one sum, what the tests hold the fused
+    // kernel to
+    int xcg_meta_spin_fused = 1;
     std::vector<double> becke_tab_host;
     std::string last_error;
     std::vector<Timing> timings;
@@ -1510,7 +1518,7 @@ __global__ void k_accumulate_chunk(long n2, int add, const double *__restrict__ 
     if (i == 0) *e = add ? *e + *ec : *ec;
 }
 
-// What tells the six gradient-side entries apart: the entry's name, its sentence for a null pointer, what a failed allocation
+// What tells the eight gradient-side entries apart: the entry's name, its sentence for a null pointer, what a failed allocation
 // of the padded matrices and of the slabs and a failed density or pointwise launch are called, the timer label of that
 // pointwise kernel (the closed-shell gradient's is launch_xc_points' own), the number of spins and whether the entry forms
 // tau.  A meta entry counts ao_grad and ao_hess among the pointers of `needs`; the others name them in sentences of their own.
@@ -1520,8 +1528,8 @@ struct XcgEntry {
     bool meta;
 };
 
-// What the six refuse first, in this order for every entry: the solver's kind, two spins with tau (no kernel takes them:
-// no entry asks), a null pointer, the sizes and a null ao_grad on a gradient-corrected solver (sizes_ok), for a gradient a
+// What the eight refuse first, in this order for every entry: the solver's kind, a null pointer, the sizes and a null ao_grad
+// on a gradient-corrected solver (sizes_ok), for a gradient a
 // null ao_hess on such a solver and a null ao_grad on any other, then quirks = 1 where the potentials are derivatives of the
 // energy.  The callers go on with the LDS request (a gradient) and, last, the device: every fault of the arguments can be
 // told apart from "no usable HIP device", and nothing has touched the device by then.
@@ -1529,10 +1537,6 @@ bool xcg_enter(XCSolver *s, const XcgEntry &E, bool gradient, long ngrid, int na
                const double *w, const double *ao_grad, const double *ao_hess, const double *out)
 {
     if (!enter_kind(s, 0, E.meta ? E.who : nullptr)) return false;
-    if (E.meta && E.nspin == 2) {
-        set_error(s, "%s: the open-shell meta-GGA gradient is not built (no kernel takes two spins and tau)", E.who);
-        return false;
-    }
     bool ptrs = ao && out && (w || !gradient) && (!E.meta || (ao_grad && (ao_hess || !gradient)));
     for (int sp = 0; sp < E.nspin; ++sp) ptrs = ptrs && dm[sp];
     if (!ptrs) {
@@ -1557,10 +1561,11 @@ bool reserve_xcg(XCSolver *s, const XcgEntry &E, const SweepPlan &P, long ngrid,
                         (!(parts & WS_COEF) || reserve(s, s->xcg_ct, ng, "hipMalloc(meta gradient tau coefficient)", false))));
 }
 
-// The density stage the six share: the sweep's density kernels with the sweep's choices on each spin's matrix into that
+// The density stage the eight share: the sweep's density kernels with the sweep's choices on each spin's matrix into that
 // spin's planes; the padded symmetric matrix of each spin where something reads it back (`keep_dp`: k_xc_grad and k_tau do.
 // The wave-specialised density kernel symmetrises dm itself, so k_sym_dm runs here on that plan; the other plans leave the
-// matrix behind); and for a meta entry k_tau on that matrix -- compute_tau's launch half, without its second
+// matrix behind); and for a meta entry k_tau (two spins: k_tau_spin or, with "tau_spin_fused" = 0, k_tau once per spin) on
+// that matrix -- compute_tau's launch half, without its second
 // symmetrisation -- or, with both meta weights zero, the plane of zeros the pointwise kernels read.
 bool xcg_density(XCSolver *s, const XcgEntry &E, const SweepPlan &P, bool keep_dp, long ngrid, int nao, const double *const dm[2],
                  const double *ao, const double *ao_grad)
@@ -1578,27 +1583,33 @@ bool xcg_density(XCSolver *s, const XcgEntry &E, const SweepPlan &P, bool keep_d
     if (!E.meta) return true;
     double *const tau[2] = {s->xcg_tau.d(), s->xcg_tau.d() + ng};
     if (!s->meta_active) return hip_ok(s, hipMemsetAsync(tau[0], 0, sizeof(double) * E.nspin * ng, s->stream), "clear tau");
-    const TauPlan tp = tau_plan(s->num_cu, ngrid, nao);   // tp.NP = P.NP
-    ScopedTimer t(s, "tau");
-    return launch_tau_stage(s, tp, false, E.nspin, ngrid, nao, ao_grad, Dp, tau);
+    const bool both = E.nspin == 2 && s->tau_spin_fused;   // as compute_tau chooses: k_tau_spin, or k_tau once per spin
+    const TauPlan tp = both ? tau_spin_plan(s->num_cu, ngrid, nao) : tau_plan(s->num_cu, ngrid, nao);   // tp.NP = P.NP
+    ScopedTimer t(s, E.nspin == 1 ? "tau" : both ? "tau_spin" : "tau x2");
+    return launch_tau_stage(s, tp, both, E.nspin, ngrid, nao, ao_grad, Dp, tau);
 }
 
-// XC part of the nuclear gradient: DFT_ComputeXCGradient, DFT_ComputeXCGradientSpin and DFT_ComputeXCGradientMeta, each
-// stage once over sp < nspin.  The density stage above, the pointwise kernel of the entry's sweep exactly as that sweep runs
-// it (launch_xc_points, xc_spin.hip, xc_meta.hip), then the contraction of every spin's (coefficient planes, padded matrix)
+// XC part of the nuclear gradient: DFT_ComputeXCGradient, DFT_ComputeXCGradientSpin, DFT_ComputeXCGradientMeta and
+// DFT_ComputeXCGradientMetaSpin, each stage once over sp < nspin.  The density stage above, the pointwise kernel of the
+// entry's sweep exactly as that sweep runs it (launch_xc_points, xc_spin.hip, xc_meta.hip, xc_meta_spin.hip), then the
+// contraction of every spin's (coefficient planes, padded matrix)
 // pair with the ten planes and a fixed-order slab sum: k_xc_grad; for two spins both pairs in one launch or, with option
 // "xcg_spin_fused" = 0, one launch per spin into two slab sets; for a meta-GGA k_xc_grad_meta<true> with c0..c3 and ct in one
-// pass or, with "xcg_meta_fused" = 0, k_xc_grad and k_xc_grad_meta<false> into two slab sets.  With both meta weights zero
-// the tau stage and the tau term are left out: k_xc_grad alone, as DFT_ComputeXCGradient runs it.  Never the one-kernel plan
+// pass or, with "xcg_meta_fused" = 0, k_xc_grad and k_xc_grad_meta<false> into two slab sets; for a meta-GGA at two spins
+// k_xc_grad_meta_spin with both spins' c0..c3 and ct in one pass or, with "xcg_meta_spin_fused" = 0, that plain pair once per
+// spin into four slab sets.  With both meta weights zero the tau stage and the tau term are left out: k_xc_grad alone, as
+// DFT_ComputeXCGradient or DFT_ComputeXCGradientSpin runs it.  Never the one-kernel plan
 // for small bases (it keeps no coefficients), never recorded; asynchronous on the solver's stream.
 bool xc_gradient(XCSolver *s, const XcgEntry &E, long ngrid, int nao, const double *const dm[2], const double *ao, const double *w,
                  const double *ao_grad, const double *ao_hess, double *out)
 {
     if (!xcg_enter(s, E, true, ngrid, nao, dm, ao, w, ao_grad, ao_hess, out)) return false;
     const bool spin = E.nspin == 2, gga = s->needs_grad, tau_term = E.meta && s->meta_active;
-    const bool fused = spin ? s->xcg_spin_fused != 0 : tau_term && s->xcg_meta_fused != 0;
-    const XcGradPlan G = xc_grad_plan(s->num_cu, gga, spin && fused ? 2 : 1, ngrid, nao);                      // k_xc_grad
-    const XcGradPlan T = tau_term ? xc_grad_meta_plan(s->num_cu, fused, ngrid, nao) : XcGradPlan{};          // k_xc_grad_meta<fused>
+    const bool fused = !tau_term ? spin && s->xcg_spin_fused != 0 : spin ? s->xcg_meta_spin_fused != 0 : s->xcg_meta_fused != 0;
+    const XcGradPlan G = xc_grad_plan(s->num_cu, gga, spin && fused && !tau_term ? 2 : 1, ngrid, nao);        // k_xc_grad
+    const XcGradPlan T = !tau_term ? XcGradPlan{}
+                         : spin && fused ? xc_grad_meta_spin_plan(s->num_cu, ngrid, nao)                        // k_xc_grad_meta_spin
+                                         : xc_grad_meta_plan(s->num_cu, fused, ngrid, nao);                     // k_xc_grad_meta<fused>
     const size_t lds = !tau_term ? G.lds : fused ? T.lds : std::max(G.lds, T.lds);
     if (lds > 160 * 1024) {
         set_error(s, "%s: nao=%d needs %zu bytes of LDS per workgroup%s", E.who, nao, lds, E.meta ? ", above the 160 KB a workgroup has" : "");
@@ -1608,21 +1619,24 @@ bool xc_gradient(XCSolver *s, const XcgEntry &E, long ngrid, int nao, const doub
     // an LDA-class solver's density kernels read ao_grad's first plane pointer only as a dummy: plan as the sweep does
     const SweepPlan P = plan_sweep(s, ngrid, nao, ao, gga ? ao_grad : nullptr, false);
     const long nxb = E.meta ? meta_points_blocks(ngrid) : spin ? spin_points_blocks(ngrid) : (ngrid + 255) / 256;
-    const int nslab = !tau_term ? (spin && !fused ? 2 : 1) * G.nwg : fused ? T.nwg : G.nwg + T.nwg;
+    const int nslab = !tau_term ? (spin && !fused ? 2 : 1) * G.nwg : fused ? T.nwg : E.nspin * (G.nwg + T.nwg);
     if (!reserve_xcg(s, E, P, ngrid, WS_ALL, nxb) ||
         !reserve(s, s->xcg_slabs, sizeof(double) * (size_t)nslab * 3 * nao, E.alloc_slabs, false) ||
         !xcg_density(s, E, P, true, ngrid, nao, dm, ao, ao_grad))
         return false;
     const Planes &a = s->xcg[0], &b = s->xcg[1];   // sigma and the Exc partials with [0] alone
     const double *Da = s->xcg_dp.d(), *Db = Da + (size_t)P.NP * P.NP;
-    double *ct = s->xcg_ct.d(), *slabs = s->xcg_slabs.d();
+    double *ct = s->xcg_ct.d(), *ctb = ct + (size_t)ngrid, *slabs = s->xcg_slabs.d();   // ctb: two spins with tau alone
+    const double *taua = s->xcg_tau.d(), *taub = taua + (size_t)ngrid;
     if (!spin && !E.meta) {   // the pointwise kernel: the first of the two stages that differ in more than their loop count
         launch_xc_points(s, ngrid, nxb, w, a);
         if (!hip_ok(s, hipGetLastError(), E.launch)) return false;
     } else {
         ScopedTimer t(s, E.timer);
         const hipError_t e =
-            E.meta ? launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), a.grad.d(), s->xcg_tau.d(), w, a.coef.d(), ct, a.partial.d())
+            E.meta && spin ? launch_xc_points_meta_spin(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), b.rho.d(), a.grad.d(), b.grad.d(), taua, taub, w,
+                                                        a.coef.d(), b.coef.d(), ct, ctb, a.partial.d())
+            : E.meta ? launch_xc_points_meta(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), a.grad.d(), taua, w, a.coef.d(), ct, a.partial.d())
                    : launch_xc_points_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
                                            gga ? b.grad.d() : nullptr, w, a.coef.d(), b.coef.d(), a.partial.d());
         if (!hip_ok(s, e, E.launch)) return false;
@@ -1630,12 +1644,16 @@ bool xc_gradient(XCSolver *s, const XcgEntry &E, long ngrid, int nao, const doub
     // ... and the contraction.  One-sided types hand over c0 = w vrho, c_k = 4 w vsigma grad_k rho; B3LYP half of each (its M + M^T)
     const double fac = s->type == SOLVER_B3LYP ? 2.0 : 1.0;
     struct Form { const char *timer, *what; };
-    const Form form = tau_term ? (fused ? Form{"xc_grad_meta", "meta XC gradient launch (fused)"} : Form{"xc_grad + xc_grad_tau", "meta XC gradient launch"})
+    const Form form = tau_term && spin ? (fused ? Form{"xc_grad_meta_spin", "spin meta XC gradient launch (fused)"}
+                                                : Form{"xc_grad + xc_grad_tau, per spin", "spin meta XC gradient launch"})
+                      : tau_term ? (fused ? Form{"xc_grad_meta", "meta XC gradient launch (fused)"} : Form{"xc_grad + xc_grad_tau", "meta XC gradient launch"})
                       : spin   ? Form{"xc_grad_spin", fused ? "XC spin gradient launch (fused)" : "XC spin gradient launch"}
                                : Form{"xc_grad", "XC gradient launch"};
     ScopedTimer t(s, form.timer);
     const hipError_t e =
-        tau_term ? (fused ? launch_xc_grad_meta_fused(s->stream, T, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), ct, Da, slabs, out)
+        tau_term && spin ? (fused ? launch_xc_grad_meta_spin_fused(s->stream, T, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), ct, ctb, Da, Db, slabs, out)
+                                  : launch_xc_grad_meta_spin_plain(s->stream, G, T, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), ct, ctb, Da, Db, slabs, out))
+        : tau_term ? (fused ? launch_xc_grad_meta_fused(s->stream, T, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), ct, Da, slabs, out)
                           : launch_xc_grad_meta_plain(s->stream, G, T, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), ct, Da, slabs, out))
         : spin   ? (fused ? launch_xc_grad_spin_fused(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Da, Db, slabs, out)
                           : launch_xc_grad_spin(s->stream, G, gga, fac, ngrid, nao, ao, ao_grad, ao_hess, a.coef.d(), b.coef.d(), Da, Db, slabs, out))
@@ -1645,7 +1663,8 @@ bool xc_gradient(XCSolver *s, const XcgEntry &E, long ngrid, int nao, const doub
 
 // The energy per volume of the functional at the density of the call -- DFT_ComputeXCEnergyDensity, its open-shell
 // counterpart (DFT_ComputeXCSpin's refusal) and the meta-GGA's, at the density and tau of dm: the density stage above, then
-// the body of the entry's pointwise kernel with unit weight (k_xc_edens, the spin-resolved body, k_xc_edens_meta).  Nothing
+// the body of the entry's pointwise kernel with unit weight (k_xc_edens, the spin-resolved body, k_xc_edens_meta,
+// k_xc_edens_meta_spin).  Nothing
 // here reads the padded matrix but k_tau.  Never the one-kernel plan, never recorded; asynchronous on the solver's stream.
 bool xc_energy_density(XCSolver *s, const XcgEntry &E, long ngrid, int nao, const double *const dm[2], const double *ao, const double *ao_grad,
                        double *e_out)
@@ -1657,7 +1676,9 @@ bool xc_energy_density(XCSolver *s, const XcgEntry &E, long ngrid, int nao, cons
     const Planes &a = s->xcg[0], &b = s->xcg[1];
     ScopedTimer t(s, E.timer);
     const hipError_t e =
-        E.meta         ? launch_xc_edens_meta(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), a.grad.d(), s->xcg_tau.d(), e_out)
+        E.meta && E.nspin == 2 ? launch_xc_edens_meta_spin(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), b.rho.d(), a.grad.d(), b.grad.d(),
+                                                           s->xcg_tau.d(), s->xcg_tau.d() + (size_t)ngrid, e_out)
+        : E.meta       ? launch_xc_edens_meta(s->stream, s->mix.c, s->meta, ngrid, a.rho.d(), a.grad.d(), s->xcg_tau.d(), e_out)
         : E.nspin == 2 ? launch_xc_edens_spin(s->stream, xc_type_index(s), gga, s->mix.c, ngrid, a.rho.d(), b.rho.d(), gga ? a.grad.d() : nullptr,
                                               gga ? b.grad.d() : nullptr, e_out)
                        : launch_xc_edens(s->stream, xc_type_index(s), gga, s->mix.c, s->quirks, ngrid, a.rho.d(), a.sigma.d(), a.grad.d(), e_out);
@@ -2397,6 +2418,22 @@ int DFT_ComputeXCGradientMeta(XCSolver *s, long long ngrid, int nao, unsigned lo
                        (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
 }
 
+int DFT_ComputeXCGradientMetaSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                                  unsigned long long d_ao, unsigned long long d_weights, unsigned long long d_ao_grad,
+                                  unsigned long long d_ao_hess, unsigned long long d_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    static const XcgEntry E{"DFT_ComputeXCGradientMetaSpin",
+                            "DFT_ComputeXCGradientMetaSpin needs both density matrices, the AO values, the grid weights, ao_grad (tau is made of "
+                            "the gradient planes), ao_hess and the output: a pointer is null",
+                            "hipMalloc(meta gradient Dsym of both spins)", "hipMalloc(spin meta gradient slabs)",
+                            "spin meta gradient: density launch", "spin meta pointwise launch", "xc_points_meta_spin", 2, true};
+    const double *const dm[2] = {(const double *)d_dm_a, (const double *)d_dm_b};
+    return xc_gradient(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_weights, (const double *)d_ao_grad,
+                       (const double *)d_ao_hess, (double *)d_out) ? 0 : -1;
+}
+
 int DFT_ComputeXCEnergyDensity(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm, unsigned long long d_ao,
                                unsigned long long d_ao_grad, unsigned long long d_e_out)
 {
@@ -2432,6 +2469,20 @@ int DFT_ComputeXCEnergyDensityMeta(XCSolver *s, long long ngrid, int nao, unsign
                             "hipMalloc(meta gradient Dsym)", nullptr, "meta gradient: density launch", "meta energy density launch",
                             "xc_edens_meta", 1, true};
     const double *const dm[2] = {(const double *)d_dm, nullptr};
+    return xc_energy_density(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
+}
+
+int DFT_ComputeXCEnergyDensityMetaSpin(XCSolver *s, long long ngrid, int nao, unsigned long long d_dm_a, unsigned long long d_dm_b,
+                                       unsigned long long d_ao, unsigned long long d_ao_grad, unsigned long long d_e_out)
+{
+    if (!s) return -1;
+    DeviceGuard dg(s);
+    static const XcgEntry E{"DFT_ComputeXCEnergyDensityMetaSpin",
+                            "DFT_ComputeXCEnergyDensityMetaSpin needs both density matrices, the AO values, ao_grad (tau is made of the "
+                            "gradient planes) and the output: a pointer is null",
+                            "hipMalloc(meta gradient Dsym of both spins)", nullptr, "spin meta gradient: density launch",
+                            "spin meta energy density launch", "xc_edens_meta_spin", 2, true};
+    const double *const dm[2] = {(const double *)d_dm_a, (const double *)d_dm_b};
     return xc_energy_density(s, E, (long)ngrid, nao, dm, (const double *)d_ao, (const double *)d_ao_grad, (double *)d_e_out) ? 0 : -1;
 }
 
@@ -2510,6 +2561,7 @@ int DFT_SetOption(XCSolver *s, const char *key, double value)
     if (!strcmp(key, "xcg_spin_fused")) { s->xcg_spin_fused = value != 0.0; return 0; }
     if (!strcmp(key, "meta_fused")) { s->meta_fused = value != 0.0; return 0; }
     if (!strcmp(key, "xcg_meta_fused")) { s->xcg_meta_fused = value != 0.0; return 0; }
+    if (!strcmp(key, "xcg_meta_spin_fused")) { s->xcg_meta_spin_fused = value != 0.0; return 0; }
     if (!strcmp(key, "tau_spin_fused")) { s->tau_spin_fused = value != 0.0; return 0; }
     return -1;
 }
@@ -2539,6 +2591,7 @@ double DFT_GetOption(XCSolver *s, const char *key)
     if (!strcmp(key, "xcg_spin_fused")) return s->xcg_spin_fused;
     if (!strcmp(key, "meta_fused")) return s->meta_fused;
     if (!strcmp(key, "xcg_meta_fused")) return s->xcg_meta_fused;
+    if (!strcmp(key, "xcg_meta_spin_fused")) return s->xcg_meta_spin_fused;
     if (!strcmp(key, "tau_spin_fused")) return s->tau_spin_fused;
     if (!strcmp(key, "dm_factor_rank")) return s->dm_factor_rank;                              // the rank its attempt found (0: rejected / not attempted)
     return unknown;

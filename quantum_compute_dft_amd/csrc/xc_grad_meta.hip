@@ -219,6 +219,12 @@ hipError_t launch_xc_grad_meta_plain(hipStream_t st, const XcGradPlan &pg, const
     return launch_xc_grad_sum(st, nao, pg.nwg + pt.nwg, slabs, out);
 }
 
+hipError_t launch_xc_grad_tau_slabs(hipStream_t st, const XcGradPlan &pt, long ngrid, int nao, const double *ao_grad, const double *hess,
+                                    const double *ct, const double *Dp, double *slabs)
+{
+    return launch_slabs<false>(st, pt, ngrid, nao, nullptr, ao_grad, hess, nullptr, ct, Dp, slabs);
+}
+
 hipError_t launch_xc_edens_meta(hipStream_t st, const double *mix8, const double *meta2, long ngrid, const double *rho, const double *grad,
                                 const double *tau, double *e)
 {

@@ -30,6 +30,11 @@ hipError_t launch_xc_grad_meta_plain(hipStream_t st, const XcGradPlan &pg, const
                                      const double *ao_grad, const double *hess, const double *coef, const double *ct, const double *Dp,
                                      double *slabs, double *out);
 
+// The tau term alone without the sum, for a caller that sums slab sets of several kernels (xc_grad_meta_spin.hip):
+// k_xc_grad_meta<false> (plan pt) into pt.nwg slabs of (nao, 3).
+hipError_t launch_xc_grad_tau_slabs(hipStream_t st, const XcGradPlan &pt, long ngrid, int nao, const double *ao_grad, const double *hess,
+                                    const double *ct, const double *Dp, double *slabs);
+
 // e[g] = the energy per volume of xc::meta_point's body at (rho, grad rho, tau)[g], unit weight (k_xc_edens_meta).
 // grad: three per point, interleaved, as the density kernels write it.
 hipError_t launch_xc_edens_meta(hipStream_t st, const double *mix8, const double *meta2, long ngrid, const double *rho, const double *grad,

@@ -162,7 +162,13 @@ def build_parser():
     p.add_argument("--open-shell-meta", action="store_true",
                    help="with --spin and a meta-GGA (TPSS, TPSSh, expressions with tpss_x / tpss_c): run the unrestricted loop on the "
                         "spin-resolved meta-GGA sweep (DFT_ComputeXCMetaSpin: tau and the tau term of the potential per spin); without "
-                        "the flag --spin refuses a meta-GGA.  Response, excitations and gradients of such a state are not built")
+                        "the flag --spin refuses a meta-GGA.  Response and excitations of such a state are not built; its nuclear "
+                        "gradient is, on request (--open-shell-meta-gradient)")
+    p.add_argument("--open-shell-meta-gradient", action="store_true",
+                   help="with --spin N --open-shell-meta --open-shell-gradient, --gradient / --optimize and a meta-GGA: the nuclear "
+                        "gradient of the unrestricted meta-GGA state with the tau term of either spin in the XC force "
+                        "(gradients.nuclear_gradient_uks(meta=True), DFT_ComputeXCGradientMetaSpin), in every step of --optimize too; "
+                        "--grid-response and --grad2e are honoured.  Without the flag the gradient of such a state is refused")
     p.add_argument("--meta-gradient", action="store_true",
                    help="with --gradient / --optimize and a meta-GGA (TPSS, TPSSh, expressions with tpss_x / tpss_c): the closed-shell "
                         "nuclear gradient with the tau term of the XC force (gradients.nuclear_gradient(meta=True), "
@@ -213,6 +219,16 @@ def main(argv=None):
                     "state is not built")
         if not (args.gradient or args.optimize):
             p.error("--meta-gradient goes with --gradient or --optimize")
+    if args.open_shell_meta_gradient:
+        if not fn.needs_tau:
+            p.error(f"--open-shell-meta-gradient is for a meta-GGA: {args.functional} carries no tpss_x / tpss_c weight; "
+                    "--open-shell-gradient alone runs it")
+        missing = [flag for flag, on in (("--spin N", args.spin is not None), ("--open-shell-meta", args.open_shell_meta),
+                                         ("--open-shell-gradient", args.open_shell_gradient),
+                                         ("--gradient or --optimize", args.gradient or args.optimize)) if not on]
+        if missing:
+            p.error("--open-shell-meta-gradient goes with --spin N --open-shell-meta --open-shell-gradient and --gradient or --optimize: "
+                    + ", ".join(missing) + (" is" if len(missing) == 1 else " are") + " missing")
     if fn.needs_tau:
         if args.spin is not None and not args.open_shell_meta:
             p.error(f"--spin: {args.functional} is a meta-GGA and the unrestricted loop is not built for meta-GGA functionals unless "
@@ -222,10 +238,13 @@ def main(argv=None):
                          ("--open-shell-response", args.open_shell_response), ("--open-shell-gradient", args.open_shell_gradient),
                          ("--grid-response", args.grid_response)):
             by_request = flag in ("--gradient", "--optimize", "--grid-response")
-            if on and not (by_request and args.meta_gradient):
+            uks_request = by_request or flag == "--open-shell-gradient"
+            if on and not (by_request and args.meta_gradient) and not (uks_request and args.open_shell_meta_gradient):
                 p.error(f"{flag}: {args.functional} is a meta-GGA and this feature is not built for meta-GGA functionals "
                         "(only the ground state is: closed shell, and open shell with --spin N --open-shell-meta)" +
-                        ("; the closed-shell nuclear gradient is too, but only on request: add --meta-gradient "
+                        ("; the nuclear gradient of the unrestricted state is too, but only on request: add "
+                         "--open-shell-meta-gradient (DFT_ComputeXCGradientMetaSpin)" if uks_request and args.spin is not None else
+                         "; the closed-shell nuclear gradient is too, but only on request: add --meta-gradient "
                          "(DFT_ComputeXCGradientMeta)" if by_request else ""))
     if args.xc_occ is None:
         args.xc_occ = None if fn.needs_tau else 1
@@ -431,7 +450,7 @@ def main(argv=None):
         from . import gradients, optimize
         nuclear_gradient = gradients.nuclear_gradient_uks if uks else gradients.nuclear_gradient
         grad_kw = dict(two_electron=args.grad2e, grid_response=True) if args.grid_response else dict(two_electron=args.grad2e)
-        if args.meta_gradient:
+        if args.meta_gradient or args.open_shell_meta_gradient:
             grad_kw["meta"] = True
         grad, grad_terms = nuclear_gradient(inp, res, backend, args.functional, **grad_kw)
         print_gradient(inp.symbols, grad, args.grid_response)
@@ -442,7 +461,7 @@ def main(argv=None):
             if uks:
                 be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, device_resident=False,
                                       fused_tail=False, eigensolver="exact", ao_mode=args.ao, xc_occ=None if args.xc_occ is None else bool(args.xc_occ))
-                res_k = scf.run_uks(inp_k, be_k, args.functional, log=None)
+                res_k = scf.run_uks(inp_k, be_k, args.functional, log=None, meta=args.open_shell_meta)
             else:
                 be_k = scf.HipBackend(inp_k, args.functional, args.lib, quirks=bool(args.quirks), device=device, eigensolver=args.eigensolver,
                                       ao_mode=args.ao, xc_occ=None if args.xc_occ is None else bool(args.xc_occ))

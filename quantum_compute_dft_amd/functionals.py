@@ -130,6 +130,11 @@ OPEN_SHELL_META_HINT = ("the open-shell ground state is too, but only on request
 META_GRADIENT_HINT = ("the closed-shell nuclear gradient is too, but only on request: gradients.nuclear_gradient(..., meta=True) / the "
                       "driver's --meta-gradient, which go through HipBackend.xc_gradient_meta (DFT_ComputeXCGradientMeta)")
 
+# What the open-shell gradient refusals add: the nuclear gradient of an open-shell meta-GGA is built, but opt-in
+OPEN_SHELL_META_GRADIENT_HINT = ("the open-shell nuclear gradient is too, but only on request: gradients.nuclear_gradient_uks(..., "
+                                 "meta=True) / the driver's --open-shell-meta-gradient, which go through "
+                                 "HipBackend.xc_gradient_meta_spin (DFT_ComputeXCGradientMetaSpin)")
+
 
 def refuse_meta(spec, what, hint=None):
     """ValueError when `spec` is a meta-GGA: `what` (a sentence's subject) is built for LDA / GGA / hybrid functionals only.

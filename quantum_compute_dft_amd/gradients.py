@@ -12,7 +12,9 @@ DFT_EvalAOHess / DFT_ComputeXCGradient (csrc/xc_grad.hip; solver.eval_ao_hess / 
 scf.HipBackend.xc_gradient) below.  `nuclear_gradient_uks` is the same assembly for a run_uks state: W = sum_s D_s F_s D_s, the
 two-electron term with the spin density beside the total one (integrals.grad2e_spin / DFT_Grad2eSpin), the XC term once
 per spin (xc_gradient_spin_host / DFT_ComputeXCGradientSpin).  `nuclear_gradient(meta=True)` is the closed-shell assembly for a
-meta-GGA: the same terms, the XC part with the tau term (xc_gradient_meta_host / DFT_ComputeXCGradientMeta, csrc/xc_grad_meta.hip).
+meta-GGA: the same terms, the XC part with the tau term (xc_gradient_meta_host / DFT_ComputeXCGradientMeta, csrc/xc_grad_meta.hip);
+`nuclear_gradient_uks(meta=True)` the open-shell one (xc_gradient_meta_spin_host / DFT_ComputeXCGradientMetaSpin,
+csrc/xc_grad_meta_spin.hip).
 
     G[mu, x] = d/dt Exc  when, in column mu only,  ao[:, mu] -> ao[:, mu] - t ao_grad[x][:, mu]  and
                ao_grad[k][:, mu] -> ao_grad[k][:, mu] - t ao_hess[xk][:, mu]          (dm and the weights fixed)
@@ -238,6 +240,41 @@ def xc_energy_density_meta_host(functional, dm, ao, ao_grad):
     return metagga.point_meta_host(functional, rho, g, tau, np.ones(ao.shape[0]))["e"]
 
 
+def xc_gradient_meta_spin_host(functional, dm_a, dm_b, ao, weights, ao_grad, ao_hess, tau_term=True):
+    """G (nao, 3) of DFT_ComputeXCGradientMetaSpin from AO planes in numpy: the derivative of metagga.xc_meta_spin_host's Exc
+    under the column replacement above, both spin density matrices and the weights fixed.  xc_gradient_meta_host's terms once
+    per spin with the spin point's coefficients (metagga.point_meta_spin_host: c_s0..c_s3 one-sided, ct_s = w e_tau_s / 2),
+    Ds_s the symmetric part of dm_s and Y_sk = ao_grad[k] Ds_s:
+
+        G[mu, x] = sum_s { G_gga[mu, x; c_s0..c_s3, Ds_s] - 2 sum_g ct_s sum_k ao_hess[xk][g, mu] Y_sk[g, mu] }.
+
+    A spin without electrons contributes nothing; a functional without a meta weight has ct_s = 0 and gets
+    xc_gradient_spin_host's G of the same mix.  tau_term=False leaves the second sum out (for the tests)."""
+    from . import metagga
+    ao, gr, hs = _meta_planes("xc_gradient_meta_spin_host", ao, ao_grad, ao_hess)
+    dms = [np.asarray(d, dtype=np.float64) for d in (dm_a, dm_b)]
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    ra, ga, ta, rb, gb, tb = metagga.density_spin_host(dms[0], dms[1], ao, gr)
+    p = metagga.point_meta_spin_host(functional, ra, rb, ga, gb, ta, tb, w)
+    G = _xc_contract(1.0, True, ao, gr, hs, [(dms[0], p["coef_a"]), (dms[1], p["coef_b"])])
+    for dm, ct in zip(dms, (p["ct_a"], p["ct_b"])):
+        if tau_term and np.any(ct != 0.0):
+            ds = 0.5 * (dm + dm.T)
+            Y = [gr[k] @ ds for k in range(3)]
+            for x in range(3):
+                G[:, x] -= 2.0 * np.einsum("g,gm->m", ct, sum(hs[HESS_INDEX[x][k]] * Y[k] for k in range(3)))
+    return G
+
+
+def xc_energy_density_meta_spin_host(functional, dm_a, dm_b, ao, ao_grad):
+    """e_g (ngrid,) of DFT_ComputeXCEnergyDensityMetaSpin from AO planes in numpy: the energy per volume of the spin meta point
+    at the densities and taus of dm_a / dm_b, without the weight (metagga.point_meta_spin_host with unit weights)."""
+    from . import metagga
+    ao, gr = _meta_planes("xc_energy_density_meta_spin_host", ao, ao_grad)
+    ra, ga, ta, rb, gb, tb = metagga.density_spin_host(np.asarray(dm_a, dtype=np.float64), np.asarray(dm_b, dtype=np.float64), ao, gr)
+    return metagga.point_meta_spin_host(functional, ra, rb, ga, gb, ta, tb, np.ones(ao.shape[0]))["e"]
+
+
 def _grid_of(grids, symbols, atom_xyz, who):
     """(owner, atomic weights, charges) of a grid that says which atom each point moves with, checked against the atoms."""
     own, w0 = getattr(grids, "atom_index", None), getattr(grids, "atomic_weights", None)
@@ -310,6 +347,18 @@ def xc_grid_response_meta_host(functional, dm, shells, grids, symbols, atom_xyz,
         grids, symbols, atom_xyz,
         lambda r: xc_gradient_meta_host(f, dm, ao[r], w[r], gr[:, r], hs[:, r]),
         lambda r: xc_energy_density_meta_host(f, dm, ao[r], gr[:, r]), "xc_grid_response_meta_host")
+
+
+def xc_grid_response_meta_spin_host(functional, dm_a, dm_b, shells, grids, symbols, atom_xyz, planes=None):
+    """xc_grid_response_meta_host for an open-shell state: xc_gradient_meta_spin_host per atom block and
+    xc_energy_density_meta_spin_host's e."""
+    f = functionals.resolve(functional)
+    ao, gr, hs = planes if planes is not None else ao_planes_host(shells, grids.coords)
+    w = np.asarray(grids.weights, dtype=np.float64)
+    return _xc_grid_response_host(
+        grids, symbols, atom_xyz,
+        lambda r: xc_gradient_meta_spin_host(f, dm_a, dm_b, ao[r], w[r], gr[:, r], hs[:, r]),
+        lambda r: xc_energy_density_meta_spin_host(f, dm_a, dm_b, ao[r], gr[:, r]), "xc_grid_response_meta_spin_host")
 
 
 def sum_over_atoms(shells, G):
@@ -398,7 +447,7 @@ def _checked(who, inp, backend, functional, two_electron, device_method, wrong_r
     f = functionals.resolve(functional if functional is not None else backend.functional)
     if meta:
         if not f.needs_tau:
-            raise ValueError(f"{who}(meta=True) is the gradient of a meta-GGA (DFT_ComputeXCGradientMeta): {f.name} is not one (it "
+            raise ValueError(f"{who}(meta=True) is the gradient of a meta-GGA (DFT_ComputeXCGradientMeta / MetaSpin): {f.name} is not one (it "
                              "carries no tpss_x / tpss_c weight); its gradient is meta=False's")
         return f, f.weight_vector() + f.meta_weight_vector()
     functionals.refuse_meta(f, who, hint)
@@ -413,11 +462,12 @@ def _assemble(inp, backend, f, wv, dm, W, two_electron, mats, host_extra, grid_r
     """(g, terms) from the total density dm, W and the finished two-electron term.  mats: the matrices of the XC term --
     (dm,) for the closed shell (backend.xc_gradient / xc_grid_response, xc_gradient_host / xc_grid_response_host otherwise),
     (dm_a, dm_b) for an open-shell state (the *_spin ones); host_extra: what the host functions take behind them (quirks).
-    meta: the closed shell of a meta-GGA (the *_meta ones; wv then carries the meta weights too, so that TPSS, whose eight are
-    all zero, keeps its XC term)."""
+    meta: a meta-GGA (the *_meta ones for the closed shell, the *_meta_spin ones for an open-shell state; wv then carries the
+    meta weights too, so that TPSS, whose eight are all zero, keeps its XC term)."""
     spin = len(mats) == 2
-    sfx = "_spin" if spin else "_meta" if meta else ""
-    host_gradient, host_grid = (xc_gradient_spin_host, xc_grid_response_spin_host) if spin else \
+    sfx = ("_meta" if meta else "") + ("_spin" if spin else "")
+    host_gradient, host_grid = (xc_gradient_meta_spin_host, xc_grid_response_meta_spin_host) if spin and meta else \
+                               (xc_gradient_spin_host, xc_grid_response_spin_host) if spin else \
                                (xc_gradient_meta_host, xc_grid_response_meta_host) if meta else (xc_gradient_host, xc_grid_response_host)
     sh, xyz = inp.shells, np.asarray(inp.atom_xyz, dtype=np.float64)
     z = np.array([basis.atomic_number(s) for s in inp.symbols], dtype=np.float64)
@@ -490,7 +540,7 @@ def nuclear_gradient(inp, scf_result, backend, functional=None, quirks=None, two
     return _assemble(inp, backend, f, wv, dm, W, g2e, (dm,), () if meta else (quirks,), grid_response, meta)
 
 
-def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron="host", grid_response=False):
+def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron="host", grid_response=False, meta=False):
     """(g (natm, 3) in Ha / bohr, terms): dE/dR_A of the converged unrestricted state `uks_result` (scf.run_uks), with
     nuclear_gradient's five terms and its conventions (fixed quadrature points and weights).  With D = D_a + D_b:
 
@@ -502,10 +552,19 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
                        planes evaluated here otherwise
 
     A spin without electrons has D_s = 0 and contributes nothing.  Point charges are served through "external".
-    `grid_response` = True adds "xc_grid" as in nuclear_gradient (backend.xc_grid_response_spin / xc_grid_response_spin_host)."""
+    `grid_response` = True adds "xc_grid" as in nuclear_gradient (backend.xc_grid_response_spin / xc_grid_response_spin_host).
+    `meta` = True (the driver's --open-shell-meta-gradient): the functional is a meta-GGA, the state scf.run_uks(meta=True)'s.
+    F_s then comes from backend.uks_meta_parts (refused where the backend has none) and the XC terms carry the tau term of
+    either spin -- backend.xc_gradient_meta_spin / xc_grid_response_meta_spin (scf.HipBackend: DFT_ComputeXCGradientMetaSpin)
+    where the backend has them, xc_gradient_meta_spin_host / xc_grid_response_meta_spin_host otherwise.  A functional that is
+    no meta-GGA is refused; without the keyword a meta-GGA is refused, as before this assembly existed."""
     wrong = None if ("dm_a" in uks_result and "dm_b" in uks_result) else \
         "nuclear_gradient_uks needs a scf.run_uks result (dm_a, dm_b); nuclear_gradient serves the closed shell"
-    f, wv = _checked("nuclear_gradient_uks", inp, backend, functional, two_electron, "grad2e_spin", wrong, grid_response)
+    f, wv = _checked("nuclear_gradient_uks", inp, backend, functional, two_electron, "grad2e_spin", wrong, grid_response, meta,
+                     functionals.OPEN_SHELL_META_GRADIENT_HINT)
+    if meta and not hasattr(backend, "uks_meta_parts"):
+        raise ValueError("nuclear_gradient_uks(meta=True) takes the Fock matrices of a meta-GGA from backend.uks_meta_parts "
+                         "(scf.HipBackend: DFT_ComputeXCMetaSpin); this backend has none")
     if getattr(backend, "dm_factor", False):
         raise ValueError("nuclear_gradient_uks takes the density matrices themselves: run without dm_factor")
     if bool(getattr(backend, "quirks", getattr(backend, "q", False))) and _has_quirky(wv):
@@ -521,7 +580,7 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
         n = int(uks_result[key]) if key in uks_result else int(round(float(np.sum(d * S))))
         coccs.append(np.ascontiguousarray(C0[:, ::-1][:, :n] * np.sqrt(np.maximum(e0[::-1][:n], 0.0))))
     want_k = f.c_hf != 0.0
-    J, Ka, Kb, _, Va, Vb = backend.uks_parts(dms[0], dms[1], coccs[0], coccs[1], want_k)
+    J, Ka, Kb, _, Va, Vb = (backend.uks_meta_parts if meta else backend.uks_parts)(dms[0], dms[1], coccs[0], coccs[1], want_k)
     W = np.zeros_like(S)
     for d, V, K in ((dms[0], Va, Ka), (dms[1], Vb, Kb)):
         F = inp.Hcore + J + 0.5 * (V + V.T) - (f.c_hf * K if (want_k and K is not None) else 0.0)
@@ -529,4 +588,4 @@ def nuclear_gradient_uks(inp, uks_result, backend, functional=None, two_electron
     W = 0.5 * (W + W.T)
     dm, ms = np.ascontiguousarray(dms[0] + dms[1]), np.ascontiguousarray(dms[0] - dms[1])
     g2e = backend.grad2e_spin(dms[0], dms[1], f.c_hf) if two_electron == "device" else integrals.grad2e_spin(inp.shells, dm, ms, f.c_hf)
-    return _assemble(inp, backend, f, wv, dm, W, g2e, tuple(dms), (), grid_response)
+    return _assemble(inp, backend, f, wv, dm, W, g2e, tuple(dms), (), grid_response, meta)

@@ -788,13 +788,15 @@ class HipBackend:
 
     def _xc_gradient_calls(self, *dms, meta=False):
         """(entry, edens): the library calls of a grid slice for one matrix (the closed shell; meta: of a meta-GGA, through
-        DFT_ComputeXCGradientMeta / DFT_ComputeXCEnergyDensityMeta) or two (an open-shell state): entry(m, ao, w, d_out, gr, hs)
+        DFT_ComputeXCGradientMeta / DFT_ComputeXCEnergyDensityMeta) or two (an open-shell state; meta: through
+        DFT_ComputeXCGradientMetaSpin / DFT_ComputeXCEnergyDensityMetaSpin): entry(m, ao, w, d_out, gr, hs)
         the XC gradient, edens(m, ao, gr, d_e) the energy density, on the uploaded matrices.  The flag travels on the entry
         (entry.meta): whoever runs it refuses a meta-GGA unless the entry is the meta-GGA's own."""
         if len(dms) == 2:
-            self._uks_check()
+            self._uks_check(meta=meta)
         d, s = [self._dev(x) for x in dms], self.solver
-        grad, dens = (s.compute_xc_gradient_meta, s.compute_xc_energy_density_meta) if meta else \
+        grad, dens = (s.compute_xc_gradient_meta_spin, s.compute_xc_energy_density_meta_spin) if meta and len(dms) == 2 else \
+                     (s.compute_xc_gradient_meta, s.compute_xc_energy_density_meta) if meta else \
                      (s.compute_xc_gradient_spin, s.compute_xc_energy_density_spin) if len(dms) == 2 else \
                      (s.compute_xc_gradient, s.compute_xc_energy_density)
         entry = lambda m, ao, w, out, gr, hs: grad(m, self.nao, *d, ao, w, out, gr, hs)      # noqa: E731
@@ -915,7 +917,7 @@ class HipBackend:
     def _meta_gradient_check(self, who):
         if not self.meta:
             raise ValueError(f"{who} is the gradient of a meta-GGA (DFT_ComputeXCGradientMeta): {self.functional} is not one (it "
-                             f"carries no tpss_x / tpss_c weight); its gradient is {who[:-5]}")
+                             f"carries no tpss_x / tpss_c weight); its gradient is {who.replace('_meta', '')}")
 
     def xc_gradient_meta(self, dm, slice_rows=None):
         """xc_gradient for a meta-GGA: G (nao, 3) with the tau term (DFT_ComputeXCGradientMeta), summed over slices of the grid
@@ -927,6 +929,18 @@ class HipBackend:
         """xc_grid_response for a meta-GGA: DFT_ComputeXCGradientMeta and DFT_ComputeXCEnergyDensityMeta per block."""
         self._meta_gradient_check("xc_grid_response_meta")
         return self._xc_grid_response(slice_rows, *self._xc_gradient_calls(dm, meta=True))
+
+    def xc_gradient_meta_spin(self, dm_a, dm_b, slice_rows=None):
+        """xc_gradient_spin for a meta-GGA: G (nao, 3) with the tau term of either spin (DFT_ComputeXCGradientMetaSpin), summed
+        over slices of the grid exactly as xc_gradient does.  Refuses what xc_gradient_spin refuses but the meta-GGA, and a
+        functional that is not one."""
+        self._meta_gradient_check("xc_gradient_meta_spin")
+        return self._xc_gradient_slices(slice_rows, self._xc_gradient_calls(dm_a, dm_b, meta=True)[0])
+
+    def xc_grid_response_meta_spin(self, dm_a, dm_b, slice_rows=None):
+        """xc_grid_response_spin for a meta-GGA: DFT_ComputeXCGradientMetaSpin and DFT_ComputeXCEnergyDensityMetaSpin per block."""
+        self._meta_gradient_check("xc_grid_response_meta_spin")
+        return self._xc_grid_response(slice_rows, *self._xc_gradient_calls(dm_a, dm_b, meta=True))
 
     def ground_state_parts_meta(self, dm, cocc, want_k):
         """ground_state_parts for a meta-GGA (the Fock matrix of W in the gradient): set_state and fock_parts, which sweep through

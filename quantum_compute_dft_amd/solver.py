@@ -453,13 +453,13 @@ class DFTSolverWrapper:
         return rc
 
     def _xc_gradient(self, fn, dms, ngrid, nao, d_ao, d_weights, d_out, d_ao_grad, d_ao_hess):
-        """The three gradient entries: `fn` takes the matrices `dms`, then ao, the weights, ao_grad, ao_hess and the output."""
+        """The four gradient entries: `fn` takes the matrices `dms`, then ao, the weights, ao_grad, ao_hess and the output."""
         rc = fn(self.solver, int(ngrid), int(nao), *(_u64(_ptr(d)) for d in (*dms, d_ao, d_weights, d_ao_grad, d_ao_hess, d_out)))
         self._check()
         return rc
 
     def _xc_energy_density(self, fn, dms, ngrid, nao, d_ao, d_e_out, d_ao_grad):
-        """The three energy-density entries: `fn` takes the matrices `dms`, then ao, ao_grad and the output."""
+        """The four energy-density entries: `fn` takes the matrices `dms`, then ao, ao_grad and the output."""
         rc = fn(self.solver, int(ngrid), int(nao), *(_u64(_ptr(d)) for d in (*dms, d_ao, d_ao_grad, d_e_out)))
         self._check()
         return rc
@@ -510,6 +510,33 @@ class DFTSolverWrapper:
         """e_g of a meta-GGA at the density and tau of d_dm into d_e_out (ngrid) without the weight
         (DFT_ComputeXCEnergyDensityMeta): sum_g w_g e_g is compute_xc_meta's Exc.  Asynchronous on the solver's stream."""
         return self._xc_energy_density(self._declare_meta_gradient().DFT_ComputeXCEnergyDensityMeta, [d_dm], ngrid, nao, d_ao, d_e_out, d_ao_grad)
+
+    def _declare_meta_spin_gradient(self):
+        L = self.lib
+        # added without a change of DFT_GetVersion: a library without them cannot serve the gradient of an open-shell meta-GGA
+        if not hasattr(L, "DFT_ComputeXCGradientMetaSpin") or not hasattr(L, "DFT_ComputeXCEnergyDensityMetaSpin"):
+            raise RuntimeError("the library has no DFT_ComputeXCGradientMetaSpin / DFT_ComputeXCEnergyDensityMetaSpin: it cannot run "
+                               "the nuclear gradient of an open-shell meta-GGA")
+        L.DFT_ComputeXCGradientMetaSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + [_u64] * 7
+        L.DFT_ComputeXCGradientMetaSpin.restype = ctypes.c_int
+        L.DFT_ComputeXCEnergyDensityMetaSpin.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + [_u64] * 5
+        L.DFT_ComputeXCEnergyDensityMetaSpin.restype = ctypes.c_int
+        return L
+
+    def compute_xc_gradient_meta_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_weights, d_out, d_ao_grad=None, d_ao_hess=None):
+        """G (nao, 3) into d_out (DFT_ComputeXCGradientMetaSpin): the derivative of compute_xc_meta_spin's Exc by the centre of
+        every basis function at fixed points and weights, the tau term of either spin included
+        (gradients.xc_gradient_meta_spin_host is its host counterpart); a solver with meta weights, d_ao_grad and d_ao_hess
+        always.  Option xcg_meta_spin_fused chooses the one-pass kernel (1) or the plain form (0).  Asynchronous on the
+        solver's stream."""
+        return self._xc_gradient(self._declare_meta_spin_gradient().DFT_ComputeXCGradientMetaSpin, [d_dm_a, d_dm_b], ngrid, nao, d_ao,
+                                 d_weights, d_out, d_ao_grad, d_ao_hess)
+
+    def compute_xc_energy_density_meta_spin(self, ngrid, nao, d_dm_a, d_dm_b, d_ao, d_e_out, d_ao_grad=None):
+        """e_g of a meta-GGA at the spin densities and taus of d_dm_a / d_dm_b into d_e_out (ngrid) without the weight
+        (DFT_ComputeXCEnergyDensityMetaSpin): sum_g w_g e_g is compute_xc_meta_spin's Exc.  Asynchronous on the solver's stream."""
+        return self._xc_energy_density(self._declare_meta_spin_gradient().DFT_ComputeXCEnergyDensityMetaSpin, [d_dm_a, d_dm_b], ngrid, nao,
+                                       d_ao, d_e_out, d_ao_grad)
 
     def becke_weight_gradient(self, ngrid, atom_xyz, atom_radius, d_coords, d_owner, d_f, d_out, d_cell_out=None):
         """sum_g f_g D_B cell_g into d_out (natm, 3) (DFT_BeckeWeightGradient; grid_gen.becke_weight_gradient_host is its
